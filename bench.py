@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: contrastive-step samples/s (protein-text pairs) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: one process per GPU over RCCL.  Under a launcher (torch.distributed.run sets RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_*) this process IS one rank; without one, this process only starts the N ranks as fresh child processes -- it never
@@ -16,11 +16,14 @@ Llama-3.1-8B-Instruct shapes, bf16, 16 x 1024 residues / 16 x 128 text tokens pe
 weights and random residues/tokens from the repo's counter-hash generator (no checkpoints or
 datasets exist offline).  Weak scaling: per-GPU batch fixed, value = N * B * K / max-over-ranks time.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields.  A plain run does only what that line's headline needs: set-up,
+warm-up, the K timed steps, the outputs of the last timed step (--dump-outputs), the line.  --full adds, after the timed
+steps, every further measurement:
   "roofline":     dominant kernel (bf16 MFMA GEMM): algorithmic FLOPs per launch / its mean launch duration,
                   measured live with HIP events on the launch stream, vs the 2.5 PFLOP/s dense bf16 peak
   "cpu_baseline": the numpy oracle (a port of the reference algorithm, fp32) timed on the host cores on a
                   bounded sample of the same workload (rank 0, N = 1 only)
+  config.*_check: one-stream rate, batch 64, the cfg5 share, the ragged batch, `generate`, forward-only (N = 1 only)
 """
 import argparse
 import ctypes
@@ -48,14 +51,14 @@ def parse():
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch override")
     ap.add_argument("--segments", type=int, default=1, help="contrastive_num_segments")
     ap.add_argument("--eval-mode", action="store_true", help="no adapter dropout (default: train mode, p=0.3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--rehearse-shared-gpu", action="store_true",
                     help="REHEARSAL, not a measurement: all --gpus N ranks share GPU 0 and talk over gloo (RCCL refuses two ranks on one "
                          "device) -- runs this script's own multi-rank path (launcher, rank setup, barriers, max-over-ranks timing, the "
                          "trainer's collectives) on a one-GPU box; the JSON line says so in `data`")
     ap.add_argument("--gemm-policy", type=int, default=0, help="p2t_set_gemm_policy for A/B runs (0 = the library's default; include/p2t_hip.h)")
     ap.add_argument("--event-steps", type=int, default=3,
-                    help="timed steps whose MFMA launches are bracketed by HIP events for the roofline block "
+                    help="(--full) timed steps whose MFMA launches are bracketed by HIP events for the roofline block "
                          "(default: the last 3 of the timed steps -- the event records cost ~1.5 %% of the step when on every launch; "
                          "-1 = all, 0 = none)")
     ap.add_argument("--no-overlap", action="store_true",
@@ -64,14 +67,23 @@ def parse():
                          "roofline block's per-kernel event times always come from a separate single-stream pass after the timed region")
     ap.add_argument("--overlap", action="store_true", help="(default since round 3; accepted for old command lines)")
     ap.add_argument("--no-generate-check", action="store_true",
-                    help="skip the extra (untimed-for-`value`) measurement of `generate`: ms per KV-cache decode step at 8 prompts and its HBM roofline")
+                    help="(--full) skip the extra (untimed-for-`value`) measurement of `generate`: ms per KV-cache decode step at 8 prompts and its HBM roofline")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="do not enqueue the next step's frozen towers beside this step's backward / optimizer tail (the timed default does)")
-    ap.add_argument("--cpu-sample", type=int, default=1, help="pairs of the benchmarked config in the CPU-baseline sample")
-    ap.add_argument("--cpu-cfg2", action="store_true", help="also time config 2 on the CPU (1 warm-up + 1 repetition, ~1.5 min)")
+    ap.add_argument("--cpu-sample", type=int, default=1, help="(--full) pairs of the benchmarked config in the CPU-baseline sample")
+    ap.add_argument("--cpu-cfg2", action="store_true", help="(--full) also time config 2 on the CPU (1 warm-up + 1 repetition, ~1.5 min)")
     ap.add_argument("--no-batch64-check", action="store_true",
-                    help="skip the extra (untimed-for-`value`) measurement at the north-star batch 64 x 1024")
-    return ap.parse_args()
+                    help="(--full) skip the extra (untimed-for-`value`) measurements at the north-star batch 64 x 1024 (batch 64, cfg5 share, ragged, generate)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every measurement beyond the headline: the roofline block's event pass, the "
+                         "batch-64 / cfg5 / ragged / generate / forward-only checks and the CPU baseline (the options marked (--full) tune them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (its loss, the adapter's updated fp32 parameters and its gradients; a fixed "
+                         "seeded sample of the two weight matrices) as DIR/<name>.npy, float32, untimed")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 class GpuWeights:
@@ -269,6 +281,32 @@ def generate_check(model, llama, Tp, dev, B=8, n_prompt=64, n_new=33):
             "frac_of_hbm_peak": round((w_bytes + kv_bytes) / dt / 8e12, 3)}
 
 
+DUMP_SAMPLE = 1 << 21       # elements kept of a larger array: at most four sampled arrays (8 MB each) + the small ones stay under 64 MB
+
+
+def dump_outputs(trainer, loss, out_dir):
+    """What the last timed step computed, as float32 DIR/<name>.npy: the loss ContrastiveTrainer.step returned, and the adapter's
+    fp32 master parameters after its AdamW update together with the gradients it computed.  An array of more than DUMP_SAMPLE
+    elements is cut to a fixed sample of its flattened elements (sorted indices from a seed-0 generator that depends on the size
+    alone), so two runs with the same arguments compare element for element."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    names = ("fc1_weight", "fc1_bias", "fc2_weight", "fc2_bias")
+    arrays = {"loss": loss}
+    arrays.update({f"adapter_{n}": p for n, p in zip(names, trainer.p)})
+    arrays.update({f"adapter_{n}_grad": g for n, g in zip(names, trainer.g)})
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+
+
 def spawn_ranks(n: int) -> int:
     """Start `n` ranks of this script (same argv) as child processes with the torch.distributed environment set, before
     anything in THIS process has touched the GPU (no torch import here).  Rank 0's stdout is relayed line by line; the
@@ -383,12 +421,14 @@ def main():
         loss = trainer.step(batch, next_batch=batch if (pipeline and i + 1 < args.steps) else None)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, loss, args.dump_outputs)      # before anything below steps the trainer again
     loss = trainer.global_loss(loss)            # mean over ranks (a copy; outside the timed region)
     # Per-kernel event times for the roofline block: a SEPARATE pass on one stream after the timed region (with two streams an
     # event pair around a launch also spans whatever the other stream runs meanwhile).  One un-timed step to settle, then
     # `ev_steps` steps with every MFMA launch bracketed by HIP events on its launch stream; also timed as a whole = the
-    # single-stream rate of the same step.
-    ev_steps = args.steps if args.event_steps < 0 else min(args.event_steps, args.steps)
+    # single-stream rate of the same step.  --full only.
+    ev_steps = 0 if not args.full else args.steps if args.event_steps < 0 else min(args.event_steps, args.steps)
     ms = (ctypes.c_double * 3)()
     cnt = (ctypes.c_int64 * 3)()
     fl = (ctypes.c_double * 3)()
@@ -448,24 +488,25 @@ def main():
                        "algorithmic_tflop_per_sample": round(f["total"] / 1e12, 4),
                        "step_tflops_per_gpu": round(step_tflops, 1), "step_frac_of_bf16_peak": round(step_tflops / PEAK_BF16_TFLOPS, 4),
                        "loss": round(loss_val, 5)},
-            "roofline": {"bound": "mfma", "kernel_src_sha16": kernel_src_sha16(),
-                         "kernel": ("gemm_nt_fp8_w4_kernel + gemm_nt_fp8_kernel (e4m3 16x16x128 block-scaled MFMA GEMM: four-wave persistent form, eight-wave per-tile form, all epilogues)" if fp8 else
-                                    "gemm_nt_w4_kernel + gemm_nt_mfma*_kernel (bf16 16x16x32 MFMA GEMM: four-wave persistent form, eight-wave persistent / per-tile / split-K-tail forms, all epilogues)"),
-                         "achieved": round(achieved, 1), "peak": PEAK_FP8_TFLOPS if fp8 else PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / (PEAK_FP8_TFLOPS if fp8 else PEAK_BF16_TFLOPS), 4),
-                         "frac_of_bf16_peak": round(achieved / PEAK_BF16_TFLOPS, 4),
-                         "traffic": pmc_traffic(args.config, B, "gemm_nt_fp8*" if fp8 else "gemm_nt_mfma*"),
-                         "launches_per_step": round(launches_step, 1), "avg_launch_ms": round(avg_ms, 4),
-                         "gemm_ms_per_step": round(ms[dom] / max(ev_steps, 1), 3), "attention_ms_per_step": round(ms[1] / max(ev_steps, 1), 3),
-                         "bf16_gemm_ms_per_step": round(ms[0] / max(ev_steps, 1), 3),
-                         "event_steps": ev_steps,
-                         "event_pass": f"{ev_steps} single-stream steps after the timed region (HIP events on the launch stream; the rocprofv3 "
-                                       "summary under profiles/ is `bench.py --no-overlap`)",
-                         "attention_tflops": round(fl[1] / max(ms[1], 1e-9) / 1e9, 1)},
         }
+        if args.full:
+            out["roofline"] = {"bound": "mfma", "kernel_src_sha16": kernel_src_sha16(),
+                               "kernel": ("gemm_nt_fp8_w4_kernel + gemm_nt_fp8_kernel (e4m3 16x16x128 block-scaled MFMA GEMM: four-wave persistent form, eight-wave per-tile form, all epilogues)" if fp8 else
+                                          "gemm_nt_w4_kernel + gemm_nt_mfma*_kernel (bf16 16x16x32 MFMA GEMM: four-wave persistent form, eight-wave persistent / per-tile / split-K-tail forms, all epilogues)"),
+                               "achieved": round(achieved, 1), "peak": PEAK_FP8_TFLOPS if fp8 else PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                               "frac": round(achieved / (PEAK_FP8_TFLOPS if fp8 else PEAK_BF16_TFLOPS), 4),
+                               "frac_of_bf16_peak": round(achieved / PEAK_BF16_TFLOPS, 4),
+                               "traffic": pmc_traffic(args.config, B, "gemm_nt_fp8*" if fp8 else "gemm_nt_mfma*"),
+                               "launches_per_step": round(launches_step, 1), "avg_launch_ms": round(avg_ms, 4),
+                               "gemm_ms_per_step": round(ms[dom] / max(ev_steps, 1), 3), "attention_ms_per_step": round(ms[1] / max(ev_steps, 1), 3),
+                               "bf16_gemm_ms_per_step": round(ms[0] / max(ev_steps, 1), 3),
+                               "event_steps": ev_steps,
+                               "event_pass": f"{ev_steps} single-stream steps after the timed region (HIP events on the launch stream; the rocprofv3 "
+                                             "summary under profiles/ is `bench.py --no-overlap`)",
+                               "attention_tflops": round(fl[1] / max(ms[1], 1e-9) / 1e9, 1)}
         if fp8:
             out["config"]["step_frac_of_fp8_peak"] = round(step_tflops / PEAK_FP8_TFLOPS, 4)
-        if world == 1 and not args.no_batch64_check and B != 64 and args.config in ("cfg3", "cfg4"):
+        if args.full and world == 1 and not args.no_batch64_check and B != 64 and args.config in ("cfg3", "cfg4"):
             # BASELINE.json north_star quotes its >= 40 % target "at batch 64 x 1024 residues": measured here, after
             # and outside the timed region that produces `value`, on the same model.
             pid64, pm64 = synth.protein_batch(99, 64, Tp)
@@ -482,7 +523,7 @@ def main():
             tf64 = f["total"] * 64 / dt64 / 1e12
             out["config"]["batch64_check"] = {"samples_per_s": round(64 / dt64, 2), "ms_per_step": round(dt64 * 1e3, 2),
                                               "step_tflops": round(tf64, 1), "frac_of_bf16_peak": round(tf64 / PEAK_BF16_TFLOPS, 4)}
-        if world == 1 and not args.no_batch64_check and args.config in ("cfg3", "cfg4"):
+        if args.full and world == 1 and not args.no_batch64_check and args.config in ("cfg3", "cfg4"):
             # BASELINE.json configs[4]'s one-GPU share (the same models with fp8-e4m3 tower GEMMs, batch 64 x 1024 residues) on the
             # model already built: driver-visible beside the bf16 headline.  Outside the timed region;
             # 1 settling step, then 3 timed on two streams, then 2 single-stream steps with every fp8 GEMM launch bracketed by HIP
@@ -525,7 +566,7 @@ def main():
                 out["config"]["cfg5_check"] = {"error": f"{type(e).__name__}: {e}"[:300]}
             finally:
                 model.set_gemm_dtype("model")
-        if world == 1 and not args.no_batch64_check and args.config in ("cfg3", "cfg4", "cfg5"):
+        if args.full and world == 1 and not args.no_batch64_check and args.config in ("cfg3", "cfg4", "cfg5"):
             # Ragged workload: 64 pairs with protein lengths from a clipped log-normal (median ~315
             # residues, the shape of UniProt lengths; crop at 1024), once as the padded 64 x T_max step and once
             # length-sorted (data.sort_batch_by_length) and cut into segments that each run at their own longest length
@@ -566,7 +607,7 @@ def main():
         if one_stream_rate is not None:
             # the same step on ONE stream, taken from the event pass above (includes the ~1.5 % cost of the event records)
             out["config"]["one_stream_check"] = {"samples_per_s": round(one_stream_rate, 2)}
-        if world == 1 and not args.no_generate_check and not args.no_batch64_check and args.config in ("cfg3", "cfg4"):
+        if args.full and world == 1 and not args.no_generate_check and not args.no_batch64_check and args.config in ("cfg3", "cfg4"):
             # `generate` of the same model (reference models/modeling_esm2llama_instruct.py:217-251): 8 prompts of T_p placeholders + 64
             # tokens, greedy; per decode step = (time of 33 new tokens - time of 1) / 32.  HBM-bound: every decoder weight + the KV cache
             # once per step.  Not part of `value`; a failure here is reported, never fatal to the headline.
@@ -576,7 +617,7 @@ def main():
                 out["config"]["generate_check"] = {"error": f"{type(e).__name__}: {e}"[:300]}
             finally:
                 model.train(not args.eval_mode)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # forward + loss only (eval mode): the quantity the CPU baseline below measures
             trainer.evaluate(batch)
             torch.cuda.synchronize()

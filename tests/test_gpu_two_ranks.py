@@ -123,7 +123,7 @@ def test_bench_py_four_ranks_rehearsal_on_one_gpu():
     """`python bench.py --gpus 4 --rehearse-shared-gpu --config cfg1`: bench.py's own launcher and rank logic at four ranks (the most
     this box's process guard leaves room for): one JSON line, n_gpus 4, global batch 4 x 4, a finite loss."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--rehearse-shared-gpu", "--config", "cfg1", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-batch64-check"]
+           "--full", "--no-cpu-baseline", "--no-batch64-check"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -139,7 +139,7 @@ def test_bench_py_two_ranks_rehearsal_on_one_gpu():
     """`python bench.py --gpus 2 --rehearse-shared-gpu`: bench.py's OWN multi-rank path (self-launch of the ranks, rank setup, barriers,
     max-over-ranks timing, rank 0's JSON line, the trainer's collectives) with both ranks on the one GPU over gloo."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-shared-gpu", "--config", "cfg2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-batch64-check"]
+           "--full", "--no-cpu-baseline", "--no-batch64-check"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]

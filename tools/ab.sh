@@ -4,6 +4,7 @@
 # tools/ab/libp2t_<VARIANT>.so through P2T_HIP_LIB); prints
 # samples/s, ms/step, GEMM ms/step, GEMM TF/s.  AB_ARGS = extra bench.py arguments (e.g. "--config cfg5")
 cd "$(dirname "$0")/.."
+AB_ARGS="--full $AB_ARGS"           # the GEMM / attention columns come from the roofline block of a --full run
 mkdir -p gpurun_out
 for rep in 1 2; do
   for v in "$@"; do

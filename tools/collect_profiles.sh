@@ -10,11 +10,11 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 if [ -z "$PMC_ONLY" ]; then
 echo "== bench $CFG"
-timeout -k 10 400 python3 bench.py --config $CFG --steps 10 --warmup 3 $EXTRA > $OUT/bench.json.log 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --config $CFG --steps 10 --warmup 3 --full $EXTRA > $OUT/bench.json.log 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
 tail -c 600 $OUT/bench.json.log; echo
 echo "== rocprofv3 kernel stats"
 # (--no-overlap: per-kernel durations on ONE stream, comparable with the roofline block's single-stream event pass)
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --config $CFG --steps 10 --warmup 3 --no-cpu-baseline --no-batch64-check --no-overlap $EXTRA > $OUT/bench_under_rocprof.json.log 2> $OUT/rocprof.err || { echo "rocprof stats failed"; tail -5 $OUT/rocprof.err; exit 1; }
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --config $CFG --steps 10 --warmup 3 --full --no-cpu-baseline --no-batch64-check --no-overlap $EXTRA > $OUT/bench_under_rocprof.json.log 2> $OUT/rocprof.err || { echo "rocprof stats failed"; tail -5 $OUT/rocprof.err; exit 1; }
 find $OUT/stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/kernel_stats.csv
 find $OUT/stats -name "*kernel_trace.csv" -delete                     # per-dispatch trace: large, the stats file is what is kept
 head -5 $OUT/kernel_stats.csv
