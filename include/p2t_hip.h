@@ -141,7 +141,8 @@ int p2t_rmsnorm_fp8(const float* x, int64_t ld_x, const float* w, float eps, voi
  * applied by the instruction), fp32 accumulate, the epilogues of p2t_gemm_nt (all but GELU_BWD).  A8 / W8: e4m3 bytes,
  * row strides lda / ldw in BYTES (multiples of 16), K % 128 == 0 with the padding zeroed; a_scale [M], w_scale [N] E8M0
  * bytes.  tile: 0 auto (the persistent four-wave kernel when the shape has no edge tiles, K % 256 == 0 and at least one tile per
- * CU; else the per-tile kernel), 4 = four-wave kernel required, 128 / 256 = per-tile kernel of that tile height.  P2T_EPI_GELU_FP8: out is e4m3 bytes [M, ldc bytes] (columns N up to
+ * CU; else the per-tile kernel), 4 = four-wave kernel required, 128 / 256 = per-tile kernel of that tile height; any other
+ * tile is P2T_ERR_ARG (the lab build adds its ablation / stamp forms).  P2T_EPI_GELU_FP8: out is e4m3 bytes [M, ldc bytes] (columns N up to
  * the next multiple of 128 zeroed), out_row_scale the E8M0 byte of every output row (an input: see p2t_layernorm_fp8). */
 int p2t_gemm_nt_fp8(const void* A, int64_t lda, const uint8_t* a_scale, const void* W, int64_t ldw, const uint8_t* w_scale,
                     const float* bias, void* out, int64_t ldc, void* z, int64_t M, int64_t N, int64_t K, int out_dtype,

@@ -263,12 +263,7 @@ int launch_attn_fwd64(const void* q, const void* k, const void* v, const uint8_t
                       int B, int T, int nh, int nkv, int d, int causal, float* lse, hipStream_t s) {
     P2T_REQUIRE(attn_fwd64_eligible(ld_out, T, nh, nkv, d, 64, 1), "attention(fwd64): unsupported shape d=%d heads %d/%d", d, nh, nkv);
     const int n_blocks = (int)(ceil_div(T, 256) * nh * B);
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus = n & ~7 ? n & ~7 : 8;
-    }
+    const int cus = cu_count() & ~7 ? cu_count() & ~7 : 8;
     const dim3 grid((unsigned)(n_blocks < cus ? n_blocks : cus));
     const int out_cols = (int)(round_up((int64_t)nh * d, 64) < ld_out ? round_up((int64_t)nh * d, 64) : ld_out);
 #ifdef P2T_LAB

@@ -40,6 +40,8 @@ void set_error(const char* fmt, ...);
         if (_r != P2T_OK) return _r;                                                          \
     } while (0)
 
+int cu_count();      // compute units of the current device (misc.hip: cached per device; 256 if the query fails)
+
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 static inline int64_t ceil_div(int64_t x, int64_t m) { return (x + m - 1) / m; }
 static inline size_t dtype_size(int dt) { return dt == P2T_BF16 ? 2 : 4; }

@@ -106,7 +106,7 @@ int gemm_nt(const GemmArgs& a, hipStream_t s) {
     }
     if (can_mfma && a.use_mfma != 0) {
         const int pi = prof_begin(s, 0, 2.0 * (double)a.M * (double)a.N * (double)a.K);
-        const int rc = launch_gemm_mfma(a.A, a.lda, a.W, a.ldw, a.M, (int)a.N, (int)a.K, n_cover, out_dtype, a.epilogue, ep, a.tile, a.fix_ws,
+        const int rc = launch_gemm_mfma(a.A, a.lda, a.W, a.ldw, a.M, (int)a.N, (int)a.K, n_cover, out_dtype, a.epilogue, ep, a.fix_ws,
                                         a.fix_bytes, a.fix_epoch, s);
         prof_end(s, pi);
         return rc;
@@ -153,6 +153,10 @@ extern "C" int p2t_prof_enable(int on) {
 
 #ifdef P2T_LAB
 namespace p2t { void set_cu_override(int n); }
+static bool lab_policy_known(int policy) {
+    return policy == 0 || policy == 1 || policy == 2 || policy == 3 || policy == 4 || policy == 5 || policy == 6 || policy == 7 || policy == 8 ||
+           policy == 9 || policy == 10 || policy == 12 || policy == 128 || policy == 256;
+}
 #endif
 extern "C" int p2t_set_gemm_policy(int policy) {
 #ifdef P2T_LAB
@@ -160,8 +164,7 @@ extern "C" int p2t_set_gemm_policy(int policy) {
         p2t::set_cu_override(policy - 1000);
         return P2T_OK;
     }
-    P2T_REQUIRE(policy == 0 || policy == 1 || policy == 2 || policy == 3 || policy == 4 || policy == 5 || policy == 6 || policy == 7 || policy == 8 || policy == 9 || policy == 10 || policy == 12 || policy == 128 || policy == 256,
-                "p2t_set_gemm_policy (lab build): unknown policy %d", policy);
+    P2T_REQUIRE(lab_policy_known(policy), "p2t_set_gemm_policy (lab build): unknown policy %d", policy);
 #else
     P2T_REQUIRE(policy == 0 || policy == 9, "p2t_set_gemm_policy: policy %d is not in the product library (0 = default, 9 = without the four-wave kernels; "
                 "the other launch forms are in the lab build, tools/lab/)", policy);
@@ -178,6 +181,25 @@ extern "C" int p2t_is_lab_build(void) {
     return 0;
 #endif
 }
+
+#ifdef P2T_LAB
+/* Lab build only: the launch plan that p2t_gemm_nt (dtype P2T_BF16, `policy` as for p2t_set_gemm_policy) or p2t_gemm_nt_fp8
+ * (dtype P2T_FP8, `policy` = its tile; 9 = tile 0 under p2t_set_gemm_policy(9)) would launch on `cus` compute units with
+ * `fix_bytes` of split-K fix-up workspace (0: none) -- without a launch or any other HIP call.  GELU is planned without dropout.
+ * out[5] = {form (p2t::GemmForm), grid, n_full, n_tail, half_tail}. */
+extern "C" int p2t_lab_gemm_plan(int dtype, int64_t M, int64_t N, int64_t K, int64_t n_cover, int64_t lda, int64_t ldw, int epilogue, int out_dtype,
+                                 int policy, int cus, size_t fix_bytes, int64_t* out) {
+    P2T_REQUIRE(out && M > 0 && N > 0 && K > 0 && n_cover >= N && N < (1 << 30) && K < (1 << 30) && n_cover < (1 << 30) && cus > 0,
+                "p2t_lab_gemm_plan: bad arguments");
+    P2T_REQUIRE(dtype == P2T_BF16 || dtype == P2T_FP8, "p2t_lab_gemm_plan: dtype %d", dtype);
+    P2T_REQUIRE(dtype == P2T_FP8 || lab_policy_known(policy), "p2t_lab_gemm_plan: unknown policy %d", policy);
+    const GemmFacts f = gemm_facts(M, (int)N, (int)K, (int)n_cover, lda, ldw, cus, fix_bytes);
+    const GemmPlan p = dtype == P2T_BF16 ? plan_gemm_mfma(f, epilogue, out_dtype, policy)
+                                         : plan_gemm_fp8(f, epilogue, out_dtype, policy == 9 ? 0 : policy, policy == 9);
+    out[0] = p.form; out[1] = p.grid; out[2] = p.n_full; out[3] = p.n_tail; out[4] = p.half_tail;
+    return P2T_OK;
+}
+#endif
 
 extern "C" int p2t_prof_collect(double* ms, int64_t* launches, double* flops, int n_classes) {
     P2T_REQUIRE(ms && launches && flops && n_classes >= 2 && n_classes <= 8, "p2t_prof_collect: bad arguments");
@@ -207,6 +229,13 @@ extern "C" size_t p2t_gemm_fix_workspace_bytes(void) { return gemm_fix_workspace
 extern "C" int p2t_gemm_nt_fp8(const void* A, int64_t lda, const uint8_t* a_scale, const void* W, int64_t ldw, const uint8_t* w_scale,
                                const float* bias, void* out, int64_t ldc, void* z, int64_t M, int64_t N, int64_t K, int out_dtype,
                                int epilogue, int accumulate, int tile, const uint8_t* out_row_scale, p2t_stream stream) {
+#ifdef P2T_LAB
+    // lab: the K-loop ablations (1001-1003) and the stamped four-wave kernel (2001-2005, 2011: 64 workgroups) of gemm_fp8.hip
+    P2T_REQUIRE(tile == 0 || tile == 4 || tile == 128 || tile == 256 || (tile >= 1001 && tile <= 1003) || (tile >= 2001 && tile <= 2005) || tile == 2011,
+                "p2t_gemm_nt_fp8 (lab build): unknown tile %d", tile);
+#else
+    P2T_REQUIRE(tile == 0 || tile == 4 || tile == 128 || tile == 256, "p2t_gemm_nt_fp8: tile %d is not 0, 4, 128 or 256", tile);
+#endif
     GemmArgs a{A, lda, W, ldw, bias, out, ldc, z, M, N, K, P2T_FP8, out_dtype, epilogue, accumulate, 1, -1, 0.f, 0, tile};
     a.a_scale = a_scale; a.w_scale = w_scale; a.out_row_scale = out_row_scale;
     return gemm_nt(a, (hipStream_t)stream);

@@ -49,7 +49,7 @@ __device__ __forceinline__ f32x4 mfma_bf16_pair(const v8i& a, const v8i& b, f32x
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8v, ahi), __builtin_bit_cast(bf16x8v, bhi), c, 0, 0, 0);
 }
 
-// ABL (lab only, results are garbage): 1 = no DMA in the K loop, 2 = no fragment reloads, 3 = neither -- what the loop costs
+// ABL (lab build only, results are garbage): 1 = no DMA in the K loop, 2 = no fragment reloads, 3 = neither -- what the loop costs
 // without its global->LDS traffic / its LDS reads (tools/microbench.py fp8abl)
 template <int MT, typename Epi, bool F8 = true, int ABL = 0>
 __global__ void __launch_bounds__(512)
@@ -248,65 +248,95 @@ template <typename Epi>
 constexpr bool kHasFp8W4 = std::is_same<Epi, EpiStore<bf16_t>>::value || std::is_same<Epi, EpiResid>::value || std::is_same<Epi, EpiSwiglu<bf16_t>>::value ||
                            std::is_same<Epi, EpiQkvRope<bf16_t>>::value || std::is_same<Epi, EpiGeluFp8>::value;
 
+// 256-row tiles unless 128-row tiles fill the chip better (the bf16 rule).  tile: 0 = four-wave persistent kernel when the shape
+// allows (not under p2t_set_gemm_policy(9)), else the per-tile kernel; 4 = four-wave kernel or GEMM_NONE; 128 / 256 = per-tile
+// eight-wave kernel of that height.  Lab build: 1001-1003 = K-loop ablation ABL of the 256-row kernel, 2001-2005 = stamped
+// four-wave kernel (variant tile - 2000), 2011 = variant 1 on 64 workgroups -- bf16 stores only.
+template <typename Epi>
+static GemmPlan plan_shape8(const GemmFacts& f, int tile, bool no_w4) {
+    if ((tile == 0 && !no_w4) || tile == 4) {
+        if (kHasFp8W4<Epi> && fp8_w4_fits(f.M, f.N, f.K, f.n_cover, f.lda, f.ldw, f.cus)) return {FP8_W4, f.cus, f.items};
+        if (tile == 4) return {};
+    }
+#ifdef P2T_LAB
+    if constexpr (std::is_same<Epi, EpiStore<bf16_t>>::value) {
+        if (tile >= 1001 && tile <= 1003) return {FP8_ABLATION, f.items, f.items, 0, 0, tile - 1000};
+        if (tile >= 2001 && tile <= 2005) return {FP8_STAMPS, f.cus, f.items, 0, 0, tile - 2000};
+        if (tile == 2011) return {FP8_STAMPS, 64, f.items, 0, 0, 1};
+    }
+#endif
+    const bool rows128 = tile == 128 || (tile != 256 && small_tiles_pay(f));
+    const int64_t g = rows128 ? ceil_div(f.M, 128) * f.tn : f.items;
+    return {rows128 ? FP8_TILE128 : FP8_TILE256, g, g};
+}
+
 template <typename Epi>
 static int launch_shape8(const void* A, int64_t lda, const uint8_t* a_scale, const void* W, int64_t ldw, const uint8_t* w_scale, int64_t M,
                          int N, int K, int n_cover, const EpiParams& ep, int tile, hipStream_t s) {
-    // 256-row tiles unless 128-row tiles fill the chip better (same rule as the bf16 per-tile kernels)
-    int cus = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-    // tile: 0 = four-wave persistent kernel when the shape allows, else the per-tile kernel below; 4 = four-wave kernel or
-    // error; 128 / 256 = per-tile eight-wave kernel of that height
-    if ((tile == 0 && get_gemm_policy() != 9) || tile == 4) {      // p2t_set_gemm_policy(9): without the four-wave forms (A/B, identity tests)
-        if constexpr (kHasFp8W4<Epi>) {
-            const int rc = launch_gemm_fp8_w4<Epi>(A, lda, a_scale, W, ldw, w_scale, M, N, K, n_cover, cus, ep, s);
-            if (rc != P2T_ERR_UNSUPPORTED) return rc;
-        }
-        if (tile == 4) {
-            set_error("gemm (fp8): the four-wave kernel needs M, N %% 256 == 0, K %% 256 == 0, K >= 512, at least one tile per CU and a bf16 / fp32-residual / e4m3 epilogue");
-            return P2T_ERR_UNSUPPORTED;
-        }
-    }
-    const int64_t tn = ceil_div(n_cover, 256), tm256 = ceil_div(M, 256), tm128 = ceil_div(M, 128);
-    const double cost256 = (double)ceil_div(tm256 * tn, cus);
-    const double cost128 = (double)ceil_div(tm128 * tn, cus) * 0.625 * 1.08;
+    const GemmFacts f = gemm_facts(M, N, K, n_cover, lda, ldw, cu_count(), 0);
+    const GemmPlan p = plan_shape8<Epi>(f, tile, get_gemm_policy() == 9);      // p2t_set_gemm_policy(9): without the four-wave forms
+    switch (p.form) {
+        case FP8_W4:
+            if constexpr (kHasFp8W4<Epi>) return launch_gemm_fp8_w4<Epi>(A, lda, a_scale, W, ldw, w_scale, M, N, K, n_cover, (int)p.grid, ep, s);
+            break;
+        case FP8_TILE256: return launch_cfg8<8, Epi>(A, lda, a_scale, W, ldw, w_scale, M, N, K, n_cover, ep, s);
+        case FP8_TILE128: return launch_cfg8<4, Epi>(A, lda, a_scale, W, ldw, w_scale, M, N, K, n_cover, ep, s);
 #ifdef P2T_LAB
-    if constexpr (std::is_same<Epi, EpiStore<bf16_t>>::value) {
-        if (tile >= 2001 && tile <= 2005) return launch_gemm_fp8_w4_diag(tile - 2000, A, lda, a_scale, W, ldw, w_scale, M, N, K, n_cover, cus, ep, s);
-        if (tile == 2011) return launch_gemm_fp8_w4_diag(1, A, lda, a_scale, W, ldw, w_scale, M, N, K, n_cover, 64, ep, s);      // stamps, 64 workgroups only
-    }
+        case FP8_STAMPS:
+            return launch_gemm_fp8_w4_diag(p.variant, A, lda, a_scale, W, ldw, w_scale, M, N, K, n_cover, (int)p.grid, ep, s);
+        case FP8_ABLATION:
+            if constexpr (std::is_same<Epi, EpiStore<bf16_t>>::value) {
+                const int tiles_m = (int)ceil_div(M, 256), tiles_n = (int)f.tn;
+                const dim3 grid((unsigned)p.grid);
+                const uint8_t *a = (const uint8_t*)A, *w = (const uint8_t*)W;
+                if (p.variant == 1) gemm_nt_fp8_kernel<8, Epi, true, 1><<<grid, 512, 0, s>>>(a, lda, a_scale, w, ldw, w_scale, M, N, K, tiles_m, tiles_n, n_cover, ep);
+                if (p.variant == 2) gemm_nt_fp8_kernel<8, Epi, true, 2><<<grid, 512, 0, s>>>(a, lda, a_scale, w, ldw, w_scale, M, N, K, tiles_m, tiles_n, n_cover, ep);
+                if (p.variant == 3) gemm_nt_fp8_kernel<8, Epi, true, 3><<<grid, 512, 0, s>>>(a, lda, a_scale, w, ldw, w_scale, M, N, K, tiles_m, tiles_n, n_cover, ep);
+                P2T_LAUNCH_CHECK();
+                return P2T_OK;
+            }
+            break;
 #endif
-    if constexpr (std::is_same<Epi, EpiStore<bf16_t>>::value) {
-        if (tile >= 1001 && tile <= 1003) {
-            const int tiles_m = (int)tm256, tiles_n = (int)tn;
-            const dim3 grid((unsigned)(tiles_m * tiles_n));
-            if (tile == 1001) gemm_nt_fp8_kernel<8, Epi, true, 1><<<grid, 512, 0, s>>>((const uint8_t*)A, lda, a_scale, (const uint8_t*)W, ldw, w_scale, M, N, K, tiles_m, tiles_n, n_cover, ep);
-            if (tile == 1002) gemm_nt_fp8_kernel<8, Epi, true, 2><<<grid, 512, 0, s>>>((const uint8_t*)A, lda, a_scale, (const uint8_t*)W, ldw, w_scale, M, N, K, tiles_m, tiles_n, n_cover, ep);
-            if (tile == 1003) gemm_nt_fp8_kernel<8, Epi, true, 3><<<grid, 512, 0, s>>>((const uint8_t*)A, lda, a_scale, (const uint8_t*)W, ldw, w_scale, M, N, K, tiles_m, tiles_n, n_cover, ep);
-            P2T_LAUNCH_CHECK();
-            return P2T_OK;
-        }
     }
-    if (tile == 256 || (tile != 128 && cost256 <= cost128)) return launch_cfg8<8, Epi>(A, lda, a_scale, W, ldw, w_scale, M, N, K, n_cover, ep, s);
-    return launch_cfg8<4, Epi>(A, lda, a_scale, W, ldw, w_scale, M, N, K, n_cover, ep, s);
+    set_error("gemm (fp8): the four-wave kernel needs M, N %% 256 == 0, K %% 256 == 0, K >= 512, at least one tile per CU and a bf16 / fp32-residual / e4m3 epilogue");
+    return P2T_ERR_UNSUPPORTED;
+}
+
+// The epilogue functor of (epilogue, out_dtype) on the fp8 path; fn(Epi{}) for it (GELU always in its dropout-capable form).
+template <typename Fn>
+static auto with_epilogue8(int epilogue, int out_dtype, Fn&& fn) -> decltype(fn(EpiResid{})) {
+    const bool ob = out_dtype == P2T_BF16;
+    switch (epilogue) {
+        case P2T_EPI_STORE: return ob ? fn(EpiStore<bf16_t>{}) : fn(EpiStore<float>{});
+        case P2T_EPI_GELU: return ob ? fn(EpiGelu<bf16_t, true>{}) : fn(EpiGelu<float, true>{});
+        case P2T_EPI_RESID: return fn(EpiResid{});
+        case P2T_EPI_SWIGLU: return ob ? fn(EpiSwiglu<bf16_t>{}) : fn(EpiSwiglu<float>{});
+        case P2T_EPI_STORE_F32: return fn(EpiF32{});
+        case P2T_EPI_QKV_ROPE: return ob ? fn(EpiQkvRope<bf16_t>{}) : fn(EpiQkvRope<float>{});
+        case P2T_EPI_GELU_FP8: return fn(EpiGeluFp8{});
+    }
+    return fn(nullptr);
 }
 
 int launch_gemm_fp8(const void* A, int64_t lda, const uint8_t* a_scale, const void* W, int64_t ldw, const uint8_t* w_scale, int64_t M, int N,
                     int K, int n_cover, int out_dtype, int epilogue, const EpiParams& ep, int tile, hipStream_t s) {
-    const bool ob = out_dtype == P2T_BF16;
-#define P2T_FP8_CASE(E) return launch_shape8<E>(A, lda, a_scale, W, ldw, w_scale, M, N, K, n_cover, ep, tile, s)
-    switch (epilogue) {
-        case P2T_EPI_STORE: if (ob) P2T_FP8_CASE(EpiStore<bf16_t>); else P2T_FP8_CASE(EpiStore<float>);
-        case P2T_EPI_GELU: { using GeluB = EpiGelu<bf16_t, true>; using GeluF = EpiGelu<float, true>; if (ob) P2T_FP8_CASE(GeluB); else P2T_FP8_CASE(GeluF); }
-        case P2T_EPI_RESID: P2T_FP8_CASE(EpiResid);
-        case P2T_EPI_SWIGLU: if (ob) P2T_FP8_CASE(EpiSwiglu<bf16_t>); else P2T_FP8_CASE(EpiSwiglu<float>);
-        case P2T_EPI_STORE_F32: P2T_FP8_CASE(EpiF32);
-        case P2T_EPI_QKV_ROPE: if (ob) P2T_FP8_CASE(EpiQkvRope<bf16_t>); else P2T_FP8_CASE(EpiQkvRope<float>);
-        case P2T_EPI_GELU_FP8: P2T_FP8_CASE(EpiGeluFp8);
-    }
-#undef P2T_FP8_CASE
-    set_error("gemm (fp8): unsupported epilogue %d", epilogue);
-    return P2T_ERR_ARG;
+    return with_epilogue8(epilogue, out_dtype, [&](auto e) {
+        using Epi = decltype(e);
+        if constexpr (std::is_same<Epi, std::nullptr_t>::value) {
+            set_error("gemm (fp8): unsupported epilogue %d", epilogue);
+            return P2T_ERR_ARG;
+        } else {
+            return launch_shape8<Epi>(A, lda, a_scale, W, ldw, w_scale, M, N, K, n_cover, ep, tile, s);
+        }
+    });
+}
+
+GemmPlan plan_gemm_fp8(const GemmFacts& f, int epilogue, int out_dtype, int tile, bool no_w4) {
+    return with_epilogue8(epilogue, out_dtype, [&](auto e) {
+        using Epi = decltype(e);
+        if constexpr (std::is_same<Epi, std::nullptr_t>::value) return GemmPlan{};
+        else return plan_shape8<Epi>(f, tile, no_w4);
+    });
 }
 
 #ifdef P2T_LAB

@@ -308,13 +308,17 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+bool fp8_w4_fits(int64_t M, int N, int K, int n_cover, int64_t lda, int64_t ldw, int grid) {
+    return M % 256 == 0 && N % 256 == 0 && n_cover == N && K % 256 == 0 && K >= 512 && (M / 256) * (N / 256) >= grid &&
+           (int64_t)256 * (lda > ldw ? lda : ldw) < ((int64_t)1 << 32);
+}
+
 // Persistent four-wave fp8 GEMM.  P2T_ERR_UNSUPPORTED when the shape is not eligible (the caller falls back to gemm_fp8.hip).
 template <typename Epi>
 int launch_gemm_fp8_w4(const void* A, int64_t lda, const uint8_t* a_scale, const void* W, int64_t ldw, const uint8_t* w_scale, int64_t M, int N,
                        int K, int n_cover, int grid, const EpiParams& ep, hipStream_t s) {
+    if (!fp8_w4_fits(M, N, K, n_cover, lda, ldw, grid)) return P2T_ERR_UNSUPPORTED;
     const int64_t items = (M / 256) * (N / 256);
-    if (M % 256 || N % 256 || n_cover != N || K % 256 || K < 512 || items < grid || (int64_t)256 * (lda > ldw ? lda : ldw) >= ((int64_t)1 << 32))
-        return P2T_ERR_UNSUPPORTED;
     gemm_nt_fp8_w4_kernel<Epi><<<dim3((unsigned)grid), 256, 0, s>>>((const uint8_t*)A, lda, a_scale, (const uint8_t*)W, ldw, w_scale, M, N, K,
                                                                   (int)(M / 256), N / 256, (int)items, ep);
     P2T_LAUNCH_CHECK();

@@ -483,42 +483,46 @@ constexpr bool kHasW4Pairs = std::is_same<Epi, EpiResid>::value || std::is_same<
 template <typename Epi>
 constexpr bool kHasW4 = std::is_same<Epi, EpiStore<bf16_t>>::value || std::is_same<Epi, EpiStore<float>>::value || std::is_same<Epi, EpiResid>::value ||
                         std::is_same<Epi, EpiQkvRope<bf16_t>>::value || std::is_same<Epi, EpiGelu<bf16_t>>::value || std::is_same<Epi, EpiSwiglu<bf16_t>>::value;
+// the epilogue code / output type under which launch_gemm_w4 (one tile per block) takes Epi; -1: it has no such form
+template <typename Epi>
+constexpr int kW4TileCode = std::is_same<Epi, EpiStore<bf16_t>>::value || std::is_same<Epi, EpiStore<float>>::value ? P2T_EPI_STORE
+                            : std::is_same<Epi, EpiResid>::value                                                     ? P2T_EPI_RESID
+                            : std::is_same<Epi, EpiGelu<bf16_t>>::value                                              ? P2T_EPI_GELU
+                            : std::is_same<Epi, EpiQkvRope<bf16_t>>::value                                           ? P2T_EPI_QKV_ROPE
+                                                                                                                      : -1;
+template <typename Epi>
+constexpr int kW4TileOut = std::is_same<Epi, EpiResid>::value || std::is_same<Epi, EpiStore<float>>::value ? P2T_F32 : P2T_BF16;
 
-template <int MT, typename Epi>
-static int launch_cfg(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int N, int K, int n_cover,
-                      const EpiParams& ep, hipStream_t s) {
-    constexpr int BM = 2 * MT * 16;
-    const int tiles_m = (int)ceil_div(M, BM), tiles_n = (int)ceil_div(n_cover, 256);
-    gemm_nt_mfma_kernel<MT, Epi><<<dim3((unsigned)(tiles_m * tiles_n)), 512, 0, s>>>(
-        (const bf16_t*)A, lda, (const bf16_t*)W, ldw, M, N, K, tiles_m, tiles_n, n_cover, ep);
-    P2T_LAUNCH_CHECK();
-    return P2T_OK;
+// What the launch policy knows about an epilogue
+struct EpiTraits {
+    bool rmw;           // read-modify-write of the output (the residual stream)
+    bool w4;            // has the four-wave persistent form
+    bool w4_pairs;      // has the four-wave split-K pair form
+    bool w4_tile;       // the default policy runs it on the four-wave per-tile form at three quarters of a round
+};
+template <typename Epi>
+constexpr EpiTraits kEpiTraits = {Epi::kRmw, kHasW4<Epi>, kHasW4Pairs<Epi>,
+                                  std::is_same<Epi, EpiQkvRope<bf16_t>>::value || std::is_same<Epi, EpiStore<bf16_t>>::value};
+
+GemmFacts gemm_facts(int64_t M, int N, int K, int n_cover, int64_t lda, int64_t ldw, int cus, size_t fix_bytes) {
+    GemmFacts f;
+    f.M = M; f.lda = lda; f.ldw = ldw; f.N = N; f.K = K; f.n_cover = n_cover; f.cus = cus; f.fix_bytes = fix_bytes;
+    f.ns = K >> 5;
+    f.tn = ceil_div(n_cover, 256);
+    f.items = ceil_div(M, 256) * f.tn;
+    f.rem = f.items % cus;
+    f.whole_tiles = M % 256 == 0 && N % 256 == 0 && n_cover == N;
+    f.stride32 = (int64_t)256 * (lda > ldw ? lda : ldw) * 2 < ((int64_t)1 << 32);
+    return f;
 }
 
 // measured (profiles/r01_microbench_v2.log): a 128-row tile takes ~0.62 of a 256-row tile.  A mixed grid (whole
 // rounds of 256-row tiles + the leftover rows as 128-row tiles) was tried against the 2.5-round N = 2560 GEMMs and
-// measured 5-13 % SLOWER than plain 256-row tiles, so it is not used.
-constexpr double kSmallTileCost = 0.625;
-
-// Compute units of the current device (256 on MI355X; fewer on a partitioned one): the persistent grid is one block per
-// CU and the "round" arithmetic of the launch policy counts in CUs.
-#ifdef P2T_LAB
-static std::atomic<int> g_cu_override{0};       // lab build: p2t_set_gemm_policy(1000 + n) makes the launch policy count n compute units
-void set_cu_override(int n) { g_cu_override.store(n, std::memory_order_relaxed); }
-#endif
-static int cu_count() {
-#ifdef P2T_LAB
-    if (const int o = g_cu_override.load(std::memory_order_relaxed)) return o;
-#endif
-    static int cached[16] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    if (cached[dev] == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cached[dev] = n;
-    }
-    return cached[dev];
+// measured 5-13 % SLOWER than plain 256-row tiles, so it is not used.  The fp8 per-tile kernels follow the same rule.
+bool small_tiles_pay(const GemmFacts& f) {
+    const double cost256 = (double)ceil_div(f.items, f.cus);
+    const double cost128 = (double)ceil_div(ceil_div(f.M, 128) * f.tn, f.cus) * 0.625 * 1.08;
+    return cost256 > cost128;
 }
 
 // Launch-form override (p2t_set_gemm_policy): 0 = the measured default policy below; 9 = the same policy without the four-wave
@@ -535,141 +539,207 @@ constexpr size_t kFixHeader = 2048, kFixSlab = 256 * 256 * sizeof(float);
 size_t gemm_fix_workspace_bytes() { return kFixHeader + 128 * kFixSlab; }
 size_t gemm_fix_header_bytes() { return kFixHeader; }
 
-static bool split_fix(SplitFix& f, void* fix_ws, size_t fix_bytes, unsigned fix_epoch, int64_t n_tiles) {
-    if (!fix_ws || fix_bytes < kFixHeader + (size_t)n_tiles * kFixSlab) return false;
+static bool fix_fits(const GemmFacts& f, int64_t n_tiles) { return f.fix_bytes >= kFixHeader + (size_t)n_tiles * kFixSlab; }
+
+static SplitFix split_fix(void* fix_ws, unsigned fix_epoch) {
+    SplitFix f{};
     f.flag = (unsigned*)fix_ws;
     f.timeout = fault_word_ptr();
     f.slab = (float*)((char*)fix_ws + kFixHeader);
     f.epoch = fix_epoch;
-    return f.timeout != nullptr;
+    return f;
+}
+
+// ---- the default launch policy.  Every threshold is a measurement (profiles/r01_microbench_v*.log, r02_microbench_w4.log):
+//   (1) shapes without edge tiles and at least one whole round of 256 x 256 tiles on the CUs: PERSISTENT kernels (one block per
+//       CU walks the tile list; the K loops of consecutive tiles form one stream of stages) -- the four-wave kernel for the
+//       epilogues it is built for, else the eight-wave one.  A partial last round runs as split-K pairs when K is long enough
+//       for half a K loop to outweigh the slab hand-off (K >= 6144), else on the eight-wave kernel as 128-row halves, and as
+//       whole tiles otherwise;
+//   (2) smaller grids: three quarters of a round or more -> four-wave kernel, one tile per block; at most half a round with
+//       K >= 8192 -> every tile as a split-K pair on two CUs; otherwise the eight-wave per-tile kernel at the tile height
+//       (256 / 128 rows) that fills the chip better, with split-K tails when they pay.
+
+// the persistent kernels' precondition: no edge tiles, at least one whole round, K a multiple of 128 and at least 384
+static bool persist_fits(const GemmFacts& f) { return f.whole_tiles && f.items >= f.cus && (f.ns & 3) == 0 && f.ns >= 12; }
+
+// (1) whole rounds, or long K, or many rounds (QKV: +13 %), or a read-modify-write of the residual stream (o-proj, 2.5 rounds:
+// with the stream cold in HBM, as inside a step, the undrained stores win 0.4 % of the step; with it hot in the Infinity Cache,
+// as in the micro-benchmark, the per-tile kernel is 6 % ahead)
+static bool persist_pays(const GemmFacts& f, const EpiTraits& t) {
+    return persist_fits(f) && (f.rem == 0 || f.ns >= 128 || f.items >= 4 * f.cus || t.rmw);
+}
+
+// eight-wave persistent kernel.  A partial last round of at most half a round (and 128 tiles): as split-K pairs if `pairs` and
+// the fix-up fits, else as 128-row halves if `halves` (no hand-off: one 128 x 256 tile time instead of a whole one), else whole
+static GemmPlan persist8(const GemmFacts& f, bool pairs, bool halves) {
+    GemmPlan p{GEMM_PERSIST, f.cus, f.items};
+    if (f.rem == 0 || 2 * f.rem > f.cus || f.rem > 128) return p;
+    pairs = pairs && (f.ns & 7) == 0 && fix_fits(f, f.rem);
+    if (pairs || halves) {
+        p.n_full = f.items - f.rem;
+        p.n_tail = f.rem;
+        p.half_tail = !pairs;
+    }
+    return p;
+}
+
+// four-wave persistent kernel; a partial last round of at most half a round as split-K pairs in the same stream if `pairs` and
+// the fix-up fits
+static GemmPlan persist4(const GemmFacts& f, bool pairs, int sched = 1) {
+    const int64_t t = pairs && f.rem > 0 && 2 * f.rem <= f.cus && fix_fits(f, f.rem) ? f.rem : 0;
+    const int64_t n = f.items - t;
+    return {GEMM_W4_PERSIST, n < f.cus ? n : f.cus, n, t, 0, sched};
+}
+
+static GemmPlan per_tile8(const GemmFacts& f, bool rows128) {
+    const int64_t g = rows128 ? ceil_div(f.M, 128) * f.tn : f.items;
+    return {rows128 ? GEMM_TILE128 : GEMM_TILE256, g, g};
+}
+
+static bool pairs_pay(const GemmFacts& f) { return f.ns >= 192; }     // split-K pairs of a partial persistent round: K >= 6144
+
+static GemmPlan plan_persist(const GemmFacts& f, const EpiTraits& t, bool no_w4) {
+    // the fix-up tiles run un-overlapped after the tile loop (~50 us): it pays when half a tile time is well above that.
+    // Four-wave, measured cold (profiles/r02_microbench_w4.log): FFN-down K = 10240: 752 us as pairs vs 821 as whole tiles;
+    // QKV K = 2560: 496 vs 521 (an extra round of whole tiles is cheaper than the second ring fill + the slab).  Eight-wave:
+    // K = 10240 +7 %, K = 4096 (SwiGLU GEMM of the text tower, 3.5 rounds) -7 %; the 128-row halves for shorter K, measured cold:
+    // QKV 7.5 rounds -4.6 %, o-proj 2.5 rounds -3.7 %.
+    if (t.w4 && !no_w4 && f.stride32) return persist4(f, pairs_pay(f));
+    return persist8(f, pairs_pay(f), true);
+}
+
+static GemmPlan plan_per_tile(const GemmFacts& f, const EpiTraits& t, bool no_w4) {
+    const int64_t items = f.items;
+    // QKV of the text tower at 2 048 tokens (192 tiles): 1 319 TFLOP/s vs 1 163 for the eight-wave per-tile kernel; below that
+    // fill, or with the fp32 read-modify-write epilogue, the eight-wave forms stay ahead
+    if (t.w4_tile && !no_w4 && f.whole_tiles && items < f.cus && items * 4 >= f.cus * 3 && f.K % 128 == 0 && f.K >= 256 && f.stride32)
+        return {GEMM_W4_TILE, items, items};
+    // at most half a round and a long K: every tile as two K halves on two CUs (half a tile time + the slab hand-off) instead of a
+    // full round of 128-row tiles.  FFN-down of the text tower at 2 048 tokens (128 tiles, K = 14 336): 185 us on the four-wave
+    // kernel vs 204 for the eight-wave pair kernel; at K = 4 096 (o-proj) the slab hand-off costs more than it saves (81 vs 73 us)
+    const bool half_round_long_k = items * 2 <= f.cus && items * 8 >= f.cus * 3 && f.K >= 8192 && fix_fits(f, items);
+    if (t.w4_pairs && !no_w4 && f.whole_tiles && half_round_long_k && f.K % 128 == 0 && f.stride32) return {GEMM_W4_PAIRS, 2 * items, 0, items};
+    if (half_round_long_k) return {GEMM_SPLITK, 2 * items, 0, items};
+    if (small_tiles_pay(f)) return per_tile8(f, true);
+    // split-K tail: the tiles of a partial last round (at most half a round) as two K halves each; measured
+    // (profiles/r01_microbench_v3.log): pays for long K (FFN-down +8 %) or many full rounds (QKV +5 %), not at K = 2560 with two
+    // full rounds (o-proj)
+    const int64_t n_full = (items / f.cus) * f.cus, n_tail = items - n_full;
+    if (n_full > 0 && n_tail > 0 && n_tail <= 128 && (f.ns >= 128 || (f.ns >= 64 && n_full >= 4 * f.cus)) && fix_fits(f, n_tail))
+        return {GEMM_SPLITK, n_full + 2 * n_tail, n_full, n_tail};
+    return per_tile8(f, false);
+}
+
+static GemmPlan plan_default(const GemmFacts& f, const EpiTraits& t, bool no_w4) {
+    return persist_pays(f, t) ? plan_persist(f, t, no_w4) : plan_per_tile(f, t, no_w4);
 }
 
 #ifdef P2T_LAB
 #include "../../tools/lab/gemm_forms_lab.h"
 #endif
 
-// The default launch policy.  Every threshold is a measurement (profiles/r01_microbench_v*.log, r02_microbench_w4.log):
-//   (1) shapes without edge tiles and at least one whole round of 256 x 256 tiles on the CUs: PERSISTENT kernels (one block per
-//       CU walks the tile list; the K loops of consecutive tiles form one stream of stages) -- the four-wave kernel for the
-//       epilogues it is built for, else the eight-wave one.  A partial last round runs as split-K pairs when K is long enough
-//       for half a K loop to outweigh the slab hand-off (four-wave: K >= 6144 inside the same kernel; eight-wave: the same
-//       threshold, else as 128-row halves), and as whole tiles otherwise;
-//   (2) smaller grids: three quarters of a round or more -> four-wave kernel, one tile per block; at most half a round with
-//       K >= 8192 -> every tile as a split-K pair on two CUs; otherwise the eight-wave per-tile kernel at the tile height
-//       (256 / 128 rows) that fills the chip better, with split-K tails when they pay.
+template <typename Epi>
+static GemmPlan plan_shape(const GemmFacts& f, int policy) {
+#ifdef P2T_LAB
+    if (policy != 0 && policy != 9) return plan_lab<Epi>(f, policy);
+#endif
+    return plan_default(f, kEpiTraits<Epi>, policy == 9);
+}
+
+// Compute units the launch policy counts (the lab build can override them: p2t_set_gemm_policy(1000 + n))
+static int policy_cus() {
+#ifdef P2T_LAB
+    if (const int o = lab_cu_override()) return o;
+#endif
+    return cu_count();
+}
+
 template <typename Epi>
 static int launch_shape(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int N, int K, int n_cover,
-                        const EpiParams& ep, int tile, void* fix_ws, size_t fix_bytes, unsigned fix_epoch, hipStream_t s) {
-    const int policy = tile ? tile : g_gemm_policy.load(std::memory_order_relaxed);
+                        const EpiParams& ep, void* fix_ws, size_t fix_bytes, unsigned fix_epoch, hipStream_t s) {
+    const GemmFacts f = gemm_facts(M, N, K, n_cover, lda, ldw, policy_cus(), fix_ws && fault_word_ptr() ? fix_bytes : 0);
+    const GemmPlan p = plan_shape<Epi>(f, get_gemm_policy());
+    const SplitFix fix = p.n_tail > 0 && !p.half_tail ? split_fix(fix_ws, fix_epoch) : SplitFix{};
+    const bf16_t* a = (const bf16_t*)A;
+    const bf16_t* w = (const bf16_t*)W;
+    const dim3 grid((unsigned)p.grid);
+    const int tm256 = (int)ceil_div(M, 256), tn = (int)f.tn;
+    auto no_form = [&] {
+        set_error("gemm: launch form %d does not exist for this epilogue", p.form);
+        return P2T_ERR_UNSUPPORTED;
+    };
+    switch (p.form) {
+        case GEMM_TILE128:
+            gemm_nt_mfma_kernel<4, Epi><<<grid, 512, 0, s>>>(a, lda, w, ldw, M, N, K, (int)ceil_div(M, 128), tn, n_cover, ep);
+            break;
+        case GEMM_TILE256:
+            gemm_nt_mfma_kernel<8, Epi><<<grid, 512, 0, s>>>(a, lda, w, ldw, M, N, K, tm256, tn, n_cover, ep);
+            break;
+        case GEMM_SPLITK:
+            gemm_nt_mfma_tail_kernel<Epi><<<grid, 512, 0, s>>>(a, lda, w, ldw, M, N, K, tm256, tn, (int)p.n_full, (int)p.n_tail, n_cover, ep, fix);
+            break;
+        case GEMM_PERSIST:
+            gemm_nt_mfma_persist_kernel<Epi><<<grid, 512, 0, s>>>(a, lda, w, ldw, M, N, K, tm256, tn, (int)p.n_full, (int)p.n_tail, p.half_tail,
+                                                                  n_cover, ep, fix);
+            break;
+        case GEMM_W4_TILE:
+            return launch_gemm_w4(A, lda, W, ldw, M, N, K, n_cover, kW4TileOut<Epi>, kW4TileCode<Epi>, ep, s);
+        case GEMM_W4_PERSIST:
+            if constexpr (kHasW4<Epi>) return launch_gemm_w4_persist<Epi>(A, lda, W, ldw, M, N, K, (int)p.n_full, (int)p.n_tail, f.cus, ep, fix, s, p.variant);
+            else return no_form();
+        case GEMM_W4_PAIRS:
+            if constexpr (kHasW4Pairs<Epi>) return launch_gemm_w4_pairs<Epi>(A, lda, W, ldw, M, N, K, (int)p.n_tail, ep, fix, s);
+            else return no_form();
 #ifdef P2T_LAB
-    if (policy != 0 && policy != 9) return launch_shape_lab<Epi>(A, lda, W, ldw, M, N, K, n_cover, ep, policy, fix_ws, fix_bytes, fix_epoch, s);
+        case GEMM_K64:
+            return launch_gemm_bf16_k64(A, lda, W, ldw, M, N, K, n_cover, kK64Out<Epi>, kK64Code<Epi>, ep, s);
 #endif
-    const bool no_w4 = policy == 9;
-    const int kCUs = cu_count();
-    const int ns = K >> 5;
-    const int64_t tn = ceil_div(n_cover, 256), tm256 = ceil_div(M, 256), tm128 = ceil_div(M, 128);
-    const int64_t items = tm256 * tn, rem = items % kCUs;
-    const bool whole_tiles = M % 256 == 0 && N % 256 == 0 && n_cover == N;
-    const bool stride32 = (int64_t)256 * (lda > ldw ? lda : ldw) * 2 < ((int64_t)1 << 32);     // four-wave kernels: 32-bit lane offsets
-    // ---- (1) persistent kernels
-    // whole rounds, or long K, or many rounds (QKV: +13 %), or a read-modify-write of the residual stream (o-proj, 2.5 rounds:
-    // with the stream cold in HBM, as inside a step, the undrained stores win)
-    if (whole_tiles && items >= kCUs && (ns & 3) == 0 && ns >= 12 && (rem == 0 || ns >= 128 || items >= 4 * kCUs || Epi::kRmw)) {
-        const bool pairs_fit = rem > 0 && 2 * rem <= kCUs;
-        if constexpr (kHasW4<Epi>) {
-            if (!no_w4 && stride32) {
-                // FFN-down K = 10240: 752 us as pairs vs 821 as whole tiles; QKV K = 2560: 521 vs 496
-                SplitFix f4{};
-                const int64_t t4 = pairs_fit && ns >= 192 && split_fix(f4, fix_ws, fix_bytes, fix_epoch, rem) ? rem : 0;
-                return launch_gemm_w4_persist<Epi>(A, lda, W, ldw, M, N, K, (int)(items - t4), (int)t4, kCUs, ep, f4, s);
-            }
-        }
-        SplitFix fix{};
-        int64_t n_full = items, n_tail = 0;
-        int half_tail = 0;
-        if (pairs_fit && rem <= 128 && (ns & 7) == 0 && ns >= 192 && split_fix(fix, fix_ws, fix_bytes, fix_epoch, rem)) {
-            n_full = items - rem;
-            n_tail = rem;
-        } else if (pairs_fit && rem <= 128) {           // K too short for split-K to pay: the leftover tiles as 128-row halves
-            n_full = items - rem;
-            n_tail = rem;
-            half_tail = 1;
-        }
-        gemm_nt_mfma_persist_kernel<Epi><<<dim3(kCUs), 512, 0, s>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, M, N, K, (int)tm256, (int)tn,
-                                                                  (int)n_full, (int)n_tail, half_tail, n_cover, ep, fix);
-        P2T_LAUNCH_CHECK();
-        return P2T_OK;
+        default:
+            return no_form();
     }
-    // ---- (2) less than a round, or edge tiles
-    if constexpr (std::is_same<Epi, EpiQkvRope<bf16_t>>::value || std::is_same<Epi, EpiStore<bf16_t>>::value) {
-        // QKV of the text tower at 2 048 tokens (192 tiles): 1 319 TFLOP/s vs 1 163 for the eight-wave per-tile kernel; below that
-        // fill, or with the fp32 read-modify-write epilogue, the eight-wave forms stay ahead
-        if (!no_w4 && whole_tiles && items < kCUs && items * 4 >= kCUs * 3 && K % 128 == 0 && K >= 256) {
-            const int rc = launch_gemm_w4(A, lda, W, ldw, M, N, K, n_cover, P2T_BF16, std::is_same<Epi, EpiQkvRope<bf16_t>>::value ? P2T_EPI_QKV_ROPE : P2T_EPI_STORE, ep, s);
-            if (rc != P2T_ERR_UNSUPPORTED) return rc;
-        }
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
+// The epilogue functor of (epilogue, out_dtype); fn(Epi{}) for it.  GELU with dropout or a saved pre-activation takes the
+// dropout form.
+template <typename Fn>
+static auto with_epilogue(int epilogue, int out_dtype, bool gelu_drop, Fn&& fn) -> decltype(fn(EpiResid{})) {
+    const bool ob = out_dtype == P2T_BF16;
+    switch (epilogue) {
+        case P2T_EPI_STORE: return ob ? fn(EpiStore<bf16_t>{}) : fn(EpiStore<float>{});
+        case P2T_EPI_GELU:
+            if (gelu_drop) return ob ? fn(EpiGelu<bf16_t, true>{}) : fn(EpiGelu<float, true>{});
+            return ob ? fn(EpiGelu<bf16_t>{}) : fn(EpiGelu<float>{});
+        case P2T_EPI_RESID: return fn(EpiResid{});
+        case P2T_EPI_SWIGLU: return ob ? fn(EpiSwiglu<bf16_t>{}) : fn(EpiSwiglu<float>{});
+        case P2T_EPI_STORE_F32: return fn(EpiF32{});
+        case P2T_EPI_GELU_BWD: return ob ? fn(EpiGeluBwd<bf16_t>{}) : fn(EpiGeluBwd<float>{});
+        case P2T_EPI_QKV_ROPE: return ob ? fn(EpiQkvRope<bf16_t>{}) : fn(EpiQkvRope<float>{});
     }
-    const bool half_round_long_k = items * 2 <= kCUs && items * 8 >= kCUs * 3 && K >= 8192;
-    if constexpr (kHasW4Pairs<Epi>) {
-        // FFN-down of the text tower at 2 048 tokens (128 tiles, K = 14 336): 185 vs 204 us for the eight-wave pair kernel; at
-        // K = 4 096 (o-proj) the slab hand-off costs more than it saves (81 vs 73 us)
-        SplitFix f4{};
-        if (!no_w4 && whole_tiles && half_round_long_k && K % 128 == 0 && stride32 && split_fix(f4, fix_ws, fix_bytes, fix_epoch, items))
-            return launch_gemm_w4_pairs<Epi>(A, lda, W, ldw, M, N, K, (int)items, ep, f4, s);
-    }
-    SplitFix fix{};
-    if (half_round_long_k && split_fix(fix, fix_ws, fix_bytes, fix_epoch, items)) {
-        // every tile as two K halves on two CUs (half a tile time + the slab hand-off) instead of a full round of 128-row tiles
-        gemm_nt_mfma_tail_kernel<Epi><<<dim3((unsigned)(2 * items)), 512, 0, s>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, M, N, K, (int)tm256,
-                                                                                 (int)tn, 0, (int)items, n_cover, ep, fix);
-        P2T_LAUNCH_CHECK();
-        return P2T_OK;
-    }
-    const double cost256 = (double)ceil_div(items, kCUs);
-    const double cost128 = (double)ceil_div(tm128 * tn, kCUs) * kSmallTileCost * 1.08;
-    if (cost256 > cost128) return launch_cfg<4, Epi>(A, lda, W, ldw, M, N, K, n_cover, ep, s);
-    // split-K tail: the tiles of a partial last round (at most half a round) as two K halves each; pays for long K (FFN-down
-    // +8 %) or many full rounds (QKV +5 %), not at K = 2560 with two full rounds (o-proj)
-    const int64_t n_full = (items / kCUs) * kCUs, n_tail = items - n_full;
-    if (n_full > 0 && n_tail > 0 && n_tail <= 128 && (ns >= 128 || (ns >= 64 && n_full >= 4 * kCUs)) && split_fix(fix, fix_ws, fix_bytes, fix_epoch, n_tail)) {
-        gemm_nt_mfma_tail_kernel<Epi><<<dim3((unsigned)(n_full + 2 * n_tail)), 512, 0, s>>>((const bf16_t*)A, lda, (const bf16_t*)W, ldw, M, N, K,
-                                                                                            (int)tm256, (int)tn, (int)n_full, (int)n_tail, n_cover, ep, fix);
-        P2T_LAUNCH_CHECK();
-        return P2T_OK;
-    }
-    return launch_cfg<8, Epi>(A, lda, W, ldw, M, N, K, n_cover, ep, s);
+    return fn(nullptr);
 }
 
 int launch_gemm_mfma(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int N, int K, int n_cover,
-                     int out_dtype, int epilogue, const EpiParams& ep, int tile, void* fix_ws, size_t fix_bytes,
-                     unsigned fix_epoch, hipStream_t s) {
-    const bool ob = out_dtype == P2T_BF16;
-    switch (epilogue) {
-        case P2T_EPI_STORE:
-            return ob ? launch_shape<EpiStore<bf16_t>>(A, lda, W, ldw, M, N, K, n_cover, ep, tile, fix_ws, fix_bytes, fix_epoch, s)
-                      : launch_shape<EpiStore<float>>(A, lda, W, ldw, M, N, K, n_cover, ep, tile, fix_ws, fix_bytes, fix_epoch, s);
-        case P2T_EPI_GELU:
-            if (ep.drop_p > 0.f || ep.z)
-                return ob ? launch_shape<EpiGelu<bf16_t, true>>(A, lda, W, ldw, M, N, K, n_cover, ep, tile, fix_ws, fix_bytes, fix_epoch, s)
-                          : launch_shape<EpiGelu<float, true>>(A, lda, W, ldw, M, N, K, n_cover, ep, tile, fix_ws, fix_bytes, fix_epoch, s);
-            return ob ? launch_shape<EpiGelu<bf16_t>>(A, lda, W, ldw, M, N, K, n_cover, ep, tile, fix_ws, fix_bytes, fix_epoch, s)
-                      : launch_shape<EpiGelu<float>>(A, lda, W, ldw, M, N, K, n_cover, ep, tile, fix_ws, fix_bytes, fix_epoch, s);
-        case P2T_EPI_RESID:
-            return launch_shape<EpiResid>(A, lda, W, ldw, M, N, K, n_cover, ep, tile, fix_ws, fix_bytes, fix_epoch, s);
-        case P2T_EPI_SWIGLU:
-            return ob ? launch_shape<EpiSwiglu<bf16_t>>(A, lda, W, ldw, M, N, K, n_cover, ep, tile, fix_ws, fix_bytes, fix_epoch, s)
-                      : launch_shape<EpiSwiglu<float>>(A, lda, W, ldw, M, N, K, n_cover, ep, tile, fix_ws, fix_bytes, fix_epoch, s);
-        case P2T_EPI_STORE_F32:
-            return launch_shape<EpiF32>(A, lda, W, ldw, M, N, K, n_cover, ep, tile, fix_ws, fix_bytes, fix_epoch, s);
-        case P2T_EPI_GELU_BWD:
-            return ob ? launch_shape<EpiGeluBwd<bf16_t>>(A, lda, W, ldw, M, N, K, n_cover, ep, tile, fix_ws, fix_bytes, fix_epoch, s)
-                      : launch_shape<EpiGeluBwd<float>>(A, lda, W, ldw, M, N, K, n_cover, ep, tile, fix_ws, fix_bytes, fix_epoch, s);
-        case P2T_EPI_QKV_ROPE:
-            return ob ? launch_shape<EpiQkvRope<bf16_t>>(A, lda, W, ldw, M, N, K, n_cover, ep, tile, fix_ws, fix_bytes, fix_epoch, s)
-                      : launch_shape<EpiQkvRope<float>>(A, lda, W, ldw, M, N, K, n_cover, ep, tile, fix_ws, fix_bytes, fix_epoch, s);
-    }
-    set_error("gemm: unknown epilogue %d", epilogue);
-    return P2T_ERR_ARG;
+                     int out_dtype, int epilogue, const EpiParams& ep, void* fix_ws, size_t fix_bytes, unsigned fix_epoch, hipStream_t s) {
+    return with_epilogue(epilogue, out_dtype, ep.drop_p > 0.f || ep.z, [&](auto e) {
+        using Epi = decltype(e);
+        if constexpr (std::is_same<Epi, std::nullptr_t>::value) {
+            set_error("gemm: unknown epilogue %d", epilogue);
+            return P2T_ERR_ARG;
+        } else {
+            return launch_shape<Epi>(A, lda, W, ldw, M, N, K, n_cover, ep, fix_ws, fix_bytes, fix_epoch, s);
+        }
+    });
+}
+
+GemmPlan plan_gemm_mfma(const GemmFacts& f, int epilogue, int out_dtype, int policy) {
+    return with_epilogue(epilogue, out_dtype, false, [&](auto e) {
+        using Epi = decltype(e);
+        if constexpr (std::is_same<Epi, std::nullptr_t>::value) return GemmPlan{};
+        else return plan_shape<Epi>(f, policy);
+    });
 }
 
 }  // namespace p2t

@@ -36,8 +36,8 @@ int launch_qk_norm_rope(const void* qkv, int64_t ldq, const float* cs, const flo
 int launch_gemm_simple(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int N, int K, int n_cover, int dtype,
                        int out_dtype, int epilogue, const EpiParams& ep, hipStream_t s);
 int launch_gemm_mfma(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int N, int K, int n_cover,
-                     int out_dtype, int epilogue, const EpiParams& ep, int tile, void* fix_ws, size_t fix_bytes,
-                     unsigned fix_epoch, hipStream_t s);
+                     int out_dtype, int epilogue, const EpiParams& ep, void* fix_ws, size_t fix_bytes, unsigned fix_epoch,
+                     hipStream_t s);
 // fp8 path (quant.hip, gemm_fp8.hip)
 int launch_quant_rows(const void* x, int dtype, int64_t ld_x, int64_t rows, int64_t cols, void* q, int64_t ld_q, uint8_t* scale,
                       hipStream_t s);
@@ -51,6 +51,48 @@ int launch_rmsnorm_fp8_few(const float* x, int64_t ld_x, const float* w, float e
                            hipStream_t s);
 int launch_gemm_fp8(const void* A, int64_t lda, const uint8_t* a_scale, const void* W, int64_t ldw, const uint8_t* w_scale, int64_t M, int N,
                     int K, int n_cover, int out_dtype, int epilogue, const EpiParams& ep, int tile, hipStream_t s);
+// ---- GEMM launch plans: the launch policy of gemm_mfma.hip / gemm_fp8.hip as pure host code (no HIP call), apart from the
+// launch itself, so that it can be queried (lab build: p2t_lab_gemm_plan) and tested without a GPU
+enum GemmForm : int {
+    GEMM_NONE = 0,      // no form of this path takes the call (fp8 tile 4 on a shape the four-wave kernel does not take)
+    GEMM_TILE128,       // gemm_nt_mfma_kernel, one 128 x 256 tile per block
+    GEMM_TILE256,       // gemm_nt_mfma_kernel, one 256 x 256 tile per block
+    GEMM_SPLITK,        // gemm_nt_mfma_tail_kernel: n_full whole tiles, then n_tail tiles as split-K pairs on two blocks each
+    GEMM_PERSIST,       // gemm_nt_mfma_persist_kernel: n_full tiles walked by one block per CU, then n_tail split-K pairs / 128-row halves
+    GEMM_W4_TILE,       // gemm_w4.hip, one tile per block
+    GEMM_W4_PERSIST,    // gemm_w4.hip persistent: n_full tiles, then n_tail split-K pairs in the same stream
+    GEMM_W4_PAIRS,      // gemm_w4.hip: every one of the n_tail tiles as a split-K pair
+    GEMM_K64,           // lab: bf16 operands through gemm_fp8.hip's 64-deep skeleton
+    FP8_TILE128,        // gemm_nt_fp8_kernel, 128-row tiles
+    FP8_TILE256,        // gemm_nt_fp8_kernel, 256-row tiles
+    FP8_W4,             // gemm_fp8_w4.hip persistent
+    FP8_ABLATION,       // lab: gemm_nt_fp8_kernel with K-loop ablation `variant` (results are garbage)
+    FP8_STAMPS,         // lab: gemm_fp8_w4.hip with per-workgroup stamps, variant `variant`
+};
+struct GemmPlan {
+    int form = GEMM_NONE;
+    int64_t grid = 0;             // workgroups
+    int64_t n_full = 0;           // tiles run whole (the persistent forms: walked by the grid)
+    int64_t n_tail = 0;           // tiles run as split-K pairs (or 128-row halves: half_tail)
+    int half_tail = 0;
+    int variant = 0;              // GEMM_W4_PERSIST: instruction order of the K loop (1 = the product's); FP8_ABLATION / FP8_STAMPS: which
+};
+// the facts of one call that the launch policy reads
+struct GemmFacts {
+    int64_t M, lda, ldw;
+    int N, K, n_cover, cus;
+    size_t fix_bytes;             // usable split-K fix-up workspace (0: none)
+    int ns;                       // 32-deep K stages
+    int64_t tn, items, rem;       // 256-column tile columns; 256 x 256 tiles; tiles of a partial last round on `cus` CUs
+    bool whole_tiles;             // no edge tiles
+    bool stride32;                // the four-wave kernels' 32-bit lane offsets reach every row
+};
+GemmFacts gemm_facts(int64_t M, int N, int K, int n_cover, int64_t lda, int64_t ldw, int cus, size_t fix_bytes);
+bool small_tiles_pay(const GemmFacts& f);      // 128-row tiles fill the chip better than 256-row ones
+GemmPlan plan_gemm_mfma(const GemmFacts& f, int epilogue, int out_dtype, int policy);   // policy: p2t_set_gemm_policy
+GemmPlan plan_gemm_fp8(const GemmFacts& f, int epilogue, int out_dtype, int tile, bool no_w4);
+bool fp8_w4_fits(int64_t M, int N, int K, int n_cover, int64_t lda, int64_t ldw, int grid);    // gemm_fp8_w4.hip takes the shape
+
 unsigned* fault_word_ptr();            // the GPU's sticky fault word (misc.hip); nullptr if the symbol cannot be resolved
 int get_gemm_policy();
 void set_gemm_policy(int policy);       // launch-form override of the MFMA GEMM (tests / experiments), 0 = default
@@ -62,7 +104,7 @@ struct GemmArgs {
     int64_t M; int64_t N; int64_t K; int dtype; int out_dtype; int epilogue; int accumulate; int use_mfma;
     int n_zero;                 // -1: default (next multiple of 64, clipped to ldc)
     float drop_p; uint64_t drop_seed;
-    int tile;                   // 0 auto, 128, 256 (rows of the MFMA block tile)
+    int tile;                   // fp8 only: 0 auto, 4 four-wave kernel, 128 / 256 rows of the per-tile kernel (bf16: p2t_set_gemm_policy)
     // P2T_EPI_QKV_ROPE only (head_dim 64 or 128): rotary table [T, head_dim], outputs [B, heads, T, head_dim]
     const float* cs = nullptr; void* q = nullptr; void* k = nullptr; void* v = nullptr;
     int seq = 0, nh = 0, nkv = 0; float q_scale = 1.f; int head_dim = 64;

@@ -43,6 +43,17 @@ unsigned* fault_word_ptr() {
     return p;
 }
 
+int cu_count() {
+    static std::atomic<int> cache[32] = {};
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    const bool slot = dev >= 0 && dev < 32;
+    if (slot && (n = cache[dev].load(std::memory_order_relaxed)) > 0) return n;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    if (slot) cache[dev].store(n, std::memory_order_relaxed);
+    return n;
+}
+
 // sums[0] += loss, sums[1] += 1 (train_contrast.py:443-444: `ddp_loss[0] += batch_loss_value; ddp_loss[1] += 1`);
 // grad_norm given (an optimizer step ran): sums[2] += grad_norm, sums[3] += 1 (:461-462).
 // flags[0] = number of "impossible" batch losses so far (NaN, inf or <= 0: the condition of :433), flags[1] = batch index of

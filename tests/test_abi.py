@@ -41,6 +41,8 @@ def test_argument_errors_without_gpu():
         _lib.call("p2t_gemm_nt", None, 64, None, 64, None, None, 64, None, 8, 16, 64, 0, 0, 0, 0, -1, None, 0, 0, None)
     with pytest.raises(ValueError):
         _lib.call("p2t_layernorm", None, 4, None, None, 1e-5, None, 4, 1, 4, 0, None)
+    with pytest.raises(ValueError, match="tile 1001"):         # the fp8 K-loop ablations are in the lab build only
+        _lib.call("p2t_gemm_nt_fp8", None, 128, None, None, 128, None, None, None, 64, None, 8, 16, 128, 1, 0, 0, 1001, None, None)
     cfg = _lib.EsmConfigC(n_layers=1, hidden=64, ffn=128, heads=4, head_dim=16, vocab=33, dtype=0)
     assert _lib.call("p2t_esm2_workspace_bytes", ctypes.byref(cfg), 2, 16) > 0
     assert _lib.call("p2t_esm2_workspace_bytes", ctypes.byref(cfg), 0, 16) == 0

@@ -2,8 +2,9 @@
 """Kernel micro-benchmarks on the GPU box (HIP-event timed, random data): GEMM shapes of the
 cfg-3 towers, attention, norms.  Usage: python tools/microbench.py [gemm] [attn] [norm]
 
-The `gemm` / `cold` / `ksweep` modes force launch forms through p2t_set_gemm_policy: run them against the LAB build
-(P2T_HIP_LIB=tools/build/libp2t_lab.so, `make -C prot2text-v2-esm3_amd/csrc lab`); the product library only knows 0 and 9."""
+The `gemm` / `cold` / `ksweep` modes force launch forms through p2t_set_gemm_policy, and `fp8abl` runs the fp8 K-loop ablations
+(tile 1001-1003): run them against the LAB build (P2T_HIP_LIB=tools/build/libp2t_lab.so, `make -C prot2text-v2-esm3_amd/csrc lab`);
+the product library only knows policies 0 and 9 and fp8 tiles 0, 4, 128 and 256."""
 import os
 import sys
 
@@ -240,7 +241,7 @@ def bench_skinny():
 
 
 def bench_fp8abl():
-    """Lab ablations of the fp8 K loop (per-tile kernel, garbage results): full / no DMA / no fragment reloads / neither."""
+    """Lab ablations of the fp8 K loop (per-tile kernel, garbage results; lab build only): full / no DMA / no fragment reloads / neither."""
     for name, M, N, K in (("esm qkv b64", 65536, 7680, 2560), ("esm fc2 b64", 65536, 2560, 10240), ("square 8k", 8192, 8192, 8192)):
         a, w = rand((M, K)), rand((N, K), scale=0.05)
         a8, sa = ops.quant_rows_fp8(a)
