@@ -14,6 +14,7 @@
  *   p2t_l2norm_rows           torch.nn.functional.normalize(p=2, dim=-1), train_contrast.py:354,365
  *   p2t_infonce_forward/_backward  SegmentedBatchInfoNCELoss / BatchInfoNCELoss, train_contrast.py:72-114
  *   p2t_clip_adamw_step       clip_grad_norm_ + AdamW.step, train_contrast.py:453-465,621-626
+ *   p2t_clip_adamw_flat       the same over one flat buffer with a segment table, train_instruct.py:431-447
  *
  * Conventions: plain pointers and sizes, no framework types.  All pointers are DEVICE pointers
  * unless named host_*.  Every call only ENQUEUES work on `stream` (a hipStream_t passed as void*),
@@ -549,6 +550,36 @@ int p2t_clip_adamw_step(int n_tensors, float* const* params, const float* const*
                         const int64_t* shadow_ld, int shadow_dtype, int step, double lr, double beta1, double beta2,
                         double eps, double weight_decay, double max_norm, float* grad_norm_out, float* scratch,
                         p2t_stream stream);
+
+/* Flat form of the same step (stage 2: hundreds of tensors in one buffer).  params / grads / exp_avg / exp_avg_sq: f32 [n] device
+ * vectors, 16-byte aligned, n % 16 == 0.  segments (device): one p2t_flat_segment per trained tensor, offsets multiples of 16
+ * elements, no overlap; elements between segments are padding (their gradient must be 0, they are never written).  chunks (device):
+ * n_chunks pieces (segment, flat start, count <= P2T_FLAT_CHUNK) that tile every segment exactly; one block each, so no element
+ * searches for its segment.  A segment's shadow (optional) receives RNE(scale * p) for element j at
+ * shadow[(j / cols) * ld + j % cols] (rows * cols == numel); padding rows / columns of the shadow are never written.
+ * Two launches whatever the number of segments: partial sums of g^2 (P2T_FLAT_NORM_BLOCKS of them, into scratch f32
+ * [P2T_FLAT_NORM_BLOCKS]), then clip_grad_norm_(max_norm) + torch's AdamW, every block re-adding the partials in one fixed order
+ * (bit-identical norm, no atomics).  max_norm <= 0 or >= 1e30 = no clipping; grad_norm_out f32 [1] (device, optional): total
+ * norm before clipping. */
+#define P2T_FLAT_NORM_BLOCKS 1024
+#define P2T_FLAT_CHUNK 4096
+typedef struct {
+    int64_t offset;                      /* first element in the flat buffers (multiple of 16) */
+    int64_t numel;
+    void* shadow;                        /* NULL: no shadow */
+    int64_t rows, cols, ld;              /* shadow matrix [rows, cols] at row stride ld (elements) */
+    float scale;                         /* shadow = RNE(scale * p) */
+    int32_t shadow_dtype;                /* P2T_F32 | P2T_BF16 */
+} p2t_flat_segment;
+typedef struct {
+    int64_t start;                       /* flat index of the chunk's first element */
+    int32_t segment;                     /* index into the segment table */
+    int32_t count;                       /* elements, 1 .. P2T_FLAT_CHUNK */
+} p2t_flat_chunk;
+int p2t_clip_adamw_flat(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                        const p2t_flat_segment* segments, const p2t_flat_chunk* chunks, int64_t n_chunks, int step,
+                        double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm,
+                        float* grad_norm_out, float* scratch, p2t_stream stream);
 
 #ifdef __cplusplus
 }

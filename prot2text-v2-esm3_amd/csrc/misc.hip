@@ -212,6 +212,8 @@ extern "C" size_t p2t_struct_size(int which) {
         case 9: return sizeof(p2t_llama_layer_t);
         case 10: return sizeof(p2t_kv_cache);
         case 11: return sizeof(p2t_llama_layer_stream);
+        case 12: return sizeof(p2t_flat_segment);
+        case 13: return sizeof(p2t_flat_chunk);
     }
     return 0;
 }

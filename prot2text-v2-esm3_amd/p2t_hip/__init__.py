@@ -7,6 +7,7 @@ scripts/train_contrast.py), implemented on libp2t_hip.so (hand-written HIP for g
                          Esm2LlamaInstructForCausalLM, BatchInfoNCELoss, SegmentedBatchInfoNCELoss,
                          readout_embeddings, get_sequence_embeddings, get_description_embeddings,
                          teacher_forcing_forward_pass, ContrastiveTrainer,
+                         InstructTrainer, save_instruct_checkpoint, load_instruct_checkpoint,   # scripts/train_instruct.py
                          train_epoch, eval_epoch, run_epochs,         # scripts/train_contrast.py:400-519, 650-701
                          iterative_generation_loop, inference_epoch)  # scripts/generate_instruct.py:50-147
 
@@ -23,7 +24,8 @@ __all__ = ["specs", "synth", "Esm2LlamaInstructConfig", "ModalityAdapterConfig",
            "get_description_embeddings", "teacher_forcing_forward_pass", "ContrastiveTrainer", "ops",
            "EsmSequenceTokenizer", "ContrastiveCollater", "DevicePrefetcher", "sort_batch_by_length", "CosineWarmupSchedule", "save_checkpoint",
            "load_model_checkpoint", "load_optimizer_scheduler_checkpoint", "train_epoch", "eval_epoch", "run_epochs",
-           "iterative_generation_loop", "inference_epoch", "load_and_merge_adapter"]
+           "iterative_generation_loop", "inference_epoch", "load_and_merge_adapter",
+           "InstructTrainer", "FlatAdamW", "save_instruct_checkpoint", "load_instruct_checkpoint", "run_instruct_epochs", "instruct_schedule"]
 
 _LAZY = {
     "Esm2LlamaInstructConfig": "configuration", "ModalityAdapterConfig": "configuration",
@@ -36,6 +38,8 @@ _LAZY = {
     "CosineWarmupSchedule": "training_state", "save_checkpoint": "training_state",
     "load_model_checkpoint": "training_state", "load_optimizer_scheduler_checkpoint": "training_state",
     "train_epoch": "loop", "eval_epoch": "loop", "run_epochs": "loop", "iterative_generation_loop": "loop", "inference_epoch": "loop", "load_and_merge_adapter": "lora",
+    "InstructTrainer": "instruct", "FlatAdamW": "instruct", "save_instruct_checkpoint": "instruct", "load_instruct_checkpoint": "instruct",
+    "run_instruct_epochs": "instruct", "instruct_schedule": "instruct",
 }
 
 

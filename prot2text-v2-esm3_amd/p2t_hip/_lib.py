@@ -91,8 +91,19 @@ class LlamaLayerStreamC(C.Structure):
     _fields_ = [(n, vp) for n in ("qkv_w", "o_w", "gu_w", "down_w")]
 
 
+class FlatSegmentC(C.Structure):
+    _fields_ = [("offset", i64), ("numel", i64), ("shadow", vp), ("rows", i64), ("cols", i64), ("ld", i64), ("scale", f32),
+                ("shadow_dtype", C.c_int32)]
+
+
+class FlatChunkC(C.Structure):
+    _fields_ = [("start", i64), ("segment", C.c_int32), ("count", C.c_int32)]
+
+
+FLAT_NORM_BLOCKS, FLAT_CHUNK = 1024, 4096            # P2T_FLAT_NORM_BLOCKS, P2T_FLAT_CHUNK
+
 _STRUCTS = [EsmConfigC, EsmLayerC, EsmWeightsC, LlamaConfigC, LlamaLayerC, LlamaWeightsC, AdapterConfigC,
-            AdapterWeightsC, AdapterSavedC, LlamaLayerTC, KvCacheC, LlamaLayerStreamC]
+            AdapterWeightsC, AdapterSavedC, LlamaLayerTC, KvCacheC, LlamaLayerStreamC, FlatSegmentC, FlatChunkC]
 
 # name -> (restype, argtypes); every symbol include/p2t_hip.h declares
 SIGNATURES = {
@@ -175,6 +186,7 @@ SIGNATURES = {
     "p2t_clip_adamw_step": (i32, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64),
                                   C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), i32, i32, f64, f64, f64, f64, f64, f64,
                                   vp, vp, vp]),
+    "p2t_clip_adamw_flat": (i32, [vp, vp, vp, vp, i64, vp, vp, i64, i32, f64, f64, f64, f64, f64, f64, vp, vp, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -47,6 +47,8 @@ class DecoderLora(nn.Module):
             raise ValueError(f"unsupported LoRA targets {bad}; decoder targets are {TARGETS}")
         self.r, self.alpha, self.p, self.targets = int(r), float(2 * r if lora_alpha is None else lora_alpha), float(lora_dropout), tuple(target_modules)
         self.seed, self.step_count = int(seed), 0
+        self.rank = 0                                   # data-parallel rank: ranks > 0 draw their own dropout masks (rank 0: unchanged)
+        self._operands, self._operand_key = {}, {}
         s = decoder.spec
         dev = decoder.model.embed_tokens.weight.device
         P = dict(decoder.model.named_parameters())
@@ -73,6 +75,25 @@ class DecoderLora(nn.Module):
             return None
         return getattr(self, self._name(i, target, "A")), getattr(self, self._name(i, target, "B"))
 
+    def set_operands(self, operands: Optional[Dict[Tuple[int, str], Tuple[torch.Tensor, torch.Tensor]]]):
+        """Register GEMM-layout operands {(layer, target): (a16, bs16)} that an optimizer keeps equal to what `_Lin` would build from
+        the masters (A [rp, K] and (alpha / r) B [N, round_up(rp, 64)] in the model dtype, zero padded); None drops them.  They
+        count as current for the masters' `_version` at this call: `mark_operands_current()` after every write of the owner."""
+        self._operands = dict(operands) if operands else {}
+        self.mark_operands_current()
+
+    def mark_operands_current(self):
+        self._operand_key = {k: (a._version, b._version) for k in self._operands for a, b in (self.get(*k),)}
+
+    def operands(self, i: int, target: str, dt) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """The registered (a16, bs16) of one projection, or None when there are none or a master changed since the owner's last
+        write (load_state_dict, copy_, ...: anything that bumps the parameter's version)."""
+        hit = self._operands.get((i, target))
+        if hit is None or hit[0].dtype != dt:
+            return None
+        a, b = self.get(i, target)
+        return hit if self._operand_key.get((i, target)) == (a._version, b._version) else None
+
     def peft_state_dict(self, prefix: str = "base_model.model.llama_decoder.model.") -> Dict[str, torch.Tensor]:
         """The adapter in the key layout p2t_hip/lora.py reads (peft's, restated without the library: unverified against it)."""
         out = {}
@@ -98,7 +119,7 @@ def _transposed(decoder, name: str) -> torch.Tensor:
 class _Lin:
     """One projection of one layer: frozen W [N, K] (+ LoRA A, B), forward y = W x + s B A drop(x) and the pieces of its backward."""
 
-    def __init__(self, decoder, lora: Optional[DecoderLora], i: int, target: str, dt):
+    def __init__(self, decoder, lora: Optional[DecoderLora], i: int, target: str, dt, dropout: Optional[float] = None):
         self.name = f"layers.{i}.{target}.weight"
         self.w = dict(decoder.model.named_parameters())[self.name].detach()
         self.decoder, self.dt = decoder, dt
@@ -110,15 +131,21 @@ class _Lin:
             s = lora.scale
             r = a.shape[0]
             rp = round_up(r, 16)                        # p2t_gemm_nt wants N % 16 == 0: the rank axis is zero-padded to rp everywhere
-            # operands of the low-rank products in the model dtype (the masters stay fp32): A [rp, K], s B [N, 64 k], zero padded
-            a16 = torch.zeros((rp, round_up(self.K, 8)), dtype=dt, device=a.device)
-            a16[:r, :self.K] = a.detach().to(dt)
-            self.a16 = a16
-            bs = torch.zeros((self.N, round_up(rp, 64)), dtype=dt, device=a.device)
-            bs[:, :r] = (b.detach() * s).to(dt)
-            self.bs16 = bs
+            # operands of the low-rank products in the model dtype (the masters stay fp32): A [rp, K], s B [N, 64 k], zero padded --
+            # the ones an optimizer registered (InstructTrainer: written by its AdamW step), else built here from the masters
+            hit = lora.operands(i, target, dt)
+            if hit is not None:
+                self.a16, self.bs16 = hit
+            else:
+                a16 = torch.zeros((rp, round_up(self.K, 8)), dtype=dt, device=a.device)
+                a16[:r, :self.K] = a.detach().to(dt)
+                self.a16 = a16
+                bs = torch.zeros((self.N, round_up(rp, 64)), dtype=dt, device=a.device)
+                bs[:, :r] = (b.detach() * s).to(dt)
+                self.bs16 = bs
             self.rp = rp
-            self.lora = (a, b, r, s, lora.p, (lora.seed * 1000003 + lora.step_count * 7919 + i * 131 + TARGETS.index(target)) & 0x7FFFFFFFFFFFFFFF)
+            seed = lora.seed * 1000003 + lora.step_count * 7919 + i * 131 + TARGETS.index(target) + lora.rank * 0x9E3779B97F4A7C15
+            self.lora = (a, b, r, s, lora.p if dropout is None else float(dropout), seed & 0x7FFFFFFFFFFFFFFF)
 
     # -- forward: f32 [M, N] (or accumulated into the fp32 residual stream `resid`)
     def forward(self, x: torch.Tensor, resid: Optional[torch.Tensor] = None):
@@ -199,7 +226,7 @@ class DecoderLoraLossFn(torch.autograd.Function):
     """LM loss of the decoder as a function of `inputs_embeds` and the LoRA parameters (frozen base weights)."""
 
     @staticmethod
-    def forward(ctx, inputs_embeds, decoder, lora, attention_mask, labels, *params):
+    def forward(ctx, inputs_embeds, decoder, lora, attention_mask, labels, opts, *params):
         s, m = decoder.spec, decoder.model
         dt = m.dtype
         B, T, H = inputs_embeds.shape
@@ -217,11 +244,12 @@ class DecoderLoraLossFn(torch.autograd.Function):
         q_fold = scale * 1.4426950408889634 if l2s else 1.0
         x = inputs_embeds.detach().to(device=dev, dtype=torch.float32).reshape(M, H).contiguous().clone()
         tape = []
+        keep = opts["keep_tape"]                        # False: forward-only loss, no layer's activations are kept
         f32v = lambda n: P[n].detach().float().contiguous()
         for i in range(L):
             p = f"layers.{i}."
-            lin = {t: _Lin(decoder, lora, i, t, dt) for t in TARGETS}
-            rec = dict(lin=lin, x_in=x.clone())
+            lin = {t: _Lin(decoder, lora, i, t, dt, opts["dropout"]) for t in TARGETS}
+            rec = dict(lin=lin, x_in=x.clone() if keep else None)
             h = ops.rmsnorm(x, f32v(p + "input_layernorm.weight"), s.rms_norm_eps, out_dtype=dt)
             parts = []
             for t in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"):
@@ -240,17 +268,18 @@ class DecoderLoraLossFn(torch.autograd.Function):
             ao = ops.attention(q4, k4, v4, key_mask, kv_info, d, 1.0 if l2s else scale, True, log2_scores=l2s, lse=lse)      # [M, QO]
             rec.update(q=q4, k=k4, v=v4, lse=lse, ao=ao)
             _, rec["u_self_attn.o_proj"] = lin["self_attn.o_proj"].forward(ao, resid=x)
-            rec["x_mid"] = x.clone()
+            rec["x_mid"] = x.clone() if keep else None
             h2 = ops.rmsnorm(x, f32v(p + "post_attention_layernorm.weight"), s.rms_norm_eps, out_dtype=dt)
             g, rec["u_mlp.gate_proj"] = lin["mlp.gate_proj"].forward(h2)
             up, rec["u_mlp.up_proj"] = lin["mlp.up_proj"].forward(h2)
             gu = _interleave(g, up, F)
             gu = ops.cast(gu, dt) if dt != torch.float32 else gu
-            rec["gu"] = gu
+            rec["gu"] = gu if keep else None
             act = torch.empty((M, round_up(F, 64)), dtype=dt, device=dev)
             call("p2t_swiglu_gu", ptr(gu), gu.stride(0), None, 0, ptr(act), act.stride(0), M, F, ops.dt_of(dt), stream())
             _, rec["u_mlp.down_proj"] = lin["mlp.down_proj"].forward(act, resid=x)
-            tape.append(rec)
+            if keep:
+                tape.append(rec)
         x_last = x
         hN = ops.rmsnorm(x_last, f32v("norm.weight"), s.rms_norm_eps, out_dtype=dt)
         logits = ops.gemm_nt(hN, decoder._lm_head_padded(), None, n=s.vocab_size, k=H, out_dtype=dt).view(B, T, -1)
@@ -343,13 +372,18 @@ class DecoderLoraLossFn(torch.autograd.Function):
             call("p2t_scale_by_device_scalar", ptr(buf), buf.numel(), ptr(gl if factor == 1.0 else (gl * factor).contiguous()), stream())
             out_params.append(buf[:rows, :cols].to(prm.dtype))
         ctx.state = None
-        return (g.view(B, T, H).to(st["in_dtype"]), None, None, None, None, *out_params)
+        return (g.view(B, T, H).to(st["in_dtype"]), None, None, None, None, None, *out_params)
 
 
-def lora_lm_loss(decoder, lora: Optional[DecoderLora], inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, labels: torch.Tensor):
-    """(loss, logits) of `llama_decoder(inputs_embeds=..., attention_mask=..., labels=...)` with the LoRA branches in the graph."""
+def lora_lm_loss(decoder, lora: Optional[DecoderLora], inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, labels: torch.Tensor,
+                 dropout: Optional[float] = None):
+    """(loss, logits) of `llama_decoder(inputs_embeds=..., attention_mask=..., labels=...)` with the LoRA branches in the graph.
+    dropout: None = the branches' own `lora.p` (every mode, as before); a value overrides it for this call and leaves the mask counter
+    where it is -- 0.0 is peft's eval mode (InstructTrainer.evaluate).  Without gradients to compute, no activation tape is kept."""
     params = tuple(lora.parameters()) if lora is not None else ()
-    if lora is not None and lora.training:
+    if lora is not None and lora.training and dropout is None:
         lora.step_count += 1                            # a fresh dropout mask per step
-    loss, logits = DecoderLoraLossFn.apply(inputs_embeds, decoder, lora, attention_mask, labels, *params)
+    keep = torch.is_grad_enabled() and (inputs_embeds.requires_grad or any(q.requires_grad for q in params))
+    opts = dict(dropout=dropout, keep_tape=keep)
+    loss, logits = DecoderLoraLossFn.apply(inputs_embeds, decoder, lora, attention_mask, labels, opts, *params)
     return loss, logits[..., : decoder.spec.vocab_size]

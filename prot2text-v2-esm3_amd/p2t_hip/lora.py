@@ -9,7 +9,7 @@ call into it -- parity unpinned against the library itself; the arithmetic is pi
                                  base_model.model.<module>.weight / .bias for every module in modules_to_save
 merged weight = W + (lora_alpha / r) * B @ A      (lora_alpha / sqrt(r) with use_rslora; A, B swapped roles with fan_in_fan_out).
 The merge is a one-time weight transformation at load (torch matmul in f32 on the device, like the packing of the engines); the
-model then runs the unchanged kernels.  Training the LoRA matrices themselves is not built."""
+model then runs the unchanged kernels.  Training the LoRA matrices: p2t_hip/instruct.py, which writes such directories."""
 from __future__ import annotations
 
 import json

@@ -2,7 +2,9 @@
 scatter -> 32-layer Llama-3.1-8B -> LM head -> shifted CE, once forward only and once as the training step `loss.backward()`
 (frozen towers, adapter trainable: training forward with the activation tape + the dX chain of csrc/llama_train.hip + adapter
 backward), with a per-kernel-family breakdown of the backward from the torch profiler-free HIP-event brackets below.
-python tools/sft_bench.py [B] > gpurun_out/sft_bench.log"""
+python tools/sft_bench.py [B] [lora] [trainer] > sft_bench.log
+`trainer`: the stage-2 InstructTrainer (LoRA r = 16 + adapter, GA 1): ms per full step, the flat clip + AdamW tail alone (bytes,
+fraction of HBM bandwidth) and the host time per step that the optimizer-written LoRA operands save."""
 import os
 import sys
 import time
@@ -104,6 +106,64 @@ def main():
               f"{dt_l * 1e3:.1f} ms/batch = {B / dt_l:.2f} samples/s; loss {float(o3.loss):.4f}; |grad| of the first B matrix "
               f"{float([q.grad for n, q in lora.named_parameters() if n.endswith('B')][0].float().norm()):.3e}; "
               f"peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB", flush=True)
+    if "trainer" in sys.argv:
+        trainer_leg(model, kw, B)
+
+
+def trainer_leg(model, kw, B):
+    """InstructTrainer at cfg3 sizes: LoRA r = 16 (alpha 32, dropout 0.1) on the 7 x 32 projections + the adapter, GA 1."""
+    from p2t_hip.decoder_train import TARGETS, _Lin
+    torch.cuda.empty_cache()
+    lora = getattr(model.llama_decoder, "lora", None) or model.add_lora(r=16, lora_alpha=32, lora_dropout=0.1)
+    model.train()
+    tr = P.InstructTrainer(model)
+    n_p = sum(tr.opt.numels)
+    tr.step(kw)
+    torch.cuda.synchronize()
+    n = 3
+    t0 = time.perf_counter()
+    for _ in range(n):
+        loss = tr.step(kw)
+    torch.cuda.synchronize()
+    dt_step = (time.perf_counter() - t0) / n
+    # the optimizer tail alone: norm + update over the flat buffers (gradients of the last step are zero by now: refill)
+    tr.opt.flat_g.normal_(0.0, 1e-3)
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    reps = 20
+    tr.opt.step(tr.step_count + 1, lr=2e-4)
+    ev0.record()
+    for k in range(reps):
+        tr.opt.step(tr.step_count + 2 + k, lr=2e-4)
+    ev1.record()
+    torch.cuda.synchronize()
+    dt_opt = ev0.elapsed_time(ev1) / reps * 1e-3
+    nbytes = tr.opt.bytes_per_step()
+    # host cost of the LoRA operands per step: every _Lin of the forward built from the masters vs taken from the trainer
+    dec, dt = model.llama_decoder, model.llama_decoder.model.dtype
+    L = dec.spec.num_hidden_layers
+
+    def build_all():
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for i in range(L):
+            for tg in TARGETS:
+                _Lin(dec, lora, i, tg, dt)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t
+    build_all()
+    t_reg = min(build_all() for _ in range(3))
+    saved = lora._operands, lora._operand_key
+    lora._operands, lora._operand_key = {}, {}
+    t_fresh = min(build_all() for _ in range(3))
+    lora._operands, lora._operand_key = saved
+    print(f"sft InstructTrainer step cfg3: B={B}, r=16 LoRA + adapter ({len(tr.params)} tensors, {n_p / 1e6:.1f} M parameters, "
+          f"{tr.opt.n_chunks} chunks), GA 1: {dt_step * 1e3:.1f} ms/step = {B / dt_step:.2f} samples/s; loss {float(loss):.4f}; "
+          f"peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB", flush=True)
+    print(f"flat clip + AdamW (p2t_clip_adamw_flat, 2 launches): {dt_opt * 1e3:.3f} ms, {nbytes / 1e9:.3f} GB moved = "
+          f"{nbytes / dt_opt / 1e12:.2f} TB/s = {nbytes / dt_opt / 8.0e12:.2f} of the 8.0 TB/s HBM peak "
+          f"({nbytes / dt_opt / 6.29e12:.2f} of the 6.29 TB/s float4 copy rate)", flush=True)
+    print(f"LoRA operands per step ({L * len(TARGETS)} projections): rebuilt from the masters {t_fresh * 1e3:.1f} ms, "
+          f"registered by the trainer {t_reg * 1e3:.1f} ms: {(t_fresh - t_reg) * 1e3:.1f} ms saved per step", flush=True)
 
 
 if __name__ == "__main__":
