@@ -387,6 +387,64 @@ int p2t_llama_train_backward(const p2t_llama_config* cfg, const p2t_llama_weight
                              const int64_t* mask, int B, int T, const float* d_out, const void* tape, size_t tape_bytes,
                              float* d_inputs_embeds, void* workspace, size_t workspace_bytes, p2t_stream stream);
 
+
+/* ---------------------------------------------------------------- packed rows (stage 2 on padding-free batches) */
+/* A packed row is a right-padded row (attention mask 1...1 0...0) whose position_ids are runs 0, 1, 2, ...: every position 0
+ * under the mask starts a new DOCUMENT (transformers' DataCollatorWithFlattening convention).  Token t of the document that
+ * starts at s = t - position_ids[t] attends to the keys s <= k <= t, and its rotary angle uses position_ids[t] instead of t.
+ * The shifted LM loss never scores a target that starts a document (the caller sets those labels to the ignore index).
+ * A packed batch made from the samples of a padded batch gives the same loss and gradients as that batch (RoPE is relative:
+ * dropping the left-pad offset only changes rounding).
+ *
+ * p2t_doc_prepare: position_ids [B, T] (int64 if pos_i64, else int32) and mask int64 [B, T] -> docs int32 [2][B][T]:
+ * docs[0][b][t] = the document start of token t, docs[1][b][t] = its end (exclusive); a padding token t is a document of its
+ * own (t, t + 1).  Both rows are non-decreasing in t, so a tile's smallest start is that of its first query and its largest
+ * end that of its last key: these are the loop bounds of the attention kernels below.  Every start lies in [0, t] and every
+ * end in [t + 1, T] whatever the input.  flags int32 [1] (device, zeroed here): bit 0 = malformed (mask not a prefix, or
+ * position_ids under the mask not runs from 0), bit 1 = position_ids is not arange(T) in every row (bit 1 clear: the batch
+ * is an ordinary one, run it without documents).  A caller must not pass docs with bit 0 set. */
+int p2t_doc_prepare(const void* position_ids, int pos_i64, const int64_t* mask, int B, int T, int32_t* docs, int32_t* flags,
+                    p2t_stream stream);
+/* p2t_qkv_post with the rotation of token t at position t - docs[0][b][t]. */
+int p2t_qkv_post_docs(const void* qkv, int64_t ldq, const float* inv_freq, float* cos_sin_scratch, const int32_t* docs, void* q,
+                      void* k, void* v, int B, int T, int nh, int nkv, int d, int dp, float q_scale, int dtype, p2t_stream stream);
+/* p2t_rope_backward_pack with the same positions. */
+int p2t_rope_backward_pack_docs(const float* dq, const float* dk, const float* dv, const float* inv_freq, float* cos_sin_scratch,
+                                const int32_t* docs, void* d_qkv, int64_t ld, int B, int T, int nh, int nkv, int d, int dp,
+                                float q_scale, int dtype, p2t_stream stream);
+/* Causal attention confined to documents (p2t_attention with causal = 1 and key >= docs[0][b][query]); lse keeps its meaning.
+ * The MFMA kernel's key loop of a 128-query tile starts at the 64-key block holding the tile's first start: whole blocks before
+ * it are skipped, only the blocks that straddle a boundary are masked per element.  use_mfma as p2t_attention, except that
+ * the hand-placed kernel (3) has no documents. */
+int p2t_attention_docs(const void* q, const void* k, const void* v, const uint8_t* key_mask, const int32_t* kv_info,
+                       const int32_t* docs, void* out, int64_t ld_out, int B, int T, int nh, int nkv, int d, int dp, float scale,
+                       int dtype, int use_mfma, int log2_scores, float* lse, p2t_stream stream);
+/* Its backward (p2t_attention_backward, causal): the dk / dv kernels end the query loop of a key tile at the tile's last
+ * document end.  GQA sums stay atomic-free. */
+int p2t_attention_backward_docs(const void* q, const void* k, const void* v, const void* o, int64_t ld_o, const void* d_o,
+                                int64_t ld_do, const float* lse, const uint8_t* key_mask, const int32_t* kv_info,
+                                const int32_t* docs, float* dq, float* dk, float* dv, float* D_scratch, int B, int T, int nh,
+                                int nkv, int d, int dp, float scale, int dtype, int log2_scores, int use_mfma, p2t_stream stream);
+/* p2t_llama_train_forward / _backward on packed rows (docs from p2t_doc_prepare, caller-owned; the tape and workspace sizes
+ * are those of the unpacked calls).  The QKV projection is stored and rotated by p2t_qkv_post's positional form instead of
+ * the fused rotary epilogue. */
+int p2t_llama_train_forward_docs(const p2t_llama_config* cfg, const p2t_llama_weights* w, const float* inputs_embeds,
+                                 const int64_t* mask, const int32_t* docs, int B, int T, float* out, void* tape, size_t tape_bytes,
+                                 void* workspace, size_t workspace_bytes, p2t_stream stream);
+int p2t_llama_train_backward_docs(const p2t_llama_config* cfg, const p2t_llama_weights* w, const p2t_llama_layer_t* wT,
+                                  const int64_t* mask, const int32_t* docs, int B, int T, const float* d_out, const void* tape,
+                                  size_t tape_bytes, float* d_inputs_embeds, void* workspace, size_t workspace_bytes,
+                                  p2t_stream stream);
+/* Per-target loss weights: p2t_cross_entropy_shifted with loss = sum of weights[b, t+1] * ce(b, t) over the counted targets
+ * (weights f32 [B, T], aligned with labels; count still counts the targets), and its backward
+ * d_logits[b, t] = weights[b, t+1] (softmax - onehot).  Per-document weights 1 / (n_docs * n_supervised(doc)) give the mean of
+ * the per-sample losses: the reference's batch_size_per_device = 1 recipe on packed rows. */
+int p2t_cross_entropy_shifted_weighted(const void* logits, int64_t ld, int dtype, const int64_t* labels, const float* weights,
+                                       int B, int T, int V, int64_t ignore_index, float* row_loss, int32_t* row_valid, float* loss,
+                                       int32_t* count, p2t_stream stream);
+int p2t_cross_entropy_shifted_weighted_backward(const void* logits, int64_t ld, int dtype, const int64_t* labels,
+                                                const float* weights, int B, int T, int V, int64_t ignore_index, void* d_logits,
+                                                int64_t ld_d, p2t_stream stream);
 /* ---------------------------------------------------------------- ModalityAdapter */
 typedef struct {
     int32_t input_dim, intermediate_dim, output_dim;

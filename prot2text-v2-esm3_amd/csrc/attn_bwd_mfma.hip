@@ -64,12 +64,14 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16 (&a)[2], int ss) {
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
-template <int DP>
+// DOC (packed rows): docs i32 [2][B][T] (kernels.h attention()): the key loop starts at the tile's first document start, as the forward's.
+template <int DP, bool DOC>
 __global__ void __launch_bounds__(256, DP == 64 ? 2 : 1) attn_bwd_dq_mfma_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                                   const bf16_t* __restrict__ o, int64_t ld_o, const bf16_t* __restrict__ d_o, int64_t ld_do,
                                                                   const float* __restrict__ lse, const uint8_t* __restrict__ key_mask,
                                                                   const int32_t* __restrict__ kv_info, float* __restrict__ dq, float* __restrict__ Dout,
-                                                                  int B, int seq, int nh, int nkv, int causal, float c_out) {
+                                                                  int B, int seq, int nh, int nkv, int causal, float c_out,
+                                                                  const int32_t* __restrict__ docs) {
     constexpr int RB = DP * 2, T_BYTES = 64 * RB, STAGE = 2 * T_BYTES, NI = DP / 32, DK = DP / 16, DT = DP / 32;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
     const int lane = threadIdx.x & 63;
@@ -93,7 +95,14 @@ __global__ void __launch_bounds__(256, DP == 64 ? 2 : 1) attn_bwd_dq_mfma_kernel
     int end = kv_info[b];
     const int prefix = kv_info[B + b];
     if (causal) end = min(end, qt * 128 + 128);
-    const int n_it = (end + 63) >> 6;
+    int it0 = 0, qlo = 0, wlo = 0;             // DOC: first 64-key block, this lane's first key, the wave's largest first key
+    if constexpr (DOC) {
+        const int32_t* ds = docs + (int64_t)b * seq;
+        it0 = __builtin_amdgcn_readfirstlane(ds[min(qt * 128, seq - 1)]) >> 6;
+        qlo = ds[qr];
+        wlo = __builtin_amdgcn_readfirstlane(ds[min(q0 + 31, seq - 1)]);
+    }
+    const int n_it = max(((end + 63) >> 6) - it0, 0);
     const bf16_t* kbase = k + ((int64_t)(b * nkv + hk) * seq) * DP;
     const bf16_t* vbase = v + ((int64_t)(b * nkv + hk) * seq) * DP;
 
@@ -137,7 +146,7 @@ __global__ void __launch_bounds__(256, DP == 64 ? 2 : 1) attn_bwd_dq_mfma_kernel
         s_voff[i] = (uint32_t)(row * RB + ((p ^ swz_g<DP>(row)) << 4));
     }
     auto stage = [&](int buf, int it) {
-        const int kb = it * 64;
+        const int kb = (it0 + it) * 64;
         const uint32_t sb = lds0 + buf * STAGE;
         const char* kt = (const char*)(kbase + (int64_t)kb * DP);
         const char* vt = (const char*)(vbase + (int64_t)kb * DP);
@@ -180,7 +189,7 @@ __global__ void __launch_bounds__(256, DP == 64 ? 2 : 1) attn_bwd_dq_mfma_kernel
         __builtin_amdgcn_s_barrier();                       // ... every wave's have, and all are done with the other buffer
         if (it + 1 < n_it) stage(BUF ^ 1, it + 1);
         const char* sb = smem + BUF * STAGE;
-        const int kb = it * 64;
+        const int kb = (it0 + it) * 64;
         f32x16 st[2], dp[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -195,9 +204,9 @@ __global__ void __launch_bounds__(256, DP == 64 ? 2 : 1) attn_bwd_dq_mfma_kernel
                 dp[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, dof[kk], kk == 0 ? init_d : dp[t], 0, 0, 0);
             }
         }
-        const bool need_mask = (kb + 64 > end) || (causal && kb + 63 > q0) || !prefix;
+        const bool need_mask = (kb + 64 > end) || (causal && kb + 63 > q0) || !prefix || (DOC && kb < wlo);
         if (need_mask) {
-            const int lim = (causal ? min(end, query + 1) : end) - kb - 8 * hh;
+            const int lim = (causal ? min(end, query + 1) : end) - kb - 8 * hh, llo = qlo - kb - 8 * hh;
             const uint8_t* mrow = key_mask + (int64_t)b * seq + kb + 8 * hh;
 #pragma unroll
             for (int t = 0; t < 2; ++t)
@@ -205,6 +214,7 @@ __global__ void __launch_bounds__(256, DP == 64 ? 2 : 1) attn_bwd_dq_mfma_kernel
                 for (int r = 0; r < 16; ++r) {
                     const int off = 32 * t + 16 * (r >> 3) + (r & 7);
                     bool ok = off < lim;
+                    if (DOC) ok = ok && off >= llo;
                     if (!prefix) ok = ok && mrow[min(off, seq - 1 - kb - 8 * hh)] != 0;
                     st[t][r] = ok ? st[t][r] : -INFINITY;
                 }
@@ -244,12 +254,13 @@ __global__ void __launch_bounds__(256, DP == 64 ? 2 : 1) attn_bwd_dq_mfma_kernel
 }
 
 // ---------------------------------------------------------------------------------------------
-template <int DP>
+// DOC (packed rows): the query loop of the key tile ends at the 64-query block holding the tile's last document end.
+template <int DP, bool DOC>
 __global__ void __launch_bounds__(256, 1) attn_bwd_dkv_mfma_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                                    const bf16_t* __restrict__ d_o, int64_t ld_do, const float* __restrict__ lse,
                                                                    const float* __restrict__ D, const uint8_t* __restrict__ key_mask,
                                                                    float* __restrict__ dk, float* __restrict__ dv, int B, int seq, int nh, int nkv,
-                                                                   int causal, float c_out) {
+                                                                   int causal, float c_out, const int32_t* __restrict__ docs) {
     constexpr int RB = DP * 2, T_BYTES = 64 * RB, STAT = 2 * T_BYTES, STAGE = 2 * T_BYTES + 512, NI = DP / 32, DK = DP / 16, DT = DP / 32;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
     const int lane = threadIdx.x & 63;
@@ -279,7 +290,14 @@ __global__ void __launch_bounds__(256, 1) attn_bwd_dkv_mfma_kernel(const bf16_t*
 
     // ---- the stream of steps: for every query head of the group, the 64-query tiles from the first one a key of this block can
     // see (causal) to the end ----
-    const int n_qt = (seq + 63) >> 6, it0 = causal ? (kt * 128) >> 6 : 0, per_head = n_qt - it0, n_steps = rep * per_head;
+    int n_qt = (seq + 63) >> 6, khi = seq, whi = seq;          // DOC: this lane's / the wave's smallest end of the visible queries
+    if constexpr (DOC) {
+        const int32_t* de = docs + (int64_t)B * seq + (int64_t)b * seq;
+        n_qt = min(n_qt, (__builtin_amdgcn_readfirstlane(de[min(kt * 128 + 127, seq - 1)]) + 63) >> 6);
+        khi = min(seq, de[kr]);
+        whi = __builtin_amdgcn_readfirstlane(min(seq, de[min(k0, seq - 1)]));
+    }
+    const int it0 = causal ? (kt * 128) >> 6 : 0, per_head = max(n_qt - it0, 0), n_steps = rep * per_head;
     const uint32_t lds0 = (uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem;
     uint32_t q_voff[NI], o_voff[NI];
     int s_row[NI];
@@ -372,8 +390,8 @@ __global__ void __launch_bounds__(256, 1) attn_bwd_dkv_mfma_kernel(const bf16_t*
         }
         // visibility: the key must be valid (lane), not after the query (causal), and the query inside the sequence
         const bool tail = qb + 64 > seq, diag = causal && qb < k0 + 32;
-        if (tail || diag || __builtin_amdgcn_ballot_w64(!kvalid) != 0) {          // wave-uniform
-            const int lo = (causal ? key : 0) - qb - 8 * hh, hi_ = seq - qb - 8 * hh;      // visible iff lo <= off < hi
+        if (tail || diag || (DOC && qb + 64 > whi) || __builtin_amdgcn_ballot_w64(!kvalid) != 0) {          // wave-uniform
+            const int lo = (causal ? key : 0) - qb - 8 * hh, hi_ = (DOC ? khi : seq) - qb - 8 * hh;      // visible iff lo <= off < hi
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -430,15 +448,19 @@ __global__ void __launch_bounds__(256, 1) attn_bwd_dkv_mfma_kernel(const bf16_t*
 // log2_scores form, bf16, head_dim == dp in {64, 128}; P2T_ERR_UNSUPPORTED otherwise (the caller runs the exact kernels).
 int launch_attn_bwd_mfma(const void* q, const void* k, const void* v, const void* o, int64_t ld_o, const void* d_o, int64_t ld_do, const float* lse,
                          const uint8_t* key_mask, const int32_t* kv_info, float* dq, float* dk, float* dv, float* D, int B, int T, int nh, int nkv,
-                         int d, int dp, int causal, hipStream_t s) {
+                         int d, int dp, int causal, hipStream_t s, const int32_t* docs) {
     if (d != dp || (dp != 64 && dp != 128) || ld_o % 8 || ld_do % 8 || (int64_t)64 * ld_do * 2 >= ((int64_t)1 << 31)) return P2T_ERR_UNSUPPORTED;
     const unsigned gq = (unsigned)(ceil_div(T, 128) * nh * B), gk = (unsigned)(ceil_div(T, 128) * nkv * B);
-#define P2T_BWD(DPV)                                                                                                                     \
-    attn_bwd_dq_mfma_kernel<DPV><<<gq, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)o, ld_o, (const bf16_t*)d_o,  \
-                                                    ld_do, lse, key_mask, kv_info, dq, D, B, T, nh, nkv, causal, kLn2);                      \
-    attn_bwd_dkv_mfma_kernel<DPV><<<gk, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, ld_do, lse, D, key_mask, \
-                                                     dk, dv, B, T, nh, nkv, causal, kLn2)
+#define P2T_BWD_K(DPV, DC)                                                                                                               \
+    attn_bwd_dq_mfma_kernel<DPV, DC><<<gq, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)o, ld_o,           \
+                                                        (const bf16_t*)d_o, ld_do, lse, key_mask, kv_info, dq, D, B, T, nh, nkv, causal, kLn2, docs); \
+    attn_bwd_dkv_mfma_kernel<DPV, DC><<<gk, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, ld_do, lse, D,  \
+                                                         key_mask, dk, dv, B, T, nh, nkv, causal, kLn2, docs)
+#define P2T_BWD(DPV)                      \
+    if (docs) { P2T_BWD_K(DPV, true); }   \
+    else { P2T_BWD_K(DPV, false); }
     if (dp == 64) { P2T_BWD(64); } else { P2T_BWD(128); }
+#undef P2T_BWD_K
 #undef P2T_BWD
     P2T_LAUNCH_CHECK();
     return P2T_OK;

@@ -44,7 +44,10 @@ __device__ __forceinline__ int swz_g(int row) {
 // of the exponentials is then folded into the QK^T MFMA as its accumulator INPUT (16 registers holding -m, rewritten only when
 // the lazy rescale moves m), and the softmax per score shrinks from fma + exp2 + add to exp2 + add: the vector pipe, not the matrix
 // pipe, bounds this kernel.
-template <int DP, bool L2S>
+// DOC (packed rows, causal): docs i32 [2][B][T] (kernels.h attention()).  The key loop of the 128-query tile starts at the 64-key block
+// holding the tile's first document start; a step masks per element only where it reaches below the largest start of the wave's
+// queries.  DOC = false compiles to the kernel without documents.
+template <int DP, bool L2S, bool DOC>
 // dp = 64: three waves per SIMD (three 48 KiB blocks per CU); the L2S form needs 16 registers more for -m and is held to that
 // budget (168 registers: two scalar-like values per step reload from scratch) -- at two waves per SIMD it measured 9 % slower
 // (profiles/r03_attn_ab.log)
@@ -52,7 +55,8 @@ __global__ void __launch_bounds__(256, DP == 64 ? 3 : 2) attn_mfma_kernel(const 
                                                         const bf16_t* __restrict__ v, const uint8_t* __restrict__ key_mask,
                                                         const int32_t* __restrict__ kv_info, bf16_t* __restrict__ out,
                                                         int64_t ld_out, int B, int seq, int nh, int nkv, int d,
-                                                        float scale_log2e, int causal, int out_cols, float* __restrict__ lse) {
+                                                        float scale_log2e, int causal, int out_cols, float* __restrict__ lse,
+                                                        const int32_t* __restrict__ docs) {
     constexpr int RB = DP * 2;                 // tile row bytes
     constexpr int T_BYTES = 64 * RB;           // one tile: 64 keys
     constexpr int STAGE = 2 * T_BYTES;         // K tile + V tile
@@ -90,7 +94,14 @@ __global__ void __launch_bounds__(256, DP == 64 ? 3 : 2) attn_mfma_kernel(const 
     int end = kv_info[b];
     const int prefix = kv_info[B + b];
     if (causal) end = min(end, qt * 128 + 128);
-    const int n_it = (end + 63) >> 6;
+    int it0 = 0, qlo = 0, wlo = 0;             // DOC: first 64-key block, this lane's first key, the wave's largest first key
+    if constexpr (DOC) {
+        const int32_t* ds = docs + (int64_t)b * seq;
+        it0 = __builtin_amdgcn_readfirstlane(ds[min(qt * 128, seq - 1)]) >> 6;
+        qlo = ds[min(query, seq - 1)];
+        wlo = __builtin_amdgcn_readfirstlane(ds[min(q0 + 31, seq - 1)]);
+    }
+    const int n_it = max(((end + 63) >> 6) - it0, 0);
 
     const bf16_t* kbase = k + ((int64_t)(b * nkv + hk) * seq) * DP;
     const bf16_t* vbase = v + ((int64_t)(b * nkv + hk) * seq) * DP;
@@ -126,7 +137,7 @@ __global__ void __launch_bounds__(256, DP == 64 ? 3 : 2) attn_mfma_kernel(const 
         s_voff[i] = (uint32_t)(row * RB + ((p ^ swz_g<DP>(row)) << 4));
     }
     auto stage = [&](int buf, int it) {
-        const int kb = it * 64;
+        const int kb = (it0 + it) * 64;
         const uint32_t sb = lds0 + buf * STAGE;
         const char* kt = (const char*)(kbase + (int64_t)kb * DP);
         const char* vt = (const char*)(vbase + (int64_t)kb * DP);
@@ -186,7 +197,7 @@ __global__ void __launch_bounds__(256, DP == 64 ? 3 : 2) attn_mfma_kernel(const 
         __builtin_amdgcn_s_barrier();
         if (it + NBUF - 1 < n_it) stage((BUF + NBUF - 1) % NBUF, it + NBUF - 1);
         const char* sb = smem + BUF * STAGE;
-        const int kb = it * 64;
+        const int kb = (it0 + it) * 64;
 
         // S^T tiles: rows = keys (permuted), cols = queries.  L2S: the accumulator starts at -m_run (0 before the first visible key)
         f32x16 st[2];
@@ -202,12 +213,21 @@ __global__ void __launch_bounds__(256, DP == 64 ? 3 : 2) attn_mfma_kernel(const 
         // sequence, causal diagonal, or a non-prefix mask): a wave-uniform branch keeps the VALU work of the
         // interior steps at max + fma + exp2 + add per score (the softmax, not the MFMAs, is the longer pipe).
         // Register r of tile t is key kb + 32t + 16(r>>3) + 8hh + (r&7).
-        const bool need_mask = (kb + 64 > end) || (causal && kb + 63 > q0) || !prefix;
+        const bool need_mask = (kb + 64 > end) || (causal && kb + 63 > q0) || !prefix || (DOC && kb < wlo);
         if (need_mask) {
             // visible keys of this lane's query: key < lim, lim = min(end, causal ? query + 1 : end); per register
             // the key is kb + 8 hh + (32 t + 16 (r >> 3) + (r & 7)), so one compare against a per-lane limit
             const int lim = (causal ? min(end, query + 1) : end) - kb - 8 * hh;
-            if (prefix) {
+            if constexpr (DOC) {                   // and key >= the document start (the wrapper requires a prefix mask)
+                const int llo = qlo - kb - 8 * hh;
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int off = 32 * t + 16 * (r >> 3) + (r & 7);
+                        st[t][r] = (off < lim && off >= llo) ? st[t][r] : -INFINITY;
+                    }
+            } else if (prefix) {
 #pragma unroll
                 for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -345,22 +365,25 @@ __global__ void __launch_bounds__(256, DP == 64 ? 3 : 2) attn_mfma_kernel(const 
 
 int launch_attn_mfma(const void* q, const void* k, const void* v, const uint8_t* key_mask, const int32_t* kv_info,
                      void* out, int64_t ld_out, int B, int T, int nh, int nkv, int d, int dp, float scale, int causal,
-                     int log2_scores, float* lse, hipStream_t s) {
+                     int log2_scores, float* lse, hipStream_t s, const int32_t* docs) {
     P2T_REQUIRE(d % 4 == 0 && (dp == 32 || dp == 64 || dp == 128) && d <= dp && nh % nkv == 0 && (nh * d) % 4 == 0 && ld_out % 4 == 0,
                 "attention(mfma): unsupported shape d=%d dp=%d heads %d/%d", d, dp, nh, nkv);
     const dim3 grid((unsigned)(ceil_div(T, 128) * nh * B));
     const int out_cols = (int)(round_up((int64_t)nh * d, 64) < ld_out ? round_up((int64_t)nh * d, 64) : ld_out);
     const float sl = scale * 1.4426950408889634f;
+#define P2T_ATTN_K(DPV, L2, DC)                                                                                              \
+    attn_mfma_kernel<DPV, L2, DC><<<grid, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, key_mask, kv_info,   \
+                                                      (bf16_t*)out, ld_out, B, T, nh, nkv, d, sl, causal, out_cols, lse, docs)
 #define P2T_ATTN(DPV)                                                                                                        \
-    if (log2_scores)                                                                                                         \
-        attn_mfma_kernel<DPV, true><<<grid, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, key_mask, kv_info, \
-                                                         (bf16_t*)out, ld_out, B, T, nh, nkv, d, sl, causal, out_cols, lse); \
-    else                                                                                                                     \
-        attn_mfma_kernel<DPV, false><<<grid, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, key_mask, kv_info, \
-                                                          (bf16_t*)out, ld_out, B, T, nh, nkv, d, sl, causal, out_cols, lse)
+    if (docs) {                                                                                                              \
+        if (log2_scores) P2T_ATTN_K(DPV, true, true); else P2T_ATTN_K(DPV, false, true);                                     \
+    } else if (log2_scores) P2T_ATTN_K(DPV, true, false);                                                                    \
+    else P2T_ATTN_K(DPV, false, false)
+    P2T_REQUIRE(!docs || causal, "attention(mfma): documents need the causal mask");
     if (dp == 32) { P2T_ATTN(32); }
     else if (dp == 64) { P2T_ATTN(64); }
     else { P2T_ATTN(128); }
+#undef P2T_ATTN_K
 #undef P2T_ATTN
     P2T_LAUNCH_CHECK();
     return P2T_OK;

@@ -15,7 +15,8 @@ __global__ void __launch_bounds__(256) attn_simple_kernel(const T* __restrict__ 
                                                           const T* __restrict__ v, const uint8_t* __restrict__ key_mask,
                                                           const int32_t* __restrict__ kv_end, T* __restrict__ out,
                                                           int64_t ld_out, int seq, int nh, int nkv, int d, int dp,
-                                                          float scale, int causal, int out_cols, float* __restrict__ lse) {
+                                                          float scale, int causal, int out_cols, float* __restrict__ lse,
+                                                          const int32_t* __restrict__ docs) {
     __shared__ float s_q[4][128];
     __shared__ float s_p[4][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -28,11 +29,12 @@ __global__ void __launch_bounds__(256) attn_simple_kernel(const T* __restrict__ 
     for (int c = lane; c < dp; c += 64) s_q[w][c] = to_f32(qrow[c]);
     int end = kv_end[b];
     if (causal) end = min(end, i + 1);
+    const int lo = docs ? docs[(int64_t)b * seq + i] : 0;           // packed rows: the first key of this query's document
     float m = -INFINITY, l = 0.f, acc0 = 0.f, acc1 = 0.f;
-    for (int j0 = 0; j0 < end; j0 += 64) {
+    for (int j0 = lo & ~63; j0 < end; j0 += 64) {
         const int j = j0 + lane;
         float s = -INFINITY;
-        if (j < end && key_mask[(int64_t)b * seq + j]) {
+        if (j >= lo && j < end && key_mask[(int64_t)b * seq + j]) {
             const T* kr = kbase + (int64_t)j * dp;
             float dot = 0.f;
             for (int c = 0; c < d; c += 4) {
@@ -77,16 +79,16 @@ __global__ void __launch_bounds__(256) attn_simple_kernel(const T* __restrict__ 
 
 int launch_attn_simple(const void* q, const void* k, const void* v, const uint8_t* key_mask, const int32_t* kv_end,
                        void* out, int64_t ld_out, int B, int T, int nh, int nkv, int d, int dp, float scale,
-                       int causal, int dtype, float* lse, hipStream_t s) {
+                       int causal, int dtype, float* lse, hipStream_t s, const int32_t* docs) {
     P2T_REQUIRE(d % 4 == 0 && d <= 128 && dp <= 128 && nh % nkv == 0, "attention: head_dim %d / heads %d/%d unsupported", d, nh, nkv);
     const dim3 grid((unsigned)ceil_div(T, 4), (unsigned)nh, (unsigned)B);
     const int out_cols = (int)(round_up((int64_t)nh * d, 64) < ld_out ? round_up((int64_t)nh * d, 64) : ld_out);
     if (dtype == P2T_BF16)
         attn_simple_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, key_mask, kv_end,
-                                                        (bf16_t*)out, ld_out, T, nh, nkv, d, dp, scale, causal, out_cols, lse);
+                                                        (bf16_t*)out, ld_out, T, nh, nkv, d, dp, scale, causal, out_cols, lse, docs);
     else
         attn_simple_kernel<float><<<grid, 256, 0, s>>>((const float*)q, (const float*)k, (const float*)v, key_mask, kv_end,
-                                                       (float*)out, ld_out, T, nh, nkv, d, dp, scale, causal, out_cols, lse);
+                                                       (float*)out, ld_out, T, nh, nkv, d, dp, scale, causal, out_cols, lse, docs);
     P2T_LAUNCH_CHECK();
     return P2T_OK;
 }

@@ -47,6 +47,58 @@ __global__ void __launch_bounds__(256) mask_prepare_kernel(const int64_t* __rest
     }
 }
 
+// Packed rows (include/p2t_hip.h, p2t_doc_prepare): one block per batch row.  Valid token t (mask a plain prefix of length n)
+// belongs to the document that starts at s = t - pos[t] and ends (exclusive) where the next document starts, or at n; a padding
+// token is a document of its own (start t, end t + 1: it sees no valid key and no query sees it).  Whatever the input, every start
+// lies in [0, t] and every end in [t + 1, T], so the loop bounds the attention kernels derive from them stay inside the row;
+// malformed input sets flags bit 0, and the caller refuses it before any attention kernel runs.
+template <typename P>
+__global__ void __launch_bounds__(256) doc_prepare_kernel(const P* __restrict__ pos, const int64_t* __restrict__ mask, int T,
+                                                          int32_t* __restrict__ docs, int32_t* __restrict__ flags) {
+    __shared__ int s_end[4], s_cnt[4];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const P* pr = pos + (int64_t)b * T;
+    const int64_t* mr = mask + (int64_t)b * T;
+    int32_t* st = docs + (int64_t)b * T;
+    int32_t* en = docs + (int64_t)gridDim.x * T + (int64_t)b * T;
+    int end = 0, cnt = 0, bits = 0;
+    for (int t = threadIdx.x; t < T; t += 256) {
+        const bool v = mr[t] != 0;
+        if (v) { end = t + 1; ++cnt; }
+        if ((int64_t)pr[t] != t) bits |= 2;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { end = max(end, __shfl_xor(end, o, 64)); cnt += __shfl_xor(cnt, o, 64); }
+    if (lane == 0) { s_end[w] = end; s_cnt[w] = cnt; }
+    __syncthreads();
+    const int n = max(max(s_end[0], s_end[1]), max(s_end[2], s_end[3]));
+    if (s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3] != n) bits |= 1;                  // not right-padded
+    for (int t = threadIdx.x; t < T; t += 256) {
+        int s = t;
+        if (t < n) {
+            const int64_t p = (int64_t)pr[t];
+            const bool ok = p >= 0 && p <= t && (t == 0 ? p == 0 : (p == 0 || p == (int64_t)pr[t - 1] + 1));
+            if (ok) s = t - (int)p; else bits |= 1;
+        }
+        st[t] = s;
+    }
+    __syncthreads();                                     // the starts of the whole row are visible to the block
+    for (int t = threadIdx.x; t < T; t += 256) {
+        int e = t + 1;
+        if (t < n) {                                     // first index after t whose start differs (starts are non-decreasing when valid)
+            const int s = st[t];
+            int lo = t + 1, hi = n;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (st[mid] > s) hi = mid; else lo = mid + 1;
+            }
+            e = lo;
+        }
+        en[t] = e;
+    }
+    if (bits) atomicOr(flags, bits);
+}
+
 // x[m, :] = mask[m] * ((id == <mask> ? 0 : table[id]) * 0.88 / (1 - ratio_b)); one wave per token.
 template <typename T>
 __global__ void __launch_bounds__(256) esm_embed_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ mask,
@@ -128,9 +180,12 @@ __global__ void __launch_bounds__(256) rope_table_kernel(const float* __restrict
 template <typename T>
 __global__ void __launch_bounds__(256) qkv_post_kernel(const T* __restrict__ qkv, int64_t ldq, const float* __restrict__ cs,
                                                        T* __restrict__ q, T* __restrict__ k, T* __restrict__ v, int seq,
-                                                       int nh, int nkv, int d, int dp, float q_scale) {
+                                                       int nh, int nkv, int d, int dp, float q_scale, const int32_t* __restrict__ docs,
+                                                       int perm128) {
     const int b = blockIdx.z, hh = blockIdx.y, t0 = blockIdx.x * 64;
     const int half = d / 2;
+    // perm128: the head's columns come in the row order of p2t_llama_layer.qkv_w at head_dim 128 (32-column blocks 0, 2, 1, 3)
+    auto col = [perm128](int c) { return perm128 && (unsigned)((c >> 5) - 1) < 2u ? c ^ 96 : c; };
     if (hh < nh + nkv) {
         const bool is_q = hh < nh;
         const int head = is_q ? hh : hh - nh;
@@ -144,8 +199,9 @@ __global__ void __launch_bounds__(256) qkv_post_kernel(const T* __restrict__ qkv
             float o1 = 0.f, o2 = 0.f;
             const T* src = qkv + ((int64_t)b * seq + t) * ldq + col0;
             if (j < half) {
-                const float x1 = to_f32(src[j]) * sc, x2 = to_f32(src[j + half]) * sc;
-                const float c = cs[(int64_t)t * d + j], s = cs[(int64_t)t * d + half + j];
+                const int pt = docs ? t - docs[(int64_t)b * seq + t] : t;          // packed rows: the position inside the document
+                const float x1 = to_f32(src[col(j)]) * sc, x2 = to_f32(src[col(j + half)]) * sc;
+                const float c = cs[(int64_t)pt * d + j], s = cs[(int64_t)pt * d + half + j];
                 o1 = x1 * c - x2 * s;
                 o2 = x2 * c + x1 * s;
             }
@@ -168,7 +224,7 @@ __global__ void __launch_bounds__(256) qkv_post_kernel(const T* __restrict__ qkv
         T* dst = v + ((int64_t)(b * nkv + head) * seq) * dp;
         for (int i = threadIdx.x; i < 64 * dp; i += 256) {
             const int tl = i / dp, c = i % dp, t = t0 + tl;
-            if (t < seq) dst[(int64_t)t * dp + c] = c < d ? qkv[((int64_t)b * seq + t) * ldq + col0 + c] : from_f32<T>(0.f);
+            if (t < seq) dst[(int64_t)t * dp + c] = c < d ? qkv[((int64_t)b * seq + t) * ldq + col0 + col(c)] : from_f32<T>(0.f);
         }
     }
 }
@@ -180,7 +236,7 @@ template <typename T>
 __global__ void __launch_bounds__(256) qk_norm_rope_kernel(const T* __restrict__ qkv, int64_t ldq, const float* __restrict__ cs,
                                                            const float* __restrict__ qw, const float* __restrict__ kw, float eps,
                                                            T* __restrict__ q, T* __restrict__ k, T* __restrict__ v, int64_t rows, int seq,
-                                                           int nh, int nkv, int d, int dp, float q_scale) {
+                                                           int nh, int nkv, int d, int dp, float q_scale, const int32_t* __restrict__ docs) {
     const int lane = threadIdx.x & 63, heads = nh + 2 * nkv, half = d / 2;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -199,7 +255,8 @@ __global__ void __launch_bounds__(256) qk_norm_rope_kernel(const T* __restrict__
         dst = is_q ? q + (((int64_t)b * nh + hh) * seq + t) * dp : k + (((int64_t)b * nkv + (hh - nh)) * seq + t) * dp;
         if (lane < half) {
             const float a1 = w[lane] * (x1 * rstd), a2 = w[lane + half] * (x2 * rstd);
-            const float c = cs[(int64_t)t * d + lane], s = cs[(int64_t)t * d + half + lane];
+            const int pt = docs ? t - docs[bt] : t;
+            const float c = cs[(int64_t)pt * d + lane], s = cs[(int64_t)pt * d + half + lane];
             const float qs = is_q ? q_scale : 1.0f;              // (the towers fold the softmax scale into q: kernels.h attention())
             dst[lane] = from_f32<T>((a1 * c - a2 * s) * qs);
             dst[lane + half] = from_f32<T>((a2 * c + a1 * s) * qs);
@@ -212,16 +269,17 @@ __global__ void __launch_bounds__(256) qk_norm_rope_kernel(const T* __restrict__
 }
 
 int launch_qk_norm_rope(const void* qkv, int64_t ldq, const float* cs, const float* q_norm_w, const float* k_norm_w, float eps, void* q,
-                        void* k, void* v, int B, int T, int nh, int nkv, int d, int dp, float q_scale, int dtype, hipStream_t s) {
+                        void* k, void* v, int B, int T, int nh, int nkv, int d, int dp, float q_scale, int dtype, hipStream_t s,
+                        const int32_t* docs) {
     P2T_REQUIRE(d % 2 == 0 && d <= 128 && dp >= d && dp <= 128 && q_norm_w && k_norm_w, "qk_norm_rope: head_dim %d (padded %d) unsupported", d, dp);
     const int64_t rows = (int64_t)B * T * (nh + 2 * nkv);
     const dim3 grid((unsigned)ceil_div(rows, 4));
     if (dtype == P2T_BF16)
         qk_norm_rope_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)qkv, ldq, cs, q_norm_w, k_norm_w, eps, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v,
-                                                          rows, T, nh, nkv, d, dp, q_scale);
+                                                          rows, T, nh, nkv, d, dp, q_scale, docs);
     else
         qk_norm_rope_kernel<float><<<grid, 256, 0, s>>>((const float*)qkv, ldq, cs, q_norm_w, k_norm_w, eps, (float*)q, (float*)k, (float*)v, rows,
-                                                         T, nh, nkv, d, dp, q_scale);
+                                                         T, nh, nkv, d, dp, q_scale, docs);
     P2T_LAUNCH_CHECK();
     return P2T_OK;
 }
@@ -229,6 +287,13 @@ int launch_qk_norm_rope(const void* qkv, int64_t ldq, const float* cs, const flo
 int launch_mask_prepare(const int64_t* ids, const int64_t* mask, int B, int T, int mask_id, int token_dropout,
                         uint8_t* key_mask, int32_t* kv_info, float* emb_scale, hipStream_t s) {
     mask_prepare_kernel<<<B, 256, 0, s>>>(ids, mask, T, mask_id, token_dropout, key_mask, kv_info, emb_scale);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
+int launch_doc_prepare(const void* pos, int pos_i64, const int64_t* mask, int B, int T, int32_t* docs, int32_t* flags, hipStream_t s) {
+    if (pos_i64) doc_prepare_kernel<int64_t><<<B, 256, 0, s>>>((const int64_t*)pos, mask, T, docs, flags);
+    else doc_prepare_kernel<int32_t><<<B, 256, 0, s>>>((const int32_t*)pos, mask, T, docs, flags);
     P2T_LAUNCH_CHECK();
     return P2T_OK;
 }
@@ -269,13 +334,13 @@ int launch_rope_table(const float* inv_freq, int T, int half, float* cs, hipStre
 }
 
 int launch_qkv_post(const void* qkv, int64_t ldq, const float* cs, void* q, void* k, void* v, int B, int T, int nh,
-                    int nkv, int d, int dp, float q_scale, int dtype, hipStream_t s) {
-    P2T_REQUIRE(d % 2 == 0 && d <= 128 && dp >= d && dp <= 128 && dp % 2 == 0, "qkv_post: head_dim %d (padded %d) unsupported", d, dp);
+                    int nkv, int d, int dp, float q_scale, int dtype, hipStream_t s, const int32_t* docs, int perm128) {
+    P2T_REQUIRE(d % 2 == 0 && d <= 128 && dp >= d && dp <= 128 && dp % 2 == 0 && (!perm128 || d == 128), "qkv_post: head_dim %d (padded %d) unsupported", d, dp);
     const dim3 grid((unsigned)ceil_div(T, 64), (unsigned)(nh + 2 * nkv), (unsigned)B);
     if (dtype == P2T_BF16)
-        qkv_post_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)qkv, ldq, cs, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v, T, nh, nkv, d, dp, q_scale);
+        qkv_post_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)qkv, ldq, cs, (bf16_t*)q, (bf16_t*)k, (bf16_t*)v, T, nh, nkv, d, dp, q_scale, docs, perm128);
     else
-        qkv_post_kernel<float><<<grid, 256, 0, s>>>((const float*)qkv, ldq, cs, (float*)q, (float*)k, (float*)v, T, nh, nkv, d, dp, q_scale);
+        qkv_post_kernel<float><<<grid, 256, 0, s>>>((const float*)qkv, ldq, cs, (float*)q, (float*)k, (float*)v, T, nh, nkv, d, dp, q_scale, docs, perm128);
     P2T_LAUNCH_CHECK();
     return P2T_OK;
 }

@@ -116,28 +116,30 @@ int gemm_nt(const GemmArgs& a, hipStream_t s) {
 
 int attention(const void* q, const void* k, const void* v, const uint8_t* key_mask, const int32_t* kv_info, void* out,
               int64_t ld_out, int B, int T, int nh, int nkv, int d, int dp, float scale, int causal, int dtype, int use_mfma,
-              int log2_scores, hipStream_t s, float* lse) {
+              int log2_scores, hipStream_t s, float* lse, const int32_t* docs) {
     P2T_REQUIRE(q && k && v && key_mask && kv_info && out && B > 0 && T > 0 && nh > 0 && nkv > 0, "attention: bad arguments");
     P2T_REQUIRE(ld_out >= (int64_t)nh * d, "attention: ld_out too small");
+    P2T_REQUIRE(!docs || causal, "attention: documents (packed rows) need the causal mask");
     if (dtype == P2T_BF16 && use_mfma != 0) {
         const int pi = prof_begin(s, 1, 4.0 * B * nh * (double)T * T * d * (causal ? 0.5 : 1.0));
         // use_mfma: 2 = the general kernel (attn_mfma.hip) even where the hand-placed one applies; 3 = require the hand-placed one
         // (a forward that also returns the log-sum-exps -- the stage-2 training forward -- stays on the general kernel unless the
         // hand-placed one is asked for: its row sums are taken over the bf16-rounded probabilities, 3e-4 off the fp32 sums the exact
         // backward rebuilds P from; the frozen towers of the contrastive step never ask for them)
-        const bool hand = use_mfma != 2 && (lse == nullptr || use_mfma == 3) && attn_fwd64_eligible(ld_out, T, nh, nkv, d, dp, log2_scores);
+        // (packed rows never take the hand-placed kernel: it has no documents)
+        const bool hand = !docs && use_mfma != 2 && (lse == nullptr || use_mfma == 3) && attn_fwd64_eligible(ld_out, T, nh, nkv, d, dp, log2_scores);
         if (use_mfma == 3 && !hand) {
-            set_error("attention: the hand-placed kernel needs head_dim padded to 64, d %% 8 == 0 and log2_scores (d=%d dp=%d)", d, dp);
+            set_error("attention: the hand-placed kernel needs head_dim padded to 64, d %% 8 == 0, log2_scores and no documents (d=%d dp=%d)", d, dp);
             return P2T_ERR_UNSUPPORTED;
         }
         const int rc = hand ? launch_attn_fwd64(q, k, v, key_mask, kv_info, out, ld_out, B, T, nh, nkv, d, causal, lse, s)
-                            : launch_attn_mfma(q, k, v, key_mask, kv_info, out, ld_out, B, T, nh, nkv, d, dp, scale, causal, log2_scores, lse, s);
+                            : launch_attn_mfma(q, k, v, key_mask, kv_info, out, ld_out, B, T, nh, nkv, d, dp, scale, causal, log2_scores, lse, s, docs);
         prof_end(s, pi);
         return rc;
     }
     P2T_REQUIRE(use_mfma <= 0, "attention: MFMA kernel needs bf16");
     // exp(ln 2 * (s - m)) = 2^(s - m)
-    return launch_attn_simple(q, k, v, key_mask, kv_info, out, ld_out, B, T, nh, nkv, d, dp, log2_scores ? kLn2 : scale, causal, dtype, lse, s);
+    return launch_attn_simple(q, k, v, key_mask, kv_info, out, ld_out, B, T, nh, nkv, d, dp, log2_scores ? kLn2 : scale, causal, dtype, lse, s, docs);
 }
 
 }  // namespace p2t
@@ -274,6 +276,31 @@ extern "C" int p2t_attention(const void* q, const void* k, const void* v, const 
                              int dtype, int use_mfma, int log2_scores, float* lse, p2t_stream stream) {
     return attention(q, k, v, key_mask, kv_info, out, ld_out, B, T, nh, nkv, d, dp, scale, causal, dtype, use_mfma, log2_scores,
                      (hipStream_t)stream, lse);
+}
+
+extern "C" int p2t_doc_prepare(const void* position_ids, int pos_i64, const int64_t* mask, int B, int T, int32_t* docs, int32_t* flags,
+                               p2t_stream stream) {
+    P2T_REQUIRE(position_ids && mask && docs && flags && B > 0 && T > 0, "p2t_doc_prepare: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    P2T_CHECK_HIP(hipMemsetAsync(flags, 0, sizeof(int32_t), s));
+    return launch_doc_prepare(position_ids, pos_i64, mask, B, T, docs, flags, s);
+}
+
+extern "C" int p2t_qkv_post_docs(const void* qkv, int64_t ldq, const float* inv_freq, float* cos_sin_scratch, const int32_t* docs, void* q,
+                                 void* k, void* v, int B, int T, int nh, int nkv, int d, int dp, float q_scale, int dtype, p2t_stream stream) {
+    P2T_REQUIRE(qkv && inv_freq && cos_sin_scratch && docs && q && k && v, "p2t_qkv_post_docs: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    P2T_TRY(launch_rope_table(inv_freq, T, d / 2, cos_sin_scratch, s));
+    return launch_qkv_post(qkv, ldq, cos_sin_scratch, q, k, v, B, T, nh, nkv, d, dp, q_scale, dtype, s, docs);
+}
+
+extern "C" int p2t_attention_docs(const void* q, const void* k, const void* v, const uint8_t* key_mask, const int32_t* kv_info, const int32_t* docs,
+                                  void* out, int64_t ld_out, int B, int T, int nh, int nkv, int d, int dp, float scale, int dtype, int use_mfma,
+                                  int log2_scores, float* lse, p2t_stream stream) {
+    P2T_REQUIRE(docs, "p2t_attention_docs: null docs");
+    P2T_REQUIRE(use_mfma != 3, "p2t_attention_docs: the hand-placed kernel has no documents");
+    return attention(q, k, v, key_mask, kv_info, out, ld_out, B, T, nh, nkv, d, dp, scale, 1, dtype, use_mfma, log2_scores, (hipStream_t)stream,
+                     lse, docs);
 }
 
 // The decode step's GEMM on its own (gemm_skinny.hip): see include/p2t_hip.h

@@ -27,11 +27,17 @@ int launch_llama_embed(const int64_t* ids, const void* table, int dtype, int H, 
 int launch_inv_freq(float* inv_freq, int half, float theta, int llama3, float factor, float low_ff, float high_ff,
                     float orig_max_pos, hipStream_t s);
 int launch_rope_table(const float* inv_freq, int T, int half, float* cs, hipStream_t s);
+// docs (optional): i32 [2][B][T] from launch_doc_prepare (packed rows): the rotation of token t uses position t - docs[0][b][t].
+// perm128: qkv comes from p2t_llama_layer.qkv_w at head_dim 128, whose rows are permuted per head for the fused rotary epilogue
 int launch_qkv_post(const void* qkv, int64_t ldq, const float* cs, void* q, void* k, void* v, int B, int T, int nh, int nkv,
-                    int d, int dp, float q_scale, int dtype, hipStream_t s);
+                    int d, int dp, float q_scale, int dtype, hipStream_t s, const int32_t* docs = nullptr, int perm128 = 0);
+// packed rows (include/p2t_hip.h, p2t_doc_prepare): position_ids (i64 or i32) + mask -> docs i32 [2][B][T] (document start, end)
+// and flags |= 1 (malformed) / 2 (not an arange); flags must be zeroed first
+int launch_doc_prepare(const void* pos, int pos_i64, const int64_t* mask, int B, int T, int32_t* docs, int32_t* flags, hipStream_t s);
 
 int launch_qk_norm_rope(const void* qkv, int64_t ldq, const float* cs, const float* q_norm_w, const float* k_norm_w, float eps, void* q,
-                        void* k, void* v, int B, int T, int nh, int nkv, int d, int dp, float q_scale, int dtype, hipStream_t s);
+                        void* k, void* v, int B, int T, int nh, int nkv, int d, int dp, float q_scale, int dtype, hipStream_t s,
+                        const int32_t* docs = nullptr);
 
 int launch_gemm_simple(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int N, int K, int n_cover, int dtype,
                        int out_dtype, int epilogue, const EpiParams& ep, hipStream_t s);
@@ -138,9 +144,10 @@ int launch_preshuffle_fp8(const void* W, int64_t ldw, int64_t N, int64_t K, void
 
 int launch_attn_simple(const void* q, const void* k, const void* v, const uint8_t* key_mask, const int32_t* kv_info, void* out,
                        int64_t ld_out, int B, int T, int nh, int nkv, int d, int dp, float scale, int causal, int dtype,
-                       float* lse, hipStream_t s);
+                       float* lse, hipStream_t s, const int32_t* docs = nullptr);
 int launch_attn_mfma(const void* q, const void* k, const void* v, const uint8_t* key_mask, const int32_t* kv_info, void* out,
-                     int64_t ld_out, int B, int T, int nh, int nkv, int d, int dp, float scale, int causal, int log2_scores, float* lse, hipStream_t s);
+                     int64_t ld_out, int B, int T, int nh, int nkv, int d, int dp, float scale, int causal, int log2_scores, float* lse, hipStream_t s,
+                     const int32_t* docs = nullptr);
 // hand-placed form for head_dim padded to 64 with log2-scores q (attn_fwd64.hip; tools/gen_attn_fwd64.py writes its loop)
 bool attn_fwd64_eligible(int64_t ld_out, int T, int nh, int nkv, int d, int dp, int log2_scores);
 int launch_attn_fwd64(const void* q, const void* k, const void* v, const uint8_t* key_mask, const int32_t* kv_info, void* out, int64_t ld_out,
@@ -149,9 +156,13 @@ int launch_attn_fwd64(const void* q, const void* k, const void* v, const uint8_t
 // ignored and p = exp2(s - m).  The towers do this for bf16 models (one multiply + add less per score in the MFMA kernel).
 int attention(const void* q, const void* k, const void* v, const uint8_t* key_mask, const int32_t* kv_info, void* out,
               int64_t ld_out, int B, int T, int nh, int nkv, int d, int dp, float scale, int causal, int dtype, int use_mfma,
-              int log2_scores, hipStream_t s, float* lse = nullptr);
+              int log2_scores, hipStream_t s, float* lse = nullptr, const int32_t* docs = nullptr);
 // lse (optional, f32 [B, nh, T]): natural-log sum-exp of the effective logits (scale * q.k, or ln 2 * q.k with log2_scores) of
 // every query row, +inf for a row without a visible key -- what the attention backward (llama_train.hip) rebuilds P from.
+// docs (optional, causal only): i32 [2][B][T] from launch_doc_prepare.  Query t sees keys docs[0][b][t] <= key <= t; both rows are
+// non-decreasing in t, so the first query of a tile holds its smallest start and the last key of a tile its largest end: the
+// kernels start the key loop at the tile's first start (64-key blocks wholly before it are skipped, not masked) and end the
+// query loop of a key tile at its last end.  Never the hand-placed kernel.
 constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
 
 // stage-2 training through the frozen decoder (llama_train.hip): the per-layer activations the backward reads again
@@ -169,9 +180,10 @@ struct LlamaTape {
     LlamaTapeLayer layer[kMaxLayers];
 };
 size_t llama_tape_plan(const p2t_llama_config* c, int B, int T, void* base, size_t bytes, LlamaTape* tape);
+// docs (optional, packed rows): i32 [2][B][T] from launch_doc_prepare -- positional rotary and document-confined attention
 int llama_forward_impl(const p2t_llama_config* c, const p2t_llama_weights* w, const int64_t* ids, const float* inputs_embeds, const int64_t* mask,
                        int B, int T, int k, float* out, void* workspace, size_t workspace_bytes, p2t_stream stream, const LlamaTape* tape,
-                       const p2t_kv_cache* kv = nullptr);
+                       const p2t_kv_cache* kv = nullptr, const int32_t* docs = nullptr);
 // generation prefill (llama_decode.hip): layer l's rotated keys / values ([B, kv_heads, T, dp]) -> the prompt segment of the cache
 int llama_kv_store(const p2t_llama_config* c, const p2t_kv_cache* kc, int layer, const void* k, const void* v, int B, int T, hipStream_t s);
 int launch_swiglu_from_gu(const void* gu, int64_t ld_gu, void* act, int64_t ld_act, int64_t M, int64_t F, int dtype, hipStream_t s);

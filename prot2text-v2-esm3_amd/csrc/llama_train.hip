@@ -167,7 +167,8 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
                                                           const T* __restrict__ o, int64_t ld_o, const T* __restrict__ d_o, int64_t ld_do,
                                                           const float* __restrict__ lse, const uint8_t* __restrict__ key_mask,
                                                           const int32_t* __restrict__ kv_end, float* __restrict__ dq, float* __restrict__ D,
-                                                          int seq, int nh, int nkv, int d, int dp, float c_s, int causal) {
+                                                          int seq, int nh, int nkv, int d, int dp, float c_s, int causal,
+                                                          const int32_t* __restrict__ docs) {
     __shared__ float s_q[4][128];
     __shared__ float s_do[4][128];
     __shared__ float s_ds[4][64];
@@ -192,11 +193,12 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
     if (lane == 0) D[(int64_t)(b * nh + h) * seq + i] = dd;
     int end = kv_end[b];
     if (causal) end = min(end, i + 1);
+    const int lo = docs ? docs[(int64_t)b * seq + i] : 0;           // packed rows: the first key of this query's document
     float acc0 = 0.f, acc1 = 0.f;
-    for (int j0 = 0; j0 < end; j0 += 64) {
+    for (int j0 = lo & ~63; j0 < end; j0 += 64) {
         const int j = j0 + lane;
         float ds = 0.f;
-        if (j < end && key_mask[(int64_t)b * seq + j]) {
+        if (j >= lo && j < end && key_mask[(int64_t)b * seq + j]) {
             const T* kr = kbase + (int64_t)j * dp;
             const T* vr = vbase + (int64_t)j * dp;
             float dot = 0.f, dpj = 0.f;
@@ -228,7 +230,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const T* __restrict__
                                                            const T* __restrict__ d_o, int64_t ld_do, const float* __restrict__ lse,
                                                            const float* __restrict__ D, const uint8_t* __restrict__ key_mask,
                                                            float* __restrict__ dk, float* __restrict__ dv, int seq, int nh, int nkv, int d,
-                                                           int dp, float c_s, int causal) {
+                                                           int dp, float c_s, int causal, const int32_t* __restrict__ docs) {
     __shared__ float s_k[4][128];
     __shared__ float s_v[4][128];
     __shared__ float s_p[4][64];
@@ -247,16 +249,17 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const T* __restrict__
     const T* vrow = v + ((int64_t)(b * nkv + hk) * seq + j) * dp;
     for (int c = lane; c < dp; c += 64) { s_k[w][c] = to_f32(krow[c]); s_v[w][c] = to_f32(vrow[c]); }
     const int rep = nh / nkv;
+    const int qend = docs ? min(seq, docs[((int64_t)gridDim.z + b) * seq + j]) : seq;      // packed rows: the end of this key's document
     float ak0 = 0.f, ak1 = 0.f, av0 = 0.f, av1 = 0.f;
     for (int r = 0; r < rep; ++r) {
         const int h = hk * rep + r;
         const T* qbase = q + ((int64_t)(b * nh + h) * seq) * dp;
         const float* lrow = lse + (int64_t)(b * nh + h) * seq;
         const float* Drow = D + (int64_t)(b * nh + h) * seq;
-        for (int i0 = causal ? (j & ~63) : 0; i0 < seq; i0 += 64) {
+        for (int i0 = causal ? (j & ~63) : 0; i0 < qend; i0 += 64) {
             const int i = i0 + lane;
             float p = 0.f, ds = 0.f;
-            if (i < seq && (!causal || i >= j)) {
+            if (i < qend && (!causal || i >= j)) {
                 const T* qr = qbase + (int64_t)i * dp;
                 const T* dor = d_o + ((int64_t)b * seq + i) * ld_do + (int64_t)h * d;
                 float dot = 0.f, dpj = 0.f;
@@ -272,7 +275,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const T* __restrict__
             }
             s_p[w][lane] = p;
             s_ds[w][lane] = ds;
-            const int ni = min(64, seq - i0);
+            const int ni = min(64, qend - i0);
             if (lane < d) {
                 for (int ii = 0; ii < ni; ++ii) {
                     av0 = fmaf(s_p[w][ii], to_f32(d_o[((int64_t)b * seq + i0 + ii) * ld_do + (int64_t)h * d + lane]), av0);
@@ -299,32 +302,34 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const T* __restrict__
 
 int launch_attn_bwd_mfma(const void* q, const void* k, const void* v, const void* o, int64_t ld_o, const void* d_o, int64_t ld_do, const float* lse,
                          const uint8_t* key_mask, const int32_t* kv_info, float* dq, float* dk, float* dv, float* D, int B, int T, int nh, int nkv,
-                         int d, int dp, int causal, hipStream_t s);       // attn_bwd_mfma.hip
+                         int d, int dp, int causal, hipStream_t s, const int32_t* docs);       // attn_bwd_mfma.hip
 
 // c_s: the factor between q.k and the logits (the softmax scale, or ln 2 in the log2_scores form).  use_mfma: -1 auto (the MFMA
 // kernels for bf16 + log2_scores + head_dim 64 / 128), 0 the exact kernels, 1 require MFMA.
 int launch_attn_bwd(const void* q, const void* k, const void* v, const void* o, int64_t ld_o, const void* d_o, int64_t ld_do, const float* lse,
                     const uint8_t* key_mask, const int32_t* kv_info, float* dq, float* dk, float* dv, float* D, int B, int T, int nh, int nkv,
-                    int d, int dp, float c_s, int causal, int dtype, hipStream_t s, int log2_scores = 0, int use_mfma = 0) {
+                    int d, int dp, float c_s, int causal, int dtype, hipStream_t s, int log2_scores = 0, int use_mfma = 0,
+                    const int32_t* docs = nullptr) {
     P2T_REQUIRE(q && k && v && o && d_o && lse && key_mask && kv_info && dq && dk && dv && D, "attention backward: null argument");
+    P2T_REQUIRE(!docs || causal, "attention backward: documents (packed rows) need the causal mask");
     P2T_REQUIRE(d % 4 == 0 && d <= 128 && (dp == 32 || dp == 64 || dp == 128) && d <= dp && nh % nkv == 0 && ld_o % 4 == 0 && ld_do % 4 == 0,
                 "attention backward: unsupported shape d=%d dp=%d heads %d/%d", d, dp, nh, nkv);
     if (dtype == P2T_BF16 && log2_scores && use_mfma != 0) {
-        const int rc = launch_attn_bwd_mfma(q, k, v, o, ld_o, d_o, ld_do, lse, key_mask, kv_info, dq, dk, dv, D, B, T, nh, nkv, d, dp, causal, s);
+        const int rc = launch_attn_bwd_mfma(q, k, v, o, ld_o, d_o, ld_do, lse, key_mask, kv_info, dq, dk, dv, D, B, T, nh, nkv, d, dp, causal, s, docs);
         if (rc != P2T_ERR_UNSUPPORTED) return rc;
     }
     P2T_REQUIRE(use_mfma != 1, "attention backward: the MFMA kernels need bf16, log2_scores and head_dim 64 / 128");
     const dim3 gq((unsigned)ceil_div(T, 4), (unsigned)nh, (unsigned)B), gk((unsigned)ceil_div(T, 4), (unsigned)nkv, (unsigned)B);
     if (dtype == P2T_BF16) {
         attn_bwd_dq_kernel<bf16_t><<<gq, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)o, ld_o, (const bf16_t*)d_o,
-                                                      ld_do, lse, key_mask, kv_info, dq, D, T, nh, nkv, d, dp, c_s, causal);
+                                                      ld_do, lse, key_mask, kv_info, dq, D, T, nh, nkv, d, dp, c_s, causal, docs);
         attn_bwd_dkv_kernel<bf16_t><<<gk, 256, 0, s>>>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, ld_do, lse, D, key_mask,
-                                                       dk, dv, T, nh, nkv, d, dp, c_s, causal);
+                                                       dk, dv, T, nh, nkv, d, dp, c_s, causal, docs);
     } else {
         attn_bwd_dq_kernel<float><<<gq, 256, 0, s>>>((const float*)q, (const float*)k, (const float*)v, (const float*)o, ld_o, (const float*)d_o, ld_do,
-                                                     lse, key_mask, kv_info, dq, D, T, nh, nkv, d, dp, c_s, causal);
+                                                     lse, key_mask, kv_info, dq, D, T, nh, nkv, d, dp, c_s, causal, docs);
         attn_bwd_dkv_kernel<float><<<gk, 256, 0, s>>>((const float*)q, (const float*)k, (const float*)v, (const float*)d_o, ld_do, lse, D, key_mask, dk,
-                                                      dv, T, nh, nkv, d, dp, c_s, causal);
+                                                      dv, T, nh, nkv, d, dp, c_s, causal, docs);
     }
     P2T_LAUNCH_CHECK();
     return P2T_OK;
@@ -337,7 +342,7 @@ int launch_attn_bwd(const void* q, const void* k, const void* v, const void* o, 
 template <typename T>
 __global__ void __launch_bounds__(256) rope_bwd_pack_kernel(const float* __restrict__ dq, const float* __restrict__ dk, const float* __restrict__ dv,
                                                             const float* __restrict__ cs, T* __restrict__ out, int64_t ld, int64_t rows, int seq,
-                                                            int nh, int nkv, int d, int dp, float q_scale) {
+                                                            int nh, int nkv, int d, int dp, float q_scale, const int32_t* __restrict__ docs) {
     const int lane = threadIdx.x & 63, heads = nh + 2 * nkv, half = d / 2;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -351,7 +356,8 @@ __global__ void __launch_bounds__(256) rope_bwd_pack_kernel(const float* __restr
         const float* src = is_q ? dq + (((int64_t)b * nh + hh) * seq + t) * dp : dk + (((int64_t)b * nkv + (hh - nh)) * seq + t) * dp;
         const float sc = is_q ? q_scale : 1.0f;
         const float o1 = src[lane] * sc, o2 = src[lane + half] * sc;
-        const float c = cs[(int64_t)t * d + lane], s = cs[(int64_t)t * d + half + lane];
+        const int pt = docs ? t - docs[bt] : t;                  // packed rows: the position inside the document
+        const float c = cs[(int64_t)pt * d + lane], s = cs[(int64_t)pt * d + half + lane];
         dst[lane] = from_f32<T>(o1 * c + o2 * s);
         dst[lane + half] = from_f32<T>(o2 * c - o1 * s);
     } else {
@@ -362,25 +368,26 @@ __global__ void __launch_bounds__(256) rope_bwd_pack_kernel(const float* __restr
 }
 
 int launch_rope_bwd_pack(const float* dq, const float* dk, const float* dv, const float* cs, void* out, int64_t ld, int B, int T, int nh, int nkv,
-                         int d, int dp, float q_scale, int dtype, hipStream_t s) {
+                         int d, int dp, float q_scale, int dtype, hipStream_t s, const int32_t* docs = nullptr) {
     P2T_REQUIRE(d % 2 == 0 && d <= 128 && dp >= d, "rope backward: head_dim %d unsupported", d);
     const int64_t rows = (int64_t)B * T * (nh + 2 * nkv);
     const dim3 grid((unsigned)ceil_div(rows, 4));
     if (dtype == P2T_BF16)
-        rope_bwd_pack_kernel<bf16_t><<<grid, 256, 0, s>>>(dq, dk, dv, cs, (bf16_t*)out, ld, rows, T, nh, nkv, d, dp, q_scale);
+        rope_bwd_pack_kernel<bf16_t><<<grid, 256, 0, s>>>(dq, dk, dv, cs, (bf16_t*)out, ld, rows, T, nh, nkv, d, dp, q_scale, docs);
     else
-        rope_bwd_pack_kernel<float><<<grid, 256, 0, s>>>(dq, dk, dv, cs, (float*)out, ld, rows, T, nh, nkv, d, dp, q_scale);
+        rope_bwd_pack_kernel<float><<<grid, 256, 0, s>>>(dq, dk, dv, cs, (float*)out, ld, rows, T, nh, nkv, d, dp, q_scale, docs);
     P2T_LAUNCH_CHECK();
     return P2T_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
 // d loss / d logits of p2t_cross_entropy_shifted: row (b, t) with a counted target y = labels[b, t+1]:
-// (softmax(logits) - onehot(y)) / count; every other row and the padding columns: 0.  One block per row.
+// (softmax(logits) - onehot(y)) / count -- or, with per-target weights, weights[b, t+1] (softmax - onehot); every other row and the
+// padding columns: 0.  One block per row.
 template <typename T>
 __global__ void __launch_bounds__(256) ce_bwd_rows_kernel(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels, int seq, int V,
                                                           int64_t ignore_index, const int32_t* __restrict__ count, T* __restrict__ dl, int64_t ld_d,
-                                                          int cols_d) {
+                                                          int cols_d, const float* __restrict__ weights) {
     __shared__ float red[4];
     const int64_t row = blockIdx.x;
     const int t = (int)(row % seq);
@@ -401,7 +408,8 @@ __global__ void __launch_bounds__(256) ce_bwd_rows_kernel(const T* __restrict__ 
     float sum = 0.f;
     for (int c = threadIdx.x; c < V; c += 256) sum += expf(to_f32(x[c]) - m);
     sum = block_sum<4>(sum, red);
-    const float inv = 1.0f / (sum * (float)count[0]), invc = 1.0f / (float)count[0];
+    const float wr = weights ? weights[row + 1] : 0.f;
+    const float inv = weights ? wr / sum : 1.0f / (sum * (float)count[0]), invc = weights ? wr : 1.0f / (float)count[0];
     for (int c = threadIdx.x; c < cols_d; c += 256) {
         float g = 0.f;
         if (c < V) g = expf(to_f32(x[c]) - m) * inv - (c == (int)label ? invc : 0.f);
@@ -497,9 +505,9 @@ extern "C" size_t p2t_llama_train_workspace_bytes(const p2t_llama_config* cfg, i
     return fwd > bwd ? fwd : bwd;
 }
 
-extern "C" int p2t_llama_train_forward(const p2t_llama_config* c, const p2t_llama_weights* w, const float* inputs_embeds, const int64_t* mask,
-                                       int B, int T, float* out, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes,
-                                       p2t_stream stream) {
+namespace {
+int llama_train_forward_impl(const p2t_llama_config* c, const p2t_llama_weights* w, const float* inputs_embeds, const int64_t* mask, const int32_t* docs,
+                             int B, int T, float* out, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, p2t_stream stream) {
     P2T_REQUIRE(c && w && inputs_embeds && mask && out && tape && workspace && B > 0 && T > 0, "p2t_llama_train_forward: null/empty argument");
     P2T_REQUIRE(!c->gemm_fp8, "p2t_llama_train_forward: the training path runs the GEMMs in the model dtype (gemm_fp8 = 0)");
     P2T_REQUIRE(c->n_layers <= LlamaTape::kMaxLayers, "p2t_llama_train_forward: more than %d layers", LlamaTape::kMaxLayers);
@@ -507,12 +515,12 @@ extern "C" int p2t_llama_train_forward(const p2t_llama_config* c, const p2t_llam
     LlamaTape t;
     llama_tape_plan(c, B, T, tape, tape_bytes, &t);
     P2T_REQUIRE(!t.overflow, "p2t_llama_train_forward: tape overflow");
-    return llama_forward_impl(c, w, nullptr, inputs_embeds, mask, B, T, c->n_layers, out, workspace, workspace_bytes, stream, &t);
+    return llama_forward_impl(c, w, nullptr, inputs_embeds, mask, B, T, c->n_layers, out, workspace, workspace_bytes, stream, &t, nullptr, docs);
 }
 
-extern "C" int p2t_llama_train_backward(const p2t_llama_config* c, const p2t_llama_weights* w, const p2t_llama_layer_t* wT, const int64_t* mask,
-                                        int B, int T, const float* d_out, const void* tape, size_t tape_bytes, float* d_inputs_embeds,
-                                        void* workspace, size_t workspace_bytes, p2t_stream stream) {
+int llama_train_backward_impl(const p2t_llama_config* c, const p2t_llama_weights* w, const p2t_llama_layer_t* wT, const int64_t* mask, const int32_t* docs,
+                              int B, int T, const float* d_out, const void* tape, size_t tape_bytes, float* d_inputs_embeds, void* workspace,
+                              size_t workspace_bytes, p2t_stream stream) {
     P2T_REQUIRE(c && w && wT && mask && d_out && tape && d_inputs_embeds && workspace && B > 0 && T > 0, "p2t_llama_train_backward: null/empty argument");
     P2T_REQUIRE(!c->gemm_fp8 && c->n_layers <= LlamaTape::kMaxLayers, "p2t_llama_train_backward: unsupported configuration");
     P2T_REQUIRE(w->layers && w->final_norm_w, "p2t_llama_train_backward: missing weights");
@@ -569,12 +577,39 @@ extern "C" int p2t_llama_train_backward(const p2t_llama_config* c, const p2t_lla
         P2T_TRY(launch_cast_rows(g, P2T_F32, H, b.g16, dt, Hp, M, H, s));
         P2T_TRY(dx_gemm(b.g16, Hp, LT.o_wT, H, (int64_t)nh * d, b.d_ao, QO, dt, P2T_EPI_STORE));
         P2T_TRY(launch_attn_bwd(S.q, S.k, S.v, S.ao, QO, b.d_ao, QO, S.lse, b.key_mask, b.kv_info, b.dq, b.dk, b.dv, b.D, B, T, nh, nkv, d, dp, c_s, 1,
-                                dt, s, l2s, -1));
-        P2T_TRY(launch_rope_bwd_pack(b.dq, b.dk, b.dv, b.cs, b.d_qkv, NQp, B, T, nh, nkv, d, dp, q_fold, dt, s));
+                                dt, s, l2s, -1, docs));
+        P2T_TRY(launch_rope_bwd_pack(b.dq, b.dk, b.dv, b.cs, b.d_qkv, NQp, B, T, nh, nkv, d, dp, q_fold, dt, s, docs));
         P2T_TRY(dx_gemm(b.d_qkv, NQp, LT.qkv_wT, NQKV, H, b.d_h, H, P2T_F32, P2T_EPI_STORE_F32));
         P2T_TRY(launch_rmsnorm_bwd(S.x_in, H, L.ln1_w, c->rms_norm_eps, b.d_h, H, P2T_F32, g, H, M, H, 1, s));
     }
     return P2T_OK;
+}
+}  // namespace
+
+extern "C" int p2t_llama_train_forward(const p2t_llama_config* c, const p2t_llama_weights* w, const float* inputs_embeds, const int64_t* mask,
+                                       int B, int T, float* out, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes,
+                                       p2t_stream stream) {
+    return llama_train_forward_impl(c, w, inputs_embeds, mask, nullptr, B, T, out, tape, tape_bytes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int p2t_llama_train_backward(const p2t_llama_config* c, const p2t_llama_weights* w, const p2t_llama_layer_t* wT, const int64_t* mask,
+                                        int B, int T, const float* d_out, const void* tape, size_t tape_bytes, float* d_inputs_embeds,
+                                        void* workspace, size_t workspace_bytes, p2t_stream stream) {
+    return llama_train_backward_impl(c, w, wT, mask, nullptr, B, T, d_out, tape, tape_bytes, d_inputs_embeds, workspace, workspace_bytes, stream);
+}
+
+extern "C" int p2t_llama_train_forward_docs(const p2t_llama_config* c, const p2t_llama_weights* w, const float* inputs_embeds, const int64_t* mask,
+                                            const int32_t* docs, int B, int T, float* out, void* tape, size_t tape_bytes, void* workspace,
+                                            size_t workspace_bytes, p2t_stream stream) {
+    P2T_REQUIRE(docs, "p2t_llama_train_forward_docs: null docs");
+    return llama_train_forward_impl(c, w, inputs_embeds, mask, docs, B, T, out, tape, tape_bytes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int p2t_llama_train_backward_docs(const p2t_llama_config* c, const p2t_llama_weights* w, const p2t_llama_layer_t* wT, const int64_t* mask,
+                                             const int32_t* docs, int B, int T, const float* d_out, const void* tape, size_t tape_bytes,
+                                             float* d_inputs_embeds, void* workspace, size_t workspace_bytes, p2t_stream stream) {
+    P2T_REQUIRE(docs, "p2t_llama_train_backward_docs: null docs");
+    return llama_train_backward_impl(c, w, wT, mask, docs, B, T, d_out, tape, tape_bytes, d_inputs_embeds, workspace, workspace_bytes, stream);
 }
 
 extern "C" int p2t_attention_backward(const void* q, const void* k, const void* v, const void* o, int64_t ld_o, const void* d_o, int64_t ld_do,
@@ -600,10 +635,27 @@ extern "C" int p2t_cross_entropy_shifted_backward(const void* logits, int64_t ld
     const int cols_d = (int)(round_up(V, 64) < ld_d ? round_up(V, 64) : ld_d);          // the K padding of the LM-head dX GEMM is zeroed
     if (dtype == P2T_BF16)
         ce_bwd_rows_kernel<bf16_t><<<(unsigned)M, 256, 0, (hipStream_t)stream>>>((const bf16_t*)logits, ld, labels, T, V, ignore_index, count,
-                                                                                 (bf16_t*)d_logits, ld_d, cols_d);
+                                                                                 (bf16_t*)d_logits, ld_d, cols_d, nullptr);
     else
         ce_bwd_rows_kernel<float><<<(unsigned)M, 256, 0, (hipStream_t)stream>>>((const float*)logits, ld, labels, T, V, ignore_index, count,
-                                                                                (float*)d_logits, ld_d, cols_d);
+                                                                                (float*)d_logits, ld_d, cols_d, nullptr);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
+extern "C" int p2t_cross_entropy_shifted_weighted_backward(const void* logits, int64_t ld, int dtype, const int64_t* labels, const float* weights,
+                                                           int B, int T, int V, int64_t ignore_index, void* d_logits, int64_t ld_d, p2t_stream stream) {
+    P2T_REQUIRE(logits && labels && weights && d_logits && B > 0 && T > 0 && V > 0 && ld >= V && ld_d >= V,
+                "p2t_cross_entropy_shifted_weighted_backward: bad arguments");
+    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_cross_entropy_shifted_weighted_backward: unsupported dtype %d", dtype);
+    const int64_t M = (int64_t)B * T;
+    const int cols_d = (int)(round_up(V, 64) < ld_d ? round_up(V, 64) : ld_d);
+    if (dtype == P2T_BF16)
+        ce_bwd_rows_kernel<bf16_t><<<(unsigned)M, 256, 0, (hipStream_t)stream>>>((const bf16_t*)logits, ld, labels, T, V, ignore_index, nullptr,
+                                                                                 (bf16_t*)d_logits, ld_d, cols_d, weights);
+    else
+        ce_bwd_rows_kernel<float><<<(unsigned)M, 256, 0, (hipStream_t)stream>>>((const float*)logits, ld, labels, T, V, ignore_index, nullptr,
+                                                                                (float*)d_logits, ld_d, cols_d, weights);
     P2T_LAUNCH_CHECK();
     return P2T_OK;
 }
@@ -650,6 +702,25 @@ extern "C" int p2t_swiglu_gu(const void* gu, int64_t ld_gu, const void* d_act, i
     if (M == 0) return P2T_OK;
     if (d_act) return launch_swiglu_gu<true>(gu, ld_gu, d_act, ld_da, out, ld_out, M, F, dtype, (hipStream_t)stream);
     return launch_swiglu_gu<false>(gu, ld_gu, nullptr, 0, out, ld_out, M, F, dtype, (hipStream_t)stream);
+}
+
+extern "C" int p2t_rope_backward_pack_docs(const float* dq, const float* dk, const float* dv, const float* inv_freq, float* cos_sin_scratch,
+                                           const int32_t* docs, void* d_qkv, int64_t ld, int B, int T, int nh, int nkv, int d, int dp, float q_scale,
+                                           int dtype, p2t_stream stream) {
+    P2T_REQUIRE(dq && dk && dv && inv_freq && cos_sin_scratch && docs && d_qkv && B > 0 && T > 0 && ld >= (int64_t)(nh + 2 * nkv) * d,
+                "p2t_rope_backward_pack_docs: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    P2T_TRY(launch_rope_table(inv_freq, T, d / 2, cos_sin_scratch, s));
+    return launch_rope_bwd_pack(dq, dk, dv, cos_sin_scratch, d_qkv, ld, B, T, nh, nkv, d, dp, q_scale, dtype, s, docs);
+}
+
+extern "C" int p2t_attention_backward_docs(const void* q, const void* k, const void* v, const void* o, int64_t ld_o, const void* d_o, int64_t ld_do,
+                                           const float* lse, const uint8_t* key_mask, const int32_t* kv_info, const int32_t* docs, float* dq, float* dk,
+                                           float* dv, float* D_scratch, int B, int T, int nh, int nkv, int d, int dp, float scale, int dtype,
+                                           int log2_scores, int use_mfma, p2t_stream stream) {
+    P2T_REQUIRE(docs, "p2t_attention_backward_docs: null docs");
+    return launch_attn_bwd(q, k, v, o, ld_o, d_o, ld_do, lse, key_mask, kv_info, dq, dk, dv, D_scratch, B, T, nh, nkv, d, dp,
+                           log2_scores ? kLn2 : scale, 1, dtype, (hipStream_t)stream, log2_scores, use_mfma, docs);
 }
 
 extern "C" int p2t_rope_backward_pack(const float* dq, const float* dk, const float* dv, const float* inv_freq, float* cos_sin_scratch, void* d_qkv,

@@ -89,6 +89,23 @@ __global__ void __launch_bounds__(1024) ce_reduce_kernel(const float* __restrict
     }
 }
 
+// loss = sum over the rows with a counted target of weights[row + 1] * row_loss[row] (the weight sits at the target's label position)
+__global__ void __launch_bounds__(1024) ce_reduce_weighted_kernel(const float* __restrict__ row_loss, const int32_t* __restrict__ row_valid,
+                                                                  const float* __restrict__ weights, int64_t M, float* __restrict__ loss,
+                                                                  int32_t* __restrict__ count) {
+    __shared__ float red[16];
+    __shared__ float redc[16];
+    float s = 0.f, c = 0.f;
+    for (int64_t i = threadIdx.x; i < M; i += 1024)
+        if (row_valid[i]) { s += weights[i + 1] * row_loss[i]; c += 1.f; }
+    s = block_sum<16>(s, red);
+    c = block_sum<16>(c, redc);
+    if (threadIdx.x == 0) {
+        *loss = s;
+        if (count) *count = (int32_t)c;
+    }
+}
+
 }  // namespace p2t
 
 using namespace p2t;
@@ -132,6 +149,24 @@ extern "C" int p2t_cross_entropy_shifted(const void* logits, int64_t ld, int dty
         ce_rows_kernel<float><<<(unsigned)M, 256, 0, s>>>((const float*)logits, ld, labels, T, V, ignore_index, row_loss, row_valid);
     P2T_LAUNCH_CHECK();
     ce_reduce_kernel<<<1, 1024, 0, s>>>(row_loss, row_valid, M, loss, count);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
+extern "C" int p2t_cross_entropy_shifted_weighted(const void* logits, int64_t ld, int dtype, const int64_t* labels, const float* weights, int B, int T,
+                                                  int V, int64_t ignore_index, float* row_loss, int32_t* row_valid, float* loss, int32_t* count,
+                                                  p2t_stream stream) {
+    P2T_REQUIRE(logits && labels && weights && row_loss && row_valid && loss && B > 0 && T > 0 && V > 0 && ld >= V,
+                "p2t_cross_entropy_shifted_weighted: bad arguments");
+    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_cross_entropy_shifted_weighted: unsupported dtype %d", dtype);
+    const int64_t M = (int64_t)B * T;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == P2T_BF16)
+        ce_rows_kernel<bf16_t><<<(unsigned)M, 256, 0, s>>>((const bf16_t*)logits, ld, labels, T, V, ignore_index, row_loss, row_valid);
+    else
+        ce_rows_kernel<float><<<(unsigned)M, 256, 0, s>>>((const float*)logits, ld, labels, T, V, ignore_index, row_loss, row_valid);
+    P2T_LAUNCH_CHECK();
+    ce_reduce_weighted_kernel<<<1, 1024, 0, s>>>(row_loss, row_valid, weights, M, loss, count);
     P2T_LAUNCH_CHECK();
     return P2T_OK;
 }

@@ -223,7 +223,7 @@ extern "C" size_t p2t_llama_workspace_bytes(const p2t_llama_config* cfg, int B, 
 // gate/up GEMM then stores them plainly and SwiGLU runs as its own pass).
 int p2t::llama_forward_impl(const p2t_llama_config* c, const p2t_llama_weights* w, const int64_t* ids, const float* inputs_embeds,
                             const int64_t* mask, int B, int T, int k, float* out, void* workspace,
-                            size_t workspace_bytes, p2t_stream stream, const LlamaTape* tape, const p2t_kv_cache* kv) {
+                            size_t workspace_bytes, p2t_stream stream, const LlamaTape* tape, const p2t_kv_cache* kv, const int32_t* docs) {
     P2T_REQUIRE(c && w && (ids || inputs_embeds) && mask && out && workspace && B > 0 && T > 0, "p2t_llama_hidden_forward: null/empty argument");
     P2T_REQUIRE(k >= 0 && k <= c->n_layers, "p2t_llama_hidden_forward: hidden_states[%d] out of range for %d layers", k, c->n_layers);
     P2T_REQUIRE(c->heads % c->kv_heads == 0 && c->head_dim % 4 == 0 && c->head_dim <= 128 && c->hidden % 16 == 0 && c->ffn % 32 == 0 &&
@@ -263,6 +263,7 @@ int p2t::llama_forward_impl(const p2t_llama_config* c, const p2t_llama_weights* 
     unsigned epoch = 0;
     auto with_fix = [&](GemmArgs& g) { g.fix_ws = b.fix; g.fix_bytes = gemm_fix_workspace_bytes(); g.fix_epoch = ++epoch; };
     P2T_REQUIRE(!c->gemm_fp8 || dt == P2T_BF16, "p2t_llama_hidden_forward: gemm_fp8 needs bf16 activations (dtype = P2T_BF16)");
+    P2T_REQUIRE(!docs || (!c->gemm_fp8 && !kv), "p2t_llama_hidden_forward: packed rows run the model-dtype GEMMs without a KV cache");
     const int64_t Hq = round_up(H, 128), Fq = round_up(F, 128), QOq = round_up((int64_t)nh * d, 128);
     for (int l = 0; c->gemm_fp8 && l < k; ++l) {
         const p2t_llama_layer& L = w->layers[l];
@@ -316,18 +317,21 @@ int p2t::llama_forward_impl(const p2t_llama_config* c, const p2t_llama_weights* 
         if (L.q_norm_w) {          // Qwen3: projection -> per-head RMSNorm -> rotation (not fusable: the norm spans the head)
             GemmArgs g1{b.h, Hp, L.qkv_w, Hp, nullptr, b.qkv, NQKV, nullptr, M, NQKV, Hp, dt, dt, P2T_EPI_STORE, 0, -1, (int)NQKV, 0.f, 0, 0};
             P2T_TRY(gemm_nt(g1, s));
-            P2T_TRY(launch_qk_norm_rope(b.qkv, NQKV, b.cs, L.q_norm_w, L.k_norm_w, c->rms_norm_eps, b.q, b.k, b.v, B, T, nh, nkv, d, dp, q_fold, dt, s));
-        } else if (d == 64 || d == 128) {
-            // bias-free QKV projection + rotary + head split in the GEMM epilogue (d = 128: rows packed per head, see the header)
+            P2T_TRY(launch_qk_norm_rope(b.qkv, NQKV, b.cs, L.q_norm_w, L.k_norm_w, c->rms_norm_eps, b.q, b.k, b.v, B, T, nh, nkv, d, dp, q_fold, dt, s,
+                                        docs));
+        } else if ((d == 64 || d == 128) && !docs) {
+            // bias-free QKV projection + rotary + head split in the GEMM epilogue (d = 128: rows packed per head, see the header);
+            // packed rows rotate by their position inside the document: GEMM + the positional qkv_post below
             GemmArgs g1{b.h, Hp, L.qkv_w, Hp, nullptr, nullptr, 0, nullptr, M, NQKV, Hp, dt, dt, P2T_EPI_QKV_ROPE, 0, -1, -1, 0.f, 0, 0};
             g1.cs = b.cs; g1.q = b.q; g1.k = b.k; g1.v = b.v; g1.seq = T; g1.nh = nh; g1.nkv = nkv; g1.q_scale = q_fold; g1.head_dim = d;
             P2T_TRY(gemm_nt(g1, s));
         } else {
             GemmArgs g1{b.h, Hp, L.qkv_w, Hp, nullptr, b.qkv, NQKV, nullptr, M, NQKV, Hp, dt, dt, P2T_EPI_STORE, 0, -1, (int)NQKV, 0.f, 0, 0};
             P2T_TRY(gemm_nt(g1, s));
-            P2T_TRY(launch_qkv_post(b.qkv, NQKV, b.cs, b.q, b.k, b.v, B, T, nh, nkv, d, dp, q_fold, dt, s));
+            // (d = 128 reaches here only with docs: qkv_w then carries the fused epilogue's row order)
+            P2T_TRY(launch_qkv_post(b.qkv, NQKV, b.cs, b.q, b.k, b.v, B, T, nh, nkv, d, dp, q_fold, dt, s, docs, d == 128));
         }
-        P2T_TRY(attention(b.q, b.k, b.v, b.key_mask, b.kv_info, b.ao, QO, B, T, nh, nkv, d, dp, scale, 1, dt, -1, l2s, s, lse));
+        P2T_TRY(attention(b.q, b.k, b.v, b.key_mask, b.kv_info, b.ao, QO, B, T, nh, nkv, d, dp, scale, 1, dt, -1, l2s, s, lse, docs));
         if (kv) P2T_TRY(llama_kv_store(c, kv, l, b.k, b.v, B, T, s));      // generation prefill: this layer's keys / values -> prompt segment
         GemmArgs g2{b.ao, QO, L.o_w, QO, nullptr, b.x, H, nullptr, M, H, QO, dt, P2T_F32, P2T_EPI_RESID, 0, -1, -1, 0.f, 0, 0};
         P2T_TRY(gemm_nt(g2, s));

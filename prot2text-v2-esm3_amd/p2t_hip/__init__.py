@@ -22,7 +22,7 @@ __all__ = ["specs", "synth", "Esm2LlamaInstructConfig", "ModalityAdapterConfig",
            "Esm2LlamaInstructForCausalLM", "EsmEncoder", "LlamaDecoder", "BatchInfoNCELoss",
            "SegmentedBatchInfoNCELoss", "readout_embeddings", "l2_normalize", "get_sequence_embeddings",
            "get_description_embeddings", "teacher_forcing_forward_pass", "ContrastiveTrainer", "ops",
-           "EsmSequenceTokenizer", "ContrastiveCollater", "DevicePrefetcher", "sort_batch_by_length", "CosineWarmupSchedule", "save_checkpoint",
+           "EsmSequenceTokenizer", "ContrastiveCollater", "DevicePrefetcher", "sort_batch_by_length", "pack_instruct_batch", "CosineWarmupSchedule", "save_checkpoint",
            "load_model_checkpoint", "load_optimizer_scheduler_checkpoint", "train_epoch", "eval_epoch", "run_epochs",
            "iterative_generation_loop", "inference_epoch", "load_and_merge_adapter",
            "InstructTrainer", "FlatAdamW", "save_instruct_checkpoint", "load_instruct_checkpoint", "run_instruct_epochs", "instruct_schedule"]
@@ -34,7 +34,7 @@ _LAZY = {
     "readout_embeddings": "contrastive", "l2_normalize": "contrastive", "get_sequence_embeddings": "contrastive",
     "get_description_embeddings": "contrastive", "teacher_forcing_forward_pass": "contrastive",
     "ContrastiveTrainer": "contrastive",
-    "EsmSequenceTokenizer": "data", "ContrastiveCollater": "data", "DevicePrefetcher": "data", "sort_batch_by_length": "data",
+    "EsmSequenceTokenizer": "data", "ContrastiveCollater": "data", "DevicePrefetcher": "data", "sort_batch_by_length": "data", "pack_instruct_batch": "data",
     "CosineWarmupSchedule": "training_state", "save_checkpoint": "training_state",
     "load_model_checkpoint": "training_state", "load_optimizer_scheduler_checkpoint": "training_state",
     "train_epoch": "loop", "eval_epoch": "loop", "run_epochs": "loop", "iterative_generation_loop": "loop", "inference_epoch": "loop", "load_and_merge_adapter": "lora",

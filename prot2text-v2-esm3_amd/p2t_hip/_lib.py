@@ -159,6 +159,17 @@ SIGNATURES = {
     "p2t_llama_train_forward": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), vp, vp, i32, i32, vp, vp, sz, vp, sz, vp]),
     "p2t_llama_train_backward": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), C.POINTER(LlamaLayerTC), vp, i32, i32, vp, vp, sz,
                                        vp, vp, sz, vp]),
+    "p2t_doc_prepare": (i32, [vp, i32, vp, i32, i32, vp, vp, vp]),
+    "p2t_qkv_post_docs": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
+    "p2t_rope_backward_pack_docs": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
+    "p2t_attention_docs": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp, vp]),
+    "p2t_attention_backward_docs": (i32, [vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32,
+                                          i32, vp]),
+    "p2t_llama_train_forward_docs": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), vp, vp, vp, i32, i32, vp, vp, sz, vp, sz, vp]),
+    "p2t_llama_train_backward_docs": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), C.POINTER(LlamaLayerTC), vp, vp, i32, i32, vp, vp,
+                                            sz, vp, vp, sz, vp]),
+    "p2t_cross_entropy_shifted_weighted": (i32, [vp, i64, i32, vp, vp, i32, i32, i32, i64, vp, vp, vp, vp, vp]),
+    "p2t_cross_entropy_shifted_weighted_backward": (i32, [vp, i64, i32, vp, vp, i32, i32, i32, i64, vp, i64, vp]),
     "p2t_esm2_workspace_bytes": (sz, [C.POINTER(EsmConfigC), i32, i32]),
     "p2t_esm2_forward": (i32, [C.POINTER(EsmConfigC), C.POINTER(EsmWeightsC), vp, vp, i32, i32, vp, i64, vp, sz, vp]),
     "p2t_llama_workspace_bytes": (sz, [C.POINTER(LlamaConfigC), i32, i32]),

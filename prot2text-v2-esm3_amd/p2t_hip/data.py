@@ -170,6 +170,91 @@ def sort_batch_by_length(batch: Dict[str, Any], descending: bool = True) -> Dict
     return out
 
 
+def pack_instruct_batch(batch: Dict[str, Any], max_tokens: int, loss_weighting: str = "token", pad_token_id: Optional[int] = None) -> Dict[str, Any]:
+    """Stage-2 batch in the reference collater's layout (dataset/dataloader.py:112-143: each row [left pad + bos + prompt with the
+    protein placeholders + description + eot + right pad]) -> the same samples packed into padding-free rows of at most
+    `max_tokens` tokens (transformers' DataCollatorWithFlattening convention, include/p2t_hip.h "packed rows"):
+
+    * both pads are stripped from every sample; samples go into rows first-fit decreasing (longest first, ties in batch order);
+    * rows are right-padded to the longest row; `position_ids` run 0, 1, 2, ... inside every sample (0 on padding);
+    * `labels` are the samples' labels with -100 at every document start and on padding;
+    * `protein_input_ids` / `protein_attention_mask` are permuted to the order in which the samples now appear (row-major), so
+      that the row-major order of the placeholders still matches the order of the encoder rows (reference :138);
+    * loss_weighting "token": no weights -- the loss is the token mean over all supervised tokens, as the padded batch's;
+      "sample": `loss_weights` f32 [rows, T] = 1 / (n_docs * n_supervised(doc)) on every supervised target -- the mean of the
+      per-sample losses, i.e. the reference's batch_size_per_device = 1 micro-batches, averaged (documents without a supervised
+      token are not counted);
+    * `pack_layout`: one (sample index, row, start, length) per sample in placement order (enough to unpack the rows).
+    A sample longer than max_tokens raises ValueError.  Works on the host batch; other per-sample entries are dropped."""
+    if loss_weighting not in ("token", "sample"):
+        raise ValueError(f"loss_weighting must be 'token' or 'sample', got {loss_weighting!r}")
+    ids, mask, labels = batch["input_ids"].cpu(), batch["attention_mask"].cpu(), batch["labels"].cpu()
+    B = int(ids.shape[0])
+    if tuple(mask.shape) != tuple(ids.shape) or tuple(labels.shape) != tuple(ids.shape):
+        raise ValueError("input_ids, attention_mask and labels must have the same [B, T] shape")
+    if pad_token_id is None:
+        pads = ids[mask == 0]
+        pad_token_id = int(pads[0]) if pads.numel() else 0
+    samples = []
+    for i in range(B):
+        keep = mask[i] != 0
+        n = int(keep.sum())
+        if n > max_tokens:
+            raise ValueError(f"sample {i} has {n} tokens, more than max_tokens = {max_tokens}")
+        idx = torch.nonzero(keep).flatten()
+        if n and int(idx[-1] - idx[0]) + 1 != n:
+            raise ValueError(f"sample {i}: the attention mask is not one contiguous run (left pad + tokens + right pad)")
+        samples.append((ids[i, keep], labels[i, keep]))
+    order = sorted(range(B), key=lambda i: -samples[i][0].numel())          # stable: ties keep the batch order
+    rows: List[List[int]] = []
+    room: List[int] = []
+    for i in order:
+        n = samples[i][0].numel()
+        for r in range(len(rows)):
+            if room[r] >= n:
+                rows[r].append(i)
+                room[r] -= n
+                break
+        else:
+            rows.append([i])
+            room.append(max_tokens - n)
+    R = len(rows)
+    T = max(max_tokens - rm for rm in room) if R else 0
+    out_ids = torch.full((R, T), pad_token_id, dtype=ids.dtype)
+    out_mask = torch.zeros((R, T), dtype=mask.dtype)
+    out_pos = torch.zeros((R, T), dtype=torch.int64)
+    out_lab = torch.full((R, T), -100, dtype=labels.dtype)
+    out_w = torch.zeros((R, T), dtype=torch.float32) if loss_weighting == "sample" else None
+    layout = []
+    n_docs = sum(1 for i in range(B) if int((samples[i][1][1:] != -100).sum()) > 0)
+    for r, members in enumerate(rows):
+        t0 = 0
+        for i in members:
+            x, y = samples[i]
+            n = x.numel()
+            out_ids[r, t0:t0 + n] = x
+            out_mask[r, t0:t0 + n] = 1
+            out_pos[r, t0:t0 + n] = torch.arange(n)
+            out_lab[r, t0:t0 + n] = y
+            out_lab[r, t0] = -100                                               # a document start is never a target
+            if out_w is not None:
+                sup = out_lab[r, t0:t0 + n] != -100
+                k = int(sup.sum())
+                if k:
+                    out_w[r, t0:t0 + n][sup] = 1.0 / (n_docs * k)
+            layout.append((i, r, t0, n))
+            t0 += n
+    placed = [i for _, members in enumerate(rows) for i in members]
+    out: Dict[str, Any] = {"input_ids": out_ids, "attention_mask": out_mask, "position_ids": out_pos, "labels": out_lab, "pack_layout": layout}
+    perm = torch.tensor(placed, dtype=torch.int64)
+    for key in ("protein_input_ids", "protein_attention_mask"):
+        if key in batch:
+            out[key] = batch[key].cpu()[perm]
+    if out_w is not None:
+        out["loss_weights"] = out_w
+    return out
+
+
 class DevicePrefetcher:
     """Iterate device-resident batches one step ahead of the consumer: tensors go through pinned host memory and are
     copied on a dedicated stream; the consumer's stream only waits on the copy event of the batch it is handed.

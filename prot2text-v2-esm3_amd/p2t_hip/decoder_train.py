@@ -238,6 +238,7 @@ class DecoderLoraLossFn(torch.autograd.Function):
         P = dict(m.named_parameters())
         mask = attention_mask.to(device=dev, dtype=torch.int64).contiguous()
         key_mask, kv_info, _ = ops.mask_prepare(mask)
+        docs, weights = opts.get("docs"), opts.get("loss_weights")      # packed rows (ops.doc_prepare) / per-target loss weights
         inv_freq = m._inv_freq().to(dev)
         l2s = dt == torch.bfloat16                       # as the towers: q carries scale * log2 e, the logits are ln 2 * q.k
         scale = float(d) ** -0.5
@@ -263,9 +264,9 @@ class DecoderLoraLossFn(torch.autograd.Function):
             qkv = ops.cast(torch.cat(parts, 1), dt) if dt != torch.float32 else torch.cat(parts, 1)
             if qkv.shape[1] % 8:
                 qkv = torch.nn.functional.pad(qkv, (0, 8 - qkv.shape[1] % 8))
-            q4, k4, v4 = ops.qkv_post(qkv.contiguous(), inv_freq, B, T, nh, nkv, d, q_fold)
+            q4, k4, v4 = ops.qkv_post(qkv.contiguous(), inv_freq, B, T, nh, nkv, d, q_fold, docs=docs)
             lse = torch.empty((B, nh, T), dtype=torch.float32, device=dev)
-            ao = ops.attention(q4, k4, v4, key_mask, kv_info, d, 1.0 if l2s else scale, True, log2_scores=l2s, lse=lse)      # [M, QO]
+            ao = ops.attention(q4, k4, v4, key_mask, kv_info, d, 1.0 if l2s else scale, True, log2_scores=l2s, lse=lse, docs=docs)      # [M, QO]
             rec.update(q=q4, k=k4, v=v4, lse=lse, ao=ao)
             _, rec["u_self_attn.o_proj"] = lin["self_attn.o_proj"].forward(ao, resid=x)
             rec["x_mid"] = x.clone() if keep else None
@@ -284,8 +285,9 @@ class DecoderLoraLossFn(torch.autograd.Function):
         hN = ops.rmsnorm(x_last, f32v("norm.weight"), s.rms_norm_eps, out_dtype=dt)
         logits = ops.gemm_nt(hN, decoder._lm_head_padded(), None, n=s.vocab_size, k=H, out_dtype=dt).view(B, T, -1)
         lab = labels.to(dev).to(torch.int64).contiguous()
-        loss, count = ops.cross_entropy_shifted(logits, lab, s.vocab_size)
+        loss, count = ops.cross_entropy_shifted(logits, lab, s.vocab_size, weights=weights)
         ctx.state = dict(decoder=decoder, tape=tape, x_last=x_last, logits=logits, labels=lab, count=count, key_mask=key_mask, kv_info=kv_info,
+                         docs=docs, weights=weights,
                          inv_freq=inv_freq, l2s=l2s, scale=scale, q_fold=q_fold, shape=(B, T, H), params=params, in_dtype=inputs_embeds.dtype)
         ctx.mark_non_differentiable(logits)
         return loss[0], logits
@@ -307,7 +309,12 @@ class DecoderLoraLossFn(torch.autograd.Function):
         logits = st["logits"]
         ld = logits.shape[2]
         d_logits = torch.empty_like(logits)
-        call("p2t_cross_entropy_shifted_backward", ptr(logits), ld, ops.dt_of(logits), ptr(st["labels"]), B, T, V, -100, ptr(st["count"]), ptr(d_logits), ld, stream())
+        if st["weights"] is not None:
+            call("p2t_cross_entropy_shifted_weighted_backward", ptr(logits), ld, ops.dt_of(logits), ptr(st["labels"]), ptr(st["weights"]), B, T, V, -100,
+                 ptr(d_logits), ld, stream())
+        else:
+            call("p2t_cross_entropy_shifted_backward", ptr(logits), ld, ops.dt_of(logits), ptr(st["labels"]), B, T, V, -100, ptr(st["count"]), ptr(d_logits),
+                 ld, stream())
         d_h = ops.gemm_nt(d_logits.view(M, ld), dec._lm_head_transposed(), None, n=H, k=round_up(V, 64), epilogue=_lib.EPI_STORE_F32)      # [M, H] f32
         g = torch.empty((M, H), dtype=torch.float32, device=dev)
 
@@ -338,12 +345,16 @@ class DecoderLoraLossFn(torch.autograd.Function):
             g16 = to_dt(g)
             d_ao = lin["self_attn.o_proj"].backward(g16, rec["ao"], rec["u_self_attn.o_proj"], None, False, False, grads)       # [M, QO]
             dq, dk, dv = ops.attention_backward(rec["q"], rec["k"], rec["v"], rec["ao"], d_ao, rec["lse"], st["key_mask"], st["kv_info"], d, c_s, True,
-                                                log2_scores=st["l2s"])
+                                                log2_scores=st["l2s"], docs=st["docs"])
             NQ = (nh + 2 * nkv) * d
             d_qkv = torch.zeros((M, round_up(NQ, 64)), dtype=dt, device=dev)
             cs = torch.empty((T, d), dtype=torch.float32, device=dev)
-            call("p2t_rope_backward_pack", ptr(dq), ptr(dk), ptr(dv), ptr(st["inv_freq"]), ptr(cs), ptr(d_qkv), d_qkv.stride(0), B, T, nh, nkv, d, dp,
-                 float(st["q_fold"]), ops.dt_of(dt), stream())
+            if st["docs"] is not None:
+                call("p2t_rope_backward_pack_docs", ptr(dq), ptr(dk), ptr(dv), ptr(st["inv_freq"]), ptr(cs), ptr(st["docs"]), ptr(d_qkv), d_qkv.stride(0),
+                     B, T, nh, nkv, d, dp, float(st["q_fold"]), ops.dt_of(dt), stream())
+            else:
+                call("p2t_rope_backward_pack", ptr(dq), ptr(dk), ptr(dv), ptr(st["inv_freq"]), ptr(cs), ptr(d_qkv), d_qkv.stride(0), B, T, nh, nkv, d, dp,
+                     float(st["q_fold"]), ops.dt_of(dt), stream())
             d_q, d_k, d_v = d_qkv[:, :nh * d], d_qkv[:, nh * d:(nh + nkv) * d], d_qkv[:, (nh + nkv) * d:NQ]
             if s.qk_norm:
                 def norm_bwd(raw, w, dy, heads):
@@ -376,14 +387,16 @@ class DecoderLoraLossFn(torch.autograd.Function):
 
 
 def lora_lm_loss(decoder, lora: Optional[DecoderLora], inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, labels: torch.Tensor,
-                 dropout: Optional[float] = None):
+                 dropout: Optional[float] = None, docs: Optional[torch.Tensor] = None, loss_weights: Optional[torch.Tensor] = None):
     """(loss, logits) of `llama_decoder(inputs_embeds=..., attention_mask=..., labels=...)` with the LoRA branches in the graph.
     dropout: None = the branches' own `lora.p` (every mode, as before); a value overrides it for this call and leaves the mask counter
-    where it is -- 0.0 is peft's eval mode (InstructTrainer.evaluate).  Without gradients to compute, no activation tape is kept."""
+    where it is -- 0.0 is peft's eval mode (InstructTrainer.evaluate).  Without gradients to compute, no activation tape is kept.
+    docs: packed rows (ops.doc_prepare: positional rotary + document-confined attention; the caller has set the labels of document
+    starts to -100); loss_weights: f32 [B, T] per-target weights (ops.cross_entropy_shifted) instead of the token mean."""
     params = tuple(lora.parameters()) if lora is not None else ()
     if lora is not None and lora.training and dropout is None:
         lora.step_count += 1                            # a fresh dropout mask per step
     keep = torch.is_grad_enabled() and (inputs_embeds.requires_grad or any(q.requires_grad for q in params))
-    opts = dict(dropout=dropout, keep_tape=keep)
+    opts = dict(dropout=dropout, keep_tape=keep, docs=docs, loss_weights=loss_weights)
     loss, logits = DecoderLoraLossFn.apply(inputs_embeds, decoder, lora, attention_mask, labels, opts, *params)
     return loss, logits[..., : decoder.spec.vocab_size]

@@ -30,7 +30,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, sharding
+from . import _lib, ops, sharding
 from ._lib import call
 from .ops import ptr, round_up, stream
 
@@ -254,7 +254,8 @@ class InstructTrainer:
             self.opt.flat_g.zero_()
         self._dirty = True
         out = self.model(input_ids=batch["input_ids"], attention_mask=batch["attention_mask"], labels=batch["labels"],
-                         protein_input_ids=batch["protein_input_ids"], protein_attention_mask=batch["protein_attention_mask"])
+                         protein_input_ids=batch["protein_input_ids"], protein_attention_mask=batch["protein_attention_mask"],
+                         position_ids=batch.get("position_ids"), loss_weights=batch.get("loss_weights"))
         loss = out.loss
         (loss / self.gradient_accumulation_steps).backward()
         self._fold_adapter_grads()
@@ -298,7 +299,8 @@ class InstructTrainer:
         m.adapter.train(False)
         try:
             embeds, mask = m(input_ids=batch["input_ids"], attention_mask=batch["attention_mask"], protein_input_ids=batch["protein_input_ids"],
-                             protein_attention_mask=batch["protein_attention_mask"], return_decoder_inputs=True)
+                             protein_attention_mask=batch["protein_attention_mask"], position_ids=batch.get("position_ids"),
+                             return_decoder_inputs=True)
         finally:
             m.adapter.train(was)
         labels = batch["labels"]
@@ -306,7 +308,14 @@ class InstructTrainer:
             raise ValueError(f"labels shape {tuple(labels.shape)} != {tuple(embeds.shape[:2])}")
         if m.llama_decoder.model.gemm_fp8:
             raise ValueError("stage-2 training runs the decoder GEMMs in the model dtype (set_gemm_dtype('model'))")
-        loss, _ = lora_lm_loss(m.llama_decoder, self.lora, embeds, mask, labels, dropout=0.0)
+        docs, weights, pos = None, batch.get("loss_weights"), batch.get("position_ids")
+        if pos is not None:                         # packed rows (p2t_hip.data.pack_instruct_batch): as LlamaDecoder.forward
+            docs = ops.doc_prepare(pos, mask.to(torch.int64).contiguous())
+            if docs is not None:
+                labels = labels.masked_fill(pos.to(labels.device) == 0, -100)
+        if weights is not None:
+            weights = weights.to(device=embeds.device, dtype=torch.float32).contiguous()
+        loss, _ = lora_lm_loss(m.llama_decoder, self.lora, embeds, mask, labels, dropout=0.0, docs=docs, loss_weights=weights)
         return loss.reshape(1)
 
     def global_loss(self, loss: torch.Tensor) -> torch.Tensor:

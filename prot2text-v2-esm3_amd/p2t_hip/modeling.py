@@ -500,9 +500,10 @@ class LlamaTextModel(nn.Module):
         self._train_engine = dict(layers=layers, keep=keep)
         return self._train_engine
 
-    def train_forward(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor):
+    def train_forward(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, docs: Optional[torch.Tensor] = None):
         """All layers + final RMSNorm from f32 [B, T, hidden] inputs, keeping the activation tape for `train_backward`
-        (p2t_llama_train_forward).  -> (post-norm hidden states f32 [B, T, hidden], tape handle)."""
+        (p2t_llama_train_forward; with `docs` from ops.doc_prepare, p2t_llama_train_forward_docs: packed rows).
+        -> (post-norm hidden states f32 [B, T, hidden], tape handle)."""
         B, T, H = inputs_embeds.shape
         L = self.spec.num_hidden_layers
         e = self.ensure_engine(L)
@@ -512,21 +513,29 @@ class LlamaTextModel(nn.Module):
         tape = torch.empty((call("p2t_llama_tape_bytes", C.byref(e["cfg"]), B, T),), dtype=torch.uint8, device=dev)
         ws = self._ws.get(torch.cuda.current_stream().cuda_stream, call("p2t_llama_train_workspace_bytes", C.byref(e["cfg"]), B, T), dev)
         out = torch.empty((B, T, H), dtype=torch.float32, device=dev)
-        call("p2t_llama_train_forward", C.byref(e["cfg"]), C.byref(e["w"]), ptr(emb), ptr(mask), B, T, ptr(out), ptr(tape), tape.numel(),
-             ptr(ws), ws.numel(), stream())
-        return out, (tape, mask, B, T)
+        if docs is not None:
+            call("p2t_llama_train_forward_docs", C.byref(e["cfg"]), C.byref(e["w"]), ptr(emb), ptr(mask), ptr(docs), B, T, ptr(out), ptr(tape),
+                 tape.numel(), ptr(ws), ws.numel(), stream())
+        else:
+            call("p2t_llama_train_forward", C.byref(e["cfg"]), C.byref(e["w"]), ptr(emb), ptr(mask), B, T, ptr(out), ptr(tape), tape.numel(),
+                 ptr(ws), ws.numel(), stream())
+        return out, (tape, mask, B, T, docs)
 
     def train_backward(self, d_out: torch.Tensor, handle) -> torch.Tensor:
         """d loss / d inputs_embeds (f32 [B, T, hidden]) from d loss / d (post-norm hidden states) and the tape."""
-        tape, mask, B, T = handle
+        tape, mask, B, T, docs = handle
         L = self.spec.num_hidden_layers
         e = self.ensure_engine(L)
         te = getattr(self, "_train_engine", None) or self._build_train_engine()
         dev = tape.device
         ws = self._ws.get(torch.cuda.current_stream().cuda_stream, call("p2t_llama_train_workspace_bytes", C.byref(e["cfg"]), B, T), dev)
         d_in = torch.empty((B, T, self.spec.hidden_size), dtype=torch.float32, device=dev)
-        call("p2t_llama_train_backward", C.byref(e["cfg"]), C.byref(e["w"]), C.cast(te["layers"], C.POINTER(_lib.LlamaLayerTC)), ptr(mask), B, T,
-             ptr(d_out.float().contiguous()), ptr(tape), tape.numel(), ptr(d_in), ptr(ws), ws.numel(), stream())
+        if docs is not None:
+            call("p2t_llama_train_backward_docs", C.byref(e["cfg"]), C.byref(e["w"]), C.cast(te["layers"], C.POINTER(_lib.LlamaLayerTC)), ptr(mask),
+                 ptr(docs), B, T, ptr(d_out.float().contiguous()), ptr(tape), tape.numel(), ptr(d_in), ptr(ws), ws.numel(), stream())
+        else:
+            call("p2t_llama_train_backward", C.byref(e["cfg"]), C.byref(e["w"]), C.cast(te["layers"], C.POINTER(_lib.LlamaLayerTC)), ptr(mask), B, T,
+                 ptr(d_out.float().contiguous()), ptr(tape), tape.numel(), ptr(d_in), ptr(ws), ws.numel(), stream())
         return d_in
 
     def ensure_engine(self, k: int):
@@ -626,16 +635,16 @@ class _DecoderLossFn(torch.autograd.Function):
     cross-entropy backward -> LM-head dX GEMM -> p2t_llama_train_backward.  All kernels hand-written; torch only links them."""
 
     @staticmethod
-    def forward(ctx, inputs_embeds, decoder, attention_mask, labels):
+    def forward(ctx, inputs_embeds, decoder, attention_mask, labels, docs=None, weights=None):
         s, m = decoder.spec, decoder.model
         B, T, H = inputs_embeds.shape
         dt = m.dtype
-        h, handle = m.train_forward(inputs_embeds, attention_mask)
+        h, handle = m.train_forward(inputs_embeds, attention_mask, docs)
         a = h.view(B * T, H) if dt == torch.float32 else ops.cast(h.view(B * T, H), dt)
         logits = ops.gemm_nt(a, decoder._lm_head_padded(), None, n=s.vocab_size, k=H, out_dtype=dt).view(B, T, -1)
         lab = labels.to(logits.device).to(torch.int64).contiguous()
-        loss, count = ops.cross_entropy_shifted(logits, lab, s.vocab_size)
-        ctx.decoder, ctx.handle, ctx.logits, ctx.labels, ctx.count = decoder, handle, logits, lab, count
+        loss, count = ops.cross_entropy_shifted(logits, lab, s.vocab_size, weights=weights)
+        ctx.decoder, ctx.handle, ctx.logits, ctx.labels, ctx.count, ctx.weights = decoder, handle, logits, lab, count, weights
         ctx.mark_non_differentiable(logits)
         return loss[0], logits
 
@@ -646,13 +655,17 @@ class _DecoderLossFn(torch.autograd.Function):
         B, T, ld = logits.shape
         H, V = s.hidden_size, s.vocab_size
         d_logits = torch.empty_like(logits)
-        call("p2t_cross_entropy_shifted_backward", ptr(logits), ld, ops.dt_of(logits), ptr(ctx.labels), B, T, V, -100, ptr(ctx.count), ptr(d_logits), ld,
-             stream())
+        if ctx.weights is not None:
+            call("p2t_cross_entropy_shifted_weighted_backward", ptr(logits), ld, ops.dt_of(logits), ptr(ctx.labels), ptr(ctx.weights), B, T, V, -100,
+                 ptr(d_logits), ld, stream())
+        else:
+            call("p2t_cross_entropy_shifted_backward", ptr(logits), ld, ops.dt_of(logits), ptr(ctx.labels), B, T, V, -100, ptr(ctx.count), ptr(d_logits), ld,
+                 stream())
         d_h = ops.gemm_nt(d_logits.view(B * T, ld), dec._lm_head_transposed(), None, n=H, k=round_up(V, 64), epilogue=_lib.EPI_STORE_F32)   # [B*T, H] f32
         d_in = dec.model.train_backward(d_h.view(B, T, H), ctx.handle)
         call("p2t_scale_by_device_scalar", ptr(d_in), d_in.numel(), ptr(g_loss.float().reshape(1).contiguous()), stream())
-        ctx.handle = ctx.logits = None                          # free the tape
-        return d_in, None, None, None
+        ctx.handle = ctx.logits = ctx.weights = None            # free the tape
+        return d_in, None, None, None, None, None
 
 
 class CausalLMOutput:
@@ -711,18 +724,26 @@ class LlamaDecoder(nn.Module):
 
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None,
                 labels=None, use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None,
-                cache_position=None, **kwargs):
+                cache_position=None, loss_weights=None, **kwargs):
         """LlamaForCausalLM.forward without a KV cache: all layers -> final RMSNorm -> LM head -> (shifted cross-entropy).
+        position_ids is accepted on the loss path only (inputs_embeds + labels): packed rows (include/p2t_hip.h, p2t_doc_prepare) --
+        every position 0 under a right-padded mask starts a document, attention stays inside each document, rotary uses the given
+        positions and the target that starts a document is never scored.  An arange per row is an ordinary batch.
+        loss_weights (not an argument of the reference; f32 [B, T] aligned with labels): loss = sum of weight * token loss instead of
+        the token mean (p2t_hip.data.pack_instruct_batch(loss_weighting="sample") writes them).
         Restates transformers/models/llama/modeling_llama.py (LlamaForCausalLM.forward) and loss_utils.ForCausalLMLoss.
         With `labels`, gradients enabled and `inputs_embeds` requiring grad (stage 2: the adapter's rows sit in it), the loss
         carries an autograd node whose backward is the hand-written chain of llama_train.hip -- the decoder's own parameters
         are frozen on this path (no weight gradients; LoRA matrices are not built yet)."""
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
-        if position_ids is not None or past_key_values is not None or use_cache or cache_position is not None:
+        loss_path = labels is not None and inputs_embeds is not None
+        if (position_ids is not None and not loss_path) or past_key_values is not None or use_cache or cache_position is not None:
             raise NotImplementedError("position_ids / past_key_values / cache_position are not arguments of this forward: the KV cache lives inside `generate` (p2t_hip/generation.py)")
         if output_attentions or output_hidden_states:
             raise NotImplementedError("output_attentions / output_hidden_states are not available from the fused decoder")
+        if loss_weights is not None and not loss_path:
+            raise ValueError("loss_weights weight the LM loss: they need labels and inputs_embeds")
         s, m = self.spec, self.model
         if s.hidden_size % 64:
             raise ValueError("the LM head path needs hidden_size % 64 == 0")
@@ -732,13 +753,28 @@ class LlamaDecoder(nn.Module):
         if lora is not None and (labels is None or inputs_embeds is None):
             raise NotImplementedError("this decoder carries LoRA adapters: only the teacher-forced LM loss (inputs_embeds + labels) runs with the "
                                       "branches in place; merge them for inference (p2t_hip.lora.load_and_merge_adapter on peft_state_dict())")
-        if labels is not None and inputs_embeds is not None and (lora is not None or
-                                                                 (torch.is_grad_enabled() and (inputs_embeds.requires_grad or lora_live))):
+        grad_path = torch.is_grad_enabled() and (inputs_embeds is not None and inputs_embeds.requires_grad or lora_live)
+        docs = None
+        if position_ids is not None:            # (loss path only, checked above)
+            B, T, _ = inputs_embeds.shape
+            dev = m.embed_tokens.weight.device
+            am = attention_mask if attention_mask is not None else torch.ones((B, T), dtype=torch.int64, device=dev)
+            docs = ops.doc_prepare(position_ids, am.to(device=dev, dtype=torch.int64).contiguous())      # None: an arange per row
+            if docs is not None:                # a target that starts a document is never scored
+                if tuple(labels.shape) != (B, T):
+                    raise ValueError(f"labels shape {tuple(labels.shape)} != {(B, T)}")
+                labels = labels.to(dev).masked_fill(position_ids.to(dev) == 0, -100)
+        if loss_path and (lora is not None or docs is not None or loss_weights is not None or grad_path):
             B, T, _ = inputs_embeds.shape
             if tuple(labels.shape) != (B, T):
                 raise ValueError(f"labels shape {tuple(labels.shape)} != {(B, T)}")
             if attention_mask is None:
                 attention_mask = torch.ones((B, T), dtype=torch.int64, device=inputs_embeds.device)
+            dev = m.embed_tokens.weight.device
+            if loss_weights is not None:
+                if tuple(loss_weights.shape) != (B, T):
+                    raise ValueError(f"loss_weights shape {tuple(loss_weights.shape)} != {(B, T)}")
+                loss_weights = loss_weights.to(device=dev, dtype=torch.float32).contiguous()
             if getattr(self, "gradient_checkpointing", False) and not getattr(self, "_warned_checkpointing", False):
                 # the caller asked for activation checkpointing (reference :253-268 forwards the flag to the decoder): the stage-2
                 # step keeps its whole activation tape (p2t_llama_tape_bytes: ~26 GB per 4 x 1216 tokens of Llama-3.1-8B) and
@@ -748,15 +784,16 @@ class LlamaDecoder(nn.Module):
                               f"({call('p2t_llama_tape_bytes', C.byref(m.ensure_engine(L)['cfg']), B, T) / 2 ** 30:.1f} GiB for this batch) and recomputes "
                               "nothing: lower the micro-batch if memory is the limit", RuntimeWarning, stacklevel=2)
                 self._warned_checkpointing = True
-            if lora is not None or s.qk_norm:
+            if lora is not None or s.qk_norm or not grad_path:
                 # LoRA branches (scripts/train_instruct.py:146-183) or Qwen3's per-head q / k norm sit between the fused blocks of
-                # p2t_llama_train_forward: the per-layer form of the same step (p2t_hip/decoder_train.py)
+                # p2t_llama_train_forward: the per-layer form of the same step (p2t_hip/decoder_train.py); it also gives the no-grad loss
+                # of packed rows / weighted targets (no activation tape kept)
                 if m.gemm_fp8:
                     raise ValueError("stage-2 training runs the decoder GEMMs in the model dtype (set_gemm_dtype('model'))")
                 from .decoder_train import lora_lm_loss
-                loss, logits = lora_lm_loss(self, lora, inputs_embeds, attention_mask, labels)
+                loss, logits = lora_lm_loss(self, lora, inputs_embeds, attention_mask, labels, docs=docs, loss_weights=loss_weights)
                 return CausalLMOutput(loss=loss, logits=logits)
-            loss, logits = _DecoderLossFn.apply(inputs_embeds, self, attention_mask, labels)
+            loss, logits = _DecoderLossFn.apply(inputs_embeds, self, attention_mask, labels, docs, loss_weights)
             return CausalLMOutput(loss=loss, logits=logits[..., : s.vocab_size])
         h = m.hidden_state(input_ids, attention_mask, L) if inputs_embeds is None else m.hidden_state_from_embeds(inputs_embeds, attention_mask, L)
         B, T, H = h.shape
@@ -918,16 +955,17 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
         self.llama_decoder.model.invalidate_engine()
         return self
 
-    def prepare_decoder_inputs(self, input_ids, encoder_hidden_states, attention_mask=None, encoder_attention_mask=None):
+    def prepare_decoder_inputs(self, input_ids, encoder_hidden_states, attention_mask=None, encoder_attention_mask=None, packed: bool = False):
         """Embed `input_ids` and replace the placeholder positions by the encoder (adapter) states, in row-major order on
         both sides -- `inputs_embeds[input_ids == placeholder_id] = encoder_hidden_states[encoder_attention_mask.bool()]`
-        (reference :108-139).  Returns (inputs_embeds f32 [B, T, H], attention_mask)."""
+        (reference :108-139).  Returns (inputs_embeds f32 [B, T, H], attention_mask).  packed: the rows hold several samples
+        each (p2t_hip.data.pack_instruct_batch), so the encoder batch may have any number of rows."""
         if input_ids is None or input_ids.dim() != 2:
             raise ValueError("input_ids must be passed to locate the placeholders")
         B, T = input_ids.shape
         dev = self.llama_decoder.model.embed_tokens.weight.device
         enc = encoder_hidden_states
-        if enc.dim() != 3 or enc.shape[0] != B:
+        if enc.dim() != 3 or (enc.shape[0] != B and not packed):
             raise ValueError(f"encoder_hidden_states must be [batch={B}, encoder_seq_len, hidden]")
         H = self.llama_decoder.spec.hidden_size
         if enc.shape[2] != H:
@@ -940,7 +978,7 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
         embeds = self.llama_decoder.model.embed(ids)
         dst_pos, n_dst = ops.positions_where(ids, int(self.config.placeholder_id))
         src_pos, n_src = ops.positions_where(encoder_attention_mask.to(dev))
-        src = enc.reshape(B * enc.shape[1], H)
+        src = enc.reshape(enc.shape[0] * enc.shape[1], H)
         if src.dtype not in (torch.float32, torch.bfloat16) or src.stride(1) != 1:
             src = src.float().contiguous()
         if torch.is_grad_enabled() and src.requires_grad:       # stage 2: the gradient of the placeholder rows reaches the adapter
@@ -956,7 +994,8 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
                 protein_input_ids=None, protein_attention_mask=None, protein_position_ids=None, protein_head_mask=None,
                 protein_inputs_embeds=None, use_cache=None, output_attentions=None, output_hidden_states=None,
                 return_dict=None, return_encoder_outputs: bool = False, return_adapter_outputs: bool = False,
-                return_decoder_inputs: bool = False, cache_position=None):
+                return_decoder_inputs: bool = False, cache_position=None, loss_weights=None):
+        """Reference :108-215.  position_ids (packed rows) and loss_weights reach LlamaDecoder.forward's loss path (see there)."""
         if protein_position_ids is not None or protein_head_mask is not None or protein_inputs_embeds is not None:
             raise NotImplementedError("protein_position_ids / protein_head_mask / protein_inputs_embeds are not supported")
         if return_encoder_outputs:                 # reference :175-189
@@ -972,13 +1011,14 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
             return adapter_output, protein_attention_mask
         inputs_embeds, attention_mask = self.prepare_decoder_inputs(input_ids=input_ids, encoder_hidden_states=adapter_output,
                                                                     attention_mask=attention_mask,
-                                                                    encoder_attention_mask=protein_attention_mask)   # :195-201
+                                                                    encoder_attention_mask=protein_attention_mask,
+                                                                    packed=position_ids is not None)                 # :195-201
         if return_decoder_inputs:                  # :202-203
             return inputs_embeds, attention_mask
         return self.llama_decoder.forward(input_ids=None, attention_mask=attention_mask, position_ids=position_ids,
                                           past_key_values=past_key_values, inputs_embeds=inputs_embeds, labels=labels,
                                           use_cache=use_cache, output_attentions=output_attentions, return_dict=return_dict,
-                                          cache_position=cache_position)                                              # :204-215
+                                          cache_position=cache_position, loss_weights=loss_weights)                   # :204-215
 
     def generate(self, inputs: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, protein_input_ids: Optional[torch.Tensor] = None,
                  protein_attention_mask: Optional[torch.Tensor] = None, protein_inputs_embeds: Optional[torch.Tensor] = None, **kwargs):

@@ -188,8 +188,9 @@ def scatter_rows(dst: torch.Tensor, dst_pos, n_dst, src: torch.Tensor, src_pos, 
          ptr(n_src), min(dst_pos.numel(), src_pos.numel()), int(H), stream())
 
 
-def cross_entropy_shifted(logits: torch.Tensor, labels: torch.Tensor, V: int, ignore_index: int = -100):
-    """HF causal-LM loss: logits [B, T, ld >= V], labels [B, T] -> (loss f32 [1], n_targets int32 [1])."""
+def cross_entropy_shifted(logits: torch.Tensor, labels: torch.Tensor, V: int, ignore_index: int = -100, weights: torch.Tensor | None = None):
+    """HF causal-LM loss: logits [B, T, ld >= V], labels [B, T] -> (loss f32 [1], n_targets int32 [1]).
+    weights (f32 [B, T], aligned with labels): loss = sum of weights[b, t+1] * ce(b, t) instead of the token mean."""
     _chk(logits.dim() == 3 and labels.dim() == 2 and tuple(logits.shape[:2]) == tuple(labels.shape) and logits.stride(2) == 1
          and logits.is_contiguous(), "cross_entropy_shifted: logits [B, T, ld] contiguous, labels [B, T]")
     B, T, ld = logits.shape
@@ -198,6 +199,11 @@ def cross_entropy_shifted(logits: torch.Tensor, labels: torch.Tensor, V: int, ig
     row_valid = torch.empty((B * T,), dtype=torch.int32, device=logits.device)
     loss = torch.empty((1,), dtype=torch.float32, device=logits.device)
     count = torch.empty((1,), dtype=torch.int32, device=logits.device)
+    if weights is not None:
+        _chk(tuple(weights.shape) == (B, T) and weights.dtype == torch.float32 and weights.is_contiguous(), "cross_entropy_shifted: weights f32 [B, T]")
+        call("p2t_cross_entropy_shifted_weighted", ptr(logits), ld, dt_of(logits), ptr(lab), ptr(weights), B, T, int(V), int(ignore_index),
+             ptr(row_loss), ptr(row_valid), ptr(loss), ptr(count), stream())
+        return loss, count
     call("p2t_cross_entropy_shifted", ptr(logits), ld, dt_of(logits), ptr(lab), B, T, int(V), int(ignore_index), ptr(row_loss),
          ptr(row_valid), ptr(loss), ptr(count), stream())
     return loss, count
@@ -240,38 +246,79 @@ def mask_prepare(mask: torch.Tensor, ids: torch.Tensor | None = None, mask_id: i
     return key_mask, kv_info, emb_scale
 
 
-def qkv_post(qkv: torch.Tensor, inv_freq: torch.Tensor, B: int, T: int, nh: int, nkv: int, d: int, q_scale: float):
+def doc_prepare(position_ids: torch.Tensor, mask: torch.Tensor):
+    """Packed rows (include/p2t_hip.h, p2t_doc_prepare): -> docs i32 [2, B, T] (document start / end of every token), or None when
+    every row's position_ids is an arange (an ordinary batch: run it without documents).  Raises ValueError on a shape mismatch,
+    a mask that is not right-padded, or position_ids that are not runs from 0 under the mask (one device sync for the verdict)."""
+    B, T = mask.shape
+    if tuple(position_ids.shape) != (B, T):
+        raise ValueError(f"position_ids shape {tuple(position_ids.shape)} != attention_mask shape {(B, T)}")
+    pos = position_ids.to(mask.device)
+    if pos.dtype not in (torch.int64, torch.int32):
+        pos = pos.to(torch.int64)
+    pos = pos.contiguous()
+    docs = torch.empty((2, B, T), dtype=torch.int32, device=mask.device)
+    flags = torch.empty((1,), dtype=torch.int32, device=mask.device)
+    call("p2t_doc_prepare", ptr(pos), int(pos.dtype == torch.int64), ptr(mask.to(torch.int64).contiguous()), B, T, ptr(docs), ptr(flags), stream())
+    f = int(flags.item())
+    if not f & 2:
+        return None
+    if f & 1:
+        raise ValueError("position_ids / attention_mask are not a packed batch: rows must be right-padded and position_ids must run "
+                         "0, 1, 2, ... within every document under the mask")
+    return docs
+
+
+def qkv_post(qkv: torch.Tensor, inv_freq: torch.Tensor, B: int, T: int, nh: int, nkv: int, d: int, q_scale: float,
+             docs: torch.Tensor | None = None):
     dp = head_dim_padded(d)
     dev, dty = qkv.device, qkv.dtype
     q = torch.empty((B, nh, T, dp), dtype=dty, device=dev)
     k = torch.empty((B, nkv, T, dp), dtype=dty, device=dev)
     v = torch.empty((B, nkv, T, dp), dtype=dty, device=dev)
     cs = torch.empty((T, d), dtype=torch.float32, device=dev)
+    if docs is not None:
+        call("p2t_qkv_post_docs", ptr(qkv), qkv.stride(0), ptr(inv_freq), ptr(cs), ptr(docs), ptr(q), ptr(k), ptr(v), B, T, nh, nkv, d, dp,
+             float(q_scale), dt_of(qkv), stream())
+        return q, k, v
     call("p2t_qkv_post", ptr(qkv), qkv.stride(0), ptr(inv_freq), ptr(cs), ptr(q), ptr(k), ptr(v), B, T, nh, nkv, d, dp,
          float(q_scale), dt_of(qkv), stream())
     return q, k, v
 
 
 def attention(q, k, v, key_mask, kv_info, d: int, scale: float, causal: bool, use_mfma: int = -1, log2_scores: bool = False,
-              lse: torch.Tensor | None = None):
+              lse: torch.Tensor | None = None, docs: torch.Tensor | None = None):
     """softmax(scale q k^T + mask) v; log2_scores: q already carries scale * log2(e) (include/p2t_hip.h, p2t_attention).
-    lse (optional f32 [B, nh, T]): filled with the rows' log-sum-exps for p2t_attention_backward."""
+    lse (optional f32 [B, nh, T]): filled with the rows' log-sum-exps for p2t_attention_backward.
+    docs (optional, from doc_prepare; causal only): attention confined to each document of a packed row (p2t_attention_docs)."""
     B, nh, T, dp = q.shape
     nkv = k.shape[1]
     ld = round_up(nh * d, 64)
     out = torch.empty((B * T, ld), dtype=q.dtype, device=q.device)
+    if docs is not None:
+        _chk(causal, "attention: documents need the causal mask")
+        call("p2t_attention_docs", ptr(q), ptr(k), ptr(v), ptr(key_mask), ptr(kv_info), ptr(docs), ptr(out), ld, B, T, nh, nkv, d, dp,
+             float(scale), dt_of(q), use_mfma, int(bool(log2_scores)), ptr(lse), stream())
+        return out
     call("p2t_attention", ptr(q), ptr(k), ptr(v), ptr(key_mask), ptr(kv_info), ptr(out), ld, B, T, nh, nkv, d, dp,
          float(scale), int(causal), dt_of(q), use_mfma, int(bool(log2_scores)), ptr(lse), stream())
     return out
 
 
-def attention_backward(q, k, v, o, d_o, lse, key_mask, kv_info, d: int, scale: float, causal: bool, log2_scores: bool = False, use_mfma: int = -1):
+def attention_backward(q, k, v, o, d_o, lse, key_mask, kv_info, d: int, scale: float, causal: bool, log2_scores: bool = False, use_mfma: int = -1,
+                       docs: torch.Tensor | None = None):
     """(dq, dk, dv) f32 in the layouts of q, k, v (include/p2t_hip.h, p2t_attention_backward); o / d_o: [B*T, ld] as `attention` returns."""
     B, nh, T, dp = q.shape
     nkv = k.shape[1]
     f = lambda h: torch.empty((B, h, T, dp), dtype=torch.float32, device=q.device)
     dq, dk, dv = f(nh), f(nkv), f(nkv)
     D = torch.empty((B, nh, T), dtype=torch.float32, device=q.device)
+    if docs is not None:
+        _chk(causal, "attention_backward: documents need the causal mask")
+        call("p2t_attention_backward_docs", ptr(q), ptr(k), ptr(v), ptr(o), o.stride(0), ptr(d_o), d_o.stride(0), ptr(lse), ptr(key_mask),
+             ptr(kv_info), ptr(docs), ptr(dq), ptr(dk), ptr(dv), ptr(D), B, T, nh, nkv, d, dp, float(scale), dt_of(q), int(bool(log2_scores)),
+             int(use_mfma), stream())
+        return dq, dk, dv
     call("p2t_attention_backward", ptr(q), ptr(k), ptr(v), ptr(o), o.stride(0), ptr(d_o), d_o.stride(0), ptr(lse), ptr(key_mask), ptr(kv_info),
          ptr(dq), ptr(dk), ptr(dv), ptr(D), B, T, nh, nkv, d, dp, float(scale), int(causal), dt_of(q), int(bool(log2_scores)), int(use_mfma), stream())
     return dq, dk, dv

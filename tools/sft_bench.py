@@ -2,9 +2,12 @@
 scatter -> 32-layer Llama-3.1-8B -> LM head -> shifted CE, once forward only and once as the training step `loss.backward()`
 (frozen towers, adapter trainable: training forward with the activation tape + the dX chain of csrc/llama_train.hip + adapter
 backward), with a per-kernel-family breakdown of the backward from the torch profiler-free HIP-event brackets below.
-python tools/sft_bench.py [B] [lora] [trainer] > sft_bench.log
+python tools/sft_bench.py [B] [lora] [trainer] [packed] > sft_bench.log
 `trainer`: the stage-2 InstructTrainer (LoRA r = 16 + adapter, GA 1): ms per full step, the flat clip + AdamW tail alone (bytes,
-fraction of HBM bandwidth) and the host time per step that the optimizer-written LoRA operands save."""
+fraction of HBM bandwidth) and the host time per step that the optimizer-written LoRA operands save.
+`packed`: InstructTrainer (r = 16) on ragged samples (tools/ragged_sweep.py's protein length draws) as padded micro-batches of 1 (the
+reference's default) and 4, and packed into rows of <= 4 x 1216 tokens (p2t_hip.data.pack_instruct_batch): samples/s and real
+(unpadded) decoder tokens/s; then the attention forward / backward of one packed row against one full causal row of the same T."""
 import os
 import sys
 import time
@@ -20,6 +23,8 @@ from p2t_hip import specs, synth                                # noqa: E402
 
 def main():
     dev = torch.device("cuda:0")
+    if sys.argv[1:2] == ["packed"]:
+        return packed_leg(dev)
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 4
     esm_name, llama_name, _, _, Tp, _ = specs.CONFIGS["cfg3"]
     esm, llama = specs.esm_spec(esm_name), specs.llama_spec(llama_name)
@@ -164,6 +169,99 @@ def trainer_leg(model, kw, B):
           f"({nbytes / dt_opt / 6.29e12:.2f} of the 6.29 TB/s float4 copy rate)", flush=True)
     print(f"LoRA operands per step ({L * len(TARGETS)} projections): rebuilt from the masters {t_fresh * 1e3:.1f} ms, "
           f"registered by the trainer {t_reg * 1e3:.1f} ms: {(t_fresh - t_reg) * 1e3:.1f} ms saved per step", flush=True)
+
+
+def packed_leg(dev, N=48, max_tokens=4 * 1216):
+    esm_name, llama_name, _, _, Tp, _ = specs.CONFIGS["cfg3"]
+    esm, llama = specs.esm_spec(esm_name), specs.llama_spec(llama_name)
+    ad = specs.adapter_spec(esm, llama)
+    model = P.Esm2LlamaInstructForCausalLM.from_specs(esm, llama, ad, dtype=torch.bfloat16, device=dev, seed=0)
+    ph = model.config.placeholder_id
+    rs = np.random.RandomState(0)
+    plen = np.clip(np.round(rs.lognormal(5.75, 0.6, N)), 16, Tp).astype(int)           # ragged_sweep.py's draws
+    dlen = np.clip(np.round(rs.lognormal(4.0, 0.5, N)), 4, 256).astype(int)
+    pid, pm = synth.protein_batch(77, N, Tp, plen.tolist())
+    samples = []
+    for i in range(N):                  # [bos, placeholders, 16 prompt tokens, description, eot]; the description is supervised
+        ids = np.concatenate([[1], np.full(plen[i], ph), rs.randint(2, 128000, 16), rs.randint(2, 128000, dlen[i]), [2]]).astype(np.int64)
+        lab = np.full_like(ids, -100)
+        lab[-dlen[i] - 1:] = ids[-dlen[i] - 1:]
+        samples.append((ids, lab))
+    real = int(sum(len(x) for x, _ in samples))
+
+    def padded(idx):                    # right-padded micro-batch of samples idx, protein rows trimmed to their longest
+        T = max(len(samples[i][0]) for i in idx)
+        ids = np.zeros((len(idx), T), np.int64); mask = np.zeros_like(ids); lab = np.full_like(ids, -100)
+        for r, i in enumerate(idx):
+            n = len(samples[i][0])
+            ids[r, :n], mask[r, :n], lab[r, :n] = samples[i][0], 1, samples[i][1]
+        tp = int(plen[idx].max())
+        return dict(input_ids=ids, attention_mask=mask, labels=lab, protein_input_ids=pid[idx, :tp], protein_attention_mask=pm[idx, :tp])
+
+    t = lambda b: {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) if isinstance(v, np.ndarray) else v.to(dev) for k, v in b.items()
+                   if k != "pack_layout"}
+    setups = {"padded B=1": [t(padded(np.array([i]))) for i in range(N)],
+              "padded B=4": [t(padded(np.arange(i, min(i + 4, N)))) for i in range(0, N, 4)]}
+    host = {k: torch.from_numpy(v) for k, v in padded(np.arange(N)).items()}
+    pk = P.pack_instruct_batch(host, max_tokens)
+    rows = []
+    for r in range(pk["input_ids"].shape[0]):
+        members = [i for i, rr, _, _ in pk["pack_layout"] if rr == r]
+        n = int(pk["attention_mask"][r].sum())
+        tp = int(plen[members].max())
+        rows.append(t(dict(input_ids=pk["input_ids"][r:r + 1, :n], attention_mask=pk["attention_mask"][r:r + 1, :n], labels=pk["labels"][r:r + 1, :n],
+                           position_ids=pk["position_ids"][r:r + 1, :n], protein_input_ids=torch.from_numpy(pid[members, :tp]),
+                           protein_attention_mask=torch.from_numpy(pm[members, :tp]))))
+    setups[f"packed rows <= {max_tokens}"] = rows
+    lora = model.add_lora(r=16, lora_alpha=32, lora_dropout=0.1)
+    model.train()
+    tr = P.InstructTrainer(model)
+    print(f"packed leg cfg3: {N} samples, protein length mean {plen.mean():.0f} (max {plen.max()}), {real} real decoder tokens "
+          f"(mean {real / N:.0f} per sample); InstructTrainer r=16, GA 1", flush=True)
+    res = {}
+    for name, mbs in setups.items():
+        tr.step(mbs[0])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for b in mbs:
+            tr.step(b)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        slots = sum(int(b["input_ids"].numel()) for b in mbs)
+        res[name] = N / dt
+        print(f"  {name:>22}: {len(mbs)} micro-batches, {slots} decoder slots ({real / slots:.2f} real): {dt * 1e3:.0f} ms = {N / dt:.2f} samples/s, "
+              f"{real / dt:.0f} real decoder tokens/s", flush=True)
+    names = list(res)
+    print(f"  packed / padded B=4 = {res[names[2]] / res[names[1]]:.2f}x, packed / padded B=1 = {res[names[2]] / res[names[0]]:.2f}x", flush=True)
+    # attention of the longest packed row against one full causal row of the same T (cfg3 heads), HIP events
+    from p2t_hip import ops
+    b = max(rows, key=lambda x: x["input_ids"].shape[1])
+    T = b["input_ids"].shape[1]
+    nh, nkv, d = llama.num_attention_heads, llama.num_key_value_heads, llama.head_dim
+    g = torch.Generator(device="cpu").manual_seed(0)
+    q, k, v = [(torch.randn((1, h, T, d), generator=g) * 0.3).to(dev, torch.bfloat16) for h in (nh, nkv, nkv)]
+    mask = torch.ones((1, T), dtype=torch.int64, device=dev)
+    key_mask, kv_info, _ = ops.mask_prepare(mask)
+    docs = ops.doc_prepare(b["position_ids"], mask)
+    d_o = (torch.randn((T, ops.round_up(nh * d, 64)), generator=g) * 0.3).to(dev, torch.bfloat16)
+    lse = torch.empty((1, nh, T), dtype=torch.float32, device=dev)
+
+    def timed(fn, reps=10):
+        fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+    for name, dc in (("full causal row", None), ("packed row", docs)):
+        fwd = lambda: ops.attention(q, k, v, key_mask, kv_info, d, 1.0, True, use_mfma=2, log2_scores=True, lse=lse, docs=dc)
+        out = fwd()
+        bwd = lambda: ops.attention_backward(q, k, v, out, d_o, lse, key_mask, kv_info, d, 0.6931471805599453, True, log2_scores=True, use_mfma=1, docs=dc)
+        print(f"  attention {name}, T={T}, {nh}/{nkv} heads x {d}: forward {timed(fwd):.3f} ms, backward {timed(bwd):.3f} ms", flush=True)
+    lens = [int(x) for x in torch.unique_consecutive(torch.cumsum((b["position_ids"][0] == 0).long(), 0), return_counts=True)[1]]
+    print(f"  packed row documents: {lens}; sum len^2 / T^2 = {sum(x * x for x in lens) / T / T:.3f}", flush=True)
 
 
 if __name__ == "__main__":
