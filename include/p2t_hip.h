@@ -473,6 +473,30 @@ int p2t_adapter_backward(const p2t_adapter_config* cfg, const p2t_adapter_weight
                          float* d_fc2_w, float* d_fc2_b, int accumulate, void* workspace, size_t workspace_bytes,
                          p2t_stream stream);
 
+/* The same backward carried to the adapter's input (stage 2 with LoRA on the encoder): d_x f32 [M, ld_dx] (+)= d loss / d x
+ * (accumulate != 0 adds), with both dropout masks and the L2-normalisation exactly as p2t_adapter_backward applies them.
+ * fc1_w / fc2_w as p2t_adapter_forward reads them; saved->z1, z2, g2 and inv_norm are required. */
+size_t p2t_adapter_backward_dx_workspace_bytes(const p2t_adapter_config* cfg, int64_t M);
+int p2t_adapter_backward_dx(const p2t_adapter_config* cfg, const p2t_adapter_weights* w, int64_t M, const p2t_adapter_saved* saved,
+                            const float* dy, float* d_x, int64_t ld_dx, int accumulate, void* workspace, size_t workspace_bytes,
+                            p2t_stream stream);
+
+/* ---------------------------------------------------------------- stage 2 through the ESM2 encoder (LoRA on its projections) */
+/* The embedding rows of p2t_esm2_forward (token dropout: <mask> rows zeroed, rows scaled by emb_scale of p2t_mask_prepare,
+ * then multiplied by the attention mask): x f32 [B*T, H]. */
+int p2t_esm2_embed(const int64_t* ids, const int64_t* mask, const void* table, int dtype, const float* emb_scale, int B, int T, int H,
+                   int vocab, int mask_id, int token_dropout, float* x, p2t_stream stream);
+/* torch.nn.LayerNorm backward with frozen weight and bias (modeling_esm.py:420-439, 517-521, 552-553): with xhat = (x - mu) r,
+ * r = rsqrt(var + eps), dx (+)= r (w dy - mean(w dy) - xhat mean(w dy xhat)).  x, dx f32, dy `dy_dtype` (F32 / BF16); cols and the
+ * strides multiples of 4; accumulate != 0 adds into dx (the residual-stream gradient). */
+int p2t_layernorm_backward(const float* x, int64_t ld_x, const float* w, float eps, const void* dy, int64_t ld_dy, int dy_dtype,
+                           float* dx, int64_t ld_dx, int64_t rows, int64_t cols, int accumulate, p2t_stream stream);
+/* GELU (erf) on a pre-activation the caller has assembled (a frozen GEMM plus a LoRA branch, which P2T_EPI_GELU cannot see):
+ * dy == NULL: out = gelu_erf(z); else out = dy * gelu_erf'(z).  [M, N] at the given strides, each of z / dy / out F32 or BF16;
+ * columns N up to min(ld_out, N rounded up to 64) - 1 of out are written as zeros (the K padding of the next GEMM). */
+int p2t_gelu_rows(const void* z, int z_dtype, int64_t ld_z, const void* dy, int dy_dtype, int64_t ld_dy, void* out, int out_dtype,
+                  int64_t ld_out, int64_t M, int64_t N, p2t_stream stream);
+
 /* ---------------------------------------------------------------- readout / normalise / loss */
 /* emb [B, T, ld] (`dtype`, or f32), mask int64 [B, T] (NULL = all ones) -> out f32 [B, D] (mean/std/last)
  * or [B, 2D] (mix).  D and ld must be multiples of 4 (vector loads). */

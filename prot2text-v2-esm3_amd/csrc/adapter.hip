@@ -161,3 +161,56 @@ extern "C" int p2t_adapter_backward(const p2t_adapter_config* cfg, const p2t_ada
     }
     return P2T_OK;
 }
+
+// The same backward carried to the adapter's INPUT (stage 2 with LoRA on the encoder: the encoder output is differentiated):
+//     dz2 = as above (mask2, gelu'(z2), the L2-normalisation)     dz1 = (dz2 W2) * mask1 * gelu'(z1)     d_x = dz1 W1
+// the masks regenerated from cfg->dropout_seed exactly as p2t_adapter_backward does.  d_x f32 [M, input_dim] at stride ld_dx.
+extern "C" size_t p2t_adapter_backward_dx_workspace_bytes(const p2t_adapter_config* cfg, int64_t M) {
+    if (!cfg || M < 0) return 0;
+    const size_t e = dtype_size(cfg->dtype);
+    const int64_t I = cfg->intermediate_dim, X = cfg->input_dim;
+    const int64_t ld1 = round_up(I, 64), ld2 = round_up(cfg->output_dim, 64);
+    size_t n = 0;
+    n += (size_t)M * ld2 * e + 256;        // dz2
+    n += (size_t)I * ld2 * e + 256;        // W2^T
+    n += (size_t)M * ld1 * e + 256;        // dz1
+    n += (size_t)X * ld1 * e + 256;        // W1^T
+    return n + 1024;
+}
+
+extern "C" int p2t_adapter_backward_dx(const p2t_adapter_config* cfg, const p2t_adapter_weights* w, int64_t M, const p2t_adapter_saved* saved,
+                                       const float* dy, float* d_x, int64_t ld_dx, int accumulate, void* workspace, size_t workspace_bytes,
+                                       p2t_stream stream) {
+    P2T_TRY(check_adapter(cfg));
+    P2T_REQUIRE(w && w->fc1_w && w->fc2_w && saved && saved->z1 && saved->z2 && saved->g2 && saved->inv_norm && dy && d_x && workspace && M >= 0,
+                "p2t_adapter_backward_dx: null argument (z1, z2, g2 and inv_norm are required)");
+    P2T_REQUIRE(ld_dx >= cfg->input_dim, "p2t_adapter_backward_dx: ld_dx must cover input_dim");
+    P2T_REQUIRE(workspace_bytes >= p2t_adapter_backward_dx_workspace_bytes(cfg, M), "p2t_adapter_backward_dx: workspace too small");
+    if (M == 0) return P2T_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int dt = cfg->dtype;
+    const size_t e = dtype_size(dt);
+    const int64_t I = cfg->intermediate_dim, O = cfg->output_dim, X = cfg->input_dim;
+    const int64_t ld1 = round_up(I, 64), ld2 = round_up(O, 64);
+    Arena ar(workspace, workspace_bytes);
+    void* dz2 = ar.take((size_t)M * ld2 * e);
+    void* w2T = ar.take((size_t)I * ld2 * e);
+    void* dz1 = ar.take((size_t)M * ld1 * e);
+    void* w1T = ar.take((size_t)X * ld1 * e);
+    P2T_REQUIRE(!ar.overflow, "p2t_adapter_backward_dx: workspace overflow");
+
+    P2T_TRY(launch_adapter_dz2(saved->g2, saved->z2, saved->inv_norm, dy, dz2, ld2, M, (int)O, dt, cfg->dropout_p,
+                               cfg->dropout_seed ^ kSeed2, s));
+    P2T_TRY(p2t_transpose(w->fc2_w, O, I, ld1, w2T, ld2, dt, stream));
+    {   // dz1 [M, I] = (dz2 [M, O] . (W2^T [I, O])^T) * mask1 * gelu'(z1)
+        GemmArgs g{dz2, ld2, w2T, ld2, nullptr, dz1, ld1, saved->z1, M, I, ld2, dt, dt, P2T_EPI_GELU_BWD, 0, -1, -1,
+                   cfg->dropout_p, cfg->dropout_seed, 0};
+        P2T_TRY(gemm_nt(g, s));
+    }
+    P2T_TRY(p2t_transpose(w->fc1_w, I, X, round_up(X, 64), w1T, ld1, dt, stream));
+    {   // d_x [M, X] (+)= dz1 [M, I] . (W1^T [X, I])^T
+        GemmArgs g{dz1, ld1, w1T, ld1, nullptr, d_x, ld_dx, nullptr, M, X, ld1, dt, P2T_F32, P2T_EPI_STORE_F32, accumulate, -1, -1, 0.f, 0, 0};
+        P2T_TRY(gemm_nt(g, s));
+    }
+    return P2T_OK;
+}

@@ -186,6 +186,12 @@ SIGNATURES = {
     "p2t_adapter_backward_workspace_bytes": (sz, [C.POINTER(AdapterConfigC), i64]),
     "p2t_adapter_backward": (i32, [C.POINTER(AdapterConfigC), C.POINTER(AdapterWeightsC), vp, i64, i64,
                                    C.POINTER(AdapterSavedC), vp, vp, vp, vp, vp, i32, vp, sz, vp]),
+    "p2t_adapter_backward_dx_workspace_bytes": (sz, [C.POINTER(AdapterConfigC), i64]),
+    "p2t_adapter_backward_dx": (i32, [C.POINTER(AdapterConfigC), C.POINTER(AdapterWeightsC), i64, C.POINTER(AdapterSavedC), vp, vp, i64, i32,
+                                      vp, sz, vp]),
+    "p2t_esm2_embed": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "p2t_layernorm_backward": (i32, [vp, i64, vp, f32, vp, i64, i32, vp, i64, i64, i64, i32, vp]),
+    "p2t_gelu_rows": (i32, [vp, i32, i64, vp, i32, i64, vp, i32, i64, i64, i64, vp]),
     "p2t_readout": (i32, [vp, i32, i64, vp, i32, i32, i32, i32, vp, vp]),
     "p2t_readout_backward": (i32, [vp, i32, i64, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "p2t_l2norm_rows": (i32, [vp, vp, vp, i64, i64, f32, vp]),
@@ -212,7 +218,7 @@ for _i, _s in enumerate(_STRUCTS):
         raise ImportError(f"ABI mismatch: {_s.__name__} is {C.sizeof(_s)} bytes here, {lib.p2t_struct_size(_i)} in the library")
 
 _NO_RC = {"p2t_gemm_fix_workspace_bytes", "p2t_version", "p2t_is_lab_build", "p2t_last_error", "p2t_struct_size", "p2t_esm2_workspace_bytes", "p2t_llama_workspace_bytes", "p2t_llama_tape_bytes", "p2t_llama_train_workspace_bytes", "p2t_llama_prefill_workspace_bytes", "p2t_llama_decode_workspace_bytes",
-          "p2t_adapter_backward_workspace_bytes"}
+          "p2t_adapter_backward_workspace_bytes", "p2t_adapter_backward_dx_workspace_bytes"}
 
 
 def call(name: str, *args):

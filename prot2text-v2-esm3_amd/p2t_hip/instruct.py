@@ -164,7 +164,8 @@ class InstructTrainer:
     def __init__(self, model, *, lr=2e-4, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, max_norm=None,
                  gradient_accumulation_steps: int = 1, schedule=None, process_group=None, train_adapter: bool = True):
         lora = getattr(model.llama_decoder, "lora", None)
-        if lora is None:
+        enc_lora = getattr(getattr(model, "esm_encoder", None), "lora", None)     # LoRA on the ESM2 encoder (p2t_hip/encoder_train.py)
+        if lora is None and enc_lora is None:
             raise ValueError("InstructTrainer trains LoRA adapters: call model.add_lora(...) first")
         if int(gradient_accumulation_steps) != gradient_accumulation_steps or gradient_accumulation_steps < 1:
             raise ValueError("gradient_accumulation_steps must be an integer >= 1")
@@ -174,7 +175,7 @@ class InstructTrainer:
             raise ValueError("betas must be two values in [0, 1)")
         if max_norm is not None and not max_norm > 0:
             raise ValueError("max_norm must be positive (None: no clipping)")
-        self.model, self.lora = model, lora
+        self.model, self.lora, self.enc_lora = model, lora, enc_lora
         self.hp = dict(lr=float(lr), betas=tuple(float(b) for b in betas), eps=float(eps), weight_decay=float(weight_decay),
                        max_norm=math.inf if max_norm is None else float(max_norm))
         self.schedule, self.group = schedule, process_group
@@ -182,26 +183,32 @@ class InstructTrainer:
         self.step_count, self.train_mode, self.train_adapter = 0, True, bool(train_adapter)
         dec = model.llama_decoder
         self.dt = dec.model.dtype
-        dev = next(lora.parameters()).device
+        dev = next((lora if lora is not None else enc_lora).parameters()).device
         self.dev = dev
         rank, world = sharding.world_info(process_group)
-        lora.rank = rank if world > 1 else 0          # each rank its own dropout masks; a single process keeps the old sequence
-        # ---- trained tensors: LoRA in peft_state_dict order, then the adapter
+        # ---- trained tensors: decoder LoRA, encoder LoRA (each in peft_state_dict order), then the adapter
         self.names: List[str] = []
         self.params: List[torch.nn.Parameter] = []
-        shadows, operands = [], {}
-        s = lora.scale
-        for i in range(dec.spec.num_hidden_layers):
-            for t in lora.targets:
-                a, b = lora.get(i, t)
-                r, K, N = a.shape[0], a.shape[1], b.shape[0]
-                rp = round_up(r, 16)
-                a16 = torch.zeros((rp, round_up(K, 8)), dtype=self.dt, device=dev)            # the layouts _Lin builds
-                bs16 = torch.zeros((N, round_up(rp, 64)), dtype=self.dt, device=dev)
-                operands[(i, t)] = (a16, bs16)
-                self.names += [f"llama_decoder.model.layers.{i}.{t}.lora_A.weight", f"llama_decoder.model.layers.{i}.{t}.lora_B.weight"]
-                self.params += [a, b]
-                shadows += [(a16, r, K, 1.0), (bs16, N, r, s)]
+        shadows, self._operands, self._enc_operands = [], {}, {}
+        towers = [(lora, "llama_decoder.model.layers", dec.spec.num_hidden_layers, self._operands, self.dt),
+                  (enc_lora, "esm_encoder.encoder.layer", model.esm_encoder.spec.num_hidden_layers if enc_lora is not None else 0, self._enc_operands,
+                   model.esm_encoder.dtype if enc_lora is not None else None)]
+        for lo, prefix, n_layers, operands, dt in towers:
+            if lo is None:
+                continue
+            lo.rank = rank if world > 1 else 0        # each rank its own dropout masks; a single process keeps the old sequence
+            s = lo.scale
+            for i in range(n_layers):
+                for t in lo.targets:
+                    a, b = lo.get(i, t)
+                    r, K, N = a.shape[0], a.shape[1], b.shape[0]
+                    rp = round_up(r, 16)
+                    a16 = torch.zeros((rp, round_up(K, 8)), dtype=dt, device=dev)             # the layouts _Lin builds
+                    bs16 = torch.zeros((N, round_up(rp, 64)), dtype=dt, device=dev)
+                    operands[(i, t)] = (a16, bs16)
+                    self.names += [f"{prefix}.{i}.{t}.lora_A.weight", f"{prefix}.{i}.{t}.lora_B.weight"]
+                    self.params += [a, b]
+                    shadows += [(a16, r, K, 1.0), (bs16, N, r, s)]
         ad = model.adapter
         ad_params = (ad.fc1.weight, ad.fc1.bias, ad.fc2.weight, ad.fc2.bias)
         self._adapter_views = self.train_adapter and ad.fc1.weight.dtype == torch.float32
@@ -213,7 +220,7 @@ class InstructTrainer:
                 shadows.append(None if self._adapter_views else (q.data.view(-1, q.shape[-1]), q.numel() // q.shape[-1], q.shape[-1], 1.0))
         else:
             ad.requires_grad_(False)
-        self.n_lora = 2 * len(operands)
+        self.n_lora = 2 * (len(self._operands) + len(self._enc_operands))
         self.opt = FlatAdamW([q.numel() for q in self.params], dev, shadows)
         with torch.no_grad():
             for k, q in enumerate(self.params):
@@ -223,9 +230,19 @@ class InstructTrainer:
                 q.data = self.opt.view(self.opt.flat_p, k, q.shape)
                 q.grad = self.opt.view(self.opt.flat_g, k, q.shape)
         self.opt.refresh_shadows()
-        lora.set_operands(operands)
-        self._operands = operands
+        for lo, ops_ in ((lora, self._operands), (enc_lora, self._enc_operands)):
+            if lo is not None:
+                lo.set_operands(ops_)
         self.grad_norm = self.opt.grad_norm
+
+    @property
+    def loras(self):
+        """The LoRA modules this trainer optimises (decoder, encoder), those that exist."""
+        return [lo for lo in (self.lora, self.enc_lora) if lo is not None]
+
+    def _mark_operands_current(self):
+        for lo in self.loras:
+            lo.mark_operands_current()
 
     # ---- protocol of loop.train_epoch / eval_epoch
     @property
@@ -274,7 +291,7 @@ class InstructTrainer:
         if self.schedule is not None:
             hp["lr"] = self.schedule.lr()
         self.opt.step(self.step_count, **hp)
-        self.lora.mark_operands_current()
+        self._mark_operands_current()
         if self.schedule is not None:
             self.schedule.step()
         self.opt.flat_g.zero_()
@@ -292,17 +309,22 @@ class InstructTrainer:
     @torch.no_grad()
     def evaluate(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
         """Forward-only loss with no activation tape, as under the reference's model.eval(): LoRA branches without dropout (peft's
-        eval mode), adapter without dropout.  The LoRA mask counter does not move."""
+        eval mode), adapter without dropout.  The LoRA mask counters do not move."""
         from .decoder_train import lora_lm_loss
         m = self.model
         was = m.adapter.training
         m.adapter.train(False)
+        enc_was = self.enc_lora.training if self.enc_lora is not None else None
+        if self.enc_lora is not None:
+            self.enc_lora.train(False)               # encoder branches: dropout 0 and no mask step in eval mode (encoder_lora_forward)
         try:
             embeds, mask = m(input_ids=batch["input_ids"], attention_mask=batch["attention_mask"], protein_input_ids=batch["protein_input_ids"],
                              protein_attention_mask=batch["protein_attention_mask"], position_ids=batch.get("position_ids"),
                              return_decoder_inputs=True)
         finally:
             m.adapter.train(was)
+            if self.enc_lora is not None:
+                self.enc_lora.train(enc_was)
         labels = batch["labels"]
         if tuple(labels.shape) != tuple(embeds.shape[:2]):
             raise ValueError(f"labels shape {tuple(labels.shape)} != {tuple(embeds.shape[:2])}")
@@ -326,7 +348,7 @@ class InstructTrainer:
     def sync_from_masters(self):
         """After the trainer wrote flat_p itself (a load): shadows, bf16 adapter tensors and the registered operands."""
         self.opt.refresh_shadows()
-        self.lora.mark_operands_current()
+        self._mark_operands_current()
 
     def adapter_state(self) -> Dict[str, torch.Tensor]:
         """The four adapter tensors (the fp32 masters when trained, the module's otherwise), checkpoint keys."""
@@ -346,16 +368,20 @@ def checkpoint_paths(save_checkpoint_dir: str, epoch_idx: int) -> Tuple[str, str
             os.path.join(save_checkpoint_dir, f"optimizer_scheduler_checkpoint_{epoch_idx}.pt"))
 
 
-def adapter_config(lora, train_adapter: bool = True) -> Dict[str, Any]:
-    """adapter_config.json of `LoraConfig(r, lora_alpha, lora_dropout, target_modules, modules_to_save)` (the keys p2t_hip/lora.py reads)."""
-    return {"peft_type": "LORA", "task_type": None, "r": lora.r, "lora_alpha": lora.alpha, "lora_dropout": lora.p, "bias": "none",
-            "target_modules": list(lora.targets), "modules_to_save": ["adapter.fc1", "adapter.fc2"] if train_adapter else None,
+def adapter_config(lora, train_adapter: bool = True, encoder_lora=None) -> Dict[str, Any]:
+    """adapter_config.json of `LoraConfig(r, lora_alpha, lora_dropout, target_modules, modules_to_save)` (the keys p2t_hip/lora.py reads);
+    target_modules lists the decoder's targets, then the encoder's (either LoRA may be None)."""
+    los = [lo for lo in (lora, encoder_lora) if lo is not None]
+    lo = los[0]
+    return {"peft_type": "LORA", "task_type": None, "r": lo.r, "lora_alpha": lo.alpha, "lora_dropout": lo.p, "bias": "none",
+            "target_modules": [t for x in los for t in x.targets], "modules_to_save": ["adapter.fc1", "adapter.fc2"] if train_adapter else None,
             "init_lora_weights": True, "use_rslora": False, "fan_in_fan_out": False, "inference_mode": True}
 
 
-def adapter_tensors(lora, adapter: Optional[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
-    """adapter_model.safetensors: DecoderLora.peft_state_dict() + base_model.model.adapter.fc1 / fc2.weight / bias (CPU, contiguous)."""
-    out = {k: v.detach().cpu().contiguous() for k, v in lora.peft_state_dict().items()}
+def adapter_tensors(lora, adapter: Optional[Dict[str, torch.Tensor]], encoder_lora=None) -> Dict[str, torch.Tensor]:
+    """adapter_model.safetensors: DecoderLora.peft_state_dict() (+ EncoderLora's) + base_model.model.adapter.fc1 / fc2.weight / bias
+    (CPU, contiguous)."""
+    out = {k: v.detach().cpu().contiguous() for lo in (lora, encoder_lora) if lo is not None for k, v in lo.peft_state_dict().items()}
     for k, v in (adapter or {}).items():
         out[_PEFT_PREFIX + k] = v.detach().cpu().contiguous()
     return out
@@ -387,13 +413,16 @@ def save_instruct_checkpoint(trainer: InstructTrainer, save_checkpoint_dir: str,
     adir, opath = checkpoint_paths(save_checkpoint_dir, epoch_idx)
     os.makedirs(adir, exist_ok=True)
     with open(os.path.join(adir, "adapter_config.json"), "w") as f:
-        json.dump(adapter_config(trainer.lora, trainer.train_adapter), f, indent=2)
-    save_file(adapter_tensors(trainer.lora, trainer.adapter_state() if trainer.train_adapter else None),
+        json.dump(adapter_config(trainer.lora, trainer.train_adapter, trainer.enc_lora), f, indent=2)
+    save_file(adapter_tensors(trainer.lora, trainer.adapter_state() if trainer.train_adapter else None, trainer.enc_lora),
               os.path.join(adir, "adapter_model.safetensors"), metadata={"format": "pt"})
     sched = trainer.schedule.state_dict() if trainer.schedule is not None else None
-    torch.save({"optimizer_state_dict": optimizer_state_dict(trainer), "scheduler_state_dict": sched,
-                "p2t_dropout_state": {"lora_step_count": int(trainer.lora.step_count), "adapter_calls": int(trainer.model.adapter._calls)}},
-               opath)
+    ds = {"adapter_calls": int(trainer.model.adapter._calls)}
+    if trainer.lora is not None:
+        ds["lora_step_count"] = int(trainer.lora.step_count)
+    if trainer.enc_lora is not None:
+        ds["encoder_lora_step_count"] = int(trainer.enc_lora.step_count)
+    torch.save({"optimizer_state_dict": optimizer_state_dict(trainer), "scheduler_state_dict": sched, "p2t_dropout_state": ds}, opath)
     return [adir, opath]
 
 
@@ -438,7 +467,10 @@ def load_instruct_checkpoint(trainer: InstructTrainer, adapter_dir: str, opt_pat
         if trainer.schedule is not None and sd.get("scheduler_state_dict") is not None:
             trainer.schedule.load_state_dict(sd["scheduler_state_dict"])
         ds = sd.get("p2t_dropout_state") or {}
-        trainer.lora.step_count = int(ds.get("lora_step_count", trainer.lora.step_count))
+        if trainer.lora is not None:
+            trainer.lora.step_count = int(ds.get("lora_step_count", trainer.lora.step_count))
+        if trainer.enc_lora is not None:
+            trainer.enc_lora.step_count = int(ds.get("encoder_lora_step_count", trainer.enc_lora.step_count))
         trainer.model.adapter._calls = int(ds.get("adapter_calls", trainer.model.adapter._calls))
     trainer.sync_from_masters()
 

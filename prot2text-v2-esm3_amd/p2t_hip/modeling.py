@@ -97,6 +97,10 @@ def _f32(v: torch.Tensor) -> torch.Tensor:
     return v if v.dtype == torch.float32 and v.is_contiguous() else v.float().contiguous()
 
 
+_ENCODER_LORA_MSG = ("this encoder carries LoRA adapters: only the stage-2 loss (Esm2LlamaInstructForCausalLM.forward) runs with the branches in place; "
+                     "merge them for inference (p2t_hip.lora.load_and_merge_adapter on peft_state_dict())")
+
+
 class _Workspace:
     """uint8 workspace tensors cached per key (the HIP stream), grow-only, reused across calls and shapes."""
 
@@ -164,6 +168,7 @@ class EsmEncoder(nn.Module):
 
     def invalidate_engine(self):
         self._engine = None
+        self.__dict__.pop("_et_wT", None)       # transposed frozen weights of the encoder-LoRA step (p2t_hip/encoder_train.py)
 
     def _build_engine(self):
         s, dt = self.spec, self.dtype
@@ -223,6 +228,8 @@ class EsmEncoder(nn.Module):
             attention_mask = torch.ones_like(input_ids)
         if tuple(attention_mask.shape) != (B, T):
             raise ValueError(f"protein_attention_mask shape {tuple(attention_mask.shape)} != input ids {(B, T)}")
+        if getattr(self, "lora", None) is not None:
+            raise NotImplementedError(_ENCODER_LORA_MSG)
         e = self._engine or self._build_engine()
         dev = self.embeddings.word_embeddings.weight.device
         ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
@@ -252,8 +259,9 @@ class EsmEncoder(nn.Module):
 # ---------------------------------------------------------------------------------------------
 class _AdapterFn(torch.autograd.Function):
     """y = normalize(drop(gelu(fc2(drop(gelu(fc1(x))))))) with the hand-written backward
-    (p2t_adapter_forward / p2t_adapter_backward).  Gradients: fc1/fc2 weight and bias only -- the
-    encoder is frozen on this path (scripts/train_contrast.py:186)."""
+    (p2t_adapter_forward / p2t_adapter_backward).  Gradients: fc1/fc2 weight and bias (the encoder is frozen in stage 1,
+    scripts/train_contrast.py:186) and, when the input requires grad (stage 2 with LoRA on the encoder), d loss / d input
+    (p2t_adapter_backward_dx, the same dropout masks)."""
 
     @staticmethod
     def forward(ctx, x_pad, w1, b1, w2, b2, adapter, use_dropout, need_grad):
@@ -295,14 +303,23 @@ class _AdapterFn(torch.autograd.Function):
         wts = _lib.AdapterWeightsC(fc1_w=w1p.data_ptr(), fc1_b=b1f.data_ptr(), fc2_w=w2p.data_ptr(), fc2_b=b2f.data_ptr())
         saved = _lib.AdapterSavedC(z1=z1.data_ptr(), h1=h1.data_ptr(), z2=z2.data_ptr(), g2=g2.data_ptr(), inv_norm=inv.data_ptr())
         s1, sb1, s2, sb2, pdt = ctx.shapes
-        g = [torch.empty(s, dtype=torch.float32, device=dev) for s in (s1, sb1, s2, sb2)]
-        nbytes = call("p2t_adapter_backward_workspace_bytes", C.byref(cfg), M)
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
         dyf = dy.float().contiguous() if (dy.dtype != torch.float32 or not dy.is_contiguous()) else dy
-        call("p2t_adapter_backward", C.byref(cfg), C.byref(wts), ptr(x_pad), x_pad.stride(0), M, C.byref(saved), ptr(dyf),
-             ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]), 0, ptr(ws), ws.numel(), stream())
-        g = [t if pdt == torch.float32 else ops.cast(t, pdt) for t in g]
-        return None, g[0], g[1], g[2], g[3], None, None, None
+        g = [None] * 4
+        if any(ctx.needs_input_grad[1:5]):
+            g = [torch.empty(s, dtype=torch.float32, device=dev) for s in (s1, sb1, s2, sb2)]
+            nbytes = call("p2t_adapter_backward_workspace_bytes", C.byref(cfg), M)
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            call("p2t_adapter_backward", C.byref(cfg), C.byref(wts), ptr(x_pad), x_pad.stride(0), M, C.byref(saved), ptr(dyf),
+                 ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]), 0, ptr(ws), ws.numel(), stream())
+            g = [t if pdt == torch.float32 else ops.cast(t, pdt) for t in g]
+        dx = None
+        if ctx.needs_input_grad[0]:
+            ld = x_pad.shape[1]
+            dx = (torch.zeros if ld > round_up(cfg.input_dim, 64) else torch.empty)((M, ld), dtype=torch.float32, device=dev)
+            nbytes = call("p2t_adapter_backward_dx_workspace_bytes", C.byref(cfg), M)
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            call("p2t_adapter_backward_dx", C.byref(cfg), C.byref(wts), M, C.byref(saved), ptr(dyf), ptr(dx), ld, 0, ptr(ws), ws.numel(), stream())
+        return dx, g[0], g[1], g[2], g[3], None, None, None
 
 
 class ModalityAdapter(nn.Module):
@@ -337,7 +354,7 @@ class ModalityAdapter(nn.Module):
     def forward_padded(self, x_pad: torch.Tensor) -> torch.Tensor:
         """x_pad: [M, ld >= round_up(input_dim, 64)] with zero padding -> [M, output_dim]."""
         params = (self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        need_grad = torch.is_grad_enabled() and (x_pad.requires_grad or any(p.requires_grad for p in params))
         return _AdapterFn.apply(x_pad, *params, self, bool(self.training), need_grad)
 
     def forward(self, hidden_states: torch.Tensor) -> torch.Tensor:
@@ -998,13 +1015,20 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
         """Reference :108-215.  position_ids (packed rows) and loss_weights reach LlamaDecoder.forward's loss path (see there)."""
         if protein_position_ids is not None or protein_head_mask is not None or protein_inputs_embeds is not None:
             raise NotImplementedError("protein_position_ids / protein_head_mask / protein_inputs_embeds are not supported")
+        enc_lora = getattr(self.esm_encoder, "lora", None)
         if return_encoder_outputs:                 # reference :175-189
+            if enc_lora is not None:
+                raise NotImplementedError(_ENCODER_LORA_MSG)
             return self.esm_encoder(input_ids=protein_input_ids, attention_mask=protein_attention_mask,
                                     output_attentions=output_attentions, output_hidden_states=output_hidden_states,
                                     return_dict=return_dict)
         if output_attentions or output_hidden_states:
             raise NotImplementedError("output_attentions / output_hidden_states are not available from the fused encoder")
-        enc = self.esm_encoder.encode(protein_input_ids, protein_attention_mask)      # [B, T, Hp], zero padded
+        if enc_lora is not None:                   # LoRA on the encoder (reference :174-193 under autograd): the per-layer step
+            from .encoder_train import encoder_lora_forward
+            enc = encoder_lora_forward(self.esm_encoder, enc_lora, protein_input_ids, protein_attention_mask)
+        else:
+            enc = self.esm_encoder.encode(protein_input_ids, protein_attention_mask)      # [B, T, Hp], zero padded
         B, T, Hp = enc.shape
         adapter_output = self.adapter.forward_padded(enc.view(B * T, Hp)).reshape(B, T, -1)   # reference :191
         if return_adapter_outputs:                 # reference :192-193
@@ -1025,6 +1049,8 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
         """Reference :217-251: `inputs` is the [prompt] only; the prompt embeddings (placeholders replaced by the adapter rows) come
         from `forward(return_decoder_inputs=True)` and go to `llama_decoder.generate(inputs_embeds=, attention_mask=, **kwargs)`.
         The output does not repeat the prompt (it went in as embeddings)."""
+        if getattr(self.esm_encoder, "lora", None) is not None:
+            raise NotImplementedError(_ENCODER_LORA_MSG)
         with torch.no_grad():
             prompt_embeds, prompt_mask = self(input_ids=inputs, attention_mask=attention_mask, protein_input_ids=protein_input_ids,
                                               protein_attention_mask=protein_attention_mask, protein_inputs_embeds=protein_inputs_embeds,
@@ -1033,18 +1059,26 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
         return self.llama_decoder.generate(inputs_embeds=prompt_embeds, attention_mask=prompt_mask, **kwargs)
 
     def add_lora(self, r: int, lora_alpha: Optional[float] = None, lora_dropout: float = 0.1, target_modules=None, seed: int = 0):
-        """`get_peft_model(model, LoraConfig(r, lora_alpha = 2 r, lora_dropout = 0.1, target_modules = [...decoder projections...],
-        modules_to_save = adapter.fc1 / fc2))` of scripts/train_instruct.py:155-183, for the decoder targets (the script's ESM-C
-        target names match no module of the ESM2 encoder): trainable A / B pairs on the seven projections of every decoder layer
-        (p2t_hip/decoder_train.py), the base weights frozen, the modality adapter left trainable.  Returns the DecoderLora module
-        (its parameters are what the optimizer takes next to the adapter's)."""
+        """`get_peft_model(model, LoraConfig(r, lora_alpha = 2 r, lora_dropout = 0.1, target_modules = [...],
+        modules_to_save = adapter.fc1 / fc2))` of scripts/train_instruct.py:155-183: trainable A / B pairs on every module a target
+        selects under peft's rule (the module name is the target or ends in "." + target; p2t_hip/encoder_train.py resolve_targets):
+        the decoder's seven projections (p2t_hip/decoder_train.py; the default `target_modules`) and ESM2's attention.self.{query,
+        key,value}, attention.output.dense, intermediate.dense, output.dense (p2t_hip/encoder_train.py; "dense" selects three of
+        them).  A name that selects nothing raises.  The base weights are frozen, the modality adapter is left trainable.
+        Returns the DecoderLora module (the EncoderLora when only encoder modules are targeted); the encoder's pairs are
+        `model.esm_encoder.lora`."""
         from .decoder_train import TARGETS, DecoderLora
-        self.llama_decoder.lora = DecoderLora(self.llama_decoder, r, lora_alpha, lora_dropout, TARGETS if target_modules is None else target_modules, seed)
+        from .encoder_train import EncoderLora, resolve_targets
+        dec, enc = resolve_targets(TARGETS if target_modules is None else target_modules)
         self.esm_encoder.requires_grad_(False)
+        if enc:
+            self.esm_encoder.lora = EncoderLora(self.esm_encoder, r, lora_alpha, lora_dropout, enc, seed)
+        if dec:
+            self.llama_decoder.lora = DecoderLora(self.llama_decoder, r, lora_alpha, lora_dropout, dec, seed)
         for n, q in self.llama_decoder.named_parameters():
             if not n.startswith("lora."):
                 q.requires_grad_(False)
-        return self.llama_decoder.lora
+        return self.llama_decoder.lora if dec else self.esm_encoder.lora
 
     def gradient_checkpointing_enable(self, gradient_checkpointing_kwargs=None):
         """Accepted for loop compatibility (reference :253-261; `transformers.Trainer(gradient_checkpointing=True)` passes

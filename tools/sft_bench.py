@@ -2,7 +2,9 @@
 scatter -> 32-layer Llama-3.1-8B -> LM head -> shifted CE, once forward only and once as the training step `loss.backward()`
 (frozen towers, adapter trainable: training forward with the activation tape + the dX chain of csrc/llama_train.hip + adapter
 backward), with a per-kernel-family breakdown of the backward from the torch profiler-free HIP-event brackets below.
-python tools/sft_bench.py [B] [lora] [trainer] [packed] > sft_bench.log
+python tools/sft_bench.py [B] [lora] [trainer] [encoder] [packed] > sft_bench.log
+`encoder`: InstructTrainer with LoRA r = 16 on the decoder's seven projections AND ESM2's six linears of every layer
+(p2t_hip/encoder_train.py: the encoder runs layer by layer with a tape and a HIP backward): ms per step and peak memory.
 `trainer`: the stage-2 InstructTrainer (LoRA r = 16 + adapter, GA 1): ms per full step, the flat clip + AdamW tail alone (bytes,
 fraction of HBM bandwidth) and the host time per step that the optimizer-written LoRA operands save.
 `packed`: InstructTrainer (r = 16) on ragged samples (tools/ragged_sweep.py's protein length draws) as padded micro-batches of 1 (the
@@ -113,6 +115,34 @@ def main():
               f"peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB", flush=True)
     if "trainer" in sys.argv:
         trainer_leg(model, kw, B)
+    if "encoder" in sys.argv:
+        encoder_leg(model, kw, B)
+
+
+def encoder_leg(model, kw, B):
+    """InstructTrainer at cfg3 sizes with LoRA r = 16 on both towers: 7 x 32 decoder projections + 6 x 36 ESM2 linears, + the adapter."""
+    from p2t_hip.decoder_train import TARGETS
+    from p2t_hip.encoder_train import TARGETS as ENC
+    torch.cuda.empty_cache()
+    model.add_lora(r=16, lora_alpha=32, lora_dropout=0.1, target_modules=list(TARGETS) + list(ENC))
+    model.train()
+    tr = P.InstructTrainer(model)
+    n_p = sum(tr.opt.numels)
+    tr.step(kw)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    n = 3
+    t0 = time.perf_counter()
+    for _ in range(n):
+        loss = tr.step(kw)
+    torch.cuda.synchronize()
+    dt_step = (time.perf_counter() - t0) / n
+    enc_cache = sum(t.numel() * t.element_size() for _, t in model.esm_encoder.__dict__.get("_et_wT", {}).values())
+    print(f"sft InstructTrainer step cfg3 with encoder LoRA: B={B}, r=16 on {len(tr.params) - 4} LoRA matrices of both towers + adapter "
+          f"({n_p / 1e6:.1f} M parameters), GA 1: {dt_step * 1e3:.1f} ms/step = {B / dt_step:.2f} samples/s; loss {float(loss):.4f}; "
+          f"peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB (resident before the step {base / 2**30:.1f} GiB, of which "
+          f"{enc_cache / 2**30:.1f} GiB are the encoder's transposed frozen weights for its dX GEMMs)", flush=True)
 
 
 def trainer_leg(model, kw, B):
