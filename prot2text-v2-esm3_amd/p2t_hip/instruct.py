@@ -32,7 +32,7 @@ import torch
 
 from . import _lib, ops, sharding
 from ._lib import call
-from .ops import ptr, round_up, stream
+from .ops import ptr, stream
 
 ALIGN = 16                                           # segment offsets: float4 access is legal everywhere
 ADAPTER_KEYS = ("adapter.fc1.weight", "adapter.fc1.bias", "adapter.fc2.weight", "adapter.fc2.bias")
@@ -190,25 +190,17 @@ class InstructTrainer:
         self.names: List[str] = []
         self.params: List[torch.nn.Parameter] = []
         shadows, self._operands, self._enc_operands = [], {}, {}
-        towers = [(lora, "llama_decoder.model.layers", dec.spec.num_hidden_layers, self._operands, self.dt),
-                  (enc_lora, "esm_encoder.encoder.layer", model.esm_encoder.spec.num_hidden_layers if enc_lora is not None else 0, self._enc_operands,
-                   model.esm_encoder.dtype if enc_lora is not None else None)]
-        for lo, prefix, n_layers, operands, dt in towers:
+        towers = [(lora, self._operands, self.dt), (enc_lora, self._enc_operands, model.esm_encoder.dtype if enc_lora is not None else None)]
+        for lo, operands, dt in towers:
             if lo is None:
                 continue
             lo.rank = rank if world > 1 else 0        # each rank its own dropout masks; a single process keeps the old sequence
-            s = lo.scale
-            for i in range(n_layers):
-                for t in lo.targets:
-                    a, b = lo.get(i, t)
-                    r, K, N = a.shape[0], a.shape[1], b.shape[0]
-                    rp = round_up(r, 16)
-                    a16 = torch.zeros((rp, round_up(K, 8)), dtype=dt, device=dev)             # the layouts _Lin builds
-                    bs16 = torch.zeros((N, round_up(rp, 64)), dtype=dt, device=dev)
-                    operands[(i, t)] = (a16, bs16)
-                    self.names += [f"{prefix}.{i}.{t}.lora_A.weight", f"{prefix}.{i}.{t}.lora_B.weight"]
-                    self.params += [a, b]
-                    shadows += [(a16, r, K, 1.0), (bs16, N, r, s)]
+            for i, t, a, b in lo.pairs():
+                a16, bs16 = operands[(i, t)] = lo.zero_operands(i, t, dt)
+                shadows += [(a16, lo.r, a.shape[1], 1.0), (bs16, b.shape[0], lo.r, lo.scale)]
+            for name, q in lo.peft_items(prefix=""):
+                self.names.append(name)
+                self.params.append(q)
         ad = model.adapter
         ad_params = (ad.fc1.weight, ad.fc1.bias, ad.fc2.weight, ad.fc2.bias)
         self._adapter_views = self.train_adapter and ad.fc1.weight.dtype == torch.float32

@@ -168,7 +168,7 @@ class EsmEncoder(nn.Module):
 
     def invalidate_engine(self):
         self._engine = None
-        self.__dict__.pop("_et_wT", None)       # transposed frozen weights of the encoder-LoRA step (p2t_hip/encoder_train.py)
+        self.__dict__.pop("_lora_wT", None)     # transposed frozen weights of the encoder-LoRA step (p2t_hip/lora_linear.py _transposed)
 
     def _build_engine(self):
         s, dt = self.spec, self.dtype
@@ -671,13 +671,7 @@ class _DecoderLossFn(torch.autograd.Function):
         s = dec.spec
         B, T, ld = logits.shape
         H, V = s.hidden_size, s.vocab_size
-        d_logits = torch.empty_like(logits)
-        if ctx.weights is not None:
-            call("p2t_cross_entropy_shifted_weighted_backward", ptr(logits), ld, ops.dt_of(logits), ptr(ctx.labels), ptr(ctx.weights), B, T, V, -100,
-                 ptr(d_logits), ld, stream())
-        else:
-            call("p2t_cross_entropy_shifted_backward", ptr(logits), ld, ops.dt_of(logits), ptr(ctx.labels), B, T, V, -100, ptr(ctx.count), ptr(d_logits), ld,
-                 stream())
+        d_logits = ops.cross_entropy_shifted_backward(logits, ctx.labels, V, ctx.count, weights=ctx.weights)
         d_h = ops.gemm_nt(d_logits.view(B * T, ld), dec._lm_head_transposed(), None, n=H, k=round_up(V, 64), epilogue=_lib.EPI_STORE_F32)   # [B*T, H] f32
         d_in = dec.model.train_backward(d_h.view(B, T, H), ctx.handle)
         call("p2t_scale_by_device_scalar", ptr(d_in), d_in.numel(), ptr(g_loss.float().reshape(1).contiguous()), stream())

@@ -188,25 +188,45 @@ def scatter_rows(dst: torch.Tensor, dst_pos, n_dst, src: torch.Tensor, src_pos, 
          ptr(n_src), min(dst_pos.numel(), src_pos.numel()), int(H), stream())
 
 
+def _ce_args(logits: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | None):
+    _chk(logits.dim() == 3 and labels.dim() == 2 and tuple(logits.shape[:2]) == tuple(labels.shape) and logits.stride(2) == 1
+         and logits.is_contiguous(), "cross_entropy_shifted: logits [B, T, ld] contiguous, labels [B, T]")
+    B, T, _ = logits.shape
+    if weights is not None:
+        _chk(tuple(weights.shape) == (B, T) and weights.dtype == torch.float32 and weights.is_contiguous(), "cross_entropy_shifted: weights f32 [B, T]")
+    return logits.shape, labels.to(torch.int64).contiguous()
+
+
 def cross_entropy_shifted(logits: torch.Tensor, labels: torch.Tensor, V: int, ignore_index: int = -100, weights: torch.Tensor | None = None):
     """HF causal-LM loss: logits [B, T, ld >= V], labels [B, T] -> (loss f32 [1], n_targets int32 [1]).
     weights (f32 [B, T], aligned with labels): loss = sum of weights[b, t+1] * ce(b, t) instead of the token mean."""
-    _chk(logits.dim() == 3 and labels.dim() == 2 and tuple(logits.shape[:2]) == tuple(labels.shape) and logits.stride(2) == 1
-         and logits.is_contiguous(), "cross_entropy_shifted: logits [B, T, ld] contiguous, labels [B, T]")
-    B, T, ld = logits.shape
-    lab = labels.to(torch.int64).contiguous()
+    (B, T, ld), lab = _ce_args(logits, labels, weights)
     row_loss = torch.empty((B * T,), dtype=torch.float32, device=logits.device)
     row_valid = torch.empty((B * T,), dtype=torch.int32, device=logits.device)
     loss = torch.empty((1,), dtype=torch.float32, device=logits.device)
     count = torch.empty((1,), dtype=torch.int32, device=logits.device)
     if weights is not None:
-        _chk(tuple(weights.shape) == (B, T) and weights.dtype == torch.float32 and weights.is_contiguous(), "cross_entropy_shifted: weights f32 [B, T]")
         call("p2t_cross_entropy_shifted_weighted", ptr(logits), ld, dt_of(logits), ptr(lab), ptr(weights), B, T, int(V), int(ignore_index),
              ptr(row_loss), ptr(row_valid), ptr(loss), ptr(count), stream())
         return loss, count
     call("p2t_cross_entropy_shifted", ptr(logits), ld, dt_of(logits), ptr(lab), B, T, int(V), int(ignore_index), ptr(row_loss),
          ptr(row_valid), ptr(loss), ptr(count), stream())
     return loss, count
+
+
+def cross_entropy_shifted_backward(logits: torch.Tensor, labels: torch.Tensor, V: int, count: torch.Tensor, weights: torch.Tensor | None = None,
+                                   ignore_index: int = -100) -> torch.Tensor:
+    """d loss / d logits of cross_entropy_shifted for the same arguments (count: the n_targets it returned; unused with weights)
+    -> d_logits like logits (columns V .. the next multiple of 64 zeroed: the K padding of the LM-head dX GEMM)."""
+    (B, T, ld), lab = _ce_args(logits, labels, weights)
+    d_logits = torch.empty_like(logits)
+    if weights is not None:
+        call("p2t_cross_entropy_shifted_weighted_backward", ptr(logits), ld, dt_of(logits), ptr(lab), ptr(weights), B, T, int(V), int(ignore_index),
+             ptr(d_logits), ld, stream())
+    else:
+        call("p2t_cross_entropy_shifted_backward", ptr(logits), ld, dt_of(logits), ptr(lab), B, T, int(V), int(ignore_index), ptr(count),
+             ptr(d_logits), ld, stream())
+    return d_logits
 
 
 def gemm_fix_workspace(device) -> torch.Tensor:

@@ -112,7 +112,7 @@ def _run(model, dec, lora, kind, p):
         for i in range(dec.spec.num_hidden_layers):
             for t in TARGETS:
                 lin = _Lin(dec, lora, i, t, dec.model.dtype)
-                seed, K = lin.lora[5], lin.K
+                seed, K = lin.seed, lin.K
                 ones = torch.ones((B * T, K), dtype=torch.float32, device=dev())
                 out = torch.empty_like(ones)
                 call("p2t_dropout_rows", ptr(ones), _lib.F32, K, ptr(out), _lib.F32, K, B * T, K, float(p), int(seed), 0, stream())

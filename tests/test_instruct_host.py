@@ -4,6 +4,7 @@ checkpoint names and key set, argument validation.  Nothing is launched."""
 import ctypes
 import json
 import os
+import types
 
 import numpy as np
 import pytest
@@ -115,23 +116,33 @@ def test_schedule_steps_once_per_optimizer_step_like_train_instruct():
             assert got == [] and sched.last_epoch == 0
 
 
-class _FakeLora(torch.nn.Module):
-    def __init__(self):
+class _StubDecoder(torch.nn.Module):
+    """The parameter names DecoderLora reads (model.layers.{i}.{target}.weight, every projection [12, 8]), on the CPU (no engine)."""
+
+    def __init__(self, n_layers=2):
         super().__init__()
-        from p2t_hip.decoder_train import TARGETS, DecoderLora
-        self.r, self.alpha, self.p, self.targets = 4, 8.0, 0.1, TARGETS
-        for i in range(2):
+        from p2t_hip.decoder_train import TARGETS
+        self.spec = types.SimpleNamespace(num_hidden_layers=n_layers)
+        self.model = torch.nn.Module()
+        self.model.layers = torch.nn.ModuleList()
+        for _ in range(n_layers):
+            layer = torch.nn.ModuleDict({"self_attn": torch.nn.ModuleDict(), "mlp": torch.nn.ModuleDict()})
             for t in TARGETS:
-                self.register_parameter(DecoderLora._name(i, t, "A"), torch.nn.Parameter(torch.randn(4, 8)))
-                self.register_parameter(DecoderLora._name(i, t, "B"), torch.nn.Parameter(torch.randn(12, 4)))
-        self.peft_state_dict = DecoderLora.peft_state_dict.__get__(self)
+                block, proj = t.split(".")
+                layer[block][proj] = torch.nn.Linear(8, 12, bias=False)
+            self.model.layers.append(layer)
 
 
-def test_checkpoint_names_config_and_safetensors_keys(tmp_path):
+def _decoder_lora():
+    from p2t_hip.decoder_train import DecoderLora
+    return DecoderLora(_StubDecoder(), 4)
+
+
+def test_checkpoint_names_config_and_safetensors_keys_of_a_decoder_lora(tmp_path):
     from safetensors.torch import load_file, save_file
     adir, opath = instruct.checkpoint_paths(str(tmp_path), 3)
     assert adir.endswith("adapter_checkpoint_3") and opath.endswith("optimizer_scheduler_checkpoint_3.pt")
-    lora = _FakeLora()
+    lora = _decoder_lora()
     ad = {k: torch.randn(5) for k in instruct.ADAPTER_KEYS}
     t = instruct.adapter_tensors(lora, ad)
     os.makedirs(adir)
@@ -156,7 +167,7 @@ def test_trainer_argument_validation():
 
     with pytest.raises(ValueError, match="add_lora"):
         instruct.InstructTrainer(_M())
-    _Dec.lora = _FakeLora()
+    _Dec.lora = _decoder_lora()
     for kw in (dict(gradient_accumulation_steps=0), dict(gradient_accumulation_steps=1.5), dict(lr=0.0), dict(eps=0.0),
                dict(weight_decay=-1.0), dict(betas=(0.9, 1.0)), dict(max_norm=0.0)):
         with pytest.raises(ValueError):

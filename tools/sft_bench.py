@@ -138,7 +138,7 @@ def encoder_leg(model, kw, B):
         loss = tr.step(kw)
     torch.cuda.synchronize()
     dt_step = (time.perf_counter() - t0) / n
-    enc_cache = sum(t.numel() * t.element_size() for _, t in model.esm_encoder.__dict__.get("_et_wT", {}).values())
+    enc_cache = sum(t.numel() * t.element_size() for _, t in model.esm_encoder.__dict__.get("_lora_wT", {}).values())
     print(f"sft InstructTrainer step cfg3 with encoder LoRA: B={B}, r=16 on {len(tr.params) - 4} LoRA matrices of both towers + adapter "
           f"({n_p / 1e6:.1f} M parameters), GA 1: {dt_step * 1e3:.1f} ms/step = {B / dt_step:.2f} samples/s; loss {float(loss):.4f}; "
           f"peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB (resident before the step {base / 2**30:.1f} GiB, of which "
@@ -147,7 +147,8 @@ def encoder_leg(model, kw, B):
 
 def trainer_leg(model, kw, B):
     """InstructTrainer at cfg3 sizes: LoRA r = 16 (alpha 32, dropout 0.1) on the 7 x 32 projections + the adapter, GA 1."""
-    from p2t_hip.decoder_train import TARGETS, _Lin
+    from p2t_hip.decoder_train import TARGETS
+    from p2t_hip.lora_linear import LoraLinear
     torch.cuda.empty_cache()
     lora = getattr(model.llama_decoder, "lora", None) or model.add_lora(r=16, lora_alpha=32, lora_dropout=0.1)
     model.train()
@@ -173,16 +174,17 @@ def trainer_leg(model, kw, B):
     torch.cuda.synchronize()
     dt_opt = ev0.elapsed_time(ev1) / reps * 1e-3
     nbytes = tr.opt.bytes_per_step()
-    # host cost of the LoRA operands per step: every _Lin of the forward built from the masters vs taken from the trainer
+    # host cost of the LoRA operands per step: every LoraLinear of the forward built from the masters vs taken from the trainer
     dec, dt = model.llama_decoder, model.llama_decoder.model.dtype
     L = dec.spec.num_hidden_layers
 
     def build_all():
         torch.cuda.synchronize()
         t = time.perf_counter()
+        P = dict(dec.model.named_parameters())             # once per pass, as the step builds it
         for i in range(L):
             for tg in TARGETS:
-                _Lin(dec, lora, i, tg, dt)
+                LoraLinear(dec.model, P, f"layers.{i}.{tg}", lora, i, tg, dt, lora.p)
         torch.cuda.synchronize()
         return time.perf_counter() - t
     build_all()
