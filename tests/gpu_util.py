@@ -31,6 +31,55 @@ def maxabs(a, b):
     return float(np.max(np.abs(np.asarray(a, dtype=np.float64) - np.asarray(b, dtype=np.float64))))
 
 
+# ---- elementwise checks of one entry point against fp64 (tests/test_gpu_stage2_ops.py, tests/test_gpu_encoder_ops.py): fp32 outputs
+# within rtol * |ref| + atol, a bf16 output within one bf16 rounding step (+ atol); output buffers are larger than the contract writes
+# and the rest holds a sentinel that must survive
+SENT = -12352.0                                          # exact in bf16 and fp32
+
+
+def _sentinel(shape, dtype):
+    return torch.full(shape, SENT, dtype=dtype, device=dev())
+
+
+def _kept(t, cols=None, rows=None):
+    """The sentinel region: columns >= cols of every row and every row >= rows."""
+    a = to_np(t)
+    out = []
+    if cols is not None:
+        out.append(a[:, cols:].ravel())
+    if rows is not None:
+        out.append(a[rows:].ravel())
+    return np.concatenate(out) if out else np.zeros(0)
+
+
+def _assert_sentinel(t, cols=None, rows=None):
+    k = _kept(t, cols, rows)
+    assert np.all(k == SENT), f"{int(np.sum(k != SENT))} stray writes"
+
+
+def _ulp_bf16(ref):
+    """One bf16 rounding step at |ref| (8 significant bits)."""
+    a = np.abs(np.asarray(ref, dtype=np.float64))
+    e = np.floor(np.log2(np.maximum(a, 1e-38)))
+    return np.exp2(e - 7)
+
+
+def _check(got, ref, dtype, rtol=1e-6, atol=1e-30, what=""):
+    got = np.asarray(got, dtype=np.float64)
+    ref = np.asarray(ref, dtype=np.float64)
+    assert np.all(np.isfinite(got)), f"{what}: non-finite output"
+    err = np.abs(got - ref)
+    bound = (_ulp_bf16(ref) + atol) if dtype == torch.bfloat16 else (rtol * np.abs(ref) + atol)
+    bad = err > bound
+    assert not bad.any(), f"{what}: {int(bad.sum())} elements off, worst {float(err.max()):.3e} at ref {float(ref.ravel()[np.argmax(err)]):.3e}"
+
+
+def _q(a, dtype):
+    """The values a tensor of `dtype` holds for a (bf16: rounded), as fp64."""
+    t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dtype)
+    return t.double().numpy()
+
+
 _OBS_PATH = None
 _TOL_TABLE = None
 

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from oracle import p2t_oracle as O
+from encoder_ops_reference import attention_fwd_bwd64
 from gpu_util import bf16r, build_model, dev, observe, rel, rnd, to_dev, to_np
 from p2t_hip import specs
 
@@ -136,33 +137,16 @@ def test_attention_lse_and_backward_vs_numpy(case):
         forms["mfma"] = ops.attention_backward(q, k, v, o, d_o, lse, key_mask, kv_info, d, scale, causal, log2_scores=True, use_mfma=1)
     # float64 reference on the stored operands
     qn, kn, vn = (to_np(t).astype(np.float64)[..., :d] for t in (q, k, v))
-    rep = nh // nkv
-    kr, vr = np.repeat(kn, rep, 1), np.repeat(vn, rep, 1)
     c_s = np.log(2.0) if l2s else scale
-    S = np.einsum("bhid,bhjd->bhij", qn, kr) * c_s
-    allowed = (mask[:, None, None, :] != 0) & (np.tril(np.ones((T, T), bool))[None, None] if causal else True)
-    S = np.where(allowed, S, -np.inf)
-    m = S.max(-1, keepdims=True)
-    m = np.where(np.isfinite(m), m, 0.0)
-    E = np.exp(S - m)
-    l = E.sum(-1, keepdims=True)
-    P = np.divide(E, l, out=np.zeros_like(E), where=l > 0)
-    want_lse = np.where(l[..., 0] > 0, m[..., 0] + np.log(np.where(l > 0, l, 1.0))[..., 0], np.inf)
+    cut = lambda t: to_np(t).astype(np.float64).reshape(B, T, -1)[..., :nh * d].reshape(B, T, nh, d).transpose(0, 2, 1, 3)
+    got_o = cut(o)                                       # D uses the STORED output, as the kernel (and torch) do
+    ref = attention_fwd_bwd64(qn, kn, vn, cut(d_o), mask, causal, c_s, o_stored=got_o)
+    want_lse, On, rows = ref["lse"], ref["o"], ref["rows"]   # rows: query rows with at least one visible key
     got_lse = to_np(lse).astype(np.float64)
-    rows = np.broadcast_to(allowed.any(-1), (B, nh, T))   # query rows with at least one visible key
     assert np.isinf(got_lse[~rows]).all() and (got_lse[~rows] > 0).all()
     assert np.abs(got_lse[rows] - want_lse[rows]).max() < (2e-5 if not l2s else 2e-2)
-    On = np.einsum("bhij,bhjd->bhid", P, vr)
-    got_o = to_np(o).astype(np.float64).reshape(B, T, -1)[..., :nh * d].reshape(B, T, nh, d).transpose(0, 2, 1, 3)
     assert rel(got_o[rows], On[rows]) < (2e-5 if not l2s else 1e-2)
-    dO = to_np(d_o).astype(np.float64).reshape(B, T, -1)[..., :nh * d].reshape(B, T, nh, d).transpose(0, 2, 1, 3)
-    Ost = got_o                                          # D uses the STORED output, as the kernel (and torch) do
-    D = (dO * Ost).sum(-1, keepdims=True)
-    dP = np.einsum("bhid,bhjd->bhij", dO, vr)
-    dS = P * (dP - D)
-    want_dq = np.einsum("bhij,bhjd->bhid", dS, kr) * c_s
-    want_dk = (np.einsum("bhij,bhid->bhjd", dS, qn) * c_s).reshape(B, nkv, rep, T, d).sum(2)
-    want_dv = np.einsum("bhij,bhid->bhjd", P, dO).reshape(B, nkv, rep, T, d).sum(2)
+    want_dq, want_dk, want_dv = ref["dq"], ref["dk"], ref["dv"]
     tol = 3e-5 if not l2s else 2e-2                      # bf16: P is rebuilt from an lse of a bf16-probability forward
     for form, (dq, dk, dv) in forms.items():
         for nm, got, want in (("dq", dq, want_dq), ("dk", dk, want_dk), ("dv", dv, want_dv)):

@@ -10,58 +10,14 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_util import dev, to_np
+from gpu_util import _assert_sentinel, _check, _q, _sentinel, dev, to_np
 from p2t_hip import _lib, ops
 from p2t_hip._lib import call
 from p2t_hip.decoder_train import _deinterleave, _interleave
 from p2t_hip.ops import ptr, round_up, stream
 
 pytestmark = pytest.mark.gpu
-SENT = -12352.0                                          # exact in bf16 and fp32
 DTS = (torch.float32, torch.bfloat16)
-
-
-def _sentinel(shape, dtype):
-    return torch.full(shape, SENT, dtype=dtype, device=dev())
-
-
-def _kept(t, cols=None, rows=None):
-    """The sentinel region: columns >= cols of every row and every row >= rows."""
-    a = to_np(t)
-    out = []
-    if cols is not None:
-        out.append(a[:, cols:].ravel())
-    if rows is not None:
-        out.append(a[rows:].ravel())
-    return np.concatenate(out) if out else np.zeros(0)
-
-
-def _assert_sentinel(t, cols=None, rows=None):
-    k = _kept(t, cols, rows)
-    assert np.all(k == SENT), f"{int(np.sum(k != SENT))} stray writes"
-
-
-def _ulp_bf16(ref):
-    """One bf16 rounding step at |ref| (8 significant bits)."""
-    a = np.abs(np.asarray(ref, dtype=np.float64))
-    e = np.floor(np.log2(np.maximum(a, 1e-38)))
-    return np.exp2(e - 7)
-
-
-def _check(got, ref, dtype, rtol=1e-6, atol=1e-30, what=""):
-    got = np.asarray(got, dtype=np.float64)
-    ref = np.asarray(ref, dtype=np.float64)
-    assert np.all(np.isfinite(got)), f"{what}: non-finite output"
-    err = np.abs(got - ref)
-    bound = (_ulp_bf16(ref) + atol) if dtype == torch.bfloat16 else (rtol * np.abs(ref) + atol)
-    bad = err > bound
-    assert not bad.any(), f"{what}: {int(bad.sum())} elements off, worst {float(err.max()):.3e} at ref {float(ref.ravel()[np.argmax(err)]):.3e}"
-
-
-def _q(a, dtype):
-    """The values a tensor of `dtype` holds for a (bf16: rounded), as fp64."""
-    t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dtype)
-    return t.double().numpy()
 
 
 # ---------------------------------------------------------------------------------------------
@@ -188,9 +144,17 @@ def test_rope_backward_pack_is_the_transposed_rotation(d, nh, nkv, kind, T, rope
     _assert_sentinel(out, cols=NQ, rows=B * T)
 
 
-@pytest.mark.parametrize("d,nh,nkv,kind,T", [(64, 4, 2, "arange", 512), (64, 4, 2, "packed", 1024), (128, 8, 2, "packed", 1024), (48, 4, 4, "arange", 256),
-                                             (128, 4, 4, "packed", 4096)])
-def test_rope_backward_is_the_adjoint_of_qkv_post(d, nh, nkv, kind, T):
+LOG2E = 1.4426950408889634
+ADJOINT_CASES = [(64, 4, 2, "arange", 512, 0.37, "llama3"), (64, 4, 2, "packed", 1024, 0.37, "llama3"), (128, 8, 2, "packed", 1024, 0.37, "llama3"),
+                 (48, 4, 4, "arange", 256, 0.37, "llama3"), (128, 4, 4, "packed", 4096, 0.37, "llama3"),
+                 # the ESM2 encoder step: nh == nkv, theta 10000, the query scale folded with log2 e (head_dim 24 / 32 pad to dp = 32)
+                 (24, 20, 20, "arange", 130, LOG2E / 24 ** 0.5, "default"), (32, 20, 20, "arange", 300, LOG2E / 32 ** 0.5, "default"),
+                 (64, 40, 40, "arange", 512, LOG2E / 64 ** 0.5, "default")]
+
+
+@pytest.mark.parametrize("d,nh,nkv,kind,T,q_scale,rope", ADJOINT_CASES,
+                         ids=["-".join(str(v) for v in c[:5]) + ("" if c[6] == "llama3" else "-esm") for c in ADJOINT_CASES])
+def test_rope_backward_is_the_adjoint_of_qkv_post(d, nh, nkv, kind, T, q_scale, rope):
     """<qkv_post(X), Y> = <X, rope_backward(Y)> in fp32: the backward transposes the forward that actually ran (same table, same positions,
     same scale fold, same head / column order)."""
     pos, mask, docs, _ = _layout(kind, T)
@@ -199,8 +163,7 @@ def test_rope_backward_is_the_adjoint_of_qkv_post(d, nh, nkv, kind, T):
     NQ = (nh + 2 * nkv) * d
     g = torch.Generator().manual_seed(11 * d + T)
     X = torch.randn((B * T, round_up(NQ, 64)), generator=g).to(dev())
-    inv = _inv_freq(d, "llama3").to(dev())
-    q_scale = 0.37
+    inv = _inv_freq(d, rope).to(dev())
     q, k, v = ops.qkv_post(X, inv, B, T, nh, nkv, d, q_scale, docs=docs)
     Y = [torch.randn(t.shape, generator=g).to(dev()) for t in (q, k, v)]
     for y in Y:
