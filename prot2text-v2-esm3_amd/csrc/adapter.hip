@@ -87,11 +87,11 @@ extern "C" int p2t_adapter_forward(const p2t_adapter_config* cfg, const p2t_adap
     const int64_t I = cfg->intermediate_dim, O = cfg->output_dim, K1 = round_up(cfg->input_dim, 64);
     const int64_t ld1 = round_up(I, 64), ld2 = round_up(O, 64);
     P2T_REQUIRE(ld_x >= K1, "p2t_adapter_forward: ld_x=%lld must cover input_dim rounded up to 64 (zero padded)", (long long)ld_x);
-    GemmArgs a{x, ld_x, w->fc1_w, K1, w->fc1_b, save->h1, ld1, save->z1, M, I, K1, dt, dt, P2T_EPI_GELU, 0, -1, -1,
-               cfg->dropout_p, cfg->dropout_seed, 0};
+    GemmArgs a(x, ld_x, w->fc1_w, K1, M, I, K1, dt, save->h1, ld1, dt, P2T_EPI_GELU);
+    a.bias = w->fc1_b; a.z = save->z1; a.drop_p = cfg->dropout_p; a.drop_seed = cfg->dropout_seed;
     P2T_TRY(gemm_nt(a, s));
-    GemmArgs b{save->h1, ld1, w->fc2_w, ld1, w->fc2_b, save->g2, ld2, save->z2, M, O, ld1, dt, dt, P2T_EPI_GELU, 0, -1, -1,
-               cfg->dropout_p, cfg->dropout_seed ^ kSeed2, 0};
+    GemmArgs b(save->h1, ld1, w->fc2_w, ld1, M, O, ld1, dt, save->g2, ld2, dt, P2T_EPI_GELU);
+    b.bias = w->fc2_b; b.z = save->z2; b.drop_p = cfg->dropout_p; b.drop_seed = cfg->dropout_seed ^ kSeed2;
     P2T_TRY(gemm_nt(b, s));
     return launch_l2norm(save->g2, dt, ld2, y, dt, ld2, save->inv_norm, M, O, 1e-12f, s);
 }
@@ -142,13 +142,14 @@ extern "C" int p2t_adapter_backward(const p2t_adapter_config* cfg, const p2t_ada
     P2T_TRY(p2t_transpose(dz2, M, O, ld2, dz2T, Mp, dt, stream));
     P2T_TRY(p2t_transpose(saved->h1, M, I, ld1, h1T, Mp, dt, stream));
     {   // dW2 [O, I] = dz2^T [O, M] . (h1^T [I, M])^T
-        GemmArgs g{dz2T, Mp, h1T, Mp, nullptr, d_fc2_w, I, nullptr, O, I, Mp, dt, P2T_F32, P2T_EPI_STORE_F32, accumulate, -1, -1, 0.f, 0, 0};
+        GemmArgs g(dz2T, Mp, h1T, Mp, O, I, Mp, dt, d_fc2_w, I, P2T_F32, P2T_EPI_STORE_F32);
+        g.accumulate = accumulate;
         P2T_TRY(gemm_nt(g, s));
     }
     P2T_TRY(p2t_transpose(w->fc2_w, O, I, ld1, w2T, ld2, dt, stream));
     {   // dz1 [M, I] = (dz2 [M, O] . (W2^T [I, O])^T) * mask1 * gelu'(z1)
-        GemmArgs g{dz2, ld2, w2T, ld2, nullptr, dz1, ld1, saved->z1, M, I, ld2, dt, dt, P2T_EPI_GELU_BWD, 0, -1, -1,
-                   cfg->dropout_p, cfg->dropout_seed, 0};
+        GemmArgs g(dz2, ld2, w2T, ld2, M, I, ld2, dt, dz1, ld1, dt, P2T_EPI_GELU_BWD);
+        g.z = saved->z1; g.drop_p = cfg->dropout_p; g.drop_seed = cfg->dropout_seed;
         P2T_TRY(gemm_nt(g, s));
     }
     P2T_TRY(launch_colsum(dz1, dt, M, I, ld1, d_fc1_b, accumulate, cs_scratch, s));
@@ -156,7 +157,8 @@ extern "C" int p2t_adapter_backward(const p2t_adapter_config* cfg, const p2t_ada
     P2T_TRY(p2t_transpose(dz1, M, I, ld1, dz1T, Mp, dt, stream));
     P2T_TRY(p2t_transpose(x, M, X, ld_x, xT, Mp, dt, stream));
     {   // dW1 [I, X] = dz1^T [I, M] . (x^T [X, M])^T
-        GemmArgs g{dz1T, Mp, xT, Mp, nullptr, d_fc1_w, X, nullptr, I, X, Mp, dt, P2T_F32, P2T_EPI_STORE_F32, accumulate, -1, -1, 0.f, 0, 0};
+        GemmArgs g(dz1T, Mp, xT, Mp, I, X, Mp, dt, d_fc1_w, X, P2T_F32, P2T_EPI_STORE_F32);
+        g.accumulate = accumulate;
         P2T_TRY(gemm_nt(g, s));
     }
     return P2T_OK;
@@ -203,13 +205,14 @@ extern "C" int p2t_adapter_backward_dx(const p2t_adapter_config* cfg, const p2t_
                                cfg->dropout_seed ^ kSeed2, s));
     P2T_TRY(p2t_transpose(w->fc2_w, O, I, ld1, w2T, ld2, dt, stream));
     {   // dz1 [M, I] = (dz2 [M, O] . (W2^T [I, O])^T) * mask1 * gelu'(z1)
-        GemmArgs g{dz2, ld2, w2T, ld2, nullptr, dz1, ld1, saved->z1, M, I, ld2, dt, dt, P2T_EPI_GELU_BWD, 0, -1, -1,
-                   cfg->dropout_p, cfg->dropout_seed, 0};
+        GemmArgs g(dz2, ld2, w2T, ld2, M, I, ld2, dt, dz1, ld1, dt, P2T_EPI_GELU_BWD);
+        g.z = saved->z1; g.drop_p = cfg->dropout_p; g.drop_seed = cfg->dropout_seed;
         P2T_TRY(gemm_nt(g, s));
     }
     P2T_TRY(p2t_transpose(w->fc1_w, I, X, round_up(X, 64), w1T, ld1, dt, stream));
     {   // d_x [M, X] (+)= dz1 [M, I] . (W1^T [X, I])^T
-        GemmArgs g{dz1, ld1, w1T, ld1, nullptr, d_x, ld_dx, nullptr, M, X, ld1, dt, P2T_F32, P2T_EPI_STORE_F32, accumulate, -1, -1, 0.f, 0, 0};
+        GemmArgs g(dz1, ld1, w1T, ld1, M, X, ld1, dt, d_x, ld_dx, P2T_F32, P2T_EPI_STORE_F32);
+        g.accumulate = accumulate;
         P2T_TRY(gemm_nt(g, s));
     }
     return P2T_OK;

@@ -99,12 +99,12 @@ int gemm_nt(const GemmArgs& a, hipStream_t s) {
     }
     const bool aligned = ((uintptr_t)a.A % 16 == 0) && ((uintptr_t)a.W % 16 == 0);
     const bool can_mfma = a.dtype == P2T_BF16 && a.K % 64 == 0 && a.lda % 8 == 0 && a.ldw % 8 == 0 && aligned;
-    if (a.use_mfma == 1 && !can_mfma) {
+    if (a.use_mfma == GEMM_KERNEL_MFMA && !can_mfma) {
         set_error("gemm_nt: MFMA kernel required but shape/dtype not eligible (dtype=%d K=%lld lda=%lld ldw=%lld)", a.dtype,
                   (long long)a.K, (long long)a.lda, (long long)a.ldw);
         return P2T_ERR_UNSUPPORTED;
     }
-    if (can_mfma && a.use_mfma != 0) {
+    if (can_mfma && a.use_mfma != GEMM_KERNEL_SIMPLE) {
         const int pi = prof_begin(s, 0, 2.0 * (double)a.M * (double)a.N * (double)a.K);
         const int rc = launch_gemm_mfma(a.A, a.lda, a.W, a.ldw, a.M, (int)a.N, (int)a.K, n_cover, out_dtype, a.epilogue, ep, a.fix_ws,
                                         a.fix_bytes, a.fix_epoch, s);
@@ -221,7 +221,8 @@ extern "C" int p2t_prof_collect(double* ms, int64_t* launches, double* flops, in
 extern "C" int p2t_gemm_nt(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* out, int64_t ldc,
                            void* z, int64_t M, int64_t N, int64_t K, int dtype, int out_dtype, int epilogue, int accumulate,
                            int use_mfma, void* fix_ws, size_t fix_ws_bytes, unsigned fix_epoch, p2t_stream stream) {
-    GemmArgs a{A, lda, W, ldw, bias, out, ldc, z, M, N, K, dtype, out_dtype, epilogue, accumulate, use_mfma, -1, 0.f, 0, 0};
+    GemmArgs a(A, lda, W, ldw, M, N, K, dtype, out, ldc, out_dtype, epilogue);
+    a.bias = bias; a.z = z; a.accumulate = accumulate; a.use_mfma = use_mfma;
     a.fix_ws = fix_ws; a.fix_bytes = fix_ws_bytes; a.fix_epoch = fix_epoch;
     return gemm_nt(a, (hipStream_t)stream);
 }
@@ -238,8 +239,9 @@ extern "C" int p2t_gemm_nt_fp8(const void* A, int64_t lda, const uint8_t* a_scal
 #else
     P2T_REQUIRE(tile == 0 || tile == 4 || tile == 128 || tile == 256, "p2t_gemm_nt_fp8: tile %d is not 0, 4, 128 or 256", tile);
 #endif
-    GemmArgs a{A, lda, W, ldw, bias, out, ldc, z, M, N, K, P2T_FP8, out_dtype, epilogue, accumulate, 1, -1, 0.f, 0, tile};
-    a.a_scale = a_scale; a.w_scale = w_scale; a.out_row_scale = out_row_scale;
+    GemmArgs a = gemm_args_fp8(A, lda, a_scale, W, w_scale, M, N, K, out, ldc, out_dtype, epilogue);
+    a.ldw = ldw;                // the caller's weight rows need not be packed
+    a.bias = bias; a.z = z; a.accumulate = accumulate; a.tile = tile; a.out_row_scale = out_row_scale;
     return gemm_nt(a, (hipStream_t)stream);
 }
 
@@ -250,8 +252,8 @@ extern "C" int p2t_gemm_qkv_rope(const void* A, int64_t lda, const void* W, int6
     P2T_REQUIRE(inv_freq && cos_sin_scratch && seq > 0 && nh > 0 && nkv > 0, "p2t_gemm_qkv_rope: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     P2T_TRY(launch_rope_table(inv_freq, seq, head_dim / 2, cos_sin_scratch, s));
-    GemmArgs a{A, lda, W, ldw, bias, nullptr, 0, nullptr, M, (int64_t)(nh + 2 * nkv) * head_dim, K, dtype, dtype, P2T_EPI_QKV_ROPE,
-               0, use_mfma, -1, 0.f, 0, 0};
+    GemmArgs a(A, lda, W, ldw, M, (int64_t)(nh + 2 * nkv) * head_dim, K, dtype, nullptr, 0, dtype, P2T_EPI_QKV_ROPE);
+    a.bias = bias; a.use_mfma = use_mfma;
     a.cs = cos_sin_scratch; a.q = q; a.k = k; a.v = v; a.seq = seq; a.nh = nh; a.nkv = nkv; a.q_scale = q_scale; a.head_dim = head_dim;
     a.fix_ws = fix_ws; a.fix_bytes = fix_ws_bytes; a.fix_epoch = fix_epoch;
     return gemm_nt(a, s);

@@ -104,13 +104,20 @@ int get_gemm_policy();
 void set_gemm_policy(int policy);       // launch-form override of the MFMA GEMM (tests / experiments), 0 = default
 size_t gemm_fix_workspace_bytes();       // split-K tail fix-up workspace (flags + slabs); header must be zeroed once per
 size_t gemm_fix_header_bytes();          // sequence of launches that use distinct epochs
-// full dispatcher behind p2t_gemm_nt (gemm.hip)
+// GemmArgs::use_mfma (bf16 / fp32 operands; fp8 has one path).  AUTO (or any other value): the MFMA kernel where the call is eligible
+// (bf16, K % 64 == 0, 16-byte rows), else the fp32-FMA kernel; SIMPLE: the fp32-FMA kernel; MFMA: P2T_ERR_UNSUPPORTED if not eligible
+enum : int { GEMM_KERNEL_AUTO = -1, GEMM_KERNEL_SIMPLE = 0, GEMM_KERNEL_MFMA = 1 };
+// full dispatcher behind p2t_gemm_nt (gemm.hip): out[M, N] = epilogue(A[M, K] . W[N, K]^T).  The constructor names what every
+// call says; everything else is set by member name where it is not the default.
 struct GemmArgs {
-    const void* A; int64_t lda; const void* W; int64_t ldw; const float* bias; void* out; int64_t ldc; void* z;
-    int64_t M; int64_t N; int64_t K; int dtype; int out_dtype; int epilogue; int accumulate; int use_mfma;
-    int n_zero;                 // -1: default (next multiple of 64, clipped to ldc)
-    float drop_p; uint64_t drop_seed;
-    int tile;                   // fp8 only: 0 auto, 4 four-wave kernel, 128 / 256 rows of the per-tile kernel (bf16: p2t_set_gemm_policy)
+    const void* A; int64_t lda; const void* W; int64_t ldw; const float* bias = nullptr; void* out; int64_t ldc; void* z = nullptr;
+    int64_t M; int64_t N; int64_t K; int dtype; int out_dtype; int epilogue; int accumulate = 0; int use_mfma = GEMM_KERNEL_AUTO;
+    int n_zero = -1;            // -1: default (next multiple of 64, clipped to ldc)
+    float drop_p = 0.f; uint64_t drop_seed = 0;
+    int tile = 0;               // fp8 only: 0 auto, 4 four-wave kernel, 128 / 256 rows of the per-tile kernel (bf16: p2t_set_gemm_policy)
+    GemmArgs(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int64_t N, int64_t K, int dtype, void* out, int64_t ldc,
+             int out_dtype, int epilogue)
+        : A(A), lda(lda), W(W), ldw(ldw), out(out), ldc(ldc), M(M), N(N), K(K), dtype(dtype), out_dtype(out_dtype), epilogue(epilogue) {}
     // P2T_EPI_QKV_ROPE only (head_dim 64 or 128): rotary table [T, head_dim], outputs [B, heads, T, head_dim]
     const float* cs = nullptr; void* q = nullptr; void* k = nullptr; void* v = nullptr;
     int seq = 0, nh = 0, nkv = 0; float q_scale = 1.f; int head_dim = 64;
@@ -121,6 +128,15 @@ struct GemmArgs {
     const uint8_t* out_row_scale = nullptr;        // P2T_EPI_GELU_FP8: E8M0 byte of every output row
 };
 int gemm_nt(const GemmArgs& a, hipStream_t s);
+// the fp8 form: A [M, K] and W [N, K] are e4m3 bytes with one E8M0 scale byte per row, W rows packed at stride K
+static inline GemmArgs gemm_args_fp8(const void* A, int64_t lda, const uint8_t* a_scale, const void* W, const uint8_t* w_scale, int64_t M, int64_t N,
+                                     int64_t K, void* out, int64_t ldc, int out_dtype, int epilogue) {
+    GemmArgs g(A, lda, W, K, M, N, K, P2T_FP8, out, ldc, out_dtype, epilogue);
+    g.use_mfma = GEMM_KERNEL_MFMA; g.a_scale = a_scale; g.w_scale = w_scale;
+    return g;
+}
+// hand the call the split-K fix-up workspace `ws` (gemm_fix_workspace_bytes()); `epoch` counts the calls since its header was zeroed
+static inline void with_fix(GemmArgs& g, void* ws, unsigned& epoch) { g.fix_ws = ws; g.fix_bytes = gemm_fix_workspace_bytes(); g.fix_epoch = ++epoch; }
 // weight-streaming GEMM for M <= 64 rows (gemm_skinny.hip): bf16, epilogues STORE / STORE_F32 / RESID / SWIGLU, no bias;
 // P2T_ERR_UNSUPPORTED for anything else
 // epilogue arguments of launch_gemm_skinny_qkv_rope: rotation at position prompt_len[row / group] + step[0] and the cache append

@@ -682,8 +682,7 @@ extern "C" int p2t_llama_decode_step(const p2t_llama_config* c, const p2t_llama_
                      int64_t N, int64_t K, int out_dtype, int epi, const SkinnyRope* ra, hipStream_t st) {
         const int r = launch_gemm_skinny_fp8(A, lda, as, pre ? pre : W, K, wsc, out, ldc, M, N, K, out_dtype, epi, ra, st, pre != nullptr);
         if (r != P2T_ERR_UNSUPPORTED || ra) return r;
-        GemmArgs g{A, lda, W, K, nullptr, out, ldc, nullptr, M, N, K, P2T_FP8, out_dtype, epi, 0, 1, -1, 0.f, 0, 0};
-        g.a_scale = as; g.w_scale = wsc;
+        GemmArgs g = gemm_args_fp8(A, lda, as, W, wsc, M, N, K, out, ldc, out_dtype, epi);
         if (epi == P2T_EPI_STORE_F32) g.n_zero = (int)N;
         return p2t::gemm_nt(g, st);
     };
@@ -736,7 +735,8 @@ extern "C" int p2t_llama_decode_step(const p2t_llama_config* c, const p2t_llama_
             if (r != P2T_ERR_UNSUPPORTED) { P2T_TRY(r); roped = true; }
         }
         if (!roped) {
-            GemmArgs g1{b.h, Hp, L.qkv_w, Hp, nullptr, b.qkv, NQKV, nullptr, M, NQKV, Hp, dt, P2T_F32, P2T_EPI_STORE_F32, 0, -1, (int)NQKV, 0.f, 0, 0};
+            GemmArgs g1(b.h, Hp, L.qkv_w, Hp, M, NQKV, Hp, dt, b.qkv, NQKV, P2T_F32, P2T_EPI_STORE_F32);
+            g1.n_zero = (int)NQKV;
             P2T_TRY(gemm_nt(g1, s, stream_w ? ws_layers[l].qkv_w : nullptr));
             {
                 const unsigned grid = (unsigned)ceil_div((int64_t)BB * (nh + 2 * nkv), 4);
@@ -756,12 +756,12 @@ extern "C" int p2t_llama_decode_step(const p2t_llama_config* c, const p2t_llama_
         }
         if (dt == P2T_BF16) P2T_TRY(launch_attn_decode_t<bf16_t>(b, cache, l, BB, nh, nkv, d, dp, c_exp, 1, QO, s));
         else P2T_TRY(launch_attn_decode_t<float>(b, cache, l, BB, nh, nkv, d, dp, c_exp, 0, QO, s));
-        GemmArgs g2{b.ao, QO, L.o_w, QO, nullptr, b.x, H, nullptr, M, H, QO, dt, P2T_F32, P2T_EPI_RESID, 0, -1, -1, 0.f, 0, 0};
+        GemmArgs g2(b.ao, QO, L.o_w, QO, M, H, QO, dt, b.x, H, P2T_F32, P2T_EPI_RESID);
         P2T_TRY(gemm_nt(g2, s, stream_w ? ws_layers[l].o_w : nullptr));
         P2T_TRY(launch_rmsnorm_few_rows(b.x, H, L.ln2_w, c->rms_norm_eps, b.h, Hp, M, H, dt, s));
-        GemmArgs g3{b.h, Hp, L.gu_w, Hp, nullptr, b.act, Fp, nullptr, M, 2 * F, Hp, dt, dt, P2T_EPI_SWIGLU, 0, -1, -1, 0.f, 0, 0};
+        GemmArgs g3(b.h, Hp, L.gu_w, Hp, M, 2 * F, Hp, dt, b.act, Fp, dt, P2T_EPI_SWIGLU);
         P2T_TRY(gemm_nt(g3, s, stream_w ? ws_layers[l].gu_w : nullptr));
-        GemmArgs g4{b.act, Fp, L.down_w, Fp, nullptr, b.x, H, nullptr, M, H, Fp, dt, P2T_F32, P2T_EPI_RESID, 0, -1, -1, 0.f, 0, 0};
+        GemmArgs g4(b.act, Fp, L.down_w, Fp, M, H, Fp, dt, b.x, H, P2T_F32, P2T_EPI_RESID);
         P2T_TRY(gemm_nt(g4, s, stream_w ? ws_layers[l].down_w : nullptr));
     }
     P2T_REQUIRE(!lm_head_preshuffled || dt == P2T_BF16, "p2t_llama_decode_step: pre-shuffled weights are a bf16 layout");
@@ -770,7 +770,7 @@ extern "C" int p2t_llama_decode_step(const p2t_llama_config* c, const p2t_llama_
     P2T_REQUIRE(!lm_head_preshuffled || M <= 64, "p2t_llama_decode_step: a pre-shuffled LM head serves at most 64 rows (got %lld): pass the row-major one",
                 (long long)M);
     P2T_TRY(launch_rmsnorm_few_rows(b.x, H, w->final_norm_w, c->rms_norm_eps, b.h, Hp, M, H, dt, s));
-    GemmArgs gh{b.h, Hp, lm_head, ld_head, nullptr, logits, ld_logits, nullptr, M, c->vocab, Hp, dt, dt, P2T_EPI_STORE, 0, -1, -1, 0.f, 0, 0};
+    GemmArgs gh(b.h, Hp, lm_head, ld_head, M, c->vocab, Hp, dt, logits, ld_logits, dt, P2T_EPI_STORE);
     P2T_TRY(gemm_nt(gh, s, lm_head_preshuffled ? lm_head : nullptr));
     advance_kernel<<<1, 1, 0, s>>>(cache->step);
     P2T_LAUNCH_CHECK();

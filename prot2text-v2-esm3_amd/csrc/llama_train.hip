@@ -557,8 +557,8 @@ int llama_train_backward_impl(const p2t_llama_config* c, const p2t_llama_weights
     unsigned epoch = 0;
     auto dx_gemm = [&](const void* A, int64_t lda, const void* WT, int64_t K, int64_t N, void* out, int64_t ldc, int out_dtype, int epi) {
         // dX[M, N] = A[M, K] . WT[N, K]^T with WT = the forward weight transposed ([N = forward K][ld >= forward N])
-        GemmArgs a{A, lda, WT, round_up(K, 64), nullptr, out, ldc, nullptr, M, N, round_up(K, 64), dt, out_dtype, epi, 0, -1, -1, 0.f, 0, 0};
-        a.fix_ws = b.fix; a.fix_bytes = gemm_fix_workspace_bytes(); a.fix_epoch = ++epoch;
+        GemmArgs a(A, lda, WT, round_up(K, 64), M, N, round_up(K, 64), dt, out, ldc, out_dtype, epi);
+        with_fix(a, b.fix, epoch);
         return gemm_nt(a, s);
     };
     for (int l = c->n_layers - 1; l >= 0; --l) {

@@ -89,6 +89,22 @@ size_t llama_plan(const p2t_llama_config* c, int B, int T, Arena* ar, LlamaBuffe
     return a.off + 256;
 }
 
+// The A operand of a projection: rows of the model dtype at stride ld (scale == nullptr), or (gemm_fp8) e4m3 bytes at stride ld
+// with one E8M0 scale byte per row.  Either way its rows are zero padded to ld, which is also the weight's row stride and the
+// GEMM's K (the width rounded up to 64 elements, or to 128 bytes).
+struct Operand { void* p; int64_t ld; uint8_t* scale; };
+
+// out[M, N] = epilogue(a . W[N, a.ld]^T); ws: the weight's row scales, read by the fp8 form only
+GemmArgs projection(const Operand& a, const void* W, const uint8_t* ws, int64_t M, int64_t N, int dt, void* out, int64_t ldc, int out_dtype, int epi) {
+    return a.scale ? gemm_args_fp8(a.p, a.ld, a.scale, W, ws, M, N, a.ld, out, ldc, out_dtype, epi)
+                   : GemmArgs(a.p, a.ld, W, a.ld, M, N, a.ld, dt, out, ldc, out_dtype, epi);
+}
+
+// "turn a model-dtype buffer into an operand": x is the operand itself, or (fp8) one quantise pass writes its e4m3 copy o
+int quantise_into(const Operand& o, const void* x, int dt, int64_t ld, int64_t M, int64_t cols, hipStream_t s) {
+    return o.scale ? launch_quant_rows(x, dt, ld, M, cols, o.p, o.ld, o.scale, s) : (int)P2T_OK;
+}
+
 }  // namespace
 
 extern "C" size_t p2t_esm2_workspace_bytes(const p2t_esm2_config* cfg, int B, int T) {
@@ -135,77 +151,62 @@ extern "C" int p2t_esm2_forward(const p2t_esm2_config* c, const p2t_esm2_weights
     const float q_scale = (l2s ? kLog2e : 1.0f) / sqrtf((float)d);
     P2T_CHECK_HIP(hipMemsetAsync(b.fix, 0, gemm_fix_header_bytes(), s));      // split-K tail flags; epochs below are unique
     unsigned epoch = 0;
-    auto with_fix = [&](GemmArgs& g) { g.fix_ws = b.fix; g.fix_bytes = gemm_fix_workspace_bytes(); g.fix_epoch = ++epoch; };
+    // gemm_fp8 (BASELINE.json configs[4]): the same layer, GEMM operands e4m3 with a power-of-two scale per row.  The LayerNorms
+    // write their output directly in that format; the attention output and the GELU output are produced in bf16 (attention reads
+    // bf16 q/k/v; GELU rows span many tiles) and quantised by one streaming pass each.  Only the model-dtype GEMMs have a split-K
+    // form, so only they take the fix-up workspace.
+    const bool fp8 = c->gemm_fp8;
     const int64_t Hq = round_up(H, 128), Fq = round_up(F, 128);
-    for (int l = 0; c->gemm_fp8 && l < c->n_layers; ++l) {
-        // fp8 GEMMs (BASELINE.json configs[4]): the same layer, operands e4m3 with a power-of-two scale per row.  The
-        // LayerNorms write their output directly in that format; the attention output and the GELU output are produced
-        // in bf16 (attention reads bf16 q/k/v; GELU rows span many tiles) and quantised by one streaming pass each.
+    const Operand h = fp8 ? Operand{b.hq, Hq, b.hs} : Operand{b.h, Hp, nullptr};
+    const Operand ao = fp8 ? Operand{b.aoq, Hq, b.aos} : Operand{b.ao, Hp, nullptr};
+    const Operand ffn = fp8 ? Operand{b.ffnq, Fq, b.ffns} : Operand{b.ffn, Fp, nullptr};
+    // "normalise into an operand": LayerNorm of the residual stream -> h (bound_*: launch_layernorm_fp8, FFN-up below)
+    auto norm_into_h = [&](const float* ln_w, const float* ln_b, float bound_w, float bound_b, uint8_t* bound_scale) {
+        return fp8 ? launch_layernorm_fp8(b.x, H, ln_w, ln_b, c->layer_norm_eps, b.hq, Hq, b.hs, M, H, bound_w, bound_b, bound_scale, s)
+                   : launch_layernorm(b.x, H, ln_w, ln_b, c->layer_norm_eps, b.h, Hp, M, H, dt, s);
+    };
+    for (int l = 0; l < c->n_layers; ++l) {
         const p2t_esm2_layer& L = w->layers[l];
-        P2T_REQUIRE(L.qkv_ws && L.o_ws && L.fc1_ws && L.fc2_ws, "p2t_esm2_forward: gemm_fp8 needs the row scales of layer %d", l);
-        auto fp8 = [&](const void* A, int64_t lda, const uint8_t* as, const void* W, const uint8_t* ws, const float* bias, void* out, int64_t ldc,
-                       int64_t N, int64_t K, int out_dtype, int epi) {
-            GemmArgs g{A, lda, W, K, bias, out, ldc, nullptr, M, N, K, P2T_FP8, out_dtype, epi, 0, 1, -1, 0.f, 0, 0};
-            g.a_scale = as; g.w_scale = ws;
-            return g;
-        };
-        P2T_TRY(launch_layernorm_fp8(b.x, H, L.ln1_w, L.ln1_b, c->layer_norm_eps, b.hq, Hq, b.hs, M, H, 0.f, 0.f, nullptr, s));
-        if (d == 64) {
-            GemmArgs g1 = fp8(b.hq, Hq, b.hs, L.qkv_w, L.qkv_ws, L.qkv_b, nullptr, 0, 3 * H, Hq, dt, P2T_EPI_QKV_ROPE);
-            g1.cs = b.cs; g1.q = b.q; g1.k = b.k; g1.v = b.v; g1.seq = T; g1.nh = nh; g1.nkv = nh; g1.q_scale = q_scale;
-            P2T_TRY(gemm_nt(g1, s));
-        } else {
-            GemmArgs g1 = fp8(b.hq, Hq, b.hs, L.qkv_w, L.qkv_ws, L.qkv_b, b.qkv, 3 * H, 3 * H, Hq, dt, P2T_EPI_STORE);
-            g1.n_zero = (int)(3 * H);
-            P2T_TRY(gemm_nt(g1, s));
-            P2T_TRY(launch_qkv_post(b.qkv, 3 * H, b.cs, b.q, b.k, b.v, B, T, nh, nh, d, dp, q_scale, dt, s));
-        }
-        P2T_TRY(attention(b.q, b.k, b.v, b.key_mask, b.kv_info, b.ao, Hp, B, T, nh, nh, d, dp, 1.0f, 0, dt, -1, l2s, s));
-        P2T_TRY(launch_quant_rows(b.ao, dt, Hp, M, H, b.aoq, Hq, b.aos, s));
-        GemmArgs g2 = fp8(b.aoq, Hq, b.aos, L.o_w, L.o_ws, L.o_b, b.x, H, H, Hq, P2T_F32, P2T_EPI_RESID);
-        P2T_TRY(gemm_nt(g2, s));
-        // FFN-up writes its GELU output straight as e4m3 when the layer carries the weight-norm bound: the per-token scale is
-        // then known before the GEMM runs (||LN(x)||_2 * max_n ||W_n||_2 + max |bias| bounds every element of the row),
-        // derived by the LayerNorm kernel that already holds the row; otherwise: bf16 output + one quantise pass
-        const bool fused_q = L.fc1_wnorm_bound > 0.f;
-        P2T_TRY(launch_layernorm_fp8(b.x, H, L.ln2_w, L.ln2_b, c->layer_norm_eps, b.hq, Hq, b.hs, M, H, L.fc1_wnorm_bound, L.fc1_babs_bound,
-                                     fused_q ? b.ffns : nullptr, s));
-        if (fused_q) {
-            GemmArgs g3 = fp8(b.hq, Hq, b.hs, L.fc1_w, L.fc1_ws, L.fc1_b, b.ffnq, Fq, F, Hq, dt, P2T_EPI_GELU_FP8);
-            g3.out_row_scale = b.ffns;
-            P2T_TRY(gemm_nt(g3, s));
-        } else {
-            GemmArgs g3 = fp8(b.hq, Hq, b.hs, L.fc1_w, L.fc1_ws, L.fc1_b, b.ffn, Fp, F, Hq, dt, P2T_EPI_GELU);
-            P2T_TRY(gemm_nt(g3, s));
-            P2T_TRY(launch_quant_rows(b.ffn, dt, Fp, M, F, b.ffnq, Fq, b.ffns, s));
-        }
-        GemmArgs g4 = fp8(b.ffnq, Fq, b.ffns, L.fc2_w, L.fc2_ws, L.fc2_b, b.x, H, H, Fq, P2T_F32, P2T_EPI_RESID);
-        P2T_TRY(gemm_nt(g4, s));
-    }
-    for (int l = 0; !c->gemm_fp8 && l < c->n_layers; ++l) {
-        const p2t_esm2_layer& L = w->layers[l];
-        P2T_TRY(launch_layernorm(b.x, H, L.ln1_w, L.ln1_b, c->layer_norm_eps, b.h, Hp, M, H, dt, s));
+        P2T_REQUIRE(!fp8 || (L.qkv_ws && L.o_ws && L.fc1_ws && L.fc2_ws), "p2t_esm2_forward: gemm_fp8 needs the row scales of layer %d", l);
+        P2T_TRY(norm_into_h(L.ln1_w, L.ln1_b, 0.f, 0.f, nullptr));
         if (d == 64) {
             // QKV projection with bias + q-scale + rotary + head split fused into the GEMM epilogue
-            GemmArgs g1{b.h, Hp, L.qkv_w, Hp, L.qkv_b, nullptr, 0, nullptr, M, 3 * H, Hp, dt, dt, P2T_EPI_QKV_ROPE, 0, -1, -1, 0.f, 0, 0};
+            GemmArgs g1 = projection(h, L.qkv_w, L.qkv_ws, M, 3 * H, dt, nullptr, 0, dt, P2T_EPI_QKV_ROPE);
+            g1.bias = L.qkv_b;
             g1.cs = b.cs; g1.q = b.q; g1.k = b.k; g1.v = b.v; g1.seq = T; g1.nh = nh; g1.nkv = nh; g1.q_scale = q_scale;
-            with_fix(g1);
+            if (!fp8) with_fix(g1, b.fix, epoch);
             P2T_TRY(gemm_nt(g1, s));
         } else {
-            GemmArgs g1{b.h, Hp, L.qkv_w, Hp, L.qkv_b, b.qkv, 3 * H, nullptr, M, 3 * H, Hp, dt, dt, P2T_EPI_STORE, 0, -1, (int)(3 * H), 0.f, 0, 0};
+            GemmArgs g1 = projection(h, L.qkv_w, L.qkv_ws, M, 3 * H, dt, b.qkv, 3 * H, dt, P2T_EPI_STORE);
+            g1.bias = L.qkv_b; g1.n_zero = (int)(3 * H);
             P2T_TRY(gemm_nt(g1, s));
             P2T_TRY(launch_qkv_post(b.qkv, 3 * H, b.cs, b.q, b.k, b.v, B, T, nh, nh, d, dp, q_scale, dt, s));
         }
         P2T_TRY(attention(b.q, b.k, b.v, b.key_mask, b.kv_info, b.ao, Hp, B, T, nh, nh, d, dp, 1.0f, 0, dt, -1, l2s, s));
-        GemmArgs g2{b.ao, Hp, L.o_w, Hp, L.o_b, b.x, H, nullptr, M, H, Hp, dt, P2T_F32, P2T_EPI_RESID, 0, -1, -1, 0.f, 0, 0};
-        with_fix(g2);
+        P2T_TRY(quantise_into(ao, b.ao, dt, Hp, M, H, s));
+        GemmArgs g2 = projection(ao, L.o_w, L.o_ws, M, H, dt, b.x, H, P2T_F32, P2T_EPI_RESID);
+        g2.bias = L.o_b;
+        if (!fp8) with_fix(g2, b.fix, epoch);
         P2T_TRY(gemm_nt(g2, s));
-        P2T_TRY(launch_layernorm(b.x, H, L.ln2_w, L.ln2_b, c->layer_norm_eps, b.h, Hp, M, H, dt, s));
-        GemmArgs g3{b.h, Hp, L.fc1_w, Hp, L.fc1_b, b.ffn, Fp, nullptr, M, F, Hp, dt, dt, P2T_EPI_GELU, 0, -1, -1, 0.f, 0, 0};
-        with_fix(g3);
-        P2T_TRY(gemm_nt(g3, s));
-        GemmArgs g4{b.ffn, Fp, L.fc2_w, Fp, L.fc2_b, b.x, H, nullptr, M, H, Fp, dt, P2T_F32, P2T_EPI_RESID, 0, -1, -1, 0.f, 0, 0};
-        with_fix(g4);
+        // fp8 FFN-up writes its GELU output straight as e4m3 when the layer carries the weight-norm bound: the per-token scale is
+        // then known before the GEMM runs (||LN(x)||_2 * max_n ||W_n||_2 + max |bias| bounds every element of the row),
+        // derived by the LayerNorm kernel that already holds the row; otherwise: bf16 output + one quantise pass
+        const bool fused_q = fp8 && L.fc1_wnorm_bound > 0.f;
+        P2T_TRY(norm_into_h(L.ln2_w, L.ln2_b, L.fc1_wnorm_bound, L.fc1_babs_bound, fused_q ? ffn.scale : nullptr));
+        if (fused_q) {
+            GemmArgs g3 = projection(h, L.fc1_w, L.fc1_ws, M, F, dt, ffn.p, ffn.ld, dt, P2T_EPI_GELU_FP8);
+            g3.bias = L.fc1_b; g3.out_row_scale = ffn.scale;
+            P2T_TRY(gemm_nt(g3, s));
+        } else {
+            GemmArgs g3 = projection(h, L.fc1_w, L.fc1_ws, M, F, dt, b.ffn, Fp, dt, P2T_EPI_GELU);
+            g3.bias = L.fc1_b;
+            if (!fp8) with_fix(g3, b.fix, epoch);
+            P2T_TRY(gemm_nt(g3, s));
+            P2T_TRY(quantise_into(ffn, b.ffn, dt, Fp, M, F, s));
+        }
+        GemmArgs g4 = projection(ffn, L.fc2_w, L.fc2_ws, M, H, dt, b.x, H, P2T_F32, P2T_EPI_RESID);
+        g4.bias = L.fc2_b;
+        if (!fp8) with_fix(g4, b.fix, epoch);
         P2T_TRY(gemm_nt(g4, s));
     }
     return launch_layernorm(b.x, H, w->final_ln_w, w->final_ln_b, c->layer_norm_eps, out, ld_out, M, H, dt, s);
@@ -261,50 +262,23 @@ int p2t::llama_forward_impl(const p2t_llama_config* c, const p2t_llama_weights* 
     const float q_fold = l2s ? scale * kLog2e : 1.0f;
     P2T_CHECK_HIP(hipMemsetAsync(b.fix, 0, gemm_fix_header_bytes(), s));      // split-K flags; epochs below are unique
     unsigned epoch = 0;
-    auto with_fix = [&](GemmArgs& g) { g.fix_ws = b.fix; g.fix_bytes = gemm_fix_workspace_bytes(); g.fix_epoch = ++epoch; };
     P2T_REQUIRE(!c->gemm_fp8 || dt == P2T_BF16, "p2t_llama_hidden_forward: gemm_fp8 needs bf16 activations (dtype = P2T_BF16)");
     P2T_REQUIRE(!docs || (!c->gemm_fp8 && !kv), "p2t_llama_hidden_forward: packed rows run the model-dtype GEMMs without a KV cache");
+    P2T_REQUIRE(!tape || !c->gemm_fp8, "p2t_llama_hidden_forward: the tape keeps model-dtype activations (gemm_fp8 = 0)");
+    // gemm_fp8: the same layer with e4m3 GEMM operands, as in p2t_esm2_forward (the RMSNorms write them, the attention output
+    // and the SwiGLU output take a quantise pass)
+    const bool fp8 = c->gemm_fp8;
     const int64_t Hq = round_up(H, 128), Fq = round_up(F, 128), QOq = round_up((int64_t)nh * d, 128);
-    for (int l = 0; c->gemm_fp8 && l < k; ++l) {
+    const Operand h = fp8 ? Operand{b.hq, Hq, b.hs} : Operand{b.h, Hp, nullptr};
+    const Operand act = fp8 ? Operand{b.actq, Fq, b.acts} : Operand{b.act, Fp, nullptr};
+    // "normalise into an operand": RMSNorm of the residual stream -> h
+    auto norm_into_h = [&](const float* ln_w) {
+        return fp8 ? launch_rmsnorm_fp8(b.x, H, ln_w, c->rms_norm_eps, b.hq, Hq, b.hs, M, H, s)
+                   : launch_rmsnorm(b.x, H, ln_w, c->rms_norm_eps, b.h, Hp, M, H, dt, s);
+    };
+    for (int l = 0; l < k; ++l) {
         const p2t_llama_layer& L = w->layers[l];
-        P2T_REQUIRE(L.qkv_ws && L.o_ws && L.gu_ws && L.down_ws, "p2t_llama_hidden_forward: gemm_fp8 needs the row scales of layer %d", l);
-        auto fp8 = [&](const void* A, int64_t lda, const uint8_t* as, const void* W, const uint8_t* ws, void* out, int64_t ldc, int64_t N,
-                       int64_t K, int out_dtype, int epi) {
-            GemmArgs g{A, lda, W, K, nullptr, out, ldc, nullptr, M, N, K, P2T_FP8, out_dtype, epi, 0, 1, -1, 0.f, 0, 0};
-            g.a_scale = as; g.w_scale = ws;
-            return g;
-        };
-        P2T_REQUIRE(!L.q_norm_w == !L.k_norm_w, "p2t_llama_hidden_forward: q_norm_w and k_norm_w go together (layer %d)", l);
-        P2T_TRY(launch_rmsnorm_fp8(b.x, H, L.ln1_w, c->rms_norm_eps, b.hq, Hq, b.hs, M, H, s));
-        if (L.q_norm_w) {          // Qwen3: projection -> per-head RMSNorm -> rotation (not fusable: the norm spans the head)
-            GemmArgs g1 = fp8(b.hq, Hq, b.hs, L.qkv_w, L.qkv_ws, b.qkv, NQKV, NQKV, Hq, dt, P2T_EPI_STORE);
-            g1.n_zero = (int)NQKV;
-            P2T_TRY(gemm_nt(g1, s));
-            P2T_TRY(launch_qk_norm_rope(b.qkv, NQKV, b.cs, L.q_norm_w, L.k_norm_w, c->rms_norm_eps, b.q, b.k, b.v, B, T, nh, nkv, d, dp, q_fold, dt, s));
-        } else if (d == 64 || d == 128) {
-            GemmArgs g1 = fp8(b.hq, Hq, b.hs, L.qkv_w, L.qkv_ws, nullptr, 0, NQKV, Hq, dt, P2T_EPI_QKV_ROPE);
-            g1.cs = b.cs; g1.q = b.q; g1.k = b.k; g1.v = b.v; g1.seq = T; g1.nh = nh; g1.nkv = nkv; g1.q_scale = q_fold; g1.head_dim = d;
-            P2T_TRY(gemm_nt(g1, s));
-        } else {
-            GemmArgs g1 = fp8(b.hq, Hq, b.hs, L.qkv_w, L.qkv_ws, b.qkv, NQKV, NQKV, Hq, dt, P2T_EPI_STORE);
-            g1.n_zero = (int)NQKV;
-            P2T_TRY(gemm_nt(g1, s));
-            P2T_TRY(launch_qkv_post(b.qkv, NQKV, b.cs, b.q, b.k, b.v, B, T, nh, nkv, d, dp, q_fold, dt, s));
-        }
-        P2T_TRY(attention(b.q, b.k, b.v, b.key_mask, b.kv_info, b.ao, QO, B, T, nh, nkv, d, dp, scale, 1, dt, -1, l2s, s));
-        if (kv) P2T_TRY(llama_kv_store(c, kv, l, b.k, b.v, B, T, s));
-        P2T_TRY(launch_quant_rows(b.ao, dt, QO, M, (int64_t)nh * d, b.aoq, QOq, b.aos, s));
-        GemmArgs g2 = fp8(b.aoq, QOq, b.aos, L.o_w, L.o_ws, b.x, H, H, QOq, P2T_F32, P2T_EPI_RESID);
-        P2T_TRY(gemm_nt(g2, s));
-        P2T_TRY(launch_rmsnorm_fp8(b.x, H, L.ln2_w, c->rms_norm_eps, b.hq, Hq, b.hs, M, H, s));
-        GemmArgs g3 = fp8(b.hq, Hq, b.hs, L.gu_w, L.gu_ws, b.act, Fp, 2 * F, Hq, dt, P2T_EPI_SWIGLU);
-        P2T_TRY(gemm_nt(g3, s));
-        P2T_TRY(launch_quant_rows(b.act, dt, Fp, M, F, b.actq, Fq, b.acts, s));
-        GemmArgs g4 = fp8(b.actq, Fq, b.acts, L.down_w, L.down_ws, b.x, H, H, Fq, P2T_F32, P2T_EPI_RESID);
-        P2T_TRY(gemm_nt(g4, s));
-    }
-    for (int l = 0; !c->gemm_fp8 && l < k; ++l) {
-        const p2t_llama_layer& L = w->layers[l];
+        P2T_REQUIRE(!fp8 || (L.qkv_ws && L.o_ws && L.gu_ws && L.down_ws), "p2t_llama_hidden_forward: gemm_fp8 needs the row scales of layer %d", l);
         P2T_REQUIRE(!L.q_norm_w == !L.k_norm_w, "p2t_llama_hidden_forward: q_norm_w and k_norm_w go together (layer %d)", l);
         float* lse = nullptr;
         if (tape) {                       // this layer's heads / attention output live on the tape instead of the shared workspace
@@ -313,40 +287,41 @@ int p2t::llama_forward_impl(const p2t_llama_config* c, const p2t_llama_weights* 
             lse = S.lse;
             P2T_CHECK_HIP(hipMemcpyAsync(S.x_in, b.x, sizeof(float) * (size_t)M * H, hipMemcpyDeviceToDevice, s));
         }
-        P2T_TRY(launch_rmsnorm(b.x, H, L.ln1_w, c->rms_norm_eps, b.h, Hp, M, H, dt, s));
-        if (L.q_norm_w) {          // Qwen3: projection -> per-head RMSNorm -> rotation (not fusable: the norm spans the head)
-            GemmArgs g1{b.h, Hp, L.qkv_w, Hp, nullptr, b.qkv, NQKV, nullptr, M, NQKV, Hp, dt, dt, P2T_EPI_STORE, 0, -1, (int)NQKV, 0.f, 0, 0};
-            P2T_TRY(gemm_nt(g1, s));
-            P2T_TRY(launch_qk_norm_rope(b.qkv, NQKV, b.cs, L.q_norm_w, L.k_norm_w, c->rms_norm_eps, b.q, b.k, b.v, B, T, nh, nkv, d, dp, q_fold, dt, s,
-                                        docs));
-        } else if ((d == 64 || d == 128) && !docs) {
+        P2T_TRY(norm_into_h(L.ln1_w));
+        if (!L.q_norm_w && (d == 64 || d == 128) && !docs) {
             // bias-free QKV projection + rotary + head split in the GEMM epilogue (d = 128: rows packed per head, see the header);
             // packed rows rotate by their position inside the document: GEMM + the positional qkv_post below
-            GemmArgs g1{b.h, Hp, L.qkv_w, Hp, nullptr, nullptr, 0, nullptr, M, NQKV, Hp, dt, dt, P2T_EPI_QKV_ROPE, 0, -1, -1, 0.f, 0, 0};
+            GemmArgs g1 = projection(h, L.qkv_w, L.qkv_ws, M, NQKV, dt, nullptr, 0, dt, P2T_EPI_QKV_ROPE);
             g1.cs = b.cs; g1.q = b.q; g1.k = b.k; g1.v = b.v; g1.seq = T; g1.nh = nh; g1.nkv = nkv; g1.q_scale = q_fold; g1.head_dim = d;
             P2T_TRY(gemm_nt(g1, s));
         } else {
-            GemmArgs g1{b.h, Hp, L.qkv_w, Hp, nullptr, b.qkv, NQKV, nullptr, M, NQKV, Hp, dt, dt, P2T_EPI_STORE, 0, -1, (int)NQKV, 0.f, 0, 0};
+            GemmArgs g1 = projection(h, L.qkv_w, L.qkv_ws, M, NQKV, dt, b.qkv, NQKV, dt, P2T_EPI_STORE);
+            g1.n_zero = (int)NQKV;
             P2T_TRY(gemm_nt(g1, s));
-            // (d = 128 reaches here only with docs: qkv_w then carries the fused epilogue's row order)
-            P2T_TRY(launch_qkv_post(b.qkv, NQKV, b.cs, b.q, b.k, b.v, B, T, nh, nkv, d, dp, q_fold, dt, s, docs, d == 128));
+            if (L.q_norm_w)            // Qwen3: projection -> per-head RMSNorm -> rotation (not fusable: the norm spans the head)
+                P2T_TRY(launch_qk_norm_rope(b.qkv, NQKV, b.cs, L.q_norm_w, L.k_norm_w, c->rms_norm_eps, b.q, b.k, b.v, B, T, nh, nkv, d, dp, q_fold, dt, s,
+                                            docs));
+            else                       // (d = 128 reaches here only with docs: qkv_w then carries the fused epilogue's row order)
+                P2T_TRY(launch_qkv_post(b.qkv, NQKV, b.cs, b.q, b.k, b.v, B, T, nh, nkv, d, dp, q_fold, dt, s, docs, d == 128));
         }
         P2T_TRY(attention(b.q, b.k, b.v, b.key_mask, b.kv_info, b.ao, QO, B, T, nh, nkv, d, dp, scale, 1, dt, -1, l2s, s, lse, docs));
         if (kv) P2T_TRY(llama_kv_store(c, kv, l, b.k, b.v, B, T, s));      // generation prefill: this layer's keys / values -> prompt segment
-        GemmArgs g2{b.ao, QO, L.o_w, QO, nullptr, b.x, H, nullptr, M, H, QO, dt, P2T_F32, P2T_EPI_RESID, 0, -1, -1, 0.f, 0, 0};
-        P2T_TRY(gemm_nt(g2, s));
+        const Operand ao = fp8 ? Operand{b.aoq, QOq, b.aos} : Operand{b.ao, QO, nullptr};      // (b.ao: this layer's, see the tape above)
+        P2T_TRY(quantise_into(ao, b.ao, dt, QO, M, (int64_t)nh * d, s));
+        P2T_TRY(gemm_nt(projection(ao, L.o_w, L.o_ws, M, H, dt, b.x, H, P2T_F32, P2T_EPI_RESID), s));
         if (tape) P2T_CHECK_HIP(hipMemcpyAsync(tape->layer[l].x_mid, b.x, sizeof(float) * (size_t)M * H, hipMemcpyDeviceToDevice, s));
-        P2T_TRY(launch_rmsnorm(b.x, H, L.ln2_w, c->rms_norm_eps, b.h, Hp, M, H, dt, s));
+        P2T_TRY(norm_into_h(L.ln2_w));
         if (tape) {
-            GemmArgs g3{b.h, Hp, L.gu_w, Hp, nullptr, tape->layer[l].gu, 2 * F, nullptr, M, 2 * F, Hp, dt, dt, P2T_EPI_STORE, 0, -1, (int)(2 * F), 0.f, 0, 0};
+            GemmArgs g3 = projection(h, L.gu_w, L.gu_ws, M, 2 * F, dt, tape->layer[l].gu, 2 * F, dt, P2T_EPI_STORE);
+            g3.n_zero = (int)(2 * F);
             P2T_TRY(gemm_nt(g3, s));
             P2T_TRY(launch_swiglu_from_gu(tape->layer[l].gu, 2 * F, b.act, Fp, M, F, dt, s));
         } else {
-            GemmArgs g3{b.h, Hp, L.gu_w, Hp, nullptr, b.act, Fp, nullptr, M, 2 * F, Hp, dt, dt, P2T_EPI_SWIGLU, 0, -1, -1, 0.f, 0, 0};
-            P2T_TRY(gemm_nt(g3, s));
+            P2T_TRY(gemm_nt(projection(h, L.gu_w, L.gu_ws, M, 2 * F, dt, b.act, Fp, dt, P2T_EPI_SWIGLU), s));
         }
-        GemmArgs g4{b.act, Fp, L.down_w, Fp, nullptr, b.x, H, nullptr, M, H, Fp, dt, P2T_F32, P2T_EPI_RESID, 0, -1, -1, 0.f, 0, 0};
-        with_fix(g4);
+        P2T_TRY(quantise_into(act, b.act, dt, Fp, M, F, s));
+        GemmArgs g4 = projection(act, L.down_w, L.down_ws, M, H, dt, b.x, H, P2T_F32, P2T_EPI_RESID);
+        if (!fp8) with_fix(g4, b.fix, epoch);       // the only GEMM of the layer that carries the split-K fix-up workspace
         P2T_TRY(gemm_nt(g4, s));
     }
     if (tape) P2T_CHECK_HIP(hipMemcpyAsync(tape->x_last, b.x, sizeof(float) * (size_t)M * H, hipMemcpyDeviceToDevice, s));
