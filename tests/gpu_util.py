@@ -117,6 +117,42 @@ def rnd(seed, name, shape, scale=1.0, offset=0.0):
     return synth.uniform_f32(seed, name, shape, scale, offset)
 
 
+def adapter_forward_case(X, I, O, M, s1=0.1, s2=0.1, p=0.3, dtype=torch.float32, extra_rows=0):
+    """One p2t_adapter_forward with dropout p on seeded inputs, its activations kept for a backward entry point, and the kernel's own
+    keep-masks read back from the non-zero entries of h1 / g2 (tests/test_gpu_encoder_lora.py, tests/test_gpu_stage1_tail.py).
+    s1 / s2: the weights' scale (the real shape: fan_in^-1/2 as nn.Linear initialises, so that pre-activations stay O(1) and the masks
+    can be read back).  y has `extra_rows` rows more than the contract writes; they hold the sentinel.
+    -> namespace: cfg / wts / saved (the C structs), p, X / I / O / M, CPU tensors x, w1, b1, w2, b2, dy (the operands as stored: bf16 ones
+    widened), m1, m2, device tensors xg, dyg, y, z1, h1, z2, g2, inv."""
+    import ctypes as C
+    from types import SimpleNamespace
+    from p2t_hip import _lib
+    from p2t_hip.ops import dt_of, ptr, round_up, stream
+    g = torch.Generator().manual_seed(3)
+    w1, b1 = torch.randn((I, X), generator=g) * s1, torch.randn(I, generator=g) * 0.1
+    w2, b2 = torch.randn((O, I), generator=g) * s2, torch.randn(O, generator=g) * 0.1
+    x = torch.randn((M, X), generator=g)
+    dy = torch.randn((M, O), generator=g)
+    D = lambda t: t.to(dev()).contiguous()
+    cfg = _lib.AdapterConfigC(input_dim=X, intermediate_dim=I, output_dim=O, dropout_p=p, dropout_seed=12345, dtype=dt_of(dtype))
+    w1p = torch.zeros((I, round_up(X, 64))); w1p[:, :X] = w1
+    w2p = torch.zeros((O, round_up(I, 64))); w2p[:, :I] = w2
+    w1p, w2p, xg = D(w1p).to(dtype), D(w2p).to(dtype), D(x).to(dtype)
+    b1g, b2g, dyg = D(b1), D(b2), D(dy)
+    wts = _lib.AdapterWeightsC(fc1_w=w1p.data_ptr(), fc1_b=b1g.data_ptr(), fc2_w=w2p.data_ptr(), fc2_b=b2g.data_ptr())
+    ld1, ld2 = round_up(I, 64), round_up(O, 64)
+    z1, h1 = torch.empty((M, ld1), dtype=dtype, device=dev()), torch.empty((M, ld1), dtype=dtype, device=dev())
+    z2, g2 = torch.empty((M, ld2), dtype=dtype, device=dev()), torch.empty((M, ld2), dtype=dtype, device=dev())
+    inv, y = torch.empty((M,), device=dev()), _sentinel((M + extra_rows, ld2), dtype)
+    saved = _lib.AdapterSavedC(z1=z1.data_ptr(), h1=h1.data_ptr(), z2=z2.data_ptr(), g2=g2.data_ptr(), inv_norm=inv.data_ptr())
+    _lib.call("p2t_adapter_forward", C.byref(cfg), C.byref(wts), ptr(xg), xg.stride(0), M, ptr(y), C.byref(saved), stream())
+    m1, m2 = (h1[:, :I] != 0).cpu(), (g2[:, :O] != 0).cpu()                    # the kernel's own keep-masks, read back
+    assert 0.5 < float(m1.float().mean()) < 0.9 and 0.5 < float(m2.float().mean()) < 0.9
+    return SimpleNamespace(cfg=cfg, wts=wts, saved=saved, p=p, X=X, I=I, O=O, M=M, x=xg.float().cpu(), w1=w1p[:, :X].float().cpu(), b1=b1,
+                           w2=w2p[:, :I].float().cpu(), b2=b2, dy=dy, m1=m1, m2=m2, xg=xg, dyg=dyg, y=y, z1=z1, h1=h1, z2=z2, g2=g2, inv=inv,
+                           _keep=(w1p, w2p, b1g, b2g))
+
+
 def build_model(esm, llama, ad, dtype, seed=0, adapter_dtype=None):
     from p2t_hip import Esm2LlamaInstructForCausalLM
     return Esm2LlamaInstructForCausalLM.from_specs(esm, llama, ad, dtype=dtype, device=dev(), seed=seed,

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import esm_lora_reference as R
-from gpu_util import build_model, dev, observe, rel, to_dev
+from gpu_util import adapter_forward_case, build_model, dev, observe, rel, to_dev
 from p2t_hip import _lib, ops, specs, synth
 from p2t_hip._lib import call
 from p2t_hip.encoder_train import TARGETS as ENC, encoder_lora_forward
@@ -117,26 +117,9 @@ def test_adapter_backward_dx_at_the_real_adapter_shape():
 def _adapter_dx_case(X, I, O, M, name, s1=0.1, s2=0.1):
     """s1 / s2: the weights' scale (the real shape: fan_in^-1/2 as nn.Linear initialises, so that pre-activations stay O(1) and the
     keep-masks can be read back from the non-zero outputs)."""
-    p = 0.3
-    g = torch.Generator().manual_seed(3)
-    w1, b1 = torch.randn((I, X), generator=g) * s1, torch.randn(I, generator=g) * 0.1
-    w2, b2 = torch.randn((O, I), generator=g) * s2, torch.randn(O, generator=g) * 0.1
-    x = torch.randn((M, X), generator=g)
-    dy = torch.randn((M, O), generator=g)
-    D = lambda t: t.to(dev()).contiguous()
-    cfg = _lib.AdapterConfigC(input_dim=X, intermediate_dim=I, output_dim=O, dropout_p=p, dropout_seed=12345, dtype=0)
-    w1p = torch.zeros((I, round_up(X, 64))); w1p[:, :X] = w1
-    w2p = torch.zeros((O, round_up(I, 64))); w2p[:, :I] = w2
-    w1p, w2p, b1g, b2g, xg, dyg = D(w1p), D(w2p), D(b1), D(b2), D(x), D(dy)
-    wts = _lib.AdapterWeightsC(fc1_w=w1p.data_ptr(), fc1_b=b1g.data_ptr(), fc2_w=w2p.data_ptr(), fc2_b=b2g.data_ptr())
-    ld1, ld2 = round_up(I, 64), round_up(O, 64)
-    z1, h1 = torch.empty((M, ld1), device=dev()), torch.empty((M, ld1), device=dev())
-    z2, g2 = torch.empty((M, ld2), device=dev()), torch.empty((M, ld2), device=dev())
-    inv, y = torch.empty((M,), device=dev()), torch.empty((M, ld2), device=dev())
-    saved = _lib.AdapterSavedC(z1=z1.data_ptr(), h1=h1.data_ptr(), z2=z2.data_ptr(), g2=g2.data_ptr(), inv_norm=inv.data_ptr())
-    call("p2t_adapter_forward", C.byref(cfg), C.byref(wts), ptr(xg), X, M, ptr(y), C.byref(saved), stream())
-    m1, m2 = (h1[:, :I] != 0).cpu(), (g2[:, :O] != 0).cpu()                    # the kernel's own keep-masks, read back
-    assert 0.5 < float(m1.float().mean()) < 0.9 and 0.5 < float(m2.float().mean()) < 0.9
+    c = adapter_forward_case(X, I, O, M, s1, s2)
+    p, cfg, wts, saved, dyg, y = c.p, c.cfg, c.wts, c.saved, c.dyg, c.y
+    x, w1, b1, w2, b2, dy, m1, m2 = c.x, c.w1, c.b1, c.w2, c.b2, c.dy, c.m1, c.m2
     nb = call("p2t_adapter_backward_dx_workspace_bytes", C.byref(cfg), M)
     ws = torch.empty((nb,), dtype=torch.uint8, device=dev())
     dx = torch.full((M, X), 3.0, device=dev())
