@@ -354,6 +354,20 @@ int p2t_rope_backward_pack(const float* dq, const float* dk, const float* dv, co
  * of (seed, element), regenerated, never stored.  p == 0: a (converting, optionally accumulating) copy. */
 int p2t_dropout_rows(const void* src, int src_dtype, int64_t ld_src, void* dst, int dst_dtype, int64_t ld_dst, int64_t M,
                      int64_t K, float p, uint64_t seed, int accumulate, p2t_stream stream);
+/* G[c, j] = sum over m < M of X'[m, c] U[m, j], c < C, j < R: the weight gradients of a LoRA branch y = W x + (alpha / r) B (A drop(x))
+ * (reference scripts/train_instruct.py:146-183, LoraConfig(r, lora_alpha, lora_dropout); p2t_hip/lora_linear.py LoraLinear.backward:
+ * dB = dy^T u with X = dy, U = u = drop(x) A^T; dA = du^T drop(x) with X = x, U = du = dy (s B), stored transposed), summed over
+ * the token axis as the activations lie in memory -- no transposed copies, no dropped copy of x.  X [M, ld_x], U [M, ld_u]:
+ * `dtype` (F32 | BF16), row-major, tokens are rows.  X' = X for p == 0, else p2t_dropout_rows' keep(seed, m C + c) ? X / (1 - p)
+ * : 0 rounded to `dtype`, computed on the fly.  G: f32, [C, ld_g] for transposed == 0, [R, ld_g] (G[j, c]) otherwise; exactly
+ * C R elements are written.  BF16: MFMA with fp32 accumulation, C % 8 == 0 and ld_x % 8 == 0; F32: FMA, any C.  M >= 1,
+ * 1 <= R <= 64.  The token axis is split over workgroups; partial sums go to `workspace` (f32 [splits, C, R], at least
+ * p2t_lora_wgrad_workspace_bytes(C, R, M) bytes: splits C R 4; 0 for arguments out of range) and are added in split order:
+ * no atomics, the same bits every run.  Anything else: P2T_ERR_ARG before any GPU call. */
+size_t p2t_lora_wgrad_workspace_bytes(int64_t C, int64_t R, int64_t M);
+int p2t_lora_wgrad(const void* X, int64_t ld_x, const void* U, int64_t ld_u, int dtype, float* G, int64_t ld_g, int transposed,
+                   int64_t M, int64_t C, int64_t R, float p, uint64_t seed, void* workspace, size_t workspace_bytes,
+                   p2t_stream stream);
 /* dst[dst_pos[r], :H] = src[src_pos[r], :H], r < min(*n_dst, *n_src), f32: the backward of p2t_scatter_rows (the
  * gradient of `inputs_embeds[placeholder_mask] = encoder_hidden_states[encoder_mask]` with respect to the encoder
  * states: call it with the two position lists swapped; rows not listed keep their contents -- zero dst first). */

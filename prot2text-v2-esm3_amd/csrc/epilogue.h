@@ -37,6 +37,10 @@ __device__ __forceinline__ bool dropout_keep(uint64_t seed, int64_t idx, float p
     const uint32_t u = (uint32_t)(mix64((uint64_t)idx + seed) >> 40);
     return (float)u >= p * 16777216.0f;
 }
+// element `idx` of a tensor under dropout(p), scale = 1 / (1 - p): what p2t_dropout_rows stores and p2t_lora_wgrad multiplies
+__device__ __forceinline__ float dropout_value(float x, uint64_t seed, int64_t idx, float p, float scale) {
+    return (p > 0.f && !dropout_keep(seed, idx, p)) ? 0.f : x * scale;
+}
 
 // GEMM outputs are hundreds of MB written once and read by a LATER kernel: non-temporal stores keep a round's
 // 32 MB of results from evicting the operand panels out of the 4 MB L2s (measured +1 % on the GEMM average).

@@ -670,8 +670,7 @@ __global__ void __launch_bounds__(256) dropout_rows_kernel(const Ts* __restrict_
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
         const int64_t m = i / K;
         const int c = (int)(i - m * K);
-        float x = to_f32(src[m * ld_src + c]);
-        x = (p > 0.f && !dropout_keep(seed, i, p)) ? 0.f : x * scale;
+        const float x = dropout_value(to_f32(src[m * ld_src + c]), seed, i, p, scale);
         Td* d = dst + m * ld_dst + c;
         *d = from_f32<Td>(accumulate ? to_f32(*d) + x : x);
     }

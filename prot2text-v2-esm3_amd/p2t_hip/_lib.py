@@ -141,7 +141,9 @@ SIGNATURES = {
     "p2t_swiglu_gu": (i32, [vp, i64, vp, i64, vp, i64, i64, i64, i32, vp]),
     "p2t_rope_backward_pack": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
     "p2t_dropout_rows": (i32, [vp, i32, i64, vp, i32, i64, i64, i64, f32, u64, i32, vp]),
-    "p2t_compact_rows": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "p2t_lora_wgrad_workspace_bytes": (sz, [i64, i64, i64]),
+    "p2t_lora_wgrad": (i32, [vp, i64, vp, i64, i32, vp, i64, i32, i64, i64, i64, f32, u64, vp, sz, vp]),
+    "p2t_compact_rows":(i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "p2t_llama_prefill_workspace_bytes": (sz, [C.POINTER(LlamaConfigC), i32, i32]),
     "p2t_llama_prefill": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), vp, vp, i32, i32, C.POINTER(KvCacheC), vp, vp, sz, vp]),
     "p2t_llama_decode_workspace_bytes": (sz, [C.POINTER(LlamaConfigC), i32, i32, i32]),
@@ -218,7 +220,7 @@ for _i, _s in enumerate(_STRUCTS):
         raise ImportError(f"ABI mismatch: {_s.__name__} is {C.sizeof(_s)} bytes here, {lib.p2t_struct_size(_i)} in the library")
 
 _NO_RC = {"p2t_gemm_fix_workspace_bytes", "p2t_version", "p2t_is_lab_build", "p2t_last_error", "p2t_struct_size", "p2t_esm2_workspace_bytes", "p2t_llama_workspace_bytes", "p2t_llama_tape_bytes", "p2t_llama_train_workspace_bytes", "p2t_llama_prefill_workspace_bytes", "p2t_llama_decode_workspace_bytes",
-          "p2t_adapter_backward_workspace_bytes", "p2t_adapter_backward_dx_workspace_bytes"}
+          "p2t_adapter_backward_workspace_bytes", "p2t_adapter_backward_dx_workspace_bytes", "p2t_lora_wgrad_workspace_bytes"}
 
 
 def call(name: str, *args):

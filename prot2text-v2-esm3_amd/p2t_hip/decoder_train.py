@@ -15,6 +15,10 @@ branch's input dropout: a counter-hash mask regenerated in the backward, never s
 with the encoder step).  torch allocates, slices, concatenates and
 wires autograd; no torch op computes on the path.
 
+Each layer is written once (`_layer_forward`).  The full-tape step keeps every layer's record; under gradient checkpointing
+(`lora_lm_loss(checkpoint=True)`, reference models/modeling_esm2llama_instruct.py:253-268) the tape keeps each layer's fp32 input alone,
+the backward runs the same body again up to `gu`, and dA / dB come from p2t_lora_wgrad (the token axis summed in place, no transposes).
+
 Parity: tests/golden/sft_lora_tiny.npz = torch autograd through the REFERENCE class with every target wrapped by a hand-written
 LoRA linear (tests/golden/make_golden.py run_sft_lora) and, for Qwen3, through HF Qwen3ForCausalLM.  `peft` is not importable in
 this image: the arithmetic is LoRA's published one, parity against peft's own code is UNPINNED (as is the checkpoint key layout
@@ -28,7 +32,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import call
-from .lora_linear import DECODER_TARGETS, LoraLinear, LoraPairs, scaled_grads
+from .lora_linear import DECODER_TARGETS, LoraLinear, LoraPairs, scaled_grads, tape_bytes
 from .ops import ptr, round_up, stream
 
 TARGETS = DECODER_TARGETS
@@ -67,6 +71,55 @@ def _deinterleave(d_gu: torch.Tensor, F: int):
     return v[:, :, 0].reshape(M, F).contiguous(), v[:, :, 1].reshape(M, F).contiguous()
 
 
+def _layer_forward(st: dict, i: int, lin: dict, x: torch.Tensor, keep: bool, stop: bool = False):
+    """Layer i of the decoder on the fp32 residual stream x [M, H] -> (the layer's record, the stream after it).  The ONE body of
+    the layer: the forward pass runs it (keep: the record holds what the backward reads, x itself as `x_in`; else only `lin`), and
+    the checkpointed backward runs it again from the kept `x_in` with stop = True, which ends at `gu` -- the stream then is
+    `x_mid`, and the down projection with its residual add is not redone."""
+    s, dt, P = st["spec"], st["dt"], st["P"]
+    B, T, H = st["shape"]
+    M = B * T
+    nh, nkv, d, F = s.num_attention_heads, s.num_key_value_heads, s.head_dim, s.intermediate_size
+    f32v = lambda n: P[n].detach().float().contiguous()
+    docs = st["docs"]
+    p = f"layers.{i}."
+    rec = dict(lin=lin, x_in=x if keep else None)
+    if keep:
+        x = x.clone()                                   # the record keeps the layer's input; the stream goes on in a copy
+    h = ops.rmsnorm(x, f32v(p + "input_layernorm.weight"), s.rms_norm_eps, out_dtype=dt)
+    parts = []
+    for t in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"):
+        y, u = lin[t].forward(h)
+        rec["u_" + t] = u
+        parts.append(y)
+    if s.qk_norm:                                       # Qwen3Attention.forward: RMSNorm over head_dim of every head, before the rotation
+        rec["q_raw"], rec["k_raw"] = parts[0], parts[1]
+        parts[0] = ops.rmsnorm(parts[0].view(M * nh, d), f32v(p + "self_attn.q_norm.weight"), s.rms_norm_eps, ld_out=d).view(M, nh * d)
+        parts[1] = ops.rmsnorm(parts[1].view(M * nkv, d), f32v(p + "self_attn.k_norm.weight"), s.rms_norm_eps, ld_out=d).view(M, nkv * d)
+    qkv = ops.cast(torch.cat(parts, 1), dt) if dt != torch.float32 else torch.cat(parts, 1)
+    if qkv.shape[1] % 8:
+        qkv = torch.nn.functional.pad(qkv, (0, 8 - qkv.shape[1] % 8))
+    q4, k4, v4 = ops.qkv_post(qkv.contiguous(), st["inv_freq"], B, T, nh, nkv, d, st["q_fold"], docs=docs)
+    lse = torch.empty((B, nh, T), dtype=torch.float32, device=x.device)
+    ao = ops.attention(q4, k4, v4, st["key_mask"], st["kv_info"], d, 1.0 if st["l2s"] else st["scale"], True, log2_scores=st["l2s"], lse=lse,
+                       docs=docs)                       # [M, QO]
+    rec.update(q=q4, k=k4, v=v4, lse=lse, ao=ao)
+    _, rec["u_self_attn.o_proj"] = lin["self_attn.o_proj"].forward(ao, resid=x)
+    rec["x_mid"] = (x if stop else x.clone()) if keep else None
+    h2 = ops.rmsnorm(x, f32v(p + "post_attention_layernorm.weight"), s.rms_norm_eps, out_dtype=dt)
+    g, rec["u_mlp.gate_proj"] = lin["mlp.gate_proj"].forward(h2)
+    up, rec["u_mlp.up_proj"] = lin["mlp.up_proj"].forward(h2)
+    gu = _interleave(g, up, F)
+    gu = ops.cast(gu, dt) if dt != torch.float32 else gu
+    rec["gu"] = gu if keep else None
+    if stop:
+        return rec, x
+    act = torch.empty((M, round_up(F, 64)), dtype=dt, device=x.device)
+    call("p2t_swiglu_gu", ptr(gu), gu.stride(0), None, 0, ptr(act), act.stride(0), M, F, ops.dt_of(dt), stream())
+    _, rec["u_mlp.down_proj"] = lin["mlp.down_proj"].forward(act, resid=x)
+    return rec, x
+
+
 class DecoderLoraLossFn(torch.autograd.Function):
     """LM loss of the decoder as a function of `inputs_embeds` and the LoRA parameters (frozen base weights)."""
 
@@ -76,7 +129,7 @@ class DecoderLoraLossFn(torch.autograd.Function):
         dt = m.dtype
         B, T, H = inputs_embeds.shape
         M = B * T
-        nh, nkv, d, F, L = s.num_attention_heads, s.num_key_value_heads, s.head_dim, s.intermediate_size, s.num_hidden_layers
+        d, F, L = s.head_dim, s.intermediate_size, s.num_hidden_layers
         if F % 32:
             raise ValueError("Llama intermediate_size must be a multiple of 32")
         dev = m.embed_tokens.weight.device
@@ -91,49 +144,27 @@ class DecoderLoraLossFn(torch.autograd.Function):
         x = inputs_embeds.detach().to(device=dev, dtype=torch.float32).reshape(M, H).contiguous().clone()
         tape = []
         keep = opts["keep_tape"]                        # False: forward-only loss, no layer's activations are kept
+        ckpt = keep and bool(opts.get("checkpoint"))    # the tape holds every layer's input alone; the backward redoes the layer
         f32v = lambda n: P[n].detach().float().contiguous()
+        st = dict(decoder=decoder, spec=s, dt=dt, P=P, tape=tape, checkpoint=ckpt, key_mask=key_mask, kv_info=kv_info, docs=docs, weights=weights,
+                  inv_freq=inv_freq, l2s=l2s, scale=scale, q_fold=q_fold, shape=(B, T, H), params=params, in_dtype=inputs_embeds.dtype)
         for i in range(L):
             p = f"layers.{i}."
             lin = {t: LoraLinear(m, P, p + t, lora, i, t, dt, opts["dropout"]) for t in TARGETS}
-            rec = dict(lin=lin, x_in=x.clone() if keep else None)
-            h = ops.rmsnorm(x, f32v(p + "input_layernorm.weight"), s.rms_norm_eps, out_dtype=dt)
-            parts = []
-            for t in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"):
-                y, u = lin[t].forward(h)
-                rec["u_" + t] = u
-                parts.append(y)
-            if s.qk_norm:                               # Qwen3Attention.forward: RMSNorm over head_dim of every head, before the rotation
-                rec["q_raw"], rec["k_raw"] = parts[0], parts[1]
-                parts[0] = ops.rmsnorm(parts[0].view(M * nh, d), f32v(p + "self_attn.q_norm.weight"), s.rms_norm_eps, ld_out=d).view(M, nh * d)
-                parts[1] = ops.rmsnorm(parts[1].view(M * nkv, d), f32v(p + "self_attn.k_norm.weight"), s.rms_norm_eps, ld_out=d).view(M, nkv * d)
-            qkv = ops.cast(torch.cat(parts, 1), dt) if dt != torch.float32 else torch.cat(parts, 1)
-            if qkv.shape[1] % 8:
-                qkv = torch.nn.functional.pad(qkv, (0, 8 - qkv.shape[1] % 8))
-            q4, k4, v4 = ops.qkv_post(qkv.contiguous(), inv_freq, B, T, nh, nkv, d, q_fold, docs=docs)
-            lse = torch.empty((B, nh, T), dtype=torch.float32, device=dev)
-            ao = ops.attention(q4, k4, v4, key_mask, kv_info, d, 1.0 if l2s else scale, True, log2_scores=l2s, lse=lse, docs=docs)      # [M, QO]
-            rec.update(q=q4, k=k4, v=v4, lse=lse, ao=ao)
-            _, rec["u_self_attn.o_proj"] = lin["self_attn.o_proj"].forward(ao, resid=x)
-            rec["x_mid"] = x.clone() if keep else None
-            h2 = ops.rmsnorm(x, f32v(p + "post_attention_layernorm.weight"), s.rms_norm_eps, out_dtype=dt)
-            g, rec["u_mlp.gate_proj"] = lin["mlp.gate_proj"].forward(h2)
-            up, rec["u_mlp.up_proj"] = lin["mlp.up_proj"].forward(h2)
-            gu = _interleave(g, up, F)
-            gu = ops.cast(gu, dt) if dt != torch.float32 else gu
-            rec["gu"] = gu if keep else None
-            act = torch.empty((M, round_up(F, 64)), dtype=dt, device=dev)
-            call("p2t_swiglu_gu", ptr(gu), gu.stride(0), None, 0, ptr(act), act.stride(0), M, F, ops.dt_of(dt), stream())
-            _, rec["u_mlp.down_proj"] = lin["mlp.down_proj"].forward(act, resid=x)
-            if keep:
+            if ckpt:
+                tape.append(dict(lin=lin, x_in=x.clone()))
+            rec, x = _layer_forward(st, i, lin, x, keep and not ckpt)
+            if keep and not ckpt:
                 tape.append(rec)
         x_last = x
         hN = ops.rmsnorm(x_last, f32v("norm.weight"), s.rms_norm_eps, out_dtype=dt)
         logits = ops.gemm_nt(hN, decoder._lm_head_padded(), None, n=s.vocab_size, k=H, out_dtype=dt).view(B, T, -1)
         lab = labels.to(dev).to(torch.int64).contiguous()
         loss, count = ops.cross_entropy_shifted(logits, lab, s.vocab_size, weights=weights)
-        ctx.state = dict(decoder=decoder, tape=tape, x_last=x_last, logits=logits, labels=lab, count=count, key_mask=key_mask, kv_info=kv_info,
-                         docs=docs, weights=weights,
-                         inv_freq=inv_freq, l2s=l2s, scale=scale, q_fold=q_fold, shape=(B, T, H), params=params, in_dtype=inputs_embeds.dtype)
+        st.update(x_last=x_last, logits=logits, labels=lab, count=count)
+        ctx.state = st
+        if keep:
+            decoder.last_tape_bytes = tape_bytes(tape, (x_last, logits, lab, count, key_mask, kv_info, docs, weights))
         ctx.mark_non_differentiable(logits)
         return loss[0], logits
 
@@ -149,7 +180,7 @@ class DecoderLoraLossFn(torch.autograd.Function):
         dp = ops.head_dim_padded(d)
         V = s.vocab_size
         dev = st["x_last"].device
-        P = dict(m.named_parameters())
+        P = st["P"]
         f32v = lambda n: P[n].detach().float().contiguous()
         ld = st["logits"].shape[2]
         d_logits = ops.cross_entropy_shifted_backward(st["logits"], st["labels"], V, st["count"], weights=st["weights"])
@@ -163,25 +194,29 @@ class DecoderLoraLossFn(torch.autograd.Function):
         grads: dict = {}
         c_s = 0.6931471805599453 if st["l2s"] else st["scale"]
         to_dt = lambda t: ops.cast(t, dt) if t.dtype != dt else t
+        ta = st["checkpoint"]                           # ... and dA / dB by p2t_lora_wgrad, straight over the token axis
         for i in range(len(st["tape"]) - 1, -1, -1):
             rec = st["tape"][i]
             lin = rec["lin"]
+            if ta:                                      # checkpointed: the layer's records again, from its input, up to gu
+                rec, _ = _layer_forward(st, i, lin, rec["x_in"], True, stop=True)
             p = f"layers.{i}."
             # ---- MLP branch: x2 = x1 + down(silu(g) u)
             g16 = to_dt(g)
             act = torch.empty((M, round_up(F, 64)), dtype=dt, device=dev)
             call("p2t_swiglu_gu", ptr(rec["gu"]), rec["gu"].stride(0), None, 0, ptr(act), act.stride(0), M, F, ops.dt_of(dt), stream())
-            d_act = lin["mlp.down_proj"].backward(g16, act, rec["u_mlp.down_proj"], None, False, False, grads)                  # [M, Fp]
+            u_down = rec["u_mlp.down_proj"] if "u_mlp.down_proj" in rec else lin["mlp.down_proj"].branch_input(act)
+            d_act = lin["mlp.down_proj"].backward(g16, act, u_down, None, False, False, grads, token_axis=ta)                  # [M, Fp]
             d_gu = torch.empty((M, 2 * F), dtype=dt, device=dev)
             call("p2t_swiglu_gu", ptr(rec["gu"]), rec["gu"].stride(0), ptr(d_act), d_act.stride(0), ptr(d_gu), d_gu.stride(0), M, F, ops.dt_of(dt), stream())
             d_gate, d_up = _deinterleave(d_gu, F)
             h2 = ops.rmsnorm(rec["x_mid"], f32v(p + "post_attention_layernorm.weight"), s.rms_norm_eps, out_dtype=dt)
-            d_h2 = lin["mlp.gate_proj"].backward(d_gate, h2, rec["u_mlp.gate_proj"], None, True, False, grads)
-            lin["mlp.up_proj"].backward(d_up, h2, rec["u_mlp.up_proj"], d_h2, True, True, grads)
+            d_h2 = lin["mlp.gate_proj"].backward(d_gate, h2, rec["u_mlp.gate_proj"], None, True, False, grads, token_axis=ta)
+            lin["mlp.up_proj"].backward(d_up, h2, rec["u_mlp.up_proj"], d_h2, True, True, grads, token_axis=ta)
             rms_bwd(rec["x_mid"], f32v(p + "post_attention_layernorm.weight"), d_h2, g, 1)
             # ---- attention branch: x1 = x + o(attn(...))
             g16 = to_dt(g)
-            d_ao = lin["self_attn.o_proj"].backward(g16, rec["ao"], rec["u_self_attn.o_proj"], None, False, False, grads)       # [M, QO]
+            d_ao = lin["self_attn.o_proj"].backward(g16, rec["ao"], rec["u_self_attn.o_proj"], None, False, False, grads, token_axis=ta)       # [M, QO]
             dq, dk, dv = ops.attention_backward(rec["q"], rec["k"], rec["v"], rec["ao"], d_ao, rec["lse"], st["key_mask"], st["kv_info"], d, c_s, True,
                                                 log2_scores=st["l2s"], docs=st["docs"])
             NQ = (nh + 2 * nkv) * d
@@ -204,9 +239,9 @@ class DecoderLoraLossFn(torch.autograd.Function):
                 d_k = norm_bwd(rec["k_raw"], p + "self_attn.k_norm.weight", d_k, nkv)
             h1 = ops.rmsnorm(rec["x_in"], f32v(p + "input_layernorm.weight"), s.rms_norm_eps, out_dtype=dt)
             pad8 = lambda t: t if (t.stride(0) % 8 == 0 and t.stride(1) == 1) else torch.nn.functional.pad(t, (0, (-t.shape[1]) % 8)).contiguous()
-            d_h1 = lin["self_attn.q_proj"].backward(pad8(d_q), h1, rec["u_self_attn.q_proj"], None, True, False, grads)
-            lin["self_attn.k_proj"].backward(pad8(d_k), h1, rec["u_self_attn.k_proj"], d_h1, True, True, grads)
-            lin["self_attn.v_proj"].backward(pad8(d_v), h1, rec["u_self_attn.v_proj"], d_h1, True, True, grads)
+            d_h1 = lin["self_attn.q_proj"].backward(pad8(d_q), h1, rec["u_self_attn.q_proj"], None, True, False, grads, token_axis=ta)
+            lin["self_attn.k_proj"].backward(pad8(d_k), h1, rec["u_self_attn.k_proj"], d_h1, True, True, grads, token_axis=ta)
+            lin["self_attn.v_proj"].backward(pad8(d_v), h1, rec["u_self_attn.v_proj"], d_h1, True, True, grads, token_axis=ta)
             rms_bwd(rec["x_in"], f32v(p + "input_layernorm.weight"), d_h1, g, 1)
             st["tape"][i] = None                        # free the layer's activations
         gl = g_loss.float().reshape(1).contiguous()
@@ -217,18 +252,22 @@ class DecoderLoraLossFn(torch.autograd.Function):
 
 
 def lora_lm_loss(decoder, lora: Optional[DecoderLora], inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, labels: torch.Tensor,
-                 dropout: Optional[float] = None, docs: Optional[torch.Tensor] = None, loss_weights: Optional[torch.Tensor] = None):
+                 dropout: Optional[float] = None, docs: Optional[torch.Tensor] = None, loss_weights: Optional[torch.Tensor] = None,
+                 checkpoint: bool = False):
     """(loss, logits) of `llama_decoder(inputs_embeds=..., attention_mask=..., labels=...)` with the LoRA branches in the graph.
     dropout: None = the branches' own `lora.p` (every mode, as before); a value overrides it for this call and leaves the mask counter
     where it is -- 0.0 is peft's eval mode (InstructTrainer.evaluate).  Without gradients to compute, no activation tape is kept.
     docs: packed rows (ops.doc_prepare: positional rotary + document-confined attention; the caller has set the labels of document
-    starts to -100); loss_weights: f32 [B, T] per-target weights (ops.cross_entropy_shifted) instead of the token mean."""
+    starts to -100); loss_weights: f32 [B, T] per-target weights (ops.cross_entropy_shifted) instead of the token mean.
+    checkpoint: gradient checkpointing -- the tape keeps each layer's fp32 input alone and the backward redoes the layer from it
+    (same kernels, same dropout seeds: the loss and every gradient but dA / dB are bit-identical to checkpoint = False; dA / dB come
+    from p2t_lora_wgrad, a differently ordered fp32 sum).  `decoder.last_tape_bytes`: the bytes of the tensors kept for the backward."""
     params = tuple(lora.parameters()) if lora is not None else ()
     if lora is not None and dropout is None:
         if lora.training:
             lora.step_count += 1                        # a fresh dropout mask per step
         dropout = lora.p                                # in every mode (peft's eval mode would be 0.0)
     keep = torch.is_grad_enabled() and (inputs_embeds.requires_grad or any(q.requires_grad for q in params))
-    opts = dict(dropout=float(dropout or 0.0), keep_tape=keep, docs=docs, loss_weights=loss_weights)
+    opts = dict(dropout=float(dropout or 0.0), keep_tape=keep, docs=docs, loss_weights=loss_weights, checkpoint=bool(checkpoint))
     loss, logits = DecoderLoraLossFn.apply(inputs_embeds, decoder, lora, attention_mask, labels, opts, *params)
     return loss, logits[..., : decoder.spec.vocab_size]

@@ -24,6 +24,8 @@ EsmLayer, transformers/models/esm/modeling_esm.py):
 The tape keeps x at the layer's input and after the attention (fp32), q / k / v, the log-sum-exps, the attention output, Z and the
 branches' u = drop(x) A^T; the backward stops at layer 0's input (the embeddings are frozen).  Dropout masks are the counter hash of
 p2t_dropout_rows, regenerated in the backward.  torch allocates, slices and wires autograd; no torch op computes on the path.
+Under gradient checkpointing (`encoder_lora_forward(checkpoint=True)`) the tape keeps each layer's fp32 input alone; the backward runs the
+layer's one body (`_layer_forward`) again up to Z and takes dA / dB from p2t_lora_wgrad.
 """
 from __future__ import annotations
 
@@ -34,7 +36,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import call
-from .lora_linear import ENCODER_TARGETS, LoraLinear, LoraPairs, resolve_targets, scaled_grads  # noqa: F401 (resolve_targets: re-exported)
+from .lora_linear import ENCODER_TARGETS, LoraLinear, LoraPairs, resolve_targets, scaled_grads, tape_bytes  # noqa: F401 (resolve_targets: re-exported)
 from .ops import ptr, round_up, stream
 
 TARGETS = ENCODER_TARGETS
@@ -60,6 +62,52 @@ def _gelu_rows(z: torch.Tensor, dy: Optional[torch.Tensor], n: int, out_dtype) -
     return out
 
 
+def _layer_forward(st: dict, i: int, lin: dict, x: torch.Tensor, keep: bool, stop: bool = False, with_lse: bool = False):
+    """Layer i of the encoder on the fp32 residual stream x [M, H] -> (the layer's record, the stream after it).  The ONE body of
+    the layer: the forward pass runs it (keep: the record holds what the backward reads, x itself as `x_in`; else only `lin`), and
+    the checkpointed backward runs it again from the kept `x_in` with stop = True, which ends at Z -- the stream then is `x_mid`,
+    and the output projection with its residual add is not redone (only u = drop(gelu(Z)) A^T of its branch is).  with_lse: the attention writes its log-sum-exps although the
+    record is not kept -- the checkpointed forward asks for it, so that it launches the attention form the recompute will launch."""
+    s, dt, P = st["spec"], st["dt"], st["P"]
+    B, T = st["shape"]
+    M, H, F = B * T, s.hidden_size, s.intermediate_size
+    nh, d, eps = s.num_attention_heads, s.head_dim, s.layer_norm_eps
+    f32v = lambda n: P[n].detach().float().contiguous()
+    p = f"encoder.layer.{i}."
+    rec = dict(lin=lin, x_in=x if keep else None)
+    if keep:
+        x = x.clone()                                   # the record keeps the layer's input; the stream goes on in a copy
+    h = ops.layernorm(x, f32v(p + "attention.LayerNorm.weight"), f32v(p + "attention.LayerNorm.bias"), eps, out_dtype=dt)
+    parts = []
+    for t in TARGETS[:3]:
+        y, rec["u_" + t] = lin[t].forward(h, keep_u=keep)
+        parts.append(y)
+    qkv = torch.cat([y[:, :H] for y in parts], 1)
+    qkv = ops.cast(qkv, dt) if dt != torch.float32 else qkv
+    q4, k4, v4 = ops.qkv_post(qkv, st["inv_freq"], B, T, nh, nh, d, st["q_fold"])
+    lse = torch.empty((B, nh, T), dtype=torch.float32, device=x.device) if keep or with_lse else None
+    ao = ops.attention(q4, k4, v4, st["key_mask"], st["kv_info"], d, 1.0, False, log2_scores=st["l2s"], lse=lse)
+    if keep:
+        rec.update(q=q4, k=k4, v=v4, lse=lse, ao=ao)
+    _, rec["u_attention.output.dense"] = lin["attention.output.dense"].forward(ao, resid=x, keep_u=keep)
+    rec["x_mid"] = (x if stop else x.clone()) if keep else None
+    h2 = ops.layernorm(x, f32v(p + "LayerNorm.weight"), f32v(p + "LayerNorm.bias"), eps, out_dtype=dt)
+    fc1 = lin["intermediate.dense"]
+    if fc1.ab is None:                                  # the fused bias + GELU epilogue, keeping Z
+        z = torch.empty((M, round_up(F, 64)), dtype=dt, device=x.device)
+        act = ops.gemm_nt(h2, fc1.w, fc1.bias, n=F, k=H, epilogue=_lib.EPI_GELU, out_dtype=dt, z=z)
+    else:                                               # the branch lands BEFORE the GELU: Z assembled in fp32, then p2t_gelu_rows
+        zf, rec["u_intermediate.dense"] = fc1.forward(h2, keep_u=keep)
+        act = None if stop and lin["output.dense"].ab is None else _gelu_rows(zf, None, F, dt)
+        z = ops.cast(zf, dt) if dt != torch.float32 else zf
+    rec["z"] = z if keep else None
+    if stop:                                            # the output projection is not redone; its branch's u is, from the forward's own
+        rec["u_output.dense"] = lin["output.dense"].branch_input(act)      # activation (gelu of the fp32 Z, not of the kept, rounded one)
+        return rec, x
+    _, rec["u_output.dense"] = lin["output.dense"].forward(act, resid=x, keep_u=keep)
+    return rec, x
+
+
 class EncoderLoraFn(torch.autograd.Function):
     """last_hidden_state of the ESM2 encoder ([B, T, Hp] in the model dtype, zero padded as `EsmEncoder.encode` returns it) as a
     function of the LoRA parameters (frozen base weights and embeddings)."""
@@ -69,7 +117,7 @@ class EncoderLoraFn(torch.autograd.Function):
         s, dt = encoder.spec, encoder.dtype
         B, T = input_ids.shape
         M, H, F = B * T, s.hidden_size, s.intermediate_size
-        nh, d, L = s.num_attention_heads, s.head_dim, s.num_hidden_layers
+        d, L = s.head_dim, s.num_hidden_layers
         Hp = round_up(H, 64)
         if H % 8 or F % 8:
             raise ValueError("the encoder LoRA step needs hidden_size and intermediate_size multiples of 8")
@@ -87,41 +135,23 @@ class EncoderLoraFn(torch.autograd.Function):
         q_fold = (1.4426950408889634 if l2s else 1.0) / math.sqrt(d)
         eps = s.layer_norm_eps
         keep = opts["keep_tape"]
+        ckpt = keep and bool(opts.get("checkpoint"))    # the tape holds every layer's input alone; the backward redoes the layer
         tape = []
+        st = dict(encoder=encoder, spec=s, dt=dt, P=P, tape=tape, checkpoint=ckpt, key_mask=key_mask, kv_info=kv_info, inv_freq=inv_freq, l2s=l2s,
+                  q_fold=q_fold, shape=(B, T), params=params)
         for i in range(L):
             p = f"encoder.layer.{i}."
             lin = {t: LoraLinear(encoder, P, p + t, lora, i, t, dt, opts["dropout"]) for t in TARGETS}
-            rec = dict(lin=lin, x_in=x.clone() if keep else None)
-            h = ops.layernorm(x, f32v(p + "attention.LayerNorm.weight"), f32v(p + "attention.LayerNorm.bias"), eps, out_dtype=dt)
-            parts = []
-            for t in TARGETS[:3]:
-                y, rec["u_" + t] = lin[t].forward(h, keep_u=keep)
-                parts.append(y)
-            qkv = torch.cat([y[:, :H] for y in parts], 1)
-            qkv = ops.cast(qkv, dt) if dt != torch.float32 else qkv
-            q4, k4, v4 = ops.qkv_post(qkv, inv_freq, B, T, nh, nh, d, q_fold)
-            lse = torch.empty((B, nh, T), dtype=torch.float32, device=dev) if keep else None
-            ao = ops.attention(q4, k4, v4, key_mask, kv_info, d, 1.0, False, log2_scores=l2s, lse=lse)
-            if keep:
-                rec.update(q=q4, k=k4, v=v4, lse=lse, ao=ao)
-            _, rec["u_attention.output.dense"] = lin["attention.output.dense"].forward(ao, resid=x, keep_u=keep)
-            rec["x_mid"] = x.clone() if keep else None
-            h2 = ops.layernorm(x, f32v(p + "LayerNorm.weight"), f32v(p + "LayerNorm.bias"), eps, out_dtype=dt)
-            fc1 = lin["intermediate.dense"]
-            if fc1.ab is None:                          # the fused bias + GELU epilogue, keeping Z
-                z = torch.empty((M, round_up(F, 64)), dtype=dt, device=dev)
-                act = ops.gemm_nt(h2, fc1.w, fc1.bias, n=F, k=H, epilogue=_lib.EPI_GELU, out_dtype=dt, z=z)
-            else:                                       # the branch lands BEFORE the GELU: Z assembled in fp32, then p2t_gelu_rows
-                zf, rec["u_intermediate.dense"] = fc1.forward(h2, keep_u=keep)
-                act = _gelu_rows(zf, None, F, dt)
-                z = ops.cast(zf, dt) if dt != torch.float32 else zf
-            rec["z"] = z if keep else None
-            _, rec["u_output.dense"] = lin["output.dense"].forward(act, resid=x, keep_u=keep)
-            if keep:
+            if ckpt:
+                tape.append(dict(lin=lin, x_in=x.clone()))
+            rec, x = _layer_forward(st, i, lin, x, keep and not ckpt, with_lse=ckpt)
+            if keep and not ckpt:
                 tape.append(rec)
         out = ops.layernorm(x, f32v("encoder.emb_layer_norm_after.weight"), f32v("encoder.emb_layer_norm_after.bias"), eps, out_dtype=dt, ld_out=Hp)
-        ctx.state = dict(encoder=encoder, tape=tape, x_last=x, key_mask=key_mask, kv_info=kv_info, inv_freq=inv_freq, l2s=l2s, q_fold=q_fold,
-                         shape=(B, T), params=params) if keep else None
+        st["x_last"] = x
+        ctx.state = st if keep else None
+        if keep:
+            encoder.last_tape_bytes = tape_bytes(tape, (x, key_mask, kv_info))
         return out.view(B, T, Hp)
 
     @staticmethod
@@ -134,7 +164,7 @@ class EncoderLoraFn(torch.autograd.Function):
         nh, d = s.num_attention_heads, s.head_dim
         dp = ops.head_dim_padded(d)
         eps = s.layer_norm_eps
-        P = dict(enc.named_parameters())
+        P = st["P"]
         dev = st["x_last"].device
         f32v = lambda n: P[n].detach().float().contiguous()
         to_dt = lambda t: ops.cast(t, dt) if t.dtype != dt else t
@@ -150,9 +180,12 @@ class EncoderLoraFn(torch.autograd.Function):
         g = torch.empty((M, H), dtype=torch.float32, device=dev)
         ln_bwd(st["x_last"], "encoder.emb_layer_norm_after.weight", dy, g, 0)
         grads: dict = {}
+        ta = st["checkpoint"]                           # checkpointed: every layer redone from its input; dA / dB by p2t_lora_wgrad
         for i in range(len(st["tape"]) - 1, -1, -1):
             rec = st["tape"][i]
             lin = rec["lin"]
+            if ta:
+                rec, _ = _layer_forward(st, i, lin, rec["x_in"], True, stop=True)
             p = f"encoder.layer.{i}."
             # ---- FFN: x2 = x1 + fc2(gelu(Z)) + b
             g16 = to_dt(g)
@@ -160,14 +193,15 @@ class EncoderLoraFn(torch.autograd.Function):
             if fc2.ab is None:                          # dZ = (dy W2) * gelu'(Z) in the dX GEMM's epilogue
                 dz = ops.gemm_nt(g16, fc2.transposed(), None, n=F, k=H, epilogue=_lib.EPI_GELU_BWD, out_dtype=dt, z=z)
             else:                                       # gelu(Z) recomputed: the branch's dA needs fc2's input
-                d_act = fc2.backward(g16, _gelu_rows(z, None, F, dt), rec["u_output.dense"], None, True, False, grads)
+                act = _gelu_rows(z, None, F, dt)
+                d_act = fc2.backward(g16, act, rec["u_output.dense"], None, True, False, grads, token_axis=ta)
                 dz = _gelu_rows(z, d_act, F, dt)
             h2 = ops.layernorm(rec["x_mid"], f32v(p + "LayerNorm.weight"), f32v(p + "LayerNorm.bias"), eps, out_dtype=dt)
-            d_h2 = lin["intermediate.dense"].backward(dz, h2, rec["u_intermediate.dense"] if "u_intermediate.dense" in rec else None, None, True, False, grads)
+            d_h2 = lin["intermediate.dense"].backward(dz, h2, rec["u_intermediate.dense"] if "u_intermediate.dense" in rec else None, None, True, False, grads, token_axis=ta)
             ln_bwd(rec["x_mid"], p + "LayerNorm.weight", d_h2, g, 1)
             # ---- attention: x1 = x + o(attn(rope(q), rope(k), v)) + b
             g16 = to_dt(g)
-            d_ao = lin["attention.output.dense"].backward(g16, rec["ao"], rec["u_attention.output.dense"], None, False, False, grads)
+            d_ao = lin["attention.output.dense"].backward(g16, rec["ao"], rec["u_attention.output.dense"], None, False, False, grads, token_axis=ta)
             dq, dk, dv = ops.attention_backward(rec["q"], rec["k"], rec["v"], rec["ao"], d_ao, rec["lse"], st["key_mask"], st["kv_info"], d, c_s, False,
                                                 log2_scores=st["l2s"])
             d_qkv = torch.zeros((M, round_up(3 * H, 64)), dtype=dt, device=dev)
@@ -177,7 +211,7 @@ class EncoderLoraFn(torch.autograd.Function):
             h1 = ops.layernorm(rec["x_in"], f32v(p + "attention.LayerNorm.weight"), f32v(p + "attention.LayerNorm.bias"), eps, out_dtype=dt)
             d_h1 = None
             for j, t in enumerate(TARGETS[:3]):
-                d_h1 = lin[t].backward(d_qkv[:, j * H:(j + 1) * H], h1, rec["u_" + t], d_h1, True, j > 0, grads)
+                d_h1 = lin[t].backward(d_qkv[:, j * H:(j + 1) * H], h1, rec["u_" + t], d_h1, True, j > 0, grads, token_axis=ta)
             ln_bwd(rec["x_in"], p + "attention.LayerNorm.weight", d_h1, g, 1)
             st["tape"][i] = None
         out_params = scaled_grads(st["params"], grads)
@@ -186,10 +220,13 @@ class EncoderLoraFn(torch.autograd.Function):
 
 
 def encoder_lora_forward(encoder, lora: EncoderLora, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
-                         dropout: Optional[float] = None) -> torch.Tensor:
+                         dropout: Optional[float] = None, checkpoint: bool = False) -> torch.Tensor:
     """last_hidden_state [B, T, Hp] of the encoder with the LoRA branches in the graph (what `EsmEncoder.encode` returns otherwise).
     dropout: None = `lora.p` in train mode (one mask step per call), 0 in eval mode (peft's nn.Dropout, no mask step -- what
-    InstructTrainer.evaluate sets); a value overrides both and leaves the mask counter where it is.  Without gradients to compute, no activation tape is kept."""
+    InstructTrainer.evaluate sets); a value overrides both and leaves the mask counter where it is.  Without gradients to compute, no activation tape is kept.
+    checkpoint: gradient checkpointing -- the tape keeps each layer's fp32 input alone and the backward redoes the layer from it (same
+    kernels, same dropout seeds; dA / dB then come from p2t_lora_wgrad, a differently ordered fp32 sum, every other value is
+    bit-identical).  `encoder.last_tape_bytes`: the bytes of the tensors kept for the backward."""
     if input_ids is None or input_ids.dim() != 2:
         raise ValueError("protein_input_ids must be a [batch, seq_len] tensor of token ids")
     if attention_mask is None:
@@ -204,5 +241,5 @@ def encoder_lora_forward(encoder, lora: EncoderLora, input_ids: torch.Tensor, at
             lora.step_count += 1                        # a fresh dropout mask per step
         dropout = lora.p if lora.training else 0.0
     keep = torch.is_grad_enabled() and any(q.requires_grad for q in params)
-    opts = dict(dropout=float(dropout), keep_tape=keep)
+    opts = dict(dropout=float(dropout), keep_tape=keep, checkpoint=bool(checkpoint))
     return EncoderLoraFn.apply(input_ids, attention_mask, encoder, lora, opts, *params)

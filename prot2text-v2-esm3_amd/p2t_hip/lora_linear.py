@@ -5,9 +5,11 @@
                     operands an optimizer may keep for them, peft's key layout.  A tower states only data (class attributes).
     LoraLinear      one frozen projection W [N, K] (+ bias) of one layer with its branch: y = W x + b + s B (A drop(x)), and its backward
     _transposed     the cached [K, N padded] copy of a frozen weight for the dX GEMMs
+    tape_bytes      the bytes a pass keeps for its backward (`last_tape_bytes` of a tower)
     scaled_grads    the collected (buffer, rows, columns, factor) gradients, scaled and cut for autograd
 
-Every product is p2t_gemm_nt; the branch's input dropout is p2t_dropout_rows (a counter-hash mask, regenerated in the backward).
+Every product is p2t_gemm_nt, but dA / dB of the checkpointed backward (p2t_lora_wgrad: the token axis summed in place); the branch's input
+dropout is p2t_dropout_rows (a counter-hash mask, regenerated in the backward).
 """
 from __future__ import annotations
 
@@ -200,12 +202,19 @@ class LoraLinear:
             y = ops.gemm_nt(x, self.w, self.bias, n=self.N, k=self.K, epilogue=_lib.EPI_STORE, out_dtype=torch.float32)
         if self.ab is None:
             return y, None
-        u = ops.gemm_nt(self.dropped(x), self.a16, None, n=self.rp, k=self.K, epilogue=_lib.EPI_STORE, out_dtype=self.dt)
+        u = self.branch_input(x)
         if resid is not None:
             ops.gemm_nt(u, self.bs16, None, n=self.N, k=self.rp, epilogue=_lib.EPI_RESID, out=resid)
         else:
             ops.gemm_nt(u, self.bs16, None, n=self.N, k=self.rp, epilogue=_lib.EPI_STORE_F32, out=y, accumulate=True)
         return y, (u if keep_u else None)
+
+    def branch_input(self, x: torch.Tensor) -> Optional[torch.Tensor]:
+        """u = drop(x) A^T [M, rp padded to 64] of the branch, None without a pair (the checkpointed backward asks for it alone where it
+        does not redo the projection)."""
+        if self.ab is None:
+            return None
+        return ops.gemm_nt(self.dropped(x), self.a16, None, n=self.rp, k=self.K, epilogue=_lib.EPI_STORE, out_dtype=self.dt)
 
     def dropped(self, x: torch.Tensor) -> torch.Tensor:
         if self.p <= 0.0:
@@ -219,8 +228,11 @@ class LoraLinear:
 
     # -- backward: dy `dt` [M, >= N] -> dX; the pair's gradients into `grads`
     def backward(self, dy: torch.Tensor, x: torch.Tensor, u: Optional[torch.Tensor], out: Optional[torch.Tensor], out_f32: bool, accumulate: bool,
-                 grads: dict) -> torch.Tensor:
-        """dX (+)= dy W (+ the branch's share); x: the projection's input as the forward saw it (before the dropout)."""
+                 grads: dict, token_axis: bool = False) -> torch.Tensor:
+        """dX (+)= dy W (+ the branch's share); x: the projection's input as the forward saw it (before the dropout).
+        token_axis: dB and dA by p2t_lora_wgrad, which sums over the token rows of dy, u, x and du as they lie in memory (the dropout of
+        x applied on the fly), instead of p2t_gemm_nt over four transposed copies and a dropped copy of x.  The two differ in the order
+        of the fp32 sum over tokens, nothing else."""
         wT = self.transposed()                                                                      # [K, N padded]
         if out_f32:
             dx = ops.gemm_nt(dy, wT, None, n=self.K, k=self.N, epilogue=_lib.EPI_STORE_F32, out=out, accumulate=accumulate)
@@ -231,10 +243,25 @@ class LoraLinear:
             return dx
         a, b = self.ab
         r, rp, M = self.r, self.rp, dy.shape[0]
-        xd = self.dropped(x)
         # du = dy (s B)  [M, rp]; dB = s dy^T u; dA = du^T drop(x); dX += drop'(du A)
         bsT = ops.transpose(self.bs16[:, :rp].contiguous(), round_up(self.N, 64))                   # [rp, N]
         du = ops.gemm_nt(dy, bsT, None, n=rp, k=self.N, epilogue=_lib.EPI_STORE, out_dtype=self.dt) # [M, 64]
+        if token_axis:
+            dB = ops.lora_wgrad(dy, u, c=self.N, r=rp)                                              # [N, rp] = dy^T u
+            dA = ops.lora_wgrad(x, du, c=self.K, r=rp, transposed=True, p=self.p, seed=self.seed)   # [rp, K] = du^T drop(x)
+        else:
+            dA, dB = self._wgrad_transposed(dy, x, u, du)
+        grads[id(a)] = (dA, r, self.K, 1.0)           # (buffer, rows, columns, factor on top of the upstream gradient)
+        grads[id(b)] = (dB, self.N, r, self.s)
+        aT = ops.transpose(self.a16[:, :self.K], round_up(rp, 8))                                   # [K, rp] = A^T
+        t = ops.gemm_nt(du, aT, None, n=self.K, k=rp, epilogue=_lib.EPI_STORE_F32)                  # [M, K] f32
+        call("p2t_dropout_rows", ptr(t), _lib.F32, t.stride(0), ptr(dx), ops.dt_of(dx), dx.stride(0), M, self.K, self.p, int(self.seed), 1, stream())
+        return dx
+
+    def _wgrad_transposed(self, dy: torch.Tensor, x: torch.Tensor, u: torch.Tensor, du: torch.Tensor):
+        """(dA [rp, K], dB [N, rp]) by p2t_gemm_nt: the token axis made contiguous (p2t_transpose) and zero padded to 64."""
+        rp, M = self.rp, dy.shape[0]
+        xd = self.dropped(x)
         dyT, uT = ops.transpose(dy[:, :self.N]), ops.transpose(u[:, :rp])                           # [N, Mp], [rp, Mp] (token axis contiguous, zero padded)
         _zero_tail(dyT, M), _zero_tail(uT, M)
         dB = torch.zeros((self.N, rp), dtype=torch.float32, device=dy.device)
@@ -242,12 +269,18 @@ class LoraLinear:
         duT, xdT = ops.transpose(du[:, :rp]), ops.transpose(xd[:, :self.K])
         _zero_tail(duT, M), _zero_tail(xdT, M)
         dA = ops.gemm_nt(duT, xdT, None, n=self.K, k=round_up(M, 64), epilogue=_lib.EPI_STORE_F32)  # [rp, K] = du^T drop(x)
-        grads[id(a)] = (dA, r, self.K, 1.0)           # (buffer, rows, columns, factor on top of the upstream gradient)
-        grads[id(b)] = (dB, self.N, r, self.s)
-        aT = ops.transpose(self.a16[:, :self.K], round_up(rp, 8))                                   # [K, rp] = A^T
-        t = ops.gemm_nt(du, aT, None, n=self.K, k=rp, epilogue=_lib.EPI_STORE_F32)                  # [M, K] f32
-        call("p2t_dropout_rows", ptr(t), _lib.F32, t.stride(0), ptr(dx), ops.dt_of(dx), dx.stride(0), M, self.K, self.p, int(self.seed), 1, stream())
-        return dx
+        return dA, dB
+
+
+def tape_bytes(tape: Sequence[dict], extra: Sequence[Optional[torch.Tensor]] = ()) -> int:
+    """Bytes of the distinct tensors a pass keeps for its backward: every tensor of the per-layer records `tape` and of `extra` (what
+    the head of the pass keeps); the LoraLinear objects of a record hold weights and operands, no activations, and count nothing."""
+    seen, total = set(), 0
+    for t in [v for rec in tape for v in rec.values()] + list(extra):
+        if isinstance(t, torch.Tensor) and t.data_ptr() not in seen:
+            seen.add(t.data_ptr())
+            total += t.numel() * t.element_size()
+    return total
 
 
 def scaled_grads(params: Sequence[nn.Parameter], grads: dict, g_loss: Optional[torch.Tensor] = None) -> list:

@@ -786,23 +786,26 @@ class LlamaDecoder(nn.Module):
                 if tuple(loss_weights.shape) != (B, T):
                     raise ValueError(f"loss_weights shape {tuple(loss_weights.shape)} != {(B, T)}")
                 loss_weights = loss_weights.to(device=dev, dtype=torch.float32).contiguous()
-            if getattr(self, "gradient_checkpointing", False) and not getattr(self, "_warned_checkpointing", False):
-                # the caller asked for activation checkpointing (reference :253-268 forwards the flag to the decoder): the stage-2
-                # step keeps its whole activation tape (p2t_llama_tape_bytes: ~26 GB per 4 x 1216 tokens of Llama-3.1-8B) and
+            per_layer = lora is not None or s.qk_norm or not grad_path
+            ckpt = bool(getattr(self, "gradient_checkpointing", False))
+            if ckpt and not per_layer and not getattr(self, "_warned_checkpointing", False):
+                # the caller asked for activation checkpointing (reference :253-268 forwards the flag to the decoder): the per-layer
+                # step below honours it; the fused frozen-decoder chain keeps its whole activation tape (p2t_llama_tape_bytes: ~26 GB per 4 x 1216 tokens of Llama-3.1-8B) and
                 # recomputes nothing -- say so once instead of silently returning no memory
                 import warnings
                 warnings.warn("gradient checkpointing was requested, but the stage-2 step of this decoder keeps the full activation tape "
                               f"({call('p2t_llama_tape_bytes', C.byref(m.ensure_engine(L)['cfg']), B, T) / 2 ** 30:.1f} GiB for this batch) and recomputes "
                               "nothing: lower the micro-batch if memory is the limit", RuntimeWarning, stacklevel=2)
                 self._warned_checkpointing = True
-            if lora is not None or s.qk_norm or not grad_path:
+            if per_layer:
                 # LoRA branches (scripts/train_instruct.py:146-183) or Qwen3's per-head q / k norm sit between the fused blocks of
                 # p2t_llama_train_forward: the per-layer form of the same step (p2t_hip/decoder_train.py); it also gives the no-grad loss
                 # of packed rows / weighted targets (no activation tape kept)
                 if m.gemm_fp8:
                     raise ValueError("stage-2 training runs the decoder GEMMs in the model dtype (set_gemm_dtype('model'))")
                 from .decoder_train import lora_lm_loss
-                loss, logits = lora_lm_loss(self, lora, inputs_embeds, attention_mask, labels, docs=docs, loss_weights=loss_weights)
+                loss, logits = lora_lm_loss(self, lora, inputs_embeds, attention_mask, labels, docs=docs, loss_weights=loss_weights,
+                                            checkpoint=ckpt)
                 return CausalLMOutput(loss=loss, logits=logits)
             loss, logits = _DecoderLossFn.apply(inputs_embeds, self, attention_mask, labels, docs, loss_weights)
             return CausalLMOutput(loss=loss, logits=logits[..., : s.vocab_size])
@@ -844,7 +847,7 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
     config_class = Esm2LlamaInstructConfig
     base_model_prefix = "model"
     main_input_name = "input_ids"
-    supports_gradient_checkpointing = True          # accepted; a no-op (the frozen towers run without autograd, see below)
+    supports_gradient_checkpointing = True          # honoured by the stage-2 LoRA steps of both towers (per-layer recompute, see below)
     _no_split_modules = ["EsmEncoder", "ModalityAdapter", "LlamaDecoder"]
     _supports_sdpa = False
     _supports_flash_attn = False
@@ -1020,7 +1023,8 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
             raise NotImplementedError("output_attentions / output_hidden_states are not available from the fused encoder")
         if enc_lora is not None:                   # LoRA on the encoder (reference :174-193 under autograd): the per-layer step
             from .encoder_train import encoder_lora_forward
-            enc = encoder_lora_forward(self.esm_encoder, enc_lora, protein_input_ids, protein_attention_mask)
+            enc = encoder_lora_forward(self.esm_encoder, enc_lora, protein_input_ids, protein_attention_mask,
+                                       checkpoint=bool(getattr(self.esm_encoder, "gradient_checkpointing", False)))
         else:
             enc = self.esm_encoder.encode(protein_input_ids, protein_attention_mask)      # [B, T, Hp], zero padded
         B, T, Hp = enc.shape
@@ -1075,19 +1079,22 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
         return self.llama_decoder.lora if dec else self.esm_encoder.lora
 
     def gradient_checkpointing_enable(self, gradient_checkpointing_kwargs=None):
-        """Accepted for loop compatibility (reference :253-261; `transformers.Trainer(gradient_checkpointing=True)` passes
-        `gradient_checkpointing_kwargs`), and a no-op by construction: activation checkpointing trades recomputation for the
-        memory autograd holds, and on this path the frozen towers run WITHOUT autograd (nothing is kept), while the adapter keeps
-        one set of activations per segment (z1, h1, z2: ContrastiveTrainer._buffers) -- `contrastive_num_segments` bounds that,
-        as it does upstream.  The stage-2 step (LM loss through the frozen decoder) is different: it keeps its whole activation
-        tape and recomputes nothing, and warns once when it runs under this flag."""
+        """Reference :253-261, which forwards the request to both towers (`transformers.Trainer(gradient_checkpointing=True)` passes
+        `gradient_checkpointing_kwargs`; they select an autograd mechanism and mean nothing here).  The stage-2 LoRA steps honour it:
+        with pairs on the decoder (or Qwen3's q / k norm) `lora_lm_loss`, and with pairs on the encoder `encoder_lora_forward`, keep
+        each layer's fp32 input alone and redo the layer in the backward (`last_tape_bytes` of the tower reports what is kept).
+        Elsewhere there is nothing to trade: in stage 1 the frozen towers run WITHOUT autograd (nothing is kept) and the adapter keeps
+        one set of activations per segment (`contrastive_num_segments` bounds that, as upstream); the fused frozen-decoder chain of
+        stage 2 without LoRA keeps its whole tape and warns once when it runs under this flag."""
         self._gradient_checkpointing_requested = True
-        self.llama_decoder.gradient_checkpointing = True      # the stage-2 step warns once that its tape is kept whole (LlamaDecoder.forward)
+        self.llama_decoder.gradient_checkpointing = True
+        self.esm_encoder.gradient_checkpointing = True
 
     def gradient_checkpointing_disable(self):
-        """No-op (reference :263-268)."""
+        """Reference :263-268: both towers keep their full tapes again."""
         self._gradient_checkpointing_requested = False
         self.llama_decoder.gradient_checkpointing = False
+        self.esm_encoder.gradient_checkpointing = False
 
     @property
     def is_gradient_checkpointing(self) -> bool:

@@ -72,6 +72,24 @@ def transpose(src: torch.Tensor, ld_dst: int | None = None) -> torch.Tensor:
     return out
 
 
+def lora_wgrad(x: torch.Tensor, u: torch.Tensor, *, c: int, r: int, transposed: bool = False, p: float = 0.0, seed: int = 0,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """G[c', j] = sum_m drop(x)[m, c'] u[m, j] over the token rows of x [M, >= c] and u [M, >= r] (p2t_lora_wgrad): f32 [c, r], or
+    [r, c] when `transposed`.  drop: p2t_dropout_rows' mask of (p, seed) over [M, c], applied on the fly; p = 0: none."""
+    _chk(x.dim() == 2 and u.dim() == 2 and x.stride(1) == 1 and u.stride(1) == 1, "lora_wgrad: 2-D row-major operands")
+    _chk(x.dtype == u.dtype and x.shape[0] == u.shape[0], "lora_wgrad: operands differ in dtype or token count")
+    _chk(x.shape[1] >= c and u.shape[1] >= r, "lora_wgrad: an operand has fewer columns than asked for")
+    M = x.shape[0]
+    if out is None:
+        out = torch.empty((r, c) if transposed else (c, r), dtype=torch.float32, device=x.device)
+    _chk(out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1, "lora_wgrad: out must be f32 row-major")
+    nbytes = call("p2t_lora_wgrad_workspace_bytes", c, r, M)
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=x.device)
+    call("p2t_lora_wgrad", ptr(x), x.stride(0), ptr(u), u.stride(0), dt_of(x), ptr(out), out.stride(0), int(transposed), M, c, r, float(p),
+         int(seed), ptr(ws), nbytes, stream())
+    return out
+
+
 def gemm_nt(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, *, n: int | None = None,
             k: int | None = None, epilogue: int = _lib.EPI_STORE, out: torch.Tensor | None = None,
             out_dtype: torch.dtype | None = None, z: torch.Tensor | None = None, accumulate: bool = False,

@@ -2,7 +2,9 @@
 scatter -> 32-layer Llama-3.1-8B -> LM head -> shifted CE, once forward only and once as the training step `loss.backward()`
 (frozen towers, adapter trainable: training forward with the activation tape + the dX chain of csrc/llama_train.hip + adapter
 backward), with a per-kernel-family breakdown of the backward from the torch profiler-free HIP-event brackets below.
-python tools/sft_bench.py [B] [lora] [trainer] [encoder] [packed] > sft_bench.log
+python tools/sft_bench.py [B] [lora] [trainer] [encoder] [packed] [checkpoint] > sft_bench.log
+`checkpoint` (with `lora` / `encoder`): the same step again under gradient_checkpointing_enable() (per-layer recompute, dA / dB by
+p2t_lora_wgrad), the two modes alternating in one process: ms per step, `last_tape_bytes` and peak memory of each.
 `encoder`: InstructTrainer with LoRA r = 16 on the decoder's seven projections AND ESM2's six linears of every layer
 (p2t_hip/encoder_train.py: the encoder runs layer by layer with a tape and a HIP backward): ms per step and peak memory.
 `trainer`: the stage-2 InstructTrainer (LoRA r = 16 + adapter, GA 1): ms per full step, the flat clip + AdamW tail alone (bytes,
@@ -100,19 +102,29 @@ def main():
             o = model(**kw)
             o.loss.backward()
             return o
-        o3 = lstep()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(2):
-            o3 = lstep()
-        torch.cuda.synchronize()
-        dt_l = (time.perf_counter() - t0) / 2
-        ga = [q.grad for q in lora.parameters() if q.grad is not None]
-        n_l = sum(q.numel() for q in lora.parameters())
-        print(f"sft LoRA train step cfg3: B={B}, r=16 on {len(ga)} of {len(list(lora.parameters()))} matrices with a gradient ({n_l / 1e6:.1f} M LoRA parameters): "
-              f"{dt_l * 1e3:.1f} ms/batch = {B / dt_l:.2f} samples/s; loss {float(o3.loss):.4f}; |grad| of the first B matrix "
-              f"{float([q.grad for n, q in lora.named_parameters() if n.endswith('B')][0].float().norm()):.3e}; "
-              f"peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB", flush=True)
+        ga_n, n_l = None, sum(q.numel() for q in lora.parameters())
+        for rnd in range(2 if "checkpoint" in sys.argv else 1):          # off, on, off, on: the modes alternate
+            for on in ((False, True) if "checkpoint" in sys.argv else (False,)):
+                model.gradient_checkpointing_enable() if on else model.gradient_checkpointing_disable()
+                o3 = lstep()
+                del o3
+                torch.cuda.synchronize()
+                torch.cuda.empty_cache()
+                torch.cuda.reset_peak_memory_stats()
+                t0 = time.perf_counter()
+                for _ in range(2):
+                    o3 = lstep()
+                torch.cuda.synchronize()
+                dt_l = (time.perf_counter() - t0) / 2
+                ga = [q.grad for q in lora.parameters() if q.grad is not None]
+                print(f"sft LoRA train step cfg3 (checkpointing {'on' if on else 'off'}, round {rnd}): B={B}, r=16 on {len(ga)} of "
+                      f"{len(list(lora.parameters()))} matrices with a gradient ({n_l / 1e6:.1f} M LoRA parameters): "
+                      f"{dt_l * 1e3:.1f} ms/batch = {B / dt_l:.2f} samples/s; loss {float(o3.loss):.4f}; |grad| of the first B matrix "
+                      f"{float([q.grad for n, q in lora.named_parameters() if n.endswith('B')][0].float().norm()):.3e}; "
+                      f"tape {model.llama_decoder.last_tape_bytes / 2**30:.2f} GiB; peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB",
+                      flush=True)
+                del o3
+        model.gradient_checkpointing_disable()
     if "trainer" in sys.argv:
         trainer_leg(model, kw, B)
     if "encoder" in sys.argv:
@@ -128,21 +140,28 @@ def encoder_leg(model, kw, B):
     model.train()
     tr = P.InstructTrainer(model)
     n_p = sum(tr.opt.numels)
-    tr.step(kw)
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    n = 3
-    t0 = time.perf_counter()
-    for _ in range(n):
-        loss = tr.step(kw)
-    torch.cuda.synchronize()
-    dt_step = (time.perf_counter() - t0) / n
-    enc_cache = sum(t.numel() * t.element_size() for _, t in model.esm_encoder.__dict__.get("_lora_wT", {}).values())
-    print(f"sft InstructTrainer step cfg3 with encoder LoRA: B={B}, r=16 on {len(tr.params) - 4} LoRA matrices of both towers + adapter "
-          f"({n_p / 1e6:.1f} M parameters), GA 1: {dt_step * 1e3:.1f} ms/step = {B / dt_step:.2f} samples/s; loss {float(loss):.4f}; "
-          f"peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB (resident before the step {base / 2**30:.1f} GiB, of which "
-          f"{enc_cache / 2**30:.1f} GiB are the encoder's transposed frozen weights for its dX GEMMs)", flush=True)
+    modes = (False, True, False, True) if "checkpoint" in sys.argv else (False,)
+    for on in modes:                                                # the modes alternate in one process
+        model.gradient_checkpointing_enable() if on else model.gradient_checkpointing_disable()
+        tr.step(kw)
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        n = 3
+        t0 = time.perf_counter()
+        for _ in range(n):
+            loss = tr.step(kw)
+        torch.cuda.synchronize()
+        dt_step = (time.perf_counter() - t0) / n
+        enc_cache = sum(t.numel() * t.element_size() for _, t in model.esm_encoder.__dict__.get("_lora_wT", {}).values())
+        print(f"sft InstructTrainer step cfg3 with encoder LoRA (checkpointing {'on' if on else 'off'}): B={B}, r=16 on {len(tr.params) - 4} LoRA "
+              f"matrices of both towers + adapter ({n_p / 1e6:.1f} M parameters), GA 1: {dt_step * 1e3:.1f} ms/step = {B / dt_step:.2f} samples/s; "
+              f"loss {float(loss):.4f}; tape decoder {model.llama_decoder.last_tape_bytes / 2**30:.2f} + encoder "
+              f"{model.esm_encoder.last_tape_bytes / 2**30:.2f} GiB; peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB (resident before "
+              f"the step {base / 2**30:.1f} GiB, of which {enc_cache / 2**30:.1f} GiB are the encoder's transposed frozen weights for its dX GEMMs)",
+              flush=True)
+    model.gradient_checkpointing_disable()
 
 
 def trainer_leg(model, kw, B):
