@@ -374,6 +374,31 @@ int p2t_lora_wgrad(const void* X, int64_t ld_x, const void* U, int64_t ld_u, int
 int p2t_gather_rows_f32(float* dst, int64_t ld_dst, const int32_t* dst_pos, const float* src, int64_t ld_src,
                         const int32_t* src_pos, const int32_t* n_dst, const int32_t* n_src, int64_t max_rows, int H,
                         p2t_stream stream);
+/* ---- LM loss over the target rows only (p2t_hip/lm_head.py; the reference's stage-2 loops read `.loss` alone, scripts/
+ * train_instruct.py:192-213, 313-349).  The three calls share one row list; none reads anything on the host.
+ *
+ * The rows (b, t), as flat indices b T + t in array order, whose labels[b, t+1] is a counted target by p2t_cross_entropy_shifted's
+ * rule (t + 1 < T, label != ignore_index, 0 <= label < V): rows int32 [cap], targets int32 [cap] (those labels), count int32 [2] =
+ * {n, overflow}.  n is the number of such rows whatever cap is; overflow = 1 when n > cap, and then only the first cap are
+ * listed.  Entries min(n, cap) .. cap of rows and targets are -1.  B T < 2^31. */
+int p2t_lm_target_rows(const int64_t* labels, int B, int T, int V, int64_t ignore_index, int cap, int32_t* rows, int32_t* targets,
+                       int32_t* count, p2t_stream stream);
+/* One chunk of LM-head logits, `dtype` (F32 | BF16) [R, ld], IN PLACE; ld a multiple of 64 with ld >= V, 16-byte aligned.  Row r
+ * of the chunk is entry first + r of the list (first + R <= cap).  For an entry below count[0] with a target y:
+ *   row_loss[first + r] = logsumexp(x[:V]) - x[y]                    (from the stored values, as p2t_cross_entropy_shifted reads them)
+ *   x[c] <- (exp(x[c] - logsumexp) - [c == y]) s_r  for c < V, 0 for V <= c < ld (whatever those columns held)
+ * with s_r = 1 / count[0] (weights == NULL: the token mean) or weights[rows[.] + 1] (f32 [n_weights] = [B T], aligned with the
+ * labels as in p2t_cross_entropy_shifted_weighted).  Every other row (at or beyond count[0], target -1) becomes all 0 with
+ * row_loss 0.  with_grad == 0: row_loss only, the logits are left as they are.  One workgroup per row, two streaming passes,
+ * fixed-order reductions: the same bits every run. */
+int p2t_lm_loss_grad_rows(void* logits, int64_t ld, int dtype, int R, int V, const int32_t* rows, const int32_t* targets,
+                          const int32_t* count, int first, int cap, const float* weights, int64_t n_weights, float* row_loss,
+                          int with_grad, p2t_stream stream);
+/* loss f32 [1] = sum of row_loss over the first min(count[0], cap) entries / count[0] (NaN when count[0] == 0, as
+ * p2t_cross_entropy_shifted), or with weights the sum of weights[rows[i] + 1] row_loss[i]; NaN when count[1] (overflow) is set --
+ * a capacity that was too small must not train silently on a subset.  One workgroup, fixed order. */
+int p2t_lm_loss_reduce(const float* row_loss, const int32_t* rows, const int32_t* count, int cap, const float* weights,
+                       int64_t n_weights, float* loss, p2t_stream stream);
 /* Transposed decoder weights for the dX GEMMs, `dtype`, one struct per layer (HOST array): each matrix is the forward
  * weight transposed -- [forward K rows][row stride = forward N rounded up to 64, zero padded] -- built once (the decoder is
  * frozen).  qkv_wT from the NATURAL row order q_proj | k_proj | v_proj (not the packed order of p2t_llama_layer.qkv_w);

@@ -206,6 +206,9 @@ int launch_swiglu_from_gu(const void* gu, int64_t ld_gu, void* act, int64_t ld_a
 // dst[m, c] = (Tdst)src[m, c] for c < cols, 0 for cols <= c < ld_dst  (a GEMM operand with its K padding)
 int launch_cast_rows(const void* src, int src_dtype, int64_t ld_src, void* dst, int dst_dtype, int64_t ld_dst, int64_t rows, int64_t cols, hipStream_t s);
 
+// lm_loss.hip (LM loss over the target rows only: p2t_lm_target_rows / p2t_lm_loss_grad_rows / p2t_lm_loss_reduce) shares nothing between
+// translation units: its three entry points are declared in include/p2t_hip.h alone
+
 // adapter tail helpers (adapter.hip)
 int launch_adapter_dz2(const void* g2, const void* z2, const float* inv_norm, const float* dy, void* dz2, int64_t ld, int64_t M,
                        int D, int dtype, float drop_p, uint64_t drop_seed, hipStream_t s);

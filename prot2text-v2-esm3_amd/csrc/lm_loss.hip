@@ -1,0 +1,197 @@
+// LM loss of the stage-2 step over the rows that carry a target only (reference scripts/train_instruct.py:192-213
+// reads `.loss` alone, never the logits):
+//   * lm_target_rows      -- the flat rows (b, t) whose labels[b, t+1] is counted, by ce_rows_kernel's rule (sft.hip), their labels
+//                            and their number, on the device;
+//   * lm_loss_grad_rows   -- one chunk of logits [R, ld] in place: row loss = logsumexp - target logit, then the row overwritten
+//                            by its own gradient (softmax - onehot) * s_r, Liger-style, so no second [R, ld] buffer ever exists;
+//   * lm_loss_reduce      -- the row losses summed in a fixed order into the token mean / the weighted sum.
+// A row of Llama's vocabulary is 128 256 elements = 256 KB in bf16, four times a CU's LDS: it is NOT staged.  Pass 1 streams it
+// once with 16-byte loads keeping a running (max, sum) per thread (online softmax: one read instead of two), pass 2 streams it
+// again -- the row was just read by the same workgroup, so it comes from L2 (4 MB per XCD holds 16 such rows, more than the
+// workgroups an XCD runs at once) -- and stores 16 bytes per lane.  Vector stores only, no atomics; every reduction has a fixed
+// order, so the same input gives the same bits.
+#include "common.h"
+#include "kernels.h"
+
+namespace p2t {
+
+// One block of 1024 threads, as positions_where_kernel: thread i owns a contiguous segment of the B*T flat rows, counts its hits,
+// the counts are scanned through LDS, and a second walk writes rows / targets below `cap`.  count = {n, n > cap}; the entries
+// min(n, cap) .. cap of rows / targets are set to -1.
+__global__ void __launch_bounds__(1024) lm_target_rows_kernel(const int64_t* __restrict__ labels, int64_t n_rows, int T_len, int V, int64_t ignore_index,
+                                                              int cap, int32_t* __restrict__ rows, int32_t* __restrict__ targets,
+                                                              int32_t* __restrict__ count) {
+    __shared__ int part[1024];
+    const int tid = threadIdx.x;
+    const int64_t seg = (n_rows + 1023) / 1024, lo = tid * seg, hi = lo + seg < n_rows ? lo + seg : n_rows;
+    auto target_of = [&](int64_t row) -> int64_t {      // the counted label of flat row (b, t), -1 without one
+        if ((int)(row % T_len) + 1 >= T_len) return -1;
+        const int64_t label = labels[row + 1];
+        return (label == ignore_index || label < 0 || label >= V) ? -1 : label;
+    };
+    int c = 0;
+    for (int64_t i = lo; i < hi; ++i) c += target_of(i) >= 0;
+    part[tid] = c;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {          // Hillis-Steele inclusive scan
+        const int add = tid >= off ? part[tid - off] : 0;
+        __syncthreads();
+        part[tid] += add;
+        __syncthreads();
+    }
+    int r = part[tid] - c;
+    for (int64_t i = lo; i < hi; ++i) {
+        const int64_t label = target_of(i);
+        if (label < 0) continue;
+        if (r < cap) { rows[r] = (int32_t)i; targets[r] = (int32_t)label; }
+        ++r;
+    }
+    const int n = part[1023];
+    for (int j = (n < cap ? n : cap) + tid; j < cap; j += 1024) { rows[j] = -1; targets[j] = -1; }
+    if (tid == 0) { count[0] = n; count[1] = n > cap; }
+}
+
+template <typename T> struct RowVec;
+template <> struct RowVec<float> {
+    static constexpr int N = 4;
+    static __device__ __forceinline__ void load(const float* p, float (&v)[4]) { load4(p, v); }
+    static __device__ __forceinline__ void store(float* p, const float (&v)[4]) { store4(p, v); }
+};
+template <> struct RowVec<bf16_t> {
+    static constexpr int N = 8;
+    static __device__ __forceinline__ void load(const bf16_t* p, float (&v)[8]) { load8(p, v); }
+    static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[8]) {
+        *reinterpret_cast<uint4*>(p) = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+    }
+};
+
+// One workgroup of 256 threads per row r of the chunk; the chunk's row r is entry first + r of rows / targets / row_loss.
+// ld is a multiple of 64 elements and x is 16-byte aligned (checked by the entry point), so every 16-byte vector lies inside the row.
+template <typename T>
+__global__ void __launch_bounds__(256) lm_loss_grad_rows_kernel(T* x_all, int64_t ld, int V, const int32_t* __restrict__ rows,
+                                                                const int32_t* __restrict__ targets, const int32_t* __restrict__ count, int first,
+                                                                const float* __restrict__ weights, int64_t n_weights, float* __restrict__ row_loss,
+                                                                int with_grad) {
+    constexpr int N = RowVec<T>::N;
+    __shared__ float red_m[4];
+    __shared__ float red_s[4];
+    const int r = first + (int)blockIdx.x;
+    T* x = x_all + (int64_t)blockIdx.x * ld;
+    const int n = count[0];
+    const int target = targets[r];
+    const int64_t wrow = (int64_t)rows[r] + 1;          // the weight sits at the target's label position
+    const bool live = r < n && target >= 0 && target < V && (!weights || (wrow > 0 && wrow < n_weights));
+    const int nvec = (int)(ld / N);
+    if (!live) {                                        // wave-uniform: a pad row / a row beyond the count
+        if (with_grad) {
+            float z[N];
+#pragma unroll
+            for (int j = 0; j < N; ++j) z[j] = 0.f;
+            for (int i = threadIdx.x; i < nvec; i += 256) RowVec<T>::store(x + (int64_t)i * N, z);
+        }
+        if (threadIdx.x == 0) row_loss[r] = 0.f;
+        return;
+    }
+    // ---- pass 1: running max and sum of exp(x - max) per thread, then merged in a fixed order
+    float m = -INFINITY, s = 0.f;
+    for (int i = threadIdx.x; i < nvec; i += 256) {
+        float v[N];
+        RowVec<T>::load(x + (int64_t)i * N, v);
+        const int c0 = i * N;
+        float vm = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < N; ++j) vm = fmaxf(vm, c0 + j < V ? v[j] : -INFINITY);       // a select: the pad columns may hold NaN
+        if (vm > m) { s *= expf(m - vm); m = vm; }      // (s is 0 while m is -inf: 0 * exp(-inf) = 0)
+        float e = 0.f;
+#pragma unroll
+        for (int j = 0; j < N; ++j) e += c0 + j < V ? expf(v[j] - m) : 0.f;
+        if (m > -INFINITY) s += e;
+    }
+    const float wm = wave_max(m);
+    s = wave_sum(m > -INFINITY ? s * expf(m - wm) : 0.f);
+    if ((threadIdx.x & 63) == 0) { red_m[threadIdx.x >> 6] = wm; red_s[threadIdx.x >> 6] = s; }
+    __syncthreads();
+    const float M = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
+    float S = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) S += red_m[w] > -INFINITY ? red_s[w] * expf(red_m[w] - M) : 0.f;
+    if (threadIdx.x == 0) row_loss[r] = logf(S) + M - to_f32(x[target]);
+    if (!with_grad) return;
+    __syncthreads();                                    // x[target] is read above before any lane overwrites it
+    // ---- pass 2: the row becomes its own gradient
+    const float s_r = weights ? weights[wrow] : 1.0f / (float)n;
+    const float inv = 1.0f / S;
+    for (int i = threadIdx.x; i < nvec; i += 256) {
+        float v[N], g[N];
+        RowVec<T>::load(x + (int64_t)i * N, v);
+        const int c0 = i * N;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const int c = c0 + j;
+            g[j] = c < V ? (expf(v[j] - M) * inv - (c == target ? 1.f : 0.f)) * s_r : 0.f;
+        }
+        RowVec<T>::store(x + (int64_t)i * N, g);
+    }
+}
+
+// loss = sum over the listed rows of row_loss (/ n: the token mean, NaN without a target as p2t_cross_entropy_shifted), or of
+// weights[row + 1] * row_loss; NaN when the list overflowed its capacity.
+__global__ void __launch_bounds__(1024) lm_loss_reduce_kernel(const float* __restrict__ row_loss, const int32_t* __restrict__ rows,
+                                                              const int32_t* __restrict__ count, int cap, const float* __restrict__ weights,
+                                                              int64_t n_weights, float* __restrict__ loss) {
+    __shared__ float red[16];
+    const int n = count[0], m = n < cap ? n : cap;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < m; i += 1024) {
+        if (weights) {
+            const int64_t wrow = (int64_t)rows[i] + 1;
+            s += (wrow > 0 && wrow < n_weights) ? weights[wrow] * row_loss[i] : 0.f;
+        } else {
+            s += row_loss[i];
+        }
+    }
+    s = block_sum<16>(s, red);
+    if (threadIdx.x == 0) *loss = count[1] ? __builtin_nanf("") : (weights ? s : s / (float)n);
+}
+
+}  // namespace p2t
+
+using namespace p2t;
+
+extern "C" int p2t_lm_target_rows(const int64_t* labels, int B, int T, int V, int64_t ignore_index, int cap, int32_t* rows, int32_t* targets,
+                                  int32_t* count, p2t_stream stream) {
+    P2T_REQUIRE(labels && rows && targets && count && B > 0 && T > 0 && V > 0 && cap > 0 && (int64_t)B * T < (1ll << 31),
+                "p2t_lm_target_rows: bad arguments");
+    lm_target_rows_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(labels, (int64_t)B * T, T, V, ignore_index, cap, rows, targets, count);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
+extern "C" int p2t_lm_loss_grad_rows(void* logits, int64_t ld, int dtype, int R, int V, const int32_t* rows, const int32_t* targets,
+                                     const int32_t* count, int first, int cap, const float* weights, int64_t n_weights, float* row_loss,
+                                     int with_grad, p2t_stream stream) {
+    P2T_REQUIRE(logits && rows && targets && count && row_loss && R > 0 && V > 0 && first >= 0 && cap > 0 && (int64_t)first + R <= cap,
+                "p2t_lm_loss_grad_rows: bad arguments");
+    P2T_REQUIRE(ld >= V && ld % 64 == 0 && ld < (1ll << 31) && ((uintptr_t)logits & 15) == 0,
+                "p2t_lm_loss_grad_rows: ld = %lld must be a multiple of 64 that holds V = %d, rows 16-byte aligned", (long long)ld, V);
+    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_lm_loss_grad_rows: unsupported dtype %d", dtype);
+    P2T_REQUIRE(!weights || n_weights > 0, "p2t_lm_loss_grad_rows: weights need their element count");
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == P2T_BF16)
+        lm_loss_grad_rows_kernel<bf16_t><<<(unsigned)R, 256, 0, s>>>((bf16_t*)logits, ld, V, rows, targets, count, first, weights, n_weights, row_loss,
+                                                                    with_grad);
+    else
+        lm_loss_grad_rows_kernel<float><<<(unsigned)R, 256, 0, s>>>((float*)logits, ld, V, rows, targets, count, first, weights, n_weights, row_loss,
+                                                                   with_grad);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
+extern "C" int p2t_lm_loss_reduce(const float* row_loss, const int32_t* rows, const int32_t* count, int cap, const float* weights,
+                                  int64_t n_weights, float* loss, p2t_stream stream) {
+    P2T_REQUIRE(row_loss && rows && count && loss && cap > 0, "p2t_lm_loss_reduce: bad arguments");
+    P2T_REQUIRE(!weights || n_weights > 0, "p2t_lm_loss_reduce: weights need their element count");
+    lm_loss_reduce_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(row_loss, rows, count, cap, weights, n_weights, loss);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}

@@ -143,6 +143,9 @@ SIGNATURES = {
     "p2t_dropout_rows": (i32, [vp, i32, i64, vp, i32, i64, i64, i64, f32, u64, i32, vp]),
     "p2t_lora_wgrad_workspace_bytes": (sz, [i64, i64, i64]),
     "p2t_lora_wgrad": (i32, [vp, i64, vp, i64, i32, vp, i64, i32, i64, i64, i64, f32, u64, vp, sz, vp]),
+    "p2t_lm_target_rows": (i32, [vp, i32, i32, i32, i64, i32, vp, vp, vp, vp]),
+    "p2t_lm_loss_grad_rows": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, i32, i32, vp, i64, vp, i32, vp]),
+    "p2t_lm_loss_reduce": (i32, [vp, vp, vp, i32, vp, i64, vp, vp]),
     "p2t_compact_rows":(i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "p2t_llama_prefill_workspace_bytes": (sz, [C.POINTER(LlamaConfigC), i32, i32]),
     "p2t_llama_prefill": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), vp, vp, i32, i32, C.POINTER(KvCacheC), vp, vp, sz, vp]),

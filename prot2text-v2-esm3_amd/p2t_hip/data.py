@@ -184,7 +184,9 @@ def pack_instruct_batch(batch: Dict[str, Any], max_tokens: int, loss_weighting: 
       "sample": `loss_weights` f32 [rows, T] = 1 / (n_docs * n_supervised(doc)) on every supervised target -- the mean of the
       per-sample losses, i.e. the reference's batch_size_per_device = 1 micro-batches, averaged (documents without a supervised
       token are not counted);
-    * `pack_layout`: one (sample index, row, start, length) per sample in placement order (enough to unpack the rows).
+    * `pack_layout`: one (sample index, row, start, length) per sample in placement order (enough to unpack the rows);
+    * `num_targets`: the number of positions t >= 1 of the packed labels that are not -100, a host upper bound on the targets the
+      LM loss counts (`forward(num_targets=...)`: under `fused_lm_loss()` it sizes the head's buffers without a device read).
     A sample longer than max_tokens raises ValueError.  Works on the host batch; other per-sample entries are dropped."""
     if loss_weighting not in ("token", "sample"):
         raise ValueError(f"loss_weighting must be 'token' or 'sample', got {loss_weighting!r}")
@@ -252,6 +254,7 @@ def pack_instruct_batch(batch: Dict[str, Any], max_tokens: int, loss_weighting: 
             out[key] = batch[key].cpu()[perm]
     if out_w is not None:
         out["loss_weights"] = out_w
+    out["num_targets"] = int((out_lab[:, 1:] != -100).sum()) if T > 1 else 0
     return out
 
 

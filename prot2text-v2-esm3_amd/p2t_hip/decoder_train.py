@@ -30,7 +30,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import _lib, ops
+from . import lm_head, ops
 from ._lib import call
 from .lora_linear import DECODER_TARGETS, LoraLinear, LoraPairs, scaled_grads, tape_bytes
 from .ops import ptr, round_up, stream
@@ -145,7 +145,6 @@ class DecoderLoraLossFn(torch.autograd.Function):
         tape = []
         keep = opts["keep_tape"]                        # False: forward-only loss, no layer's activations are kept
         ckpt = keep and bool(opts.get("checkpoint"))    # the tape holds every layer's input alone; the backward redoes the layer
-        f32v = lambda n: P[n].detach().float().contiguous()
         st = dict(decoder=decoder, spec=s, dt=dt, P=P, tape=tape, checkpoint=ckpt, key_mask=key_mask, kv_info=kv_info, docs=docs, weights=weights,
                   inv_freq=inv_freq, l2s=l2s, scale=scale, q_fold=q_fold, shape=(B, T, H), params=params, in_dtype=inputs_embeds.dtype)
         for i in range(L):
@@ -156,16 +155,20 @@ class DecoderLoraLossFn(torch.autograd.Function):
             rec, x = _layer_forward(st, i, lin, x, keep and not ckpt)
             if keep and not ckpt:
                 tape.append(rec)
-        x_last = x
-        hN = ops.rmsnorm(x_last, f32v("norm.weight"), s.rms_norm_eps, out_dtype=dt)
-        logits = ops.gemm_nt(hN, decoder._lm_head_padded(), None, n=s.vocab_size, k=H, out_dtype=dt).view(B, T, -1)
         lab = labels.to(dev).to(torch.int64).contiguous()
-        loss, count = ops.cross_entropy_shifted(logits, lab, s.vocab_size, weights=weights)
-        st.update(x_last=x_last, logits=logits, labels=lab, count=count)
+        fused = opts.get("fused")                       # LlamaDecoder.fused_lm_loss(): the target rows only, no logits (p2t_hip/lm_head.py)
+        if fused is not None:
+            loss, head = lm_head.lm_head_loss(decoder, x, lab, weights=weights, chunk_rows=fused["chunk_rows"], targets=fused.get("targets"),
+                                                   with_grad=keep)
+            logits = None
+        else:
+            loss, logits, head = lm_head.head_loss(decoder, x, lab, weights=weights)
+        st.update(head=head, fused=fused is not None, device=x.device)
         ctx.state = st
         if keep:
-            decoder.last_tape_bytes = tape_bytes(tape, (x_last, logits, lab, count, key_mask, kv_info, docs, weights))
-        ctx.mark_non_differentiable(logits)
+            decoder.last_tape_bytes = tape_bytes(tape, (*lm_head.head_saved_tensors(head), lab, key_mask, kv_info, docs, weights))
+        if logits is not None:
+            ctx.mark_non_differentiable(logits)
         return loss[0], logits
 
     @staticmethod
@@ -178,19 +181,16 @@ class DecoderLoraLossFn(torch.autograd.Function):
         M = B * T
         nh, nkv, d, F = s.num_attention_heads, s.num_key_value_heads, s.head_dim, s.intermediate_size
         dp = ops.head_dim_padded(d)
-        V = s.vocab_size
-        dev = st["x_last"].device
+        dev = st["device"]
         P = st["P"]
         f32v = lambda n: P[n].detach().float().contiguous()
-        ld = st["logits"].shape[2]
-        d_logits = ops.cross_entropy_shifted_backward(st["logits"], st["labels"], V, st["count"], weights=st["weights"])
-        d_h = ops.gemm_nt(d_logits.view(M, ld), dec._lm_head_transposed(), None, n=H, k=round_up(V, 64), epilogue=_lib.EPI_STORE_F32)      # [M, H] f32
-        g = torch.empty((M, H), dtype=torch.float32, device=dev)
+        # the head's gradient at the input of the final RMSNorm, unscaled: g_loss multiplies the whole chain at its end
+        g = lm_head.lm_head_backward(dec, st["head"], None) if st["fused"] else lm_head.head_backward(dec, st["head"])
+        st["head"] = None
 
         def rms_bwd(x, w, dy, out, acc, rows=M, cols=H):
             call("p2t_rmsnorm_backward", ptr(x), x.stride(0), ptr(w), float(s.rms_norm_eps), ptr(dy), dy.stride(0), 0 if dy.dtype == torch.float32 else 1,
                  ptr(out), out.stride(0), rows, cols, int(acc), stream())
-        rms_bwd(st["x_last"], f32v("norm.weight"), d_h, g, 0)
         grads: dict = {}
         c_s = 0.6931471805599453 if st["l2s"] else st["scale"]
         to_dt = lambda t: ops.cast(t, dt) if t.dtype != dt else t
@@ -253,7 +253,7 @@ class DecoderLoraLossFn(torch.autograd.Function):
 
 def lora_lm_loss(decoder, lora: Optional[DecoderLora], inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, labels: torch.Tensor,
                  dropout: Optional[float] = None, docs: Optional[torch.Tensor] = None, loss_weights: Optional[torch.Tensor] = None,
-                 checkpoint: bool = False):
+                 checkpoint: bool = False, fused: Optional[dict] = None):
     """(loss, logits) of `llama_decoder(inputs_embeds=..., attention_mask=..., labels=...)` with the LoRA branches in the graph.
     dropout: None = the branches' own `lora.p` (every mode, as before); a value overrides it for this call and leaves the mask counter
     where it is -- 0.0 is peft's eval mode (InstructTrainer.evaluate).  Without gradients to compute, no activation tape is kept.
@@ -261,13 +261,15 @@ def lora_lm_loss(decoder, lora: Optional[DecoderLora], inputs_embeds: torch.Tens
     starts to -100); loss_weights: f32 [B, T] per-target weights (ops.cross_entropy_shifted) instead of the token mean.
     checkpoint: gradient checkpointing -- the tape keeps each layer's fp32 input alone and the backward redoes the layer from it
     (same kernels, same dropout seeds: the loss and every gradient but dA / dB are bit-identical to checkpoint = False; dA / dB come
-    from p2t_lora_wgrad, a differently ordered fp32 sum).  `decoder.last_tape_bytes`: the bytes of the tensors kept for the backward."""
+    from p2t_lora_wgrad, a differently ordered fp32 sum).  `decoder.last_tape_bytes`: the bytes of the tensors kept for the backward.
+    fused: dict(chunk_rows=..., targets=lm_head.select_targets(...) or absent) -- the LM loss over the target rows only
+    (LlamaDecoder.fused_lm_loss; p2t_hip/lm_head.py): logits is then None, and the head keeps no [M, vocab] tensor."""
     params = tuple(lora.parameters()) if lora is not None else ()
     if lora is not None and dropout is None:
         if lora.training:
             lora.step_count += 1                        # a fresh dropout mask per step
         dropout = lora.p                                # in every mode (peft's eval mode would be 0.0)
     keep = torch.is_grad_enabled() and (inputs_embeds.requires_grad or any(q.requires_grad for q in params))
-    opts = dict(dropout=float(dropout or 0.0), keep_tape=keep, docs=docs, loss_weights=loss_weights, checkpoint=bool(checkpoint))
+    opts = dict(dropout=float(dropout or 0.0), keep_tape=keep, docs=docs, loss_weights=loss_weights, checkpoint=bool(checkpoint), fused=fused)
     loss, logits = DecoderLoraLossFn.apply(inputs_embeds, decoder, lora, attention_mask, labels, opts, *params)
-    return loss, logits[..., : decoder.spec.vocab_size]
+    return loss, (logits[..., : decoder.spec.vocab_size] if logits is not None else None)

@@ -159,10 +159,14 @@ class InstructTrainer:
     the flat buffers like the LoRA matrices; a bf16 adapter keeps its module tensors, which the optimizer writes as shadows of the
     fp32 masters, and its bf16 gradients are folded into the flat buffer after every micro-batch.
     The step adds no host synchronisation of its own (the model's placeholder-count check reads one count, as torch's boolean
-    assignment in the reference does)."""
+    assignment in the reference does).
+    fused_lm_loss=True switches the decoder to the LM loss over the target rows only (`model.fused_lm_loss()`, p2t_hip/lm_head.py) for
+    `step` and `evaluate`; a batch's `num_targets` (p2t_hip.data.pack_instruct_batch) is passed through as the host bound, without it
+    the head reads the 4-byte target count once per forward.  False (the default) leaves the model as it is."""
 
     def __init__(self, model, *, lr=2e-4, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, max_norm=None,
-                 gradient_accumulation_steps: int = 1, schedule=None, process_group=None, train_adapter: bool = True):
+                 gradient_accumulation_steps: int = 1, schedule=None, process_group=None, train_adapter: bool = True,
+                 fused_lm_loss: bool = False):
         lora = getattr(model.llama_decoder, "lora", None)
         enc_lora = getattr(getattr(model, "esm_encoder", None), "lora", None)     # LoRA on the ESM2 encoder (p2t_hip/encoder_train.py)
         if lora is None and enc_lora is None:
@@ -176,6 +180,8 @@ class InstructTrainer:
         if max_norm is not None and not max_norm > 0:
             raise ValueError("max_norm must be positive (None: no clipping)")
         self.model, self.lora, self.enc_lora = model, lora, enc_lora
+        if fused_lm_loss:
+            model.fused_lm_loss(True)
         self.hp = dict(lr=float(lr), betas=tuple(float(b) for b in betas), eps=float(eps), weight_decay=float(weight_decay),
                        max_norm=math.inf if max_norm is None else float(max_norm))
         self.schedule, self.group = schedule, process_group
@@ -264,7 +270,8 @@ class InstructTrainer:
         self._dirty = True
         out = self.model(input_ids=batch["input_ids"], attention_mask=batch["attention_mask"], labels=batch["labels"],
                          protein_input_ids=batch["protein_input_ids"], protein_attention_mask=batch["protein_attention_mask"],
-                         position_ids=batch.get("position_ids"), loss_weights=batch.get("loss_weights"))
+                         position_ids=batch.get("position_ids"), loss_weights=batch.get("loss_weights"),
+                         num_targets=batch.get("num_targets"))
         loss = out.loss
         (loss / self.gradient_accumulation_steps).backward()
         self._fold_adapter_grads()
@@ -329,7 +336,12 @@ class InstructTrainer:
                 labels = labels.masked_fill(pos.to(labels.device) == 0, -100)
         if weights is not None:
             weights = weights.to(device=embeds.device, dtype=torch.float32).contiguous()
-        loss, _ = lora_lm_loss(m.llama_decoder, self.lora, embeds, mask, labels, dropout=0.0, docs=docs, loss_weights=weights)
+        fused = getattr(m.llama_decoder, "_fused_lm_loss", None)
+        if fused is not None:                        # as LlamaDecoder.forward: the target rows are listed before the decoder is enqueued
+            from . import lm_head
+            lab = labels.to(embeds.device).to(torch.int64).contiguous()
+            fused = dict(fused, targets=lm_head.select_targets(lab, m.llama_decoder.spec.vocab_size, batch.get("num_targets")))
+        loss, _ = lora_lm_loss(m.llama_decoder, self.lora, embeds, mask, labels, dropout=0.0, docs=docs, loss_weights=weights, fused=fused)
         return loss.reshape(1)
 
     def global_loss(self, loss: torch.Tensor) -> torch.Tensor:

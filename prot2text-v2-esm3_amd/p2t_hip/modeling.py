@@ -652,31 +652,36 @@ class _DecoderLossFn(torch.autograd.Function):
     cross-entropy backward -> LM-head dX GEMM -> p2t_llama_train_backward.  All kernels hand-written; torch only links them."""
 
     @staticmethod
-    def forward(ctx, inputs_embeds, decoder, attention_mask, labels, docs=None, weights=None):
+    def forward(ctx, inputs_embeds, decoder, attention_mask, labels, docs=None, weights=None, fused=None):
+        from . import lm_head
         s, m = decoder.spec, decoder.model
         B, T, H = inputs_embeds.shape
-        dt = m.dtype
-        h, handle = m.train_forward(inputs_embeds, attention_mask, docs)
-        a = h.view(B * T, H) if dt == torch.float32 else ops.cast(h.view(B * T, H), dt)
-        logits = ops.gemm_nt(a, decoder._lm_head_padded(), None, n=s.vocab_size, k=H, out_dtype=dt).view(B, T, -1)
-        lab = labels.to(logits.device).to(torch.int64).contiguous()
-        loss, count = ops.cross_entropy_shifted(logits, lab, s.vocab_size, weights=weights)
-        ctx.decoder, ctx.handle, ctx.logits, ctx.labels, ctx.count, ctx.weights = decoder, handle, logits, lab, count, weights
+        h, handle = m.train_forward(inputs_embeds, attention_mask, docs)          # post final RMSNorm: the head runs with norm = False
+        lab = labels.to(h.device).to(torch.int64).contiguous()
+        ctx.decoder, ctx.handle, ctx.fused = decoder, handle, fused is not None
+        if fused is not None:                   # LlamaDecoder.fused_lm_loss(): the target rows only, no logits
+            loss, ctx.saved = lm_head.lm_head_loss(decoder, h.view(B * T, H), lab, weights=weights, chunk_rows=fused["chunk_rows"], norm=False,
+                                                   targets=fused["targets"], with_grad=True)
+            return loss[0], None
+        loss, logits, ctx.saved = lm_head.head_loss(decoder, h.view(B * T, H), lab, weights=weights, norm=False)
         ctx.mark_non_differentiable(logits)
         return loss[0], logits
 
     @staticmethod
     def backward(ctx, g_loss, _g_logits):
-        dec, logits = ctx.decoder, ctx.logits
-        s = dec.spec
-        B, T, ld = logits.shape
-        H, V = s.hidden_size, s.vocab_size
-        d_logits = ops.cross_entropy_shifted_backward(logits, ctx.labels, V, ctx.count, weights=ctx.weights)
-        d_h = ops.gemm_nt(d_logits.view(B * T, ld), dec._lm_head_transposed(), None, n=H, k=round_up(V, 64), epilogue=_lib.EPI_STORE_F32)   # [B*T, H] f32
-        d_in = dec.model.train_backward(d_h.view(B, T, H), ctx.handle)
-        call("p2t_scale_by_device_scalar", ptr(d_in), d_in.numel(), ptr(g_loss.float().reshape(1).contiguous()), stream())
-        ctx.handle = ctx.logits = ctx.weights = None            # free the tape
-        return d_in, None, None, None, None, None
+        from . import lm_head
+        dec = ctx.decoder
+        B, T = ctx.handle[2], ctx.handle[3]
+        H = dec.spec.hidden_size
+        if ctx.fused:                           # the head's gradient arrives scaled by g_loss; the dX chain below is linear in it
+            d_h = lm_head.lm_head_backward(dec, ctx.saved, g_loss)
+            d_in = dec.model.train_backward(d_h.view(B, T, H), ctx.handle)
+        else:
+            d_h = lm_head.head_backward(dec, ctx.saved)                             # [B*T, H] f32
+            d_in = dec.model.train_backward(d_h.view(B, T, H), ctx.handle)
+            call("p2t_scale_by_device_scalar", ptr(d_in), d_in.numel(), ptr(g_loss.float().reshape(1).contiguous()), stream())
+        ctx.handle = ctx.saved = None           # free the tape
+        return d_in, None, None, None, None, None, None
 
 
 class CausalLMOutput:
@@ -733,10 +738,27 @@ class LlamaDecoder(nn.Module):
             self._lmT_w, self._lmT_key = _pad_cols(w.detach().t().contiguous(), round_up(w.shape[0], 64), w.dtype), key
         return self._lmT_w
 
+    def fused_lm_loss(self, enabled: bool = True, chunk_rows: int = 1024):
+        """Opt in to (or out of) the LM-loss head that runs on the target rows only (p2t_hip/lm_head.py).  When on,
+        `forward(inputs_embeds=..., labels=...)` returns `CausalLMOutput(loss, logits=None)` on every stage-2 path (frozen decoder,
+        LoRA with the full tape or checkpointed, packed rows, loss_weights): the reference's train and eval loops read `.loss` only
+        (scripts/train_instruct.py:192-213, 313-349).  The rows with a counted target go through the final RMSNorm, the LM head and
+        the cross-entropy `chunk_rows` at a time (rounded up to 128), one [chunk_rows, vocab] logits buffer is all the head holds, and
+        nothing of that size is kept for the backward.  The forward without labels is unchanged.  Off by default."""
+        if int(chunk_rows) < 1:
+            raise ValueError("chunk_rows must be a positive row count")
+        self._fused_lm_loss = dict(chunk_rows=int(chunk_rows)) if enabled else None
+        return self
+
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None,
                 labels=None, use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None,
-                cache_position=None, loss_weights=None, **kwargs):
+                cache_position=None, loss_weights=None, num_targets=None, **kwargs):
         """LlamaForCausalLM.forward without a KV cache: all layers -> final RMSNorm -> LM head -> (shifted cross-entropy).
+        num_targets (not an argument of the reference; read under `fused_lm_loss()` only): a host upper bound on the number of
+        positions with a counted target (p2t_hip.data.pack_instruct_batch returns it), which sizes the fused head's buffers without
+        reading anything back.  A bound that is too small does not train on a subset: the loss is NaN, and the epoch loop's NaN
+        guard stops the run.  Without it the target rows are counted on the device and the 4-byte count is read at the top of this
+        call, before the towers are enqueued (one host sync that waits only for earlier work).
         position_ids is accepted on the loss path only (inputs_embeds + labels): packed rows (include/p2t_hip.h, p2t_doc_prepare) --
         every position 0 under a right-padded mask starts a document, attention stays inside each document, rotary uses the given
         positions and the target that starts a document is never scored.  An arange per row is an ordinary batch.
@@ -775,7 +797,7 @@ class LlamaDecoder(nn.Module):
                 if tuple(labels.shape) != (B, T):
                     raise ValueError(f"labels shape {tuple(labels.shape)} != {(B, T)}")
                 labels = labels.to(dev).masked_fill(position_ids.to(dev) == 0, -100)
-        if loss_path and (lora is not None or docs is not None or loss_weights is not None or grad_path):
+        if loss_path and (lora is not None or docs is not None or loss_weights is not None or grad_path or getattr(self, "_fused_lm_loss", None) is not None):
             B, T, _ = inputs_embeds.shape
             if tuple(labels.shape) != (B, T):
                 raise ValueError(f"labels shape {tuple(labels.shape)} != {(B, T)}")
@@ -788,6 +810,11 @@ class LlamaDecoder(nn.Module):
                 loss_weights = loss_weights.to(device=dev, dtype=torch.float32).contiguous()
             per_layer = lora is not None or s.qk_norm or not grad_path
             ckpt = bool(getattr(self, "gradient_checkpointing", False))
+            fused = getattr(self, "_fused_lm_loss", None)
+            if fused is not None:               # the target rows are listed (and, without a bound, counted) before the towers are enqueued
+                from . import lm_head
+                lab = labels.to(dev).to(torch.int64).contiguous()
+                fused = dict(fused, targets=lm_head.select_targets(lab, s.vocab_size, num_targets))
             if ckpt and not per_layer and not getattr(self, "_warned_checkpointing", False):
                 # the caller asked for activation checkpointing (reference :253-268 forwards the flag to the decoder): the per-layer
                 # step below honours it; the fused frozen-decoder chain keeps its whole activation tape (p2t_llama_tape_bytes: ~26 GB per 4 x 1216 tokens of Llama-3.1-8B) and
@@ -805,10 +832,10 @@ class LlamaDecoder(nn.Module):
                     raise ValueError("stage-2 training runs the decoder GEMMs in the model dtype (set_gemm_dtype('model'))")
                 from .decoder_train import lora_lm_loss
                 loss, logits = lora_lm_loss(self, lora, inputs_embeds, attention_mask, labels, docs=docs, loss_weights=loss_weights,
-                                            checkpoint=ckpt)
+                                            checkpoint=ckpt, fused=fused)
                 return CausalLMOutput(loss=loss, logits=logits)
-            loss, logits = _DecoderLossFn.apply(inputs_embeds, self, attention_mask, labels, docs, loss_weights)
-            return CausalLMOutput(loss=loss, logits=logits[..., : s.vocab_size])
+            loss, logits = _DecoderLossFn.apply(inputs_embeds, self, attention_mask, labels, docs, loss_weights, fused)
+            return CausalLMOutput(loss=loss, logits=logits[..., : s.vocab_size] if logits is not None else None)
         h = m.hidden_state(input_ids, attention_mask, L) if inputs_embeds is None else m.hidden_state_from_embeds(inputs_embeds, attention_mask, L)
         B, T, H = h.shape
         dt = m.dtype
@@ -1008,8 +1035,8 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
                 protein_input_ids=None, protein_attention_mask=None, protein_position_ids=None, protein_head_mask=None,
                 protein_inputs_embeds=None, use_cache=None, output_attentions=None, output_hidden_states=None,
                 return_dict=None, return_encoder_outputs: bool = False, return_adapter_outputs: bool = False,
-                return_decoder_inputs: bool = False, cache_position=None, loss_weights=None):
-        """Reference :108-215.  position_ids (packed rows) and loss_weights reach LlamaDecoder.forward's loss path (see there)."""
+                return_decoder_inputs: bool = False, cache_position=None, loss_weights=None, num_targets=None):
+        """Reference :108-215.  position_ids (packed rows), loss_weights and num_targets reach LlamaDecoder.forward's loss path (see there)."""
         if protein_position_ids is not None or protein_head_mask is not None or protein_inputs_embeds is not None:
             raise NotImplementedError("protein_position_ids / protein_head_mask / protein_inputs_embeds are not supported")
         enc_lora = getattr(self.esm_encoder, "lora", None)
@@ -1040,7 +1067,7 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
         return self.llama_decoder.forward(input_ids=None, attention_mask=attention_mask, position_ids=position_ids,
                                           past_key_values=past_key_values, inputs_embeds=inputs_embeds, labels=labels,
                                           use_cache=use_cache, output_attentions=output_attentions, return_dict=return_dict,
-                                          cache_position=cache_position, loss_weights=loss_weights)                   # :204-215
+                                          cache_position=cache_position, loss_weights=loss_weights, num_targets=num_targets)   # :204-215
 
     def generate(self, inputs: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, protein_input_ids: Optional[torch.Tensor] = None,
                  protein_attention_mask: Optional[torch.Tensor] = None, protein_inputs_embeds: Optional[torch.Tensor] = None, **kwargs):
@@ -1077,6 +1104,11 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
             if not n.startswith("lora."):
                 q.requires_grad_(False)
         return self.llama_decoder.lora if dec else self.esm_encoder.lora
+
+    def fused_lm_loss(self, enabled: bool = True, chunk_rows: int = 1024):
+        """`llama_decoder.fused_lm_loss(...)`: the stage-2 LM loss over the target rows only; `forward(labels=...)` then returns no logits."""
+        self.llama_decoder.fused_lm_loss(enabled, chunk_rows)
+        return self
 
     def gradient_checkpointing_enable(self, gradient_checkpointing_kwargs=None):
         """Reference :253-261, which forwards the request to both towers (`transformers.Trainer(gradient_checkpointing=True)` passes

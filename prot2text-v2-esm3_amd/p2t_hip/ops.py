@@ -247,6 +247,48 @@ def cross_entropy_shifted_backward(logits: torch.Tensor, labels: torch.Tensor, V
     return d_logits
 
 
+def lm_target_rows(labels: torch.Tensor, V: int, cap: int, ignore_index: int = -100, size: int | None = None):
+    """The flat rows b T + t whose labels[b, t+1] is a counted target (p2t_lm_target_rows) -> (rows int32 [size], targets int32
+    [size], count int32 [2] = {n, n > cap}), all on the device, nothing read back.  The first min(n, cap) entries are listed, every
+    other entry up to `size` (default cap; the buffers may be longer than the capacity the count is held against) is -1."""
+    _chk(labels.dim() == 2 and labels.dtype == torch.int64 and labels.is_contiguous(), "lm_target_rows: labels int64 [B, T] contiguous")
+    size = int(cap) if size is None else int(size)
+    _chk(0 < cap <= size, "lm_target_rows: need 0 < cap <= size")
+    B, T = labels.shape
+    rows = torch.full((size,), -1, dtype=torch.int32, device=labels.device)
+    targets = torch.full((size,), -1, dtype=torch.int32, device=labels.device)
+    count = torch.empty((2,), dtype=torch.int32, device=labels.device)
+    call("p2t_lm_target_rows", ptr(labels), B, T, int(V), int(ignore_index), int(cap), ptr(rows), ptr(targets), ptr(count), stream())
+    return rows, targets, count
+
+
+def lm_loss_grad_rows(logits: torch.Tensor, V: int, rows: torch.Tensor, targets: torch.Tensor, count: torch.Tensor, row_loss: torch.Tensor,
+                      first: int = 0, weights: torch.Tensor | None = None, with_grad: bool = True) -> None:
+    """One chunk of logits [R, ld] in place (p2t_lm_loss_grad_rows): row r is entry first + r of the list; row_loss[first + r] =
+    logsumexp - target logit, and (with_grad) the row becomes (softmax - onehot) * s_r, s_r = 1 / count[0] or weights[row + 1]."""
+    _chk(logits.dim() == 2 and logits.stride(1) == 1, "lm_loss_grad_rows: logits [R, ld] row-major")
+    _chk(all(t.dtype == torch.int32 and t.is_contiguous() for t in (rows, targets, count)) and count.numel() >= 2
+         and rows.numel() == targets.numel(), "lm_loss_grad_rows: rows / targets int32 [cap], count int32 [2]")
+    _chk(row_loss.dtype == torch.float32 and row_loss.is_contiguous() and row_loss.numel() >= rows.numel(), "lm_loss_grad_rows: row_loss f32 [cap]")
+    if weights is not None:
+        _chk(weights.dtype == torch.float32 and weights.is_contiguous(), "lm_loss_grad_rows: weights f32 [B, T] contiguous")
+    call("p2t_lm_loss_grad_rows", ptr(logits), logits.stride(0), dt_of(logits), logits.shape[0], int(V), ptr(rows), ptr(targets), ptr(count),
+         int(first), rows.numel(), ptr(weights), weights.numel() if weights is not None else 0, ptr(row_loss), int(bool(with_grad)), stream())
+
+
+def lm_loss_reduce(row_loss: torch.Tensor, rows: torch.Tensor, count: torch.Tensor, weights: torch.Tensor | None = None) -> torch.Tensor:
+    """loss f32 [1] of the listed rows (p2t_lm_loss_reduce): the token mean, or the weighted sum; NaN without a target or on overflow."""
+    _chk(row_loss.dtype == torch.float32 and row_loss.is_contiguous() and rows.dtype == torch.int32 and rows.is_contiguous()
+         and row_loss.numel() >= rows.numel(), "lm_loss_reduce: row_loss f32 [cap], rows int32 [cap]")
+    _chk(count.dtype == torch.int32 and count.numel() >= 2, "lm_loss_reduce: count int32 [2]")
+    if weights is not None:
+        _chk(weights.dtype == torch.float32 and weights.is_contiguous(), "lm_loss_reduce: weights f32 [B, T] contiguous")
+    loss = torch.empty((1,), dtype=torch.float32, device=row_loss.device)
+    call("p2t_lm_loss_reduce", ptr(row_loss), ptr(rows), ptr(count), rows.numel(), ptr(weights), weights.numel() if weights is not None else 0,
+         ptr(loss), stream())
+    return loss
+
+
 def gemm_fix_workspace(device) -> torch.Tensor:
     """Zeroed split-K fix-up workspace for gemm_nt(fix_ws=..., fix_epoch=1, 2, ...)."""
     return torch.zeros((call("p2t_gemm_fix_workspace_bytes"),), dtype=torch.uint8, device=device)

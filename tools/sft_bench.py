@@ -2,7 +2,11 @@
 scatter -> 32-layer Llama-3.1-8B -> LM head -> shifted CE, once forward only and once as the training step `loss.backward()`
 (frozen towers, adapter trainable: training forward with the activation tape + the dX chain of csrc/llama_train.hip + adapter
 backward), with a per-kernel-family breakdown of the backward from the torch profiler-free HIP-event brackets below.
-python tools/sft_bench.py [B] [lora] [trainer] [encoder] [packed] [checkpoint] > sft_bench.log
+python tools/sft_bench.py [B] [lora] [trainer] [encoder] [packed] [checkpoint] [fused] [targets=F] > sft_bench.log
+`fused`: every training leg once more with `model.fused_lm_loss()` (p2t_hip/lm_head.py: the LM loss over the target rows only), the
+modes alternating with the unfused ones in the same process: ms per step, peak memory and the number of target rows.
+`targets=F`: the fraction of the T decoder positions of every sample whose label is supervised (the tail of the row; default
+128 / T ~ 0.105, the description of the synthetic sample; 1.0 supervises every position).
 `checkpoint` (with `lora` / `encoder`): the same step again under gradient_checkpointing_enable() (per-layer recompute, dA / dB by
 p2t_lora_wgrad), the two modes alternating in one process: ms per step, `last_tape_bytes` and peak memory of each.
 `encoder`: InstructTrainer with LoRA r = 16 on the decoder's seven projections AND ESM2's six linears of every layer
@@ -42,7 +46,12 @@ def main():
     ids = rs.randint(0, 128000, size=(B, T)).astype(np.int64)
     ids[:, 16:16 + Tp] = ph                                         # chat template: system text, <protein placeholders>, question, answer
     labels = ids.copy()
-    labels[:, :Tp + n_prompt] = -100
+    frac = next((float(a.split("=", 1)[1]) for a in sys.argv if a.startswith("targets=")), None)
+    n_sup = n_desc if frac is None else max(1, min(T, int(round(frac * T))))
+    labels[:, :T - n_sup] = -100
+    labels[labels == ph] = 0                                       # (a supervised placeholder position: any real token id)
+    n_targets = int((labels[:, 1:] != -100).sum())
+    fused_modes = (False, True) if "fused" in sys.argv else (False,)
     pid, pmask = synth.protein_batch(5, B, Tp)
     t = lambda a: torch.from_numpy(a).to(dev)
     kw = dict(input_ids=t(ids), attention_mask=torch.ones((B, T), dtype=torch.int64, device=dev), labels=t(labels),
@@ -72,6 +81,22 @@ def main():
         o = model(**kw)
         o.loss.backward()
         return o
+    for rnd in range(2 if len(fused_modes) > 1 else 0):            # frozen step, unfused / fused alternating
+        for fz in fused_modes:
+            model.fused_lm_loss(fz)
+            step()
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            t0 = time.perf_counter()
+            for _ in range(2):
+                of = step()
+            torch.cuda.synchronize()
+            print(f"sft frozen train step cfg3 (fused LM loss {'on' if fz else 'off'}, round {rnd}): B={B}, {n_targets} target rows of {B * T}: "
+                  f"{(time.perf_counter() - t0) / 2 * 1e3:.1f} ms/batch; loss {float(of.loss):.4f}; |grad fc2.weight| "
+                  f"{float(model.adapter.fc2.weight.grad.float().norm()):.3e}; peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB", flush=True)
+            del of
+    model.fused_lm_loss(False)
     step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -85,7 +110,7 @@ def main():
     print(f"sft train step cfg3: B={B}: {dt_train * 1e3:.1f} ms/batch = {B / dt_train:.2f} samples/s, {(f + f_bwd) * B / dt_train / 1e12:.0f} TFLOP/s algorithmic "
           f"(forward {f / 1e12:.2f} + backward {f_bwd / 1e12:.2f} TF/sample); backward alone ~{(dt_train - dt) * 1e3:.1f} ms; loss {float(o2.loss):.4f}, "
           f"|grad fc2.weight| {gn:.3e}", flush=True)
-    print(f"sft forward cfg3: B={B}, {Tp} residues, {T} decoder tokens ({n_desc} supervised): {dt * 1e3:.1f} ms/batch = {B / dt:.2f} samples/s, "
+    print(f"sft forward cfg3: B={B}, {Tp} residues, {T} decoder tokens ({n_sup} supervised): {dt * 1e3:.1f} ms/batch = {B / dt:.2f} samples/s, "
           f"{B * T / dt:.0f} decoder tokens/s, {f * B / dt / 1e12:.0f} TFLOP/s algorithmic ({f / 1e12:.2f} TF/sample: ESM {f_esm / 1e12:.2f}, "
           f"decoder + LM head {f_llama / 1e12:.2f}); loss {float(out.loss):.4f}", flush=True)
     if "lora" in sys.argv:
@@ -103,9 +128,10 @@ def main():
             o.loss.backward()
             return o
         ga_n, n_l = None, sum(q.numel() for q in lora.parameters())
-        for rnd in range(2 if "checkpoint" in sys.argv else 1):          # off, on, off, on: the modes alternate
-            for on in ((False, True) if "checkpoint" in sys.argv else (False,)):
+        for rnd in range(2 if ("checkpoint" in sys.argv or "fused" in sys.argv) else 1):      # the modes alternate
+            for on, fz in [(on, fz) for on in ((False, True) if "checkpoint" in sys.argv else (False,)) for fz in fused_modes]:
                 model.gradient_checkpointing_enable() if on else model.gradient_checkpointing_disable()
+                model.fused_lm_loss(fz)
                 o3 = lstep()
                 del o3
                 torch.cuda.synchronize()
@@ -117,7 +143,8 @@ def main():
                 torch.cuda.synchronize()
                 dt_l = (time.perf_counter() - t0) / 2
                 ga = [q.grad for q in lora.parameters() if q.grad is not None]
-                print(f"sft LoRA train step cfg3 (checkpointing {'on' if on else 'off'}, round {rnd}): B={B}, r=16 on {len(ga)} of "
+                print(f"sft LoRA train step cfg3 (checkpointing {'on' if on else 'off'}, fused LM loss {'on' if fz else 'off'}, {n_targets} target rows "
+                      f"of {B * T}, round {rnd}): B={B}, r=16 on {len(ga)} of "
                       f"{len(list(lora.parameters()))} matrices with a gradient ({n_l / 1e6:.1f} M LoRA parameters): "
                       f"{dt_l * 1e3:.1f} ms/batch = {B / dt_l:.2f} samples/s; loss {float(o3.loss):.4f}; |grad| of the first B matrix "
                       f"{float([q.grad for n, q in lora.named_parameters() if n.endswith('B')][0].float().norm()):.3e}; "
@@ -125,6 +152,7 @@ def main():
                       flush=True)
                 del o3
         model.gradient_checkpointing_disable()
+        model.fused_lm_loss(False)
     if "trainer" in sys.argv:
         trainer_leg(model, kw, B)
     if "encoder" in sys.argv:
