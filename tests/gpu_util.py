@@ -74,6 +74,15 @@ def _check(got, ref, dtype, rtol=1e-6, atol=1e-30, what=""):
     assert not bad.any(), f"{what}: {int(bad.sum())} elements off, worst {float(err.max()):.3e} at ref {float(ref.ravel()[np.argmax(err)]):.3e}"
 
 
+def sample_rows(M, tile=256, offsets=(0, 15, 16, 63, 64, 127, 128, 200, 255), extra=7, seed=2024):
+    """Rows of an [M, N] GEMM output to check element by element when a host product of the whole is too slow: from every `tile`-row
+    tile its first and last row, both sides of each wave's 64-row share (the eight-wave kernels: 128-row) and of the 128-row half, and
+    `extra` rows drawn by a seeded generator -> sorted unique int64 array."""
+    rows = {t + o for t in range(0, M, tile) for o in offsets if t + o < M}
+    rows |= set(np.random.default_rng(seed).integers(0, M, extra).tolist())
+    return np.array(sorted(rows), dtype=np.int64)
+
+
 def _q(a, dtype):
     """The values a tensor of `dtype` holds for a (bf16: rounded), as fp64."""
     t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dtype)

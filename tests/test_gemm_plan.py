@@ -2,11 +2,14 @@
 split-K / 128-row-half tail tiles) that p2t_gemm_nt / p2t_gemm_nt_fp8 would launch, from pure host code.  The rows below pin the
 forms on 256 CUs with the towers' full split-K fix-up workspace: every GEMM of a cfg3 step (batch 16 and 64), bf16 under the
 default policy and under policy 9 (no four-wave kernels), fp8 at tile 0, and each forced lab policy on the shapes of
-lab_forms_cases.py::test_gemm_mfma_splitk_tail.  The lab library is loaded in a child process, so this process never maps it."""
+lab_forms_cases.py::test_gemm_mfma_splitk_tail, and every case of tests/test_gpu_gemm_forms.py (gemm_forms_cases.py).  The lab
+library is loaded in a child process, so this process never maps it."""
 import json
 import os
 import subprocess
 import sys
+
+from gemm_forms_cases import CASES as FORMS_CASES, case_id
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LAB = os.path.join(ROOT, "tools", "build", "libp2t_lab.so")
@@ -109,3 +112,19 @@ def test_plan_without_fixup_workspace():
                   (BF16, 16384, 2560, 10240, 2560, 10240, 10240, RESID, F32, 9, CUS, 0),
                   (BF16, 16384, 2560, 10240, 2560, 10240, 10240, RESID, F32, 0, CUS, 0)])
     assert got == [("tile128", 256, 256, 0, 0), ("persist", 256, 512, 128, 1), ("w4_persist", 256, 640, 0, 0)]
+
+
+def test_gemm_forms_case_plans():
+    """Every (shape, epilogue, out dtype) of tests/test_gpu_gemm_forms.py plans to the form its case names, under the default policy and
+    under policy 9: a policy change that moves a shape off its form fails here instead of hollowing out the GPU test."""
+    queries, expect = [], []
+    for c in FORMS_CASES:
+        for policy, row in ((0, c.p0), (9, c.p9)):
+            queries.append((BF16, c.M, c.N, c.K, c.N, c.K, c.K, c.code, c.out, policy, CUS, FIX_BYTES))
+            expect.append((case_id(c), policy, row))
+        assert c.p0[0] == {"w4_persist_pairs": "w4_persist"}.get(c.form, c.form), c
+    got = _plans(queries)
+    assert got == [e[2] for e in expect], [(e[:2], e[2], g) for e, g in zip(expect, got) if e[2] != g]
+    # every four-wave form, with and without in-stream pairs and with a partial round of whole tiles, is in the table
+    assert {(c.p0[0], c.p0[3] > 0, c.p0[2] % CUS != 0) for c in FORMS_CASES} >= {("w4_persist", False, False), ("w4_persist", False, True),
+                                                                                ("w4_persist", True, False), ("w4_tile", False, True), ("w4_pairs", True, False)}

@@ -10,10 +10,10 @@ import torch
 
 from oracle import p2t_oracle as O
 from gpu_util import bf16r, dev, maxabs, observe, rel, rnd, to_dev, to_np
+from helpers import (EPI_GELU, EPI_GELU_BWD, EPI_RESID, EPI_STORE, EPI_STORE_F32, EPI_SWIGLU,  # noqa: F401
+                     gemm_ref as _gemm_ref, pack_d128 as _pack_d128, qkv_rope_ref)
 
 pytestmark = pytest.mark.gpu
-
-EPI_STORE, EPI_GELU, EPI_RESID, EPI_SWIGLU, EPI_STORE_F32, EPI_GELU_BWD = range(6)
 
 
 @pytest.fixture(scope="module")
@@ -58,24 +58,6 @@ def test_cast_transpose(ops):
     assert np.array_equal(got[:, :130], a.T) and not got[:, 130:].any()
     tb = ops.transpose(to_dev(a, torch.bfloat16))
     assert np.array_equal(to_np(tb)[:, :130], bf16r(a).T)
-
-
-def _gemm_ref(a, w, bias, epi, resid=None, z=None):
-    acc = a.astype(np.float32) @ w.astype(np.float32).T
-    if epi == EPI_SWIGLU:
-        F = w.shape[0] // 2
-        v = acc.reshape(acc.shape[0], F // 32, 2, 32)
-        g, u = v[:, :, 0, :].reshape(-1, F), v[:, :, 1, :].reshape(-1, F)
-        return (g / (1 + np.exp(-g))) * u
-    if bias is not None:
-        acc = acc + bias
-    if epi == EPI_GELU:
-        return O.gelu_erf(acc)
-    if epi == EPI_RESID:
-        return resid + acc
-    if epi == EPI_GELU_BWD:
-        return acc * O.gelu_erf_grad(z)
-    return acc
 
 
 @pytest.mark.parametrize("epi", [EPI_STORE, EPI_GELU, EPI_RESID, EPI_SWIGLU, EPI_STORE_F32, EPI_GELU_BWD])
@@ -148,12 +130,6 @@ def test_gemm_mfma_matches_fma_kernel(ops):
     assert rel(r1, r0) < 2e-6
 
 
-def _pack_d128(w, heads):
-    """[heads * 128, K] -> the per-head row order 0..31, 64..95, 32..63, 96..127 of include/p2t_hip.h (p2t_llama_layer)."""
-    K = w.shape[1]
-    return np.ascontiguousarray(w.reshape(heads, 2, 2, 32, K).transpose(0, 2, 1, 3, 4).reshape(heads * 128, K))
-
-
 QKV_ROPE_CASES = [  # name, B, T, K, nh, nkv, d, bias, q_scale, rope
     ("esm_d64_bias_qscale", 2, 100, 192, 3, 3, 64, True, 64 ** -0.5, "default"),          # per-tile kernel, edge tiles in M and N
     ("esm_d64_edge_n", 4, 512, 640, 10, 10, 64, True, 64 ** -0.5, "default"),             # 8 x 7.5 tiles: edge tiles in N only
@@ -180,12 +156,7 @@ def test_qkv_rope_epilogue_vs_reference_arithmetic(ops, case, path):
     acc = a @ w.T
     if bias is not None:
         acc = acc + bias
-    x = acc.reshape(B, T, nh + 2 * nkv, d).transpose(0, 2, 1, 3)
-    cos, sin = O.rope_cos_sin(inv, np.arange(T))
-    q = x[:, :nh] * np.float32(q_scale)
-    k, v = x[:, nh:nh + nkv], x[:, nh + nkv:]
-    q = q * cos + O.rotate_half(q) * sin
-    k = k * cos + O.rotate_half(k) * sin
+    q, k, v = (x.reshape(B, T, -1, d).transpose(0, 2, 1, 3) for x in qkv_rope_ref(acc, np.tile(np.arange(T), B), nh, nkv, d, q_scale, inv))
     wd = np.concatenate([_pack_d128(w[:nh * d], nh), _pack_d128(w[nh * d:(nh + nkv) * d], nkv), _pack_d128(w[(nh + nkv) * d:], nkv)]) if d == 128 else w
     bd = bias
     if d == 128 and bias is not None:
