@@ -667,6 +667,9 @@ extern "C" int p2t_llama_decode_step(const p2t_llama_config* c, const p2t_llama_
     const float q_fold = l2s ? scale * kLog2e : 1.0f, c_exp = l2s ? 1.0f : scale * kLog2e;
     P2T_CHECK_HIP(hipMemcpyAsync(b.x, x_in, sizeof(float) * (size_t)BB * H, hipMemcpyDeviceToDevice, s));
     P2T_CHECK_HIP(hipMemsetAsync(b.ao, 0, dtype_size(dt) * (size_t)BB * QO, s));
+    // the SwiGLU epilogues write columns [0, F) of act and the down projection reads K = Fp of them against zero weight columns: what
+    // the caller's workspace held in [F, Fp) must not reach it (NaN x 0)
+    if (Fp > F) P2T_CHECK_HIP(hipMemsetAsync(b.act, 0, dtype_size(dt) * (size_t)BB * Fp, s));
     const int64_t M = BB;
     // the step's projections: the weight-streaming kernel (gemm_skinny.hip) for bf16 models, the general GEMM otherwise
     // `pre`: the pre-shuffled stream copy of the same weight (p2t_preshuffle_w), when the caller built one

@@ -104,24 +104,36 @@ def esm_embed_f32(ids, mask, table, mask_id: int, token_dropout: bool):
 
 
 # ---- attention --------------------------------------------------------------------------------------------------------------
-def attention_fwd_bwd64(q, k, v, d_o, mask, causal: bool, c_s: float, o_stored=None):
+def attention_fwd_bwd64(q, k, v, d_o, mask, causal: bool, c_s: float, o_stored=None, docs=None, bounds: bool = False):
     """Textbook attention in fp64 on stored operands, one (batch, head) at a time (B * heads * T^2 doubles never exist at once).
     q [B, nh, T, d], k / v [B, nkv, T, d], d_o [B, nh, T, d] (or None: forward only), mask [B, T] (1 = valid key), logits = c_s q k^T.
-    o_stored [B, nh, T, d]: the output D = rowsum(dO o O) is taken from (the kernel's stored one, as torch does); None: the fp64 one.
-    -> dict(lse [B, nh, T] (+inf where a row sees no key), o, rows (bool [B, nh, T]: the row sees a key), dq, dk, dv)."""
+    o_stored [B, nh, T, d]: the output D = rowsum(dO o O) is taken from (the kernel's stored one, as torch does); None: the fp64 one;
+    a callable: applied to the fp64 output of each (batch, head), e.g. its rounding to the stored dtype.
+    docs int [B, T] (or None): the start of each token's document; key j is visible to query i iff docs[b, i] <= j <= i and the mask allows it.
+    -> dict(lse [B, nh, T] (+inf where a row sees no key), o, rows (bool [B, nh, T]: the row sees a key), dq, dk, dv).
+    bounds: also n_visible [B, nh, T], p_diag [B, nh, T] (P[i, i]) and the per-element terms a rounding bound is built from:
+    A = P |v| (o); dq_abs = c_s |dS| |k|, dk_abs = c_s |dS|^T |q|, dv_abs = P^T |dO|; and with F = P o (|dO| |v|^T + rowsum(|dO| o |O|)) (what an
+    fp32 evaluation of dO v^T - D is rounded against) dq_F = c_s F |k|, dk_F = c_s F^T |q| (dv does not pass through dS: no F term)."""
     q, k, v = (np.asarray(t, dtype=np.float64) for t in (q, k, v))
     B, nh, T, d = q.shape
     nkv = k.shape[1]
     rep = nh // nkv
     out = dict(lse=np.full((B, nh, T), np.inf), o=np.zeros((B, nh, T, d)), rows=np.zeros((B, nh, T), bool))
+    if bounds:
+        out.update(A=np.zeros((B, nh, T, d)), n_visible=np.zeros((B, nh, T), np.int64), p_diag=np.zeros((B, nh, T)))
     if d_o is not None:
         d_o = np.asarray(d_o, dtype=np.float64)
         out.update(dq=np.zeros((B, nh, T, d)), dk=np.zeros((B, nkv, T, d)), dv=np.zeros((B, nkv, T, d)))
-    tri = np.tril(np.ones((T, T), bool)) if causal else None
+        if bounds:
+            out.update(dq_abs=np.zeros((B, nh, T, d)), dk_abs=np.zeros((B, nkv, T, d)), dv_abs=np.zeros((B, nkv, T, d)),
+                       dq_F=np.zeros((B, nh, T, d)), dk_F=np.zeros((B, nkv, T, d)))
+    tri = np.tril(np.ones((T, T), bool)) if causal or docs is not None else None
     for b in range(B):
         allowed = np.broadcast_to(np.asarray(mask[b] != 0)[None, :], (T, T))
-        if causal:
+        if causal or docs is not None:
             allowed = allowed & tri
+        if docs is not None:
+            allowed = allowed & (np.arange(T)[None, :] >= np.asarray(docs[b])[:, None])
         for h in range(nh):
             kk, vv = k[b, h // rep], v[b, h // rep]
             S = np.where(allowed, (q[b, h] @ kk.T) * c_s, -np.inf)
@@ -135,12 +147,25 @@ def attention_fwd_bwd64(q, k, v, d_o, mask, causal: bool, c_s: float, o_stored=N
             out["lse"][b, h] = np.where(seen, m[:, 0] + np.log(np.where(l > 0, l, 1.0))[:, 0], np.inf)
             O = P @ vv
             out["o"][b, h] = O
+            if bounds:
+                out["A"][b, h] = P @ np.abs(vv)
+                out["n_visible"][b, h] = allowed.sum(-1)
+                out["p_diag"][b, h] = np.diagonal(P)
             if d_o is None:
                 continue
             dO = d_o[b, h]
-            D = (dO * (O if o_stored is None else np.asarray(o_stored[b, h], dtype=np.float64))).sum(-1, keepdims=True)
+            Ost = O if o_stored is None else np.asarray(o_stored(O) if callable(o_stored) else o_stored[b, h], dtype=np.float64)
+            D = (dO * Ost).sum(-1, keepdims=True)
             dS = P * (dO @ vv.T - D)
             out["dq"][b, h] = (dS @ kk) * c_s
             out["dk"][b, h // rep] += (dS.T @ q[b, h]) * c_s
             out["dv"][b, h // rep] += P.T @ dO
+            if bounds:
+                aS, aq, ak, adO = np.abs(dS), np.abs(q[b, h]), np.abs(kk), np.abs(dO)
+                F = P * (adO @ np.abs(vv).T + (adO * np.abs(Ost)).sum(-1, keepdims=True))
+                out["dq_abs"][b, h] = (aS @ ak) * c_s
+                out["dk_abs"][b, h // rep] += (aS.T @ aq) * c_s
+                out["dv_abs"][b, h // rep] += P.T @ adO
+                out["dq_F"][b, h] = (F @ ak) * c_s
+                out["dk_F"][b, h // rep] += (F.T @ aq) * c_s
     return out

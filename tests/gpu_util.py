@@ -89,6 +89,66 @@ def _q(a, dtype):
     return t.double().numpy()
 
 
+# ---- attention, row by row (tests/test_gpu_attention_rows.py, tests/test_gpu_generate.py; the terms come from
+# encoder_ops_reference.attention_fwd_bwd64(bounds=True), the derivation is in tests/tolerance_changes.md)
+U_P = 2.0 ** -7 + 2.0 ** -20                             # each probability rounded to bf16 once (unit roundoff 2^-8) in the numerator and, where the row
+                                                         # sums run over the rounded P, once in the denominator; 2^-20: fp32 accumulation over <= 1100 keys
+R32 = 2.81e-5                                            # the fp32-softmax kernels: 4 x the worst err / A of attention_reference.restate_forward in fp32
+                                                         # against fp64 over the cases (tests/test_attention_reference_host.py re-measures it)
+
+
+def attn_o_bound(ref, p_bf16, out_bf16, witness=False):
+    """|o - ref| per element: one bf16 step at |ref| for a bf16 output, plus U_P * A (P rounded to bf16) or R32 * A (fp32 softmax), A = P |v|.
+    witness (q = 0: every visible p is exactly 1): the rounding of the quotient alone -- one bf16 step, fp32: 4e-7 relative."""
+    step = _ulp_bf16(ref["o"]) if out_bf16 else 0.0
+    if witness:
+        return step if out_bf16 else 4e-7 * np.abs(ref["o"])
+    return step + (U_P if p_bf16 else R32) * ref["A"]
+
+
+def attn_lse_bound(ref, sum_rounded, witness=False):
+    """|lse - ref| in natural-log units where the row sees a key (+inf, exactly, where it sees none: check_rows)."""
+    lse = np.where(np.isfinite(ref["lse"]), ref["lse"], 0.0)
+    if witness:
+        return np.full(lse.shape, 2e-6)
+    return np.full(lse.shape, 2.0 ** -7 + 1e-5) if sum_rounded else 1e-5 + 2e-6 * np.abs(lse)
+
+
+def attn_grad_bounds(ref, mfma, d):
+    """dq, dk, dv (fp32 outputs): the bf16 MFMA kernels round P and dS to bf16, 2^-7 * (the abs-sum term); the exact kernels R32 * (that term);
+    both evaluate dO v^T - D in fp32 over 2 d + 2 terms: (2 d + 2) 2^-23 * (the F term; dv does not pass through dS)."""
+    c, f = (2.0 ** -7 if mfma else R32), (2 * d + 2) * 2.0 ** -23
+    return dict(dq=c * ref["dq_abs"] + f * ref["dq_F"], dk=c * ref["dk_abs"] + f * ref["dk_F"], dv=c * ref["dv_abs"])
+
+
+def check_rows(name, parts, record=True):
+    """Every element of every query row (padded rows included) of each (label, got, ref, bound) against its own bound: |got - ref| <= bound,
+    +inf exactly where ref is +inf, finite everywhere else.  The failure names the worst (b, h, row[, column]), the count off and the
+    ratio; the worst err / bound over the parts is recorded as `name` (observe, cap 1).  -> that ratio."""
+    worst, msgs = 0.0, []
+    for label, got, ref, bound in parts:
+        got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+        bound = np.broadcast_to(np.asarray(bound, dtype=np.float64), ref.shape)
+        assert got.shape == ref.shape, (label, got.shape, ref.shape)
+        inf = np.isposinf(ref)
+        bad = np.where(inf, got != ref, ~np.isfinite(got))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            err = np.where(inf | bad, 0.0, np.abs(got - ref))
+            ratio = np.where(err <= bound, np.where(bound > 0, err / bound, 0.0), np.where(bound > 0, err / bound, np.inf))
+        ratio = np.where(bad, np.inf, ratio)
+        off = ratio > 1.0
+        at = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+        worst = max(worst, float(ratio[at]))
+        if off.any():
+            msgs.append(f"{label}: {int(off.sum())} of {off.size} elements off, worst err / bound {float(ratio[at]):.3g} at (b, h, row[, col]) = "
+                        f"{tuple(int(i) for i in at)}: got {got[at]!r}, ref {ref[at]!r}, bound {float(bound[at]):.3e}; "
+                        f"{int(off.reshape(off.shape[0], off.shape[1], off.shape[2], -1).any(-1).sum())} rows touched")
+    assert not msgs, f"{name}: " + " | ".join(msgs)
+    if record:
+        observe(name, worst, 1.0, what="ratio")
+    return worst
+
+
 _OBS_PATH = None
 _TOL_TABLE = None
 

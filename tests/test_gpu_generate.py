@@ -18,7 +18,7 @@ import pytest
 import torch
 
 from oracle import p2t_oracle as O
-from gpu_util import build_model, dev, observe, rel, rnd, to_dev, to_np
+from gpu_util import attn_o_bound, build_model, check_rows, dev, observe, rel, rnd, to_dev, to_np
 from helpers import model_weights
 from p2t_hip import specs
 
@@ -73,11 +73,12 @@ def test_compact_rows_vs_numpy():
 
 
 def _attn_ref(q, kp, vp, kg, vg, lens, step, group, scale):
-    """q [BB, nh, d]; prompt keys/values [B0, nkv, Tp, d], generated [BB, nkv, G, d] -> [BB, nh, d]"""
+    """q [BB, nh, d]; prompt keys/values [B0, nkv, Tp, d], generated [BB, nkv, G, d] -> o [BB, nh, d] and A = P |v| (the term of the
+    row check's bound, gpu_util.attn_o_bound), in the operands' precision (fp64 operands: the fp64 reference)."""
     BB, nh, d = q.shape
     nkv = kp.shape[1]
     G = nh // nkv
-    out = np.zeros((BB, nh, d), dtype=np.float32)
+    out, A = np.zeros((BB, nh, d), dtype=q.dtype), np.zeros((BB, nh, d), dtype=q.dtype)
     for bb in range(BB):
         b0 = bb // group
         for h in range(nh):
@@ -86,8 +87,8 @@ def _attn_ref(q, kp, vp, kg, vg, lens, step, group, scale):
             v = np.concatenate([vp[b0, kv, :lens[b0]], vg[bb, kv, :step + 1]], 0)
             s = (k @ q[bb, h]) * scale
             p = np.exp(s - s.max())
-            out[bb, h] = (p / p.sum()) @ v
-    return out
+            out[bb, h], A[bb, h] = (p / p.sum()) @ v, (p / p.sum()) @ np.abs(v)
+    return out, A
 
 
 @pytest.mark.parametrize("dt,use_mfma", [(torch.float32, 0), (torch.bfloat16, 0), (torch.bfloat16, 1)])
@@ -95,7 +96,10 @@ def _attn_ref(q, kp, vp, kg, vg, lens, step, group, scale):
                                    (128, 2, 2, 1, 5, 63), (64, 16, 1, 1, 200, 9)])
 def test_decode_attention_vs_numpy(dt, use_mfma, shape):
     """p2t_attention_decode (the decode step's attention on its own) against softmax(q k^T) v over the concatenated valid keys; NaN
-    behind every valid prefix proves nothing outside it is read into a result."""
+    behind every valid prefix proves nothing outside it is read into a result.  Beside the whole-tensor norm, every element of every row is
+    held to its own bound against fp64 (gpu_util.check_rows: one bf16 step + (2^-7 + 2^-20) P |v| for the bf16 kernels, which round P to
+    bf16; R32 P |v| in fp32), and a witness run (q = 0: every p is exactly 1 / n; v names segment, row, kv head and position of each key)
+    must give the exact quotient to one bf16 step (fp32: 4e-7 relative)."""
     from p2t_hip import _lib, ops
     from p2t_hip.ops import ptr, stream
     d, nh, nkv, group, n0max, step = shape
@@ -107,31 +111,57 @@ def test_decode_attention_vs_numpy(dt, use_mfma, shape):
     rs = np.random.RandomState(d + nh)
     f = lambda *s: (rs.randn(*s) * 0.7).astype(np.float32)
     q, kp, vp, kg, vg = f(BB, nh, d), f(B0, nkv, Tp, d), f(B0, nkv, Tp, d), f(BB, nkv, G, d), f(BB, nkv, G, d)
-    # garbage (NaN) behind the valid prefixes: the kernel must neither read it into a result nor multiply it by zero
-    for b in range(B0):
-        kp[b, :, lens[b]:] = np.nan; vp[b, :, lens[b]:] = np.nan
-    kg[:, :, step + 1:] = np.nan; vg[:, :, step + 1:] = np.nan
     pad = lambda a: np.concatenate([a, np.zeros(a.shape[:-1] + (dp - d,), np.float32)], -1)
     rd = lambda a: to_np(to_dev(a, dt)).astype(np.float32)
-    qd = to_dev(pad(q), dt)
-    kpd, kgd = to_dev(pad(kp), dt), to_dev(pad(kg), dt)
-    vtp, vtg = to_dev(np.ascontiguousarray(pad(vp).transpose(0, 1, 3, 2)), dt), to_dev(np.ascontiguousarray(pad(vg).transpose(0, 1, 3, 2)), dt)
     lens_d, step_d = to_dev(lens), torch.tensor([step], dtype=torch.int32, device=dev())
     scale = d ** -0.5
     l2s = dt == torch.bfloat16
     QO = ops.round_up(nh * d, 64)
-    out = torch.zeros((BB, QO), dtype=dt, device=dev())
-    _lib.call("p2t_attention_decode", ptr(qd), ptr(kpd), ptr(vtp), ptr(kgd), ptr(vtg), ptr(lens_d), ptr(step_d), B0, group, nh, nkv, d, Tp, G,
-              float(scale), int(l2s), ops.dt_of(dt), use_mfma, ptr(out), QO, stream())
-    qq = rd(pad(q))[..., :d]
-    ref = _attn_ref(qq, np.nan_to_num(rd(pad(kp)))[..., :d], np.nan_to_num(rd(pad(vp)))[..., :d], np.nan_to_num(rd(pad(kg)))[..., :d],
-                    np.nan_to_num(rd(pad(vg)))[..., :d], lens, step, group, (np.log(2.0) if l2s else scale))
-    got = to_np(out).astype(np.float32)[:, : nh * d].reshape(BB, nh, d)
-    assert np.isfinite(got).all()
+    bf = dt == torch.bfloat16
+    kind = "f32" if not bf else ("bf16_mfma" if use_mfma else "bf16")
+
+    def run(q, kp, vp, kg, vg):
+        """-> got [BB, nh, d] fp32, the operands as stored (NaN behind the prefixes replaced by 0)."""
+        kp, vp, kg, vg = (a.copy() for a in (kp, vp, kg, vg))
+        # garbage (NaN) behind the valid prefixes: the kernel must neither read it into a result nor multiply it by zero
+        for b in range(B0):
+            kp[b, :, lens[b]:] = np.nan; vp[b, :, lens[b]:] = np.nan
+        kg[:, :, step + 1:] = np.nan; vg[:, :, step + 1:] = np.nan
+        qd = to_dev(pad(q), dt)
+        kpd, kgd = to_dev(pad(kp), dt), to_dev(pad(kg), dt)
+        vtp, vtg = to_dev(np.ascontiguousarray(pad(vp).transpose(0, 1, 3, 2)), dt), to_dev(np.ascontiguousarray(pad(vg).transpose(0, 1, 3, 2)), dt)
+        out = torch.zeros((BB, QO), dtype=dt, device=dev())
+        _lib.call("p2t_attention_decode", ptr(qd), ptr(kpd), ptr(vtp), ptr(kgd), ptr(vtg), ptr(lens_d), ptr(step_d), B0, group, nh, nkv, d, Tp, G,
+                  float(scale), int(l2s), ops.dt_of(dt), use_mfma, ptr(out), QO, stream())
+        stored = [rd(pad(q))[..., :d]] + [np.nan_to_num(rd(pad(a)))[..., :d] for a in (kp, vp, kg, vg)]
+        got = to_np(out).astype(np.float32)[:, : nh * d].reshape(BB, nh, d)
+        assert np.isfinite(got).all()
+        return got, stored
+
+    got, stored = run(q, kp, vp, kg, vg)
+    c_s = np.log(2.0) if l2s else scale
+    ref, _ = _attn_ref(*stored, lens, step, group, c_s)
     if dt == torch.float32:
         assert rel(got, ref) < 3e-6
     else:
         observe(f"decode_attn[d{d},nh{nh},nkv{nkv},g{group},n{n0max},s{step}].bf16{'_mfma' if use_mfma else ''}", rel(got, ref), 1.2e-2)
+    # row by row against fp64 on the same stored operands
+    o64, A64 = _attn_ref(*(a.astype(np.float64) for a in stored), lens, step, group, c_s)
+    r64 = dict(o=o64[:, :, None], A=A64[:, :, None])
+    check_rows(f"attn_rows[decode,{kind},peaked]", [("o", got[:, :, None], r64["o"], attn_o_bound(r64, bf, bf))])
+    # witness: q = 0; key j of the prompt segment of batch row b0 holds 1 + kv + nkv b0 at column j mod c, key j of the generated segment of
+    # beam bb holds 1 + kv + nkv (B0 + bb) at column (7 j + 3) mod c: small integers, exact in bf16
+    c = min(d, 64)
+    wp, wg = np.zeros_like(vp), np.zeros_like(vg)
+    for kv in range(nkv):
+        for b in range(B0):
+            wp[b, kv, np.arange(Tp), np.arange(Tp) % c] = 1 + kv + nkv * b
+        for bb in range(BB):
+            wg[bb, kv, np.arange(G), (7 * np.arange(G) + 3) % c] = 1 + kv + nkv * (B0 + bb)
+    got, stored = run(np.zeros_like(q), kp, wp, kg, wg)
+    o64, A64 = _attn_ref(*(a.astype(np.float64) for a in stored), lens, step, group, c_s)
+    r64 = dict(o=o64[:, :, None], A=A64[:, :, None])
+    check_rows(f"attn_rows[decode,{kind},witness]", [("o", got[:, :, None], r64["o"], attn_o_bound(r64, bf, bf, witness=True))])
 
 
 @pytest.mark.parametrize("shape", [(1, 512, 64), (3, 48, 96), (8, 4096, 4096), (16, 6144, 4096), (17, 1000, 512), (32, 28672, 1024), (40, 4096, 14336),
@@ -310,6 +340,34 @@ def test_bf16_steps_vs_bf16_oracle_and_own_forward(g, case):
         full = to_np(dec(inputs_embeds=row).logits.float())[0]
         n0 = int(valid.sum())
         observe(f"generate[{case}].bf16_cache_vs_full_forward.row{b}", rel(lg[:, b], full[n0 - 1:n0 - 1 + n]), 3e-2)
+
+
+@pytest.mark.parametrize("case,dt,stream_copy", [("d16", torch.bfloat16, True), ("d16", torch.bfloat16, False), ("d128", torch.bfloat16, True),
+                                                 ("d16", torch.float32, False)])
+def test_decode_step_ignores_what_its_workspace_held(g, case, dt, stream_copy):
+    """The decode step's workspace arrives uninitialised (torch.empty): whatever it held must not reach a result.  d16 and d128 have an
+    intermediate size that is no multiple of 64 (160, 288), so the down projection reads 32 pad columns of the SwiGLU buffer per row
+    against zero weight columns; the weight-streaming GEMM's SwiGLU epilogue does not write them, and a NaN left there by an earlier
+    tensor turned that row's logits into NaN (seen as a row of token 0 from test_bf16_steps_vs_bf16_oracle_and_own_forward[d16] once
+    the tests before it had left NaN in freed memory).  Two steps from a workspace of 0xFF bytes (NaN in bf16 and in fp32) must equal,
+    bit for bit, two steps from a zeroed one."""
+    from p2t_hip.generation import DecodeEngine
+    model = _model(g, case, dt)
+    emb, mask = model(input_ids=to_dev(g["input_ids"]), attention_mask=to_dev(g["attention_mask"]), protein_input_ids=to_dev(g["protein_input_ids"]),
+                      protein_attention_mask=to_dev(g["protein_attention_mask"]), return_decoder_inputs=True)
+    eos, pad, V = torch.zeros((0,), dtype=torch.int64, device=dev()), g["meta"]["pad_id"], model.llama_decoder.spec.vocab_size
+    outs = []
+    for fill in (0x00, 0xFF):
+        eng = DecodeEngine(model.llama_decoder, emb.shape[0], 1, emb.shape[1], 8, stream_copy)
+        eng.ws.fill_(fill)
+        eng.greedy_select(eng.prefill(*eng.compact(emb, mask)), eos, pad)
+        for _ in range(2):
+            eng.feed(eng.next_tokens)
+            eng.decode_step()
+            eng.greedy_select(eng.logits, eos, pad)
+        outs.append((eng.logits[:, :V].clone(), eng.out_tokens[:, :3].clone()))
+    assert torch.isfinite(outs[1][0].float()).all()
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
 
 
 def test_sampling_is_seeded_and_respects_the_filters(g):
