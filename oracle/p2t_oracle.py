@@ -69,7 +69,7 @@ def e4m3_round(x: np.ndarray) -> np.ndarray:
 
 def e8m0_of_amax(amax: np.ndarray) -> np.ndarray:
     """Biased E8M0 exponent of a row's power-of-two scale: the smallest 2^e with amax / 2^e <= 448, by the same integer
-    rule on the f32 bits as csrc/quant.hip (e = exponent(amax) - 8 + [mantissa > 0.75]); 127 for an all-zero row."""
+    rule on the f32 bits as csrc/quant_fp8.h (e = exponent(amax) - 8 + [mantissa > 0.75]); 127 for an all-zero row."""
     u = np.ascontiguousarray(amax, dtype=F32).view(np.uint32)
     ea = ((u >> np.uint32(23)) & np.uint32(0xFF)).astype(np.int32) - 127
     e = ea - 8 + ((u & np.uint32(0x7FFFFF)) > np.uint32(0x600000)).astype(np.int32)
@@ -92,7 +92,7 @@ FP8_OPERAND_GROWTH = (1.0 + 2.0 ** -4) ** 2      # e4m3 rounding enlarges an ele
 
 def gelu_bound_scale(h: np.ndarray, w: np.ndarray, b: np.ndarray) -> np.ndarray:
     """E8M0 byte per row of the scale under which gelu(h W^T + b) is stored as e4m3 when the FFN-up GEMM writes fp8 directly
-    (csrc/quant.hip norm_fp8_kernel `bound_scale`, csrc/epilogue.h EpiGeluFp8): |gelu(z)| <= |z| <= ||h_row||_2 max_n ||W_n||_2
+    (csrc/norm.hip norm_fp8_kernel `bound_scale`, csrc/epilogue.h EpiGeluFp8): |gelu(z)| <= |z| <= ||h_row||_2 max_n ||W_n||_2
     + max_n |b_n| (Cauchy-Schwarz), the weight norm inflated by FP8_OPERAND_GROWTH for the rounded operands."""
     bw = F32(np.sqrt((w.astype(F32) ** 2).sum(-1, dtype=F32)).max() * FP8_OPERAND_GROWTH)
     bb = F32(np.abs(b).max())

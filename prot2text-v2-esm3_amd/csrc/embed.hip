@@ -346,3 +346,14 @@ int launch_qkv_post(const void* qkv, int64_t ldq, const float* cs, void* q, void
 }
 
 }  // namespace p2t
+
+using namespace p2t;
+
+// the token-dropout-scaled embedding rows of p2t_esm2_forward, f32: the frozen start of the encoder LoRA step's tape
+extern "C" int p2t_esm2_embed(const int64_t* ids, const int64_t* mask, const void* table, int dtype, const float* emb_scale, int B, int T, int H,
+                              int vocab, int mask_id, int token_dropout, float* x, p2t_stream stream) {
+    P2T_REQUIRE(ids && mask && table && emb_scale && x && B > 0 && T > 0 && H > 0 && H % 4 == 0 && vocab > 0,
+                "p2t_esm2_embed: bad arguments (hidden must be a multiple of 4)");
+    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_esm2_embed: unsupported dtype %d", dtype);
+    return launch_esm_embed(ids, mask, table, dtype, emb_scale, T, H, vocab, mask_id, token_dropout, x, (int64_t)B * T, (hipStream_t)stream);
+}

@@ -18,6 +18,9 @@ int launch_rmsnorm_few_rows(const float* x, int64_t ld_x, const float* w, float 
                             int out_dtype, hipStream_t s);     // decode step: block per row (norm.hip)
 int launch_l2norm(const void* x, int in_dtype, int64_t ld_x, void* y, int out_dtype, int64_t ld_y, float* inv_norm,
                   int64_t rows, int64_t cols, float eps, hipStream_t s);
+// g (+)= dX of RMSNorm with a frozen weight; dy: f32 or bf16 (norm.hip)
+int launch_rmsnorm_bwd(const float* x, int64_t ld_x, const float* w, float eps, const void* dy, int64_t ld_dy, int dy_dtype, float* g,
+                       int64_t ld_g, int64_t rows, int64_t cols, int accumulate, hipStream_t s);
 
 int launch_mask_prepare(const int64_t* ids, const int64_t* mask, int B, int T, int mask_id, int token_dropout,
                         uint8_t* key_mask, int32_t* kv_info, float* emb_scale, hipStream_t s);
@@ -44,14 +47,14 @@ int launch_gemm_simple(const void* A, int64_t lda, const void* W, int64_t ldw, i
 int launch_gemm_mfma(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int N, int K, int n_cover,
                      int out_dtype, int epilogue, const EpiParams& ep, void* fix_ws, size_t fix_bytes, unsigned fix_epoch,
                      hipStream_t s);
-// fp8 path (quant.hip, gemm_fp8.hip)
+// fp8 path (quant.hip, the fp8-writing norms of norm.hip, gemm_fp8.hip)
 int launch_quant_rows(const void* x, int dtype, int64_t ld_x, int64_t rows, int64_t cols, void* q, int64_t ld_q, uint8_t* scale,
                       hipStream_t s);
 int launch_layernorm_fp8(const float* x, int64_t ld_x, const float* w, const float* b, float eps, void* q, int64_t ld_q,
                          uint8_t* scale, int64_t rows, int64_t cols, float bound_w, float bound_b, uint8_t* bound_scale, hipStream_t s);
 int launch_rmsnorm_fp8(const float* x, int64_t ld_x, const float* w, float eps, void* q, int64_t ld_q, uint8_t* scale, int64_t rows,
                        int64_t cols, hipStream_t s);
-// the decode step's forms for a few rows (block per row, one round trip; quant.hip)
+// the decode step's forms for a few rows (block per row, one round trip; quant.hip, norm.hip)
 int launch_quant_rows_few(const void* x, int dtype, int64_t ld_x, int64_t rows, int64_t cols, void* q, int64_t ld_q, uint8_t* scale, hipStream_t s);
 int launch_rmsnorm_fp8_few(const float* x, int64_t ld_x, const float* w, float eps, void* q, int64_t ld_q, uint8_t* scale, int64_t rows, int64_t cols,
                            hipStream_t s);
@@ -202,12 +205,16 @@ int llama_forward_impl(const p2t_llama_config* c, const p2t_llama_weights* w, co
                        const p2t_kv_cache* kv = nullptr, const int32_t* docs = nullptr);
 // generation prefill (llama_decode.hip): layer l's rotated keys / values ([B, kv_heads, T, dp]) -> the prompt segment of the cache
 int llama_kv_store(const p2t_llama_config* c, const p2t_kv_cache* kc, int layer, const void* k, const void* v, int B, int T, hipStream_t s);
+// SwiGLU on the interleaved gate / up pre-activations gu [M, 2F], forward and backward (activations.hip)
 int launch_swiglu_from_gu(const void* gu, int64_t ld_gu, void* act, int64_t ld_act, int64_t M, int64_t F, int dtype, hipStream_t s);
-// dst[m, c] = (Tdst)src[m, c] for c < cols, 0 for cols <= c < ld_dst  (a GEMM operand with its K padding)
+int launch_swiglu_gu_bwd(const void* gu, int64_t ld_gu, const void* d_act, int64_t ld_da, void* d_gu, int64_t ld_dgu, int64_t M, int64_t F, int dtype,
+                         hipStream_t s);
+// (misc.hip) dst[m, c] = (Tdst)src[m, c] for c < cols, 0 for cols <= c < ld_dst  (a GEMM operand with its K padding)
 int launch_cast_rows(const void* src, int src_dtype, int64_t ld_src, void* dst, int dst_dtype, int64_t ld_dst, int64_t rows, int64_t cols, hipStream_t s);
 
-// lm_loss.hip (LM loss over the target rows only: p2t_lm_target_rows / p2t_lm_loss_grad_rows / p2t_lm_loss_reduce) shares nothing between
-// translation units: its three entry points are declared in include/p2t_hip.h alone
+// lm_loss.hip (the shifted cross-entropy over the full logits and over the target rows only, forward and backward) shares its label
+// rule and its row max / sum-exp between its own kernels and nothing between translation units: its seven entry points are
+// declared in include/p2t_hip.h alone
 
 // adapter tail helpers (adapter.hip)
 int launch_adapter_dz2(const void* g2, const void* z2, const float* inv_norm, const float* dy, void* dz2, int64_t ld, int64_t M,

@@ -9,151 +9,13 @@
 //   x2 = x1 + down(silu(gate(h2)) * up(h2)),  h2 = rmsnorm(x1)         -> swiglu_bwd, rmsnorm_bwd
 //   x1 = x  + o(attn(rope(q(h1)), rope(k(h1)), v(h1))), h1 = rmsnorm(x) -> attn_bwd_{dq,dkv}, rope_bwd_pack, rmsnorm_bwd
 // The residual-stream gradient stays fp32 throughout (one buffer, accumulated in place); GEMM operands are `dtype`.
+// This file is the engine and what it alone uses (the exact attention-backward fallback, the rotary backward); the row-wise kernels
+// of the chain live with their forwards: rmsnorm_bwd in norm.hip, swiglu_gu in activations.hip, cast_rows in misc.hip.
 #include "common.h"
 #include "epilogue.h"
 #include "kernels.h"
 
 namespace p2t {
-
-// ---------------------------------------------------------------------------------------------
-// y = x * rsqrt(mean(x^2) + eps) * w   ->   g (+)= r * (w dy) - x r^3 mean(w dy x).  One wave per row, two passes over the
-// row (the second hits L2).  dy: f32 or `dtype`.
-template <typename Tdy>
-__global__ void __launch_bounds__(256) rmsnorm_bwd_kernel(const float* __restrict__ x, int64_t ld_x, const float* __restrict__ w, float eps,
-                                                          const Tdy* __restrict__ dy, int64_t ld_dy, float* __restrict__ g, int64_t ld_g,
-                                                          int64_t rows, int cols, int accumulate) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const float* xr = x + row * ld_x;
-    const Tdy* dr = dy + row * ld_dy;
-    float ss = 0.f, dot = 0.f;
-    for (int c = lane * 4; c < cols; c += 256) {
-        float xv[4], dv[4], wv[4];
-        load4(xr + c, xv); load4(dr + c, dv); load4(w + c, wv);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { ss = fmaf(xv[j], xv[j], ss); dot = fmaf(dv[j] * wv[j], xv[j], dot); }
-    }
-    ss = wave_sum(ss);
-    dot = wave_sum(dot);
-    const float r = rsqrtf(ss / (float)cols + eps);
-    const float k = r * r * r * dot / (float)cols;
-    float* gr = g + row * ld_g;
-    for (int c = lane * 4; c < cols; c += 256) {
-        float xv[4], dv[4], wv[4], o[4];
-        load4(xr + c, xv); load4(dr + c, dv); load4(w + c, wv);
-        if (accumulate) load4(gr + c, o); else o[0] = o[1] = o[2] = o[3] = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] += r * (dv[j] * wv[j]) - xv[j] * k;
-        store4(gr + c, o);
-    }
-}
-
-int launch_rmsnorm_bwd(const float* x, int64_t ld_x, const float* w, float eps, const void* dy, int64_t ld_dy, int dy_dtype, float* g,
-                       int64_t ld_g, int64_t rows, int64_t cols, int accumulate, hipStream_t s) {
-    P2T_REQUIRE(cols % 4 == 0 && ld_x % 4 == 0 && ld_dy % 4 == 0 && ld_g % 4 == 0, "rmsnorm backward: cols / strides must be multiples of 4");
-    const dim3 grid((unsigned)ceil_div(rows, 4));
-    if (dy_dtype == P2T_BF16)
-        rmsnorm_bwd_kernel<bf16_t><<<grid, 256, 0, s>>>(x, ld_x, w, eps, (const bf16_t*)dy, ld_dy, g, ld_g, rows, (int)cols, accumulate);
-    else
-        rmsnorm_bwd_kernel<float><<<grid, 256, 0, s>>>(x, ld_x, w, eps, (const float*)dy, ld_dy, g, ld_g, rows, (int)cols, accumulate);
-    P2T_LAUNCH_CHECK();
-    return P2T_OK;
-}
-
-// dst[m, c] = (Tdst)src[m, c], c < cols; 0 up to ld_dst: the fp32 residual gradient as a GEMM operand (with its K padding)
-template <typename Ts, typename Td>
-__global__ void __launch_bounds__(256) cast_rows_kernel(const Ts* __restrict__ src, int64_t ld_src, Td* __restrict__ dst, int64_t ld_dst, int64_t rows,
-                                                        int cols) {
-    const int per = (int)(ld_dst / 4);
-    const int64_t n4 = rows * per, stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-        const int64_t m = i / per;
-        const int c = (int)(i - m * per) * 4;
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (c + 3 < cols) {
-            load4(src + m * ld_src + c, v);
-        } else {
-            for (int j = 0; j < 4; ++j)
-                if (c + j < cols) v[j] = to_f32(src[m * ld_src + c + j]);
-        }
-        store4(dst + m * ld_dst + c, v);
-    }
-}
-
-int launch_cast_rows(const void* src, int sd, int64_t ld_src, void* dst, int dd, int64_t ld_dst, int64_t rows, int64_t cols, hipStream_t s) {
-    P2T_REQUIRE(ld_dst % 4 == 0 && ld_src % 4 == 0 && cols <= ld_dst && cols <= ld_src, "cast_rows: strides must be multiples of 4");
-    if (rows == 0) return P2T_OK;
-    const int64_t n4 = rows * (ld_dst / 4);
-    const unsigned grid = (unsigned)(ceil_div(n4, 256) < 4096 ? ceil_div(n4, 256) : 4096);
-    if (sd == P2T_F32 && dd == P2T_BF16) cast_rows_kernel<float, bf16_t><<<grid, 256, 0, s>>>((const float*)src, ld_src, (bf16_t*)dst, ld_dst, rows, (int)cols);
-    else if (sd == P2T_F32 && dd == P2T_F32) cast_rows_kernel<float, float><<<grid, 256, 0, s>>>((const float*)src, ld_src, (float*)dst, ld_dst, rows, (int)cols);
-    else if (sd == P2T_BF16 && dd == P2T_F32) cast_rows_kernel<bf16_t, float><<<grid, 256, 0, s>>>((const bf16_t*)src, ld_src, (float*)dst, ld_dst, rows, (int)cols);
-    else P2T_REQUIRE(false, "cast_rows: dtypes %d -> %d", sd, dd);
-    P2T_LAUNCH_CHECK();
-    return P2T_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// SwiGLU on the interleaved pre-activations the gate/up GEMM writes with a plain store: 64-column block jb of gu holds
-// gate[32 jb .. +31] then up[32 jb .. +31] (the row order of gu_w, include/p2t_hip.h p2t_llama_layer).
-//   forward : act[m, f] = silu(g) * u
-//   backward: d_gu = (d_act * u * sigma(g) (1 + g (1 - sigma(g))),  d_act * silu(g))   in the same interleaved layout
-template <typename T, bool BWD>
-__global__ void __launch_bounds__(256) swiglu_gu_kernel(const T* __restrict__ gu, int64_t ld_gu, const T* __restrict__ d_act, int64_t ld_da,
-                                                        T* __restrict__ out, int64_t ld_out, int64_t M, int F, int Fo) {
-    // Fo: columns written per row of `out` in the forward (F rounded up to the next GEMM's K padding: zeros beyond F)
-    const int per = (BWD ? F : Fo) / 4;
-    const int64_t n4 = M * (int64_t)per, stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-        const int64_t m = i / per;
-        const int f = (int)(i - m * per) * 4;
-        if (!BWD && f >= F) {
-            const float z[4] = {0.f, 0.f, 0.f, 0.f};
-            store4(out + m * ld_out + f, z);
-            continue;
-        }
-        const int col = (f >> 5) * 64 + (f & 31);
-        float g[4], u[4];
-        load4(gu + m * ld_gu + col, g);
-        load4(gu + m * ld_gu + col + 32, u);
-        if (!BWD) {
-            float a[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] = silu_for<T>(g[j]) * u[j];
-            store4(out + m * ld_out + f, a);
-        } else {
-            float da[4], dg[4], du[4];
-            load4(d_act + m * ld_da + f, da);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float sg = 1.0f / (1.0f + expf(-g[j]));
-                dg[j] = da[j] * u[j] * (sg * (1.0f + g[j] * (1.0f - sg)));
-                du[j] = da[j] * (g[j] * sg);
-            }
-            store4(out + m * ld_out + col, dg);
-            store4(out + m * ld_out + col + 32, du);
-        }
-    }
-}
-
-template <bool BWD>
-static int launch_swiglu_gu(const void* gu, int64_t ld_gu, const void* d_act, int64_t ld_da, void* out, int64_t ld_out, int64_t M, int64_t F,
-                            int dtype, hipStream_t s) {
-    P2T_REQUIRE(F % 32 == 0 && ld_gu % 4 == 0 && ld_out % 4 == 0, "swiglu: F must be a multiple of 32");
-    const int64_t Fo = BWD ? F : (round_up(F, 64) < ld_out ? round_up(F, 64) : ld_out);
-    const int64_t n4 = M * (Fo / 4);
-    const unsigned grid = (unsigned)(ceil_div(n4, 256) < 4096 ? ceil_div(n4, 256) : 4096);
-    if (dtype == P2T_BF16)
-        swiglu_gu_kernel<bf16_t, BWD><<<grid, 256, 0, s>>>((const bf16_t*)gu, ld_gu, (const bf16_t*)d_act, ld_da, (bf16_t*)out, ld_out, M, (int)F, (int)Fo);
-    else
-        swiglu_gu_kernel<float, BWD><<<grid, 256, 0, s>>>((const float*)gu, ld_gu, (const float*)d_act, ld_da, (float*)out, ld_out, M, (int)F, (int)Fo);
-    P2T_LAUNCH_CHECK();
-    return P2T_OK;
-}
-int launch_swiglu_from_gu(const void* gu, int64_t ld_gu, void* act, int64_t ld_act, int64_t M, int64_t F, int dtype, hipStream_t s) {
-    return launch_swiglu_gu<false>(gu, ld_gu, nullptr, 0, act, ld_act, M, F, dtype, s);
-}
 
 // ---------------------------------------------------------------------------------------------
 // Attention backward, exact-fp32 arithmetic on `T` operands (the counterpart of attn_simple.hip; an MFMA form is the next
@@ -381,56 +243,6 @@ int launch_rope_bwd_pack(const float* dq, const float* dk, const float* dv, cons
 }
 
 // ---------------------------------------------------------------------------------------------
-// d loss / d logits of p2t_cross_entropy_shifted: row (b, t) with a counted target y = labels[b, t+1]:
-// (softmax(logits) - onehot(y)) / count -- or, with per-target weights, weights[b, t+1] (softmax - onehot); every other row and the
-// padding columns: 0.  One block per row.
-template <typename T>
-__global__ void __launch_bounds__(256) ce_bwd_rows_kernel(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels, int seq, int V,
-                                                          int64_t ignore_index, const int32_t* __restrict__ count, T* __restrict__ dl, int64_t ld_d,
-                                                          int cols_d, const float* __restrict__ weights) {
-    __shared__ float red[4];
-    const int64_t row = blockIdx.x;
-    const int t = (int)(row % seq);
-    T* dr = dl + row * ld_d;
-    int64_t label = ignore_index;
-    if (t + 1 < seq) label = labels[row + 1];
-    if (label == ignore_index || label < 0 || label >= V) {
-        for (int c = threadIdx.x; c < cols_d; c += 256) dr[c] = from_f32<T>(0.f);
-        return;
-    }
-    const T* x = logits + row * ld;
-    float m = -INFINITY;
-    for (int c = threadIdx.x; c < V; c += 256) m = fmaxf(m, to_f32(x[c]));
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float sum = 0.f;
-    for (int c = threadIdx.x; c < V; c += 256) sum += expf(to_f32(x[c]) - m);
-    sum = block_sum<4>(sum, red);
-    const float wr = weights ? weights[row + 1] : 0.f;
-    const float inv = weights ? wr / sum : 1.0f / (sum * (float)count[0]), invc = weights ? wr : 1.0f / (float)count[0];
-    for (int c = threadIdx.x; c < cols_d; c += 256) {
-        float g = 0.f;
-        if (c < V) g = expf(to_f32(x[c]) - m) * inv - (c == (int)label ? invc : 0.f);
-        dr[c] = from_f32<T>(g);
-    }
-}
-
-// dst[dst_pos[r], :H] = src[src_pos[r], :H] for r < min(*n_dst, *n_src), f32 -> f32: the backward of p2t_scatter_rows'
-// boolean-mask assignment with the roles of the two position lists swapped (rows of dst not listed stay as they are).
-__global__ void __launch_bounds__(256) gather_rows_f32_kernel(float* __restrict__ dst, int64_t ld_dst, const int32_t* __restrict__ dst_pos,
-                                                              const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ src_pos,
-                                                              const int32_t* __restrict__ n_dst, const int32_t* __restrict__ n_src, int H) {
-    const int n = min(n_dst[0], n_src[0]);
-    for (int r = blockIdx.x; r < n; r += gridDim.x) {
-        float* d = dst + (int64_t)dst_pos[r] * ld_dst;
-        const float* s = src + (int64_t)src_pos[r] * ld_src;
-        for (int c = threadIdx.x; c < H; c += 256) d[c] = s[c];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
 // tape = what the backward reads again, per layer; carved from one caller-owned buffer.
 size_t llama_tape_plan(const p2t_llama_config* c, int B, int T, void* base, size_t bytes, LlamaTape* tape) {
     const size_t e = dtype_size(c->dtype);
@@ -570,7 +382,7 @@ int llama_train_backward_impl(const p2t_llama_config* c, const p2t_llama_weights
         // ---- MLP branch: x2 = x1 + down(silu(g) u)
         P2T_TRY(launch_cast_rows(g, P2T_F32, H, b.g16, dt, Hp, M, H, s));
         P2T_TRY(dx_gemm(b.g16, Hp, LT.down_wT, H, F, b.d_act, Fp, dt, P2T_EPI_STORE));
-        P2T_TRY(launch_swiglu_gu<true>(S.gu, 2 * F, b.d_act, Fp, b.d_gu, 2 * F, M, F, dt, s));
+        P2T_TRY(launch_swiglu_gu_bwd(S.gu, 2 * F, b.d_act, Fp, b.d_gu, 2 * F, M, F, dt, s));
         P2T_TRY(dx_gemm(b.d_gu, 2 * F, LT.gu_wT, 2 * F, H, b.d_h, H, P2T_F32, P2T_EPI_STORE_F32));
         P2T_TRY(launch_rmsnorm_bwd(S.x_mid, H, L.ln2_w, c->rms_norm_eps, b.d_h, H, P2T_F32, g, H, M, H, 1, s));
         // ---- attention branch: x1 = x + o(attn(...))
@@ -620,89 +432,6 @@ extern "C" int p2t_attention_backward(const void* q, const void* k, const void* 
                            log2_scores ? kLn2 : scale, causal, dtype, (hipStream_t)stream, log2_scores, use_mfma);
 }
 
-extern "C" int p2t_rmsnorm_backward(const float* x, int64_t ld_x, const float* w, float eps, const void* dy, int64_t ld_dy, int dy_dtype, float* dx,
-                                    int64_t ld_dx, int64_t rows, int64_t cols, int accumulate, p2t_stream stream) {
-    P2T_REQUIRE(x && w && dy && dx && rows >= 0 && cols > 0, "p2t_rmsnorm_backward: bad arguments");
-    if (rows == 0) return P2T_OK;
-    return launch_rmsnorm_bwd(x, ld_x, w, eps, dy, ld_dy, dy_dtype, dx, ld_dx, rows, cols, accumulate, (hipStream_t)stream);
-}
-
-extern "C" int p2t_cross_entropy_shifted_backward(const void* logits, int64_t ld, int dtype, const int64_t* labels, int B, int T, int V,
-                                                  int64_t ignore_index, const int32_t* count, void* d_logits, int64_t ld_d, p2t_stream stream) {
-    P2T_REQUIRE(logits && labels && count && d_logits && B > 0 && T > 0 && V > 0 && ld >= V && ld_d >= V, "p2t_cross_entropy_shifted_backward: bad arguments");
-    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_cross_entropy_shifted_backward: unsupported dtype %d", dtype);
-    const int64_t M = (int64_t)B * T;
-    const int cols_d = (int)(round_up(V, 64) < ld_d ? round_up(V, 64) : ld_d);          // the K padding of the LM-head dX GEMM is zeroed
-    if (dtype == P2T_BF16)
-        ce_bwd_rows_kernel<bf16_t><<<(unsigned)M, 256, 0, (hipStream_t)stream>>>((const bf16_t*)logits, ld, labels, T, V, ignore_index, count,
-                                                                                 (bf16_t*)d_logits, ld_d, cols_d, nullptr);
-    else
-        ce_bwd_rows_kernel<float><<<(unsigned)M, 256, 0, (hipStream_t)stream>>>((const float*)logits, ld, labels, T, V, ignore_index, count,
-                                                                                (float*)d_logits, ld_d, cols_d, nullptr);
-    P2T_LAUNCH_CHECK();
-    return P2T_OK;
-}
-
-extern "C" int p2t_cross_entropy_shifted_weighted_backward(const void* logits, int64_t ld, int dtype, const int64_t* labels, const float* weights,
-                                                           int B, int T, int V, int64_t ignore_index, void* d_logits, int64_t ld_d, p2t_stream stream) {
-    P2T_REQUIRE(logits && labels && weights && d_logits && B > 0 && T > 0 && V > 0 && ld >= V && ld_d >= V,
-                "p2t_cross_entropy_shifted_weighted_backward: bad arguments");
-    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_cross_entropy_shifted_weighted_backward: unsupported dtype %d", dtype);
-    const int64_t M = (int64_t)B * T;
-    const int cols_d = (int)(round_up(V, 64) < ld_d ? round_up(V, 64) : ld_d);
-    if (dtype == P2T_BF16)
-        ce_bwd_rows_kernel<bf16_t><<<(unsigned)M, 256, 0, (hipStream_t)stream>>>((const bf16_t*)logits, ld, labels, T, V, ignore_index, nullptr,
-                                                                                 (bf16_t*)d_logits, ld_d, cols_d, weights);
-    else
-        ce_bwd_rows_kernel<float><<<(unsigned)M, 256, 0, (hipStream_t)stream>>>((const float*)logits, ld, labels, T, V, ignore_index, nullptr,
-                                                                                (float*)d_logits, ld_d, cols_d, weights);
-    P2T_LAUNCH_CHECK();
-    return P2T_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// dst (+)= keep(seed, m * K + c) ? src / (1 - p) : 0: the LoRA branch's input dropout (peft lora_dropout, train_instruct.py:158) and,
-// with the same seed, its backward (the mask is regenerated, never stored).
-template <typename Ts, typename Td>
-__global__ void __launch_bounds__(256) dropout_rows_kernel(const Ts* __restrict__ src, int64_t ld_src, Td* __restrict__ dst, int64_t ld_dst, int64_t M,
-                                                           int K, float p, float scale, uint64_t seed, int accumulate) {
-    const int64_t n = M * (int64_t)K, stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        const int64_t m = i / K;
-        const int c = (int)(i - m * K);
-        const float x = dropout_value(to_f32(src[m * ld_src + c]), seed, i, p, scale);
-        Td* d = dst + m * ld_dst + c;
-        *d = from_f32<Td>(accumulate ? to_f32(*d) + x : x);
-    }
-}
-
-extern "C" int p2t_dropout_rows(const void* src, int src_dtype, int64_t ld_src, void* dst, int dst_dtype, int64_t ld_dst, int64_t M, int64_t K, float p,
-                                uint64_t seed, int accumulate, p2t_stream stream) {
-    P2T_REQUIRE(src && dst && M >= 0 && K > 0 && ld_src >= K && ld_dst >= K && p >= 0.f && p < 1.f, "p2t_dropout_rows: bad arguments");
-    if (M == 0) return P2T_OK;
-    const float scale = 1.0f / (1.0f - p);
-    const int64_t n = M * K;
-    const unsigned grid = (unsigned)(ceil_div(n, 256) < 8192 ? ceil_div(n, 256) : 8192);
-    hipStream_t s = (hipStream_t)stream;
-#define P2T_DROP(TS, TD) dropout_rows_kernel<TS, TD><<<grid, 256, 0, s>>>((const TS*)src, ld_src, (TD*)dst, ld_dst, M, (int)K, p, scale, seed, accumulate)
-    if (src_dtype == P2T_BF16 && dst_dtype == P2T_BF16) P2T_DROP(bf16_t, bf16_t);
-    else if (src_dtype == P2T_F32 && dst_dtype == P2T_BF16) P2T_DROP(float, bf16_t);
-    else if (src_dtype == P2T_BF16 && dst_dtype == P2T_F32) P2T_DROP(bf16_t, float);
-    else if (src_dtype == P2T_F32 && dst_dtype == P2T_F32) P2T_DROP(float, float);
-    else { set_error("p2t_dropout_rows: unsupported dtypes %d -> %d", src_dtype, dst_dtype); return P2T_ERR_ARG; }
-#undef P2T_DROP
-    P2T_LAUNCH_CHECK();
-    return P2T_OK;
-}
-
-extern "C" int p2t_swiglu_gu(const void* gu, int64_t ld_gu, const void* d_act, int64_t ld_da, void* out, int64_t ld_out, int64_t M, int64_t F, int dtype,
-                             p2t_stream stream) {
-    P2T_REQUIRE(gu && out && M >= 0 && F > 0 && (dtype == P2T_F32 || dtype == P2T_BF16), "p2t_swiglu_gu: bad arguments");
-    if (M == 0) return P2T_OK;
-    if (d_act) return launch_swiglu_gu<true>(gu, ld_gu, d_act, ld_da, out, ld_out, M, F, dtype, (hipStream_t)stream);
-    return launch_swiglu_gu<false>(gu, ld_gu, nullptr, 0, out, ld_out, M, F, dtype, (hipStream_t)stream);
-}
-
 extern "C" int p2t_rope_backward_pack_docs(const float* dq, const float* dk, const float* dv, const float* inv_freq, float* cos_sin_scratch,
                                            const int32_t* docs, void* d_qkv, int64_t ld, int B, int T, int nh, int nkv, int d, int dp, float q_scale,
                                            int dtype, p2t_stream stream) {
@@ -729,13 +458,4 @@ extern "C" int p2t_rope_backward_pack(const float* dq, const float* dk, const fl
     hipStream_t s = (hipStream_t)stream;
     P2T_TRY(launch_rope_table(inv_freq, T, d / 2, cos_sin_scratch, s));
     return launch_rope_bwd_pack(dq, dk, dv, cos_sin_scratch, d_qkv, ld, B, T, nh, nkv, d, dp, q_scale, dtype, s);
-}
-
-extern "C" int p2t_gather_rows_f32(float* dst, int64_t ld_dst, const int32_t* dst_pos, const float* src, int64_t ld_src, const int32_t* src_pos,
-                                   const int32_t* n_dst, const int32_t* n_src, int64_t max_rows, int H, p2t_stream stream) {
-    P2T_REQUIRE(dst && dst_pos && src && src_pos && n_dst && n_src && max_rows > 0 && H > 0 && ld_dst >= H && ld_src >= H, "p2t_gather_rows_f32: bad arguments");
-    const unsigned grid = (unsigned)(max_rows < 4096 ? max_rows : 4096);
-    gather_rows_f32_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(dst, ld_dst, dst_pos, src, ld_src, src_pos, n_dst, n_src, H);
-    P2T_LAUNCH_CHECK();
-    return P2T_OK;
 }

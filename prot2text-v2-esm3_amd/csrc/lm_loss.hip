@@ -1,7 +1,13 @@
-// LM loss of the stage-2 step over the rows that carry a target only (reference scripts/train_instruct.py:192-213
+// The LM loss: the shifted cross-entropy of Esm2LlamaInstructForCausalLM.forward (HF LlamaForCausalLM's loss; reference
+// models/modeling_esm2llama_instruct.py:195-215), mean over (b, t < T-1, labels[b, t+1] counted) of logsumexp(logits[b, t]) -
+// logits[b, t, label], forward and backward, in its two forms.  Both live here because they share the rule for which label counts.
+//
+// Over the full logits [B*T, ld] (p2t_cross_entropy_shifted*, the default stage-2 step):
+//   * ce_rows / ce_reduce -- one block per row: row loss and validity, then the token mean, or the sum weighted per target;
+//   * ce_bwd_rows         -- (softmax - onehot) / count, or * weights[b, t+1], into d_logits.
+// Over the rows that carry a target only (reference scripts/train_instruct.py:192-213
 // reads `.loss` alone, never the logits):
-//   * lm_target_rows      -- the flat rows (b, t) whose labels[b, t+1] is counted, by ce_rows_kernel's rule (sft.hip), their labels
-//                            and their number, on the device;
+//   * lm_target_rows      -- the flat rows (b, t) whose labels[b, t+1] is counted, their labels and their number, on the device;
 //   * lm_loss_grad_rows   -- one chunk of logits [R, ld] in place: row loss = logsumexp - target logit, then the row overwritten
 //                            by its own gradient (softmax - onehot) * s_r, Liger-style, so no second [R, ld] buffer ever exists;
 //   * lm_loss_reduce      -- the row losses summed in a fixed order into the token mean / the weighted sum.
@@ -15,6 +21,126 @@
 
 namespace p2t {
 
+// the counted label of flat row (b, t): labels[b, t+1] where t + 1 < T, it is not ignore_index and it is an id of the vocabulary;
+// -1 without one
+__device__ __forceinline__ int64_t counted_label(const int64_t* __restrict__ labels, int64_t row, int T_len, int V, int64_t ignore_index) {
+    if ((int)(row % T_len) + 1 >= T_len) return -1;
+    const int64_t label = labels[row + 1];
+    return (label == ignore_index || label < 0 || label >= V) ? -1 : label;
+}
+
+// m = max of the row's V logits, s = sum of exp(x - m): two passes, one block of 256 threads (red: 4 floats of LDS)
+template <typename T>
+__device__ __forceinline__ void row_max_sumexp(const T* __restrict__ x, int V, float* red, float& m, float& s) {
+    m = -INFINITY;
+    for (int c = threadIdx.x; c < V; c += 256) m = fmaxf(m, to_f32(x[c]));
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    s = 0.f;
+    for (int c = threadIdx.x; c < V; c += 256) s += expf(to_f32(x[c]) - m);
+    s = block_sum<4>(s, red);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) ce_rows_kernel(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
+                                                      int T_len, int V, int64_t ignore_index, float* __restrict__ row_loss,
+                                                      int32_t* __restrict__ row_valid) {
+    __shared__ float red[4];
+    const int64_t row = blockIdx.x;                     // (b, t)
+    const int64_t label = counted_label(labels, row, T_len, V, ignore_index);
+    if (label < 0) {
+        if (threadIdx.x == 0) { row_loss[row] = 0.f; row_valid[row] = 0; }
+        return;
+    }
+    const T* x = logits + row * ld;
+    float m, s;
+    row_max_sumexp(x, V, red, m, s);
+    if (threadIdx.x == 0) {
+        row_loss[row] = logf(s) + m - to_f32(x[label]);
+        row_valid[row] = 1;
+    }
+}
+
+// Over the rows with a counted target: loss = mean of row_loss (no such row: 0 / 0 = NaN, as torch's mean over nothing), or with
+// weights the sum of weights[row + 1] * row_loss[row] (the weight sits at the target's label position).  A row without a target
+// holds row_loss = +0, which changes no bit of the sum, so both forms skip it.
+__global__ void __launch_bounds__(1024) ce_reduce_kernel(const float* __restrict__ row_loss, const int32_t* __restrict__ row_valid,
+                                                         const float* __restrict__ weights, int64_t M, float* __restrict__ loss,
+                                                         int32_t* __restrict__ count) {
+    __shared__ float red[16];
+    __shared__ float redc[16];
+    float s = 0.f, c = 0.f;
+    for (int64_t i = threadIdx.x; i < M; i += 1024)
+        if (row_valid[i]) {
+            if (weights) s += weights[i + 1] * row_loss[i];
+            else s += row_loss[i];
+            c += 1.f;
+        }
+    s = block_sum<16>(s, red);
+    c = block_sum<16>(c, redc);
+    if (threadIdx.x == 0) {
+        *loss = weights ? s : s / c;
+        if (count) *count = (int32_t)c;
+    }
+}
+
+// d loss / d logits: row (b, t) with a counted target y: (softmax(logits) - onehot(y)) / count -- or, with per-target weights,
+// weights[b, t+1] (softmax - onehot); every other row and the padding columns: 0.  One block per row.
+template <typename T>
+__global__ void __launch_bounds__(256) ce_bwd_rows_kernel(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels, int seq, int V,
+                                                          int64_t ignore_index, const int32_t* __restrict__ count, T* __restrict__ dl, int64_t ld_d,
+                                                          int cols_d, const float* __restrict__ weights) {
+    __shared__ float red[4];
+    const int64_t row = blockIdx.x;
+    T* dr = dl + row * ld_d;
+    const int64_t label = counted_label(labels, row, seq, V, ignore_index);
+    if (label < 0) {
+        for (int c = threadIdx.x; c < cols_d; c += 256) dr[c] = from_f32<T>(0.f);
+        return;
+    }
+    const T* x = logits + row * ld;
+    float m, sum;
+    row_max_sumexp(x, V, red, m, sum);
+    const float wr = weights ? weights[row + 1] : 0.f;
+    const float inv = weights ? wr / sum : 1.0f / (sum * (float)count[0]), invc = weights ? wr : 1.0f / (float)count[0];
+    for (int c = threadIdx.x; c < cols_d; c += 256) {
+        float g = 0.f;
+        if (c < V) g = expf(to_f32(x[c]) - m) * inv - (c == (int)label ? invc : 0.f);
+        dr[c] = from_f32<T>(g);
+    }
+}
+
+// weights == nullptr: the token mean (the backward divides by count[0]); else the weighted sum
+static int launch_ce_shifted(const void* logits, int64_t ld, int dtype, const int64_t* labels, const float* weights, int B, int T, int V,
+                             int64_t ignore_index, float* row_loss, int32_t* row_valid, float* loss, int32_t* count, hipStream_t s) {
+    const int64_t M = (int64_t)B * T;
+    if (dtype == P2T_BF16)
+        ce_rows_kernel<bf16_t><<<(unsigned)M, 256, 0, s>>>((const bf16_t*)logits, ld, labels, T, V, ignore_index, row_loss, row_valid);
+    else
+        ce_rows_kernel<float><<<(unsigned)M, 256, 0, s>>>((const float*)logits, ld, labels, T, V, ignore_index, row_loss, row_valid);
+    P2T_LAUNCH_CHECK();
+    ce_reduce_kernel<<<1, 1024, 0, s>>>(row_loss, row_valid, weights, M, loss, count);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+static int launch_ce_shifted_bwd(const void* logits, int64_t ld, int dtype, const int64_t* labels, const float* weights, const int32_t* count, int B,
+                                 int T, int V, int64_t ignore_index, void* d_logits, int64_t ld_d, hipStream_t s) {
+    const int64_t M = (int64_t)B * T;
+    const int cols_d = (int)(round_up(V, 64) < ld_d ? round_up(V, 64) : ld_d);          // the K padding of the LM-head dX GEMM is zeroed
+    if (dtype == P2T_BF16)
+        ce_bwd_rows_kernel<bf16_t><<<(unsigned)M, 256, 0, s>>>((const bf16_t*)logits, ld, labels, T, V, ignore_index, count, (bf16_t*)d_logits, ld_d,
+                                                               cols_d, weights);
+    else
+        ce_bwd_rows_kernel<float><<<(unsigned)M, 256, 0, s>>>((const float*)logits, ld, labels, T, V, ignore_index, count, (float*)d_logits, ld_d,
+                                                              cols_d, weights);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The target-rows form.
 // One block of 1024 threads, as positions_where_kernel: thread i owns a contiguous segment of the B*T flat rows, counts its hits,
 // the counts are scanned through LDS, and a second walk writes rows / targets below `cap`.  count = {n, n > cap}; the entries
 // min(n, cap) .. cap of rows / targets are set to -1.
@@ -24,13 +150,8 @@ __global__ void __launch_bounds__(1024) lm_target_rows_kernel(const int64_t* __r
     __shared__ int part[1024];
     const int tid = threadIdx.x;
     const int64_t seg = (n_rows + 1023) / 1024, lo = tid * seg, hi = lo + seg < n_rows ? lo + seg : n_rows;
-    auto target_of = [&](int64_t row) -> int64_t {      // the counted label of flat row (b, t), -1 without one
-        if ((int)(row % T_len) + 1 >= T_len) return -1;
-        const int64_t label = labels[row + 1];
-        return (label == ignore_index || label < 0 || label >= V) ? -1 : label;
-    };
     int c = 0;
-    for (int64_t i = lo; i < hi; ++i) c += target_of(i) >= 0;
+    for (int64_t i = lo; i < hi; ++i) c += counted_label(labels, i, T_len, V, ignore_index) >= 0;
     part[tid] = c;
     __syncthreads();
     for (int off = 1; off < 1024; off <<= 1) {          // Hillis-Steele inclusive scan
@@ -41,7 +162,7 @@ __global__ void __launch_bounds__(1024) lm_target_rows_kernel(const int64_t* __r
     }
     int r = part[tid] - c;
     for (int64_t i = lo; i < hi; ++i) {
-        const int64_t label = target_of(i);
+        const int64_t label = counted_label(labels, i, T_len, V, ignore_index);
         if (label < 0) continue;
         if (r < cap) { rows[r] = (int32_t)i; targets[r] = (int32_t)label; }
         ++r;
@@ -157,6 +278,39 @@ __global__ void __launch_bounds__(1024) lm_loss_reduce_kernel(const float* __res
 }  // namespace p2t
 
 using namespace p2t;
+
+extern "C" int p2t_cross_entropy_shifted(const void* logits, int64_t ld, int dtype, const int64_t* labels, int B, int T, int V,
+                                         int64_t ignore_index, float* row_loss, int32_t* row_valid, float* loss, int32_t* count,
+                                         p2t_stream stream) {
+    P2T_REQUIRE(logits && labels && row_loss && row_valid && loss && B > 0 && T > 0 && V > 0 && ld >= V,
+                "p2t_cross_entropy_shifted: bad arguments");
+    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_cross_entropy_shifted: unsupported dtype %d", dtype);
+    return launch_ce_shifted(logits, ld, dtype, labels, nullptr, B, T, V, ignore_index, row_loss, row_valid, loss, count, (hipStream_t)stream);
+}
+
+extern "C" int p2t_cross_entropy_shifted_weighted(const void* logits, int64_t ld, int dtype, const int64_t* labels, const float* weights, int B, int T,
+                                                  int V, int64_t ignore_index, float* row_loss, int32_t* row_valid, float* loss, int32_t* count,
+                                                  p2t_stream stream) {
+    P2T_REQUIRE(logits && labels && weights && row_loss && row_valid && loss && B > 0 && T > 0 && V > 0 && ld >= V,
+                "p2t_cross_entropy_shifted_weighted: bad arguments");
+    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_cross_entropy_shifted_weighted: unsupported dtype %d", dtype);
+    return launch_ce_shifted(logits, ld, dtype, labels, weights, B, T, V, ignore_index, row_loss, row_valid, loss, count, (hipStream_t)stream);
+}
+
+extern "C" int p2t_cross_entropy_shifted_backward(const void* logits, int64_t ld, int dtype, const int64_t* labels, int B, int T, int V,
+                                                  int64_t ignore_index, const int32_t* count, void* d_logits, int64_t ld_d, p2t_stream stream) {
+    P2T_REQUIRE(logits && labels && count && d_logits && B > 0 && T > 0 && V > 0 && ld >= V && ld_d >= V, "p2t_cross_entropy_shifted_backward: bad arguments");
+    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_cross_entropy_shifted_backward: unsupported dtype %d", dtype);
+    return launch_ce_shifted_bwd(logits, ld, dtype, labels, nullptr, count, B, T, V, ignore_index, d_logits, ld_d, (hipStream_t)stream);
+}
+
+extern "C" int p2t_cross_entropy_shifted_weighted_backward(const void* logits, int64_t ld, int dtype, const int64_t* labels, const float* weights,
+                                                           int B, int T, int V, int64_t ignore_index, void* d_logits, int64_t ld_d, p2t_stream stream) {
+    P2T_REQUIRE(logits && labels && weights && d_logits && B > 0 && T > 0 && V > 0 && ld >= V && ld_d >= V,
+                "p2t_cross_entropy_shifted_weighted_backward: bad arguments");
+    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_cross_entropy_shifted_weighted_backward: unsupported dtype %d", dtype);
+    return launch_ce_shifted_bwd(logits, ld, dtype, labels, weights, nullptr, B, T, V, ignore_index, d_logits, ld_d, (hipStream_t)stream);
+}
 
 extern "C" int p2t_lm_target_rows(const int64_t* labels, int B, int T, int V, int64_t ignore_index, int cap, int32_t* rows, int32_t* targets,
                                   int32_t* count, p2t_stream stream) {

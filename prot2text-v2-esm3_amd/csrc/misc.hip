@@ -176,6 +176,39 @@ static inline int stream_grid(int64_t n_items, int per_block) {
     return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
 }
 
+// dst[m, c] = (Tdst)src[m, c], c < cols; 0 up to ld_dst: the fp32 residual gradient as a GEMM operand (with its K padding)
+template <typename Ts, typename Td>
+__global__ void __launch_bounds__(256) cast_rows_kernel(const Ts* __restrict__ src, int64_t ld_src, Td* __restrict__ dst, int64_t ld_dst, int64_t rows,
+                                                        int cols) {
+    const int per = (int)(ld_dst / 4);
+    const int64_t n4 = rows * per, stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        const int64_t m = i / per;
+        const int c = (int)(i - m * per) * 4;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (c + 3 < cols) {
+            load4(src + m * ld_src + c, v);
+        } else {
+            for (int j = 0; j < 4; ++j)
+                if (c + j < cols) v[j] = to_f32(src[m * ld_src + c + j]);
+        }
+        store4(dst + m * ld_dst + c, v);
+    }
+}
+
+int launch_cast_rows(const void* src, int sd, int64_t ld_src, void* dst, int dd, int64_t ld_dst, int64_t rows, int64_t cols, hipStream_t s) {
+    P2T_REQUIRE(ld_dst % 4 == 0 && ld_src % 4 == 0 && cols <= ld_dst && cols <= ld_src, "cast_rows: strides must be multiples of 4");
+    if (rows == 0) return P2T_OK;
+    const int64_t n4 = rows * (ld_dst / 4);
+    const unsigned grid = (unsigned)(ceil_div(n4, 256) < 4096 ? ceil_div(n4, 256) : 4096);
+    if (sd == P2T_F32 && dd == P2T_BF16) cast_rows_kernel<float, bf16_t><<<grid, 256, 0, s>>>((const float*)src, ld_src, (bf16_t*)dst, ld_dst, rows, (int)cols);
+    else if (sd == P2T_F32 && dd == P2T_F32) cast_rows_kernel<float, float><<<grid, 256, 0, s>>>((const float*)src, ld_src, (float*)dst, ld_dst, rows, (int)cols);
+    else if (sd == P2T_BF16 && dd == P2T_F32) cast_rows_kernel<bf16_t, float><<<grid, 256, 0, s>>>((const bf16_t*)src, ld_src, (float*)dst, ld_dst, rows, (int)cols);
+    else P2T_REQUIRE(false, "cast_rows: dtypes %d -> %d", sd, dd);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
 size_t colsum_scratch_bytes(int64_t cols) { return sizeof(float) * (size_t)kColsumChunks * (size_t)cols; }
 
 int launch_colsum(const void* x, int dtype, int64_t rows, int64_t cols, int64_t ld, float* out, int accumulate,

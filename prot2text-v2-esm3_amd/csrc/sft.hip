@@ -3,8 +3,8 @@
 //   * positions_where      -- flat positions of the selected elements of an int64 array, in order (the row-major order
 //                             torch's boolean-mask indexing uses), plus their count;
 //   * scatter_rows         -- inputs_embeds[placeholder_mask] = encoder_hidden_states[encoder_mask];
-//   * cross_entropy_shift  -- mean over (b, t < T-1, labels[b, t+1] != ignore) of logsumexp(logits[b, t]) - logits[b, t, label].
-// All HBM-bound streaming kernels in fp32 arithmetic; reductions are deterministic (no float atomics).
+//   * gather_rows_f32      -- its backward (the two position lists swap roles).
+// The shifted cross-entropy of the same forward is in lm_loss.hip.
 #include "common.h"
 #include "kernels.h"
 
@@ -47,62 +47,16 @@ __global__ void __launch_bounds__(256) scatter_rows_kernel(float* __restrict__ d
     }
 }
 
-template <typename T>
-__global__ void __launch_bounds__(256) ce_rows_kernel(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels,
-                                                      int T_len, int V, int64_t ignore_index, float* __restrict__ row_loss,
-                                                      int32_t* __restrict__ row_valid) {
-    __shared__ float red[4];
-    const int64_t row = blockIdx.x;                     // (b, t)
-    const int t = (int)(row % T_len);
-    const int64_t label = t + 1 < T_len ? labels[row + 1] : ignore_index;
-    if (label == ignore_index || label < 0 || label >= V) {
-        if (threadIdx.x == 0) { row_loss[row] = 0.f; row_valid[row] = 0; }
-        return;
-    }
-    const T* x = logits + row * ld;
-    float m = -INFINITY;
-    for (int c = threadIdx.x; c < V; c += 256) m = fmaxf(m, to_f32(x[c]));
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float s = 0.f;
-    for (int c = threadIdx.x; c < V; c += 256) s += expf(to_f32(x[c]) - m);
-    s = block_sum<4>(s, red);
-    if (threadIdx.x == 0) {
-        row_loss[row] = logf(s) + m - to_f32(x[label]);
-        row_valid[row] = 1;
-    }
-}
-
-__global__ void __launch_bounds__(1024) ce_reduce_kernel(const float* __restrict__ row_loss, const int32_t* __restrict__ row_valid,
-                                                         int64_t M, float* __restrict__ loss, int32_t* __restrict__ count) {
-    __shared__ float red[16];
-    __shared__ float redc[16];
-    float s = 0.f, c = 0.f;
-    for (int64_t i = threadIdx.x; i < M; i += 1024) { s += row_loss[i]; c += (float)row_valid[i]; }
-    s = block_sum<16>(s, red);
-    c = block_sum<16>(c, redc);
-    if (threadIdx.x == 0) {
-        *loss = s / c;                                  // no valid target: 0 / 0 = NaN, as torch's mean over nothing
-        if (count) *count = (int32_t)c;
-    }
-}
-
-// loss = sum over the rows with a counted target of weights[row + 1] * row_loss[row] (the weight sits at the target's label position)
-__global__ void __launch_bounds__(1024) ce_reduce_weighted_kernel(const float* __restrict__ row_loss, const int32_t* __restrict__ row_valid,
-                                                                  const float* __restrict__ weights, int64_t M, float* __restrict__ loss,
-                                                                  int32_t* __restrict__ count) {
-    __shared__ float red[16];
-    __shared__ float redc[16];
-    float s = 0.f, c = 0.f;
-    for (int64_t i = threadIdx.x; i < M; i += 1024)
-        if (row_valid[i]) { s += weights[i + 1] * row_loss[i]; c += 1.f; }
-    s = block_sum<16>(s, red);
-    c = block_sum<16>(c, redc);
-    if (threadIdx.x == 0) {
-        *loss = s;
-        if (count) *count = (int32_t)c;
+// dst[dst_pos[r], :H] = src[src_pos[r], :H] for r < min(*n_dst, *n_src), f32 -> f32: the backward of p2t_scatter_rows'
+// boolean-mask assignment with the roles of the two position lists swapped (rows of dst not listed stay as they are).
+__global__ void __launch_bounds__(256) gather_rows_f32_kernel(float* __restrict__ dst, int64_t ld_dst, const int32_t* __restrict__ dst_pos,
+                                                              const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ src_pos,
+                                                              const int32_t* __restrict__ n_dst, const int32_t* __restrict__ n_src, int H) {
+    const int n = min(n_dst[0], n_src[0]);
+    for (int r = blockIdx.x; r < n; r += gridDim.x) {
+        float* d = dst + (int64_t)dst_pos[r] * ld_dst;
+        const float* s = src + (int64_t)src_pos[r] * ld_src;
+        for (int c = threadIdx.x; c < H; c += 256) d[c] = s[c];
     }
 }
 
@@ -135,38 +89,11 @@ extern "C" int p2t_scatter_rows(float* dst, int64_t ld_dst, const int32_t* dst_p
     return P2T_OK;
 }
 
-extern "C" int p2t_cross_entropy_shifted(const void* logits, int64_t ld, int dtype, const int64_t* labels, int B, int T, int V,
-                                         int64_t ignore_index, float* row_loss, int32_t* row_valid, float* loss, int32_t* count,
-                                         p2t_stream stream) {
-    P2T_REQUIRE(logits && labels && row_loss && row_valid && loss && B > 0 && T > 0 && V > 0 && ld >= V,
-                "p2t_cross_entropy_shifted: bad arguments");
-    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_cross_entropy_shifted: unsupported dtype %d", dtype);
-    const int64_t M = (int64_t)B * T;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == P2T_BF16)
-        ce_rows_kernel<bf16_t><<<(unsigned)M, 256, 0, s>>>((const bf16_t*)logits, ld, labels, T, V, ignore_index, row_loss, row_valid);
-    else
-        ce_rows_kernel<float><<<(unsigned)M, 256, 0, s>>>((const float*)logits, ld, labels, T, V, ignore_index, row_loss, row_valid);
-    P2T_LAUNCH_CHECK();
-    ce_reduce_kernel<<<1, 1024, 0, s>>>(row_loss, row_valid, M, loss, count);
-    P2T_LAUNCH_CHECK();
-    return P2T_OK;
-}
-
-extern "C" int p2t_cross_entropy_shifted_weighted(const void* logits, int64_t ld, int dtype, const int64_t* labels, const float* weights, int B, int T,
-                                                  int V, int64_t ignore_index, float* row_loss, int32_t* row_valid, float* loss, int32_t* count,
-                                                  p2t_stream stream) {
-    P2T_REQUIRE(logits && labels && weights && row_loss && row_valid && loss && B > 0 && T > 0 && V > 0 && ld >= V,
-                "p2t_cross_entropy_shifted_weighted: bad arguments");
-    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_cross_entropy_shifted_weighted: unsupported dtype %d", dtype);
-    const int64_t M = (int64_t)B * T;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == P2T_BF16)
-        ce_rows_kernel<bf16_t><<<(unsigned)M, 256, 0, s>>>((const bf16_t*)logits, ld, labels, T, V, ignore_index, row_loss, row_valid);
-    else
-        ce_rows_kernel<float><<<(unsigned)M, 256, 0, s>>>((const float*)logits, ld, labels, T, V, ignore_index, row_loss, row_valid);
-    P2T_LAUNCH_CHECK();
-    ce_reduce_weighted_kernel<<<1, 1024, 0, s>>>(row_loss, row_valid, weights, M, loss, count);
+extern "C" int p2t_gather_rows_f32(float* dst, int64_t ld_dst, const int32_t* dst_pos, const float* src, int64_t ld_src, const int32_t* src_pos,
+                                   const int32_t* n_dst, const int32_t* n_src, int64_t max_rows, int H, p2t_stream stream) {
+    P2T_REQUIRE(dst && dst_pos && src && src_pos && n_dst && n_src && max_rows > 0 && H > 0 && ld_dst >= H && ld_src >= H, "p2t_gather_rows_f32: bad arguments");
+    const unsigned grid = (unsigned)(max_rows < 4096 ? max_rows : 4096);
+    gather_rows_f32_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(dst, ld_dst, dst_pos, src, ld_src, src_pos, n_dst, n_src, H);
     P2T_LAUNCH_CHECK();
     return P2T_OK;
 }

@@ -7,7 +7,8 @@
 
 `p2t_llama_train_forward / _backward` (csrc/llama_train.hip) run the FROZEN decoder as fused blocks and hand back only the
 gradient at its inputs.  A LoRA branch sits between those blocks (y = W x + (alpha / r) B (A drop(x)) ahead of the rotation / the
-SwiGLU), and so does Qwen3's q / k norm, so this module drives the same HIP kernels one by one through the C ABI, per layer:
+SwiGLU), and so does Qwen3's q / k norm, so this module drives the same HIP kernels one by one through the C ABI (the row-wise ones:
+csrc/norm.hip, csrc/activations.hip, csrc/misc.hip; the loss: csrc/lm_loss.hip), per layer:
 p2t_rmsnorm, p2t_gemm_nt (frozen weights: MFMA where K allows; low-rank products: the same entry point), p2t_qkv_post,
 p2t_attention (+ log-sum-exps), p2t_swiglu_gu, and backwards p2t_gemm_nt on transposed weights, p2t_attention_backward,
 p2t_rope_backward_pack, p2t_rmsnorm_backward, p2t_transpose (the token axis made contiguous for dA / dB), p2t_dropout_rows (the

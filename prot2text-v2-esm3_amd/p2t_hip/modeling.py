@@ -766,7 +766,7 @@ class LlamaDecoder(nn.Module):
         the token mean (p2t_hip.data.pack_instruct_batch(loss_weighting="sample") writes them).
         Restates transformers/models/llama/modeling_llama.py (LlamaForCausalLM.forward) and loss_utils.ForCausalLMLoss.
         With `labels`, gradients enabled and `inputs_embeds` requiring grad (stage 2: the adapter's rows sit in it), the loss
-        carries an autograd node whose backward is the hand-written chain of llama_train.hip -- the decoder's own parameters
+        carries an autograd node whose backward is the hand-written chain of lm_loss.hip (cross-entropy) and llama_train.hip (decoder) -- the decoder's own parameters
         are frozen on this path (no weight gradients; LoRA matrices are not built yet)."""
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")

@@ -1,4 +1,4 @@
-"""The three kernels of csrc/lm_loss.hip (the LM loss over the target rows only), one by one against fp64 numpy computed here on the
+"""The three kernels of the target-rows form in csrc/lm_loss.hip (the LM loss over the target rows only), one by one against fp64 numpy computed here on the
 stored (rounded) inputs: the selection exactly, the row kernel's loss to 1e-5 relative and its in-place gradient to 2^-22 max|ref|
 (f32 storage) / half a bf16 step of the reference + 2^-22 max|ref| (bf16 storage), the reduction, and bit-identical repeats."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""CPU: the three entry points of csrc/lm_loss.hip (the LM loss over the target rows only) are declared, exported and bound, and every
+"""CPU: the three entry points of the target-rows form in csrc/lm_loss.hip (the LM loss over the target rows only) are declared, exported and bound, and every
 argument outside their contracts is P2T_ERR_ARG with a message before any GPU call (as tests/test_abi.py checks for the others)."""
 import os
 import re

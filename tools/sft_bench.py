@@ -1,6 +1,6 @@
 """Stage-2 (SFT) step of Esm2LlamaInstructForCausalLM at cfg3 sizes: ESM2-3B encode -> adapter -> placeholder
 scatter -> 32-layer Llama-3.1-8B -> LM head -> shifted CE, once forward only and once as the training step `loss.backward()`
-(frozen towers, adapter trainable: training forward with the activation tape + the dX chain of csrc/llama_train.hip + adapter
+(frozen towers, adapter trainable: training forward with the activation tape + the dX chain of csrc/llama_train.hip (cross-entropy: csrc/lm_loss.hip; norm / SwiGLU backwards: csrc/norm.hip, csrc/activations.hip) + adapter
 backward), with a per-kernel-family breakdown of the backward from the torch profiler-free HIP-event brackets below.
 python tools/sft_bench.py [B] [lora] [trainer] [encoder] [packed] [checkpoint] [fused] [targets=F] > sft_bench.log
 `fused`: every training leg once more with `model.fused_lm_loss()` (p2t_hip/lm_head.py: the LM loss over the target rows only), the
