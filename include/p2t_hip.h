@@ -627,6 +627,29 @@ int p2t_llama_decode_step(const p2t_llama_config* cfg, const p2t_llama_weights* 
 int p2t_greedy_select(const void* logits, int dtype, int64_t ld, int V, int BB, const int64_t* eos_ids, int n_eos,
                       int64_t pad_id, int32_t* finished, int64_t* next_tokens, int64_t* out_tokens, int64_t ld_tokens,
                       const int32_t* step, int G, p2t_stream stream);
+/* Choice by sampling, with p2t_greedy_select's arguments and bookkeeping (a finished row emits pad_id, out_tokens[r, clamp(step[0],
+ * 0, G - 1)] = next[r], finished[r] |= next[r] in eos_ids; the token is always in [0, V)): HF's TemperatureLogitsWarper ->
+ * TopKLogitsWarper -> TopPLogitsWarper and one multinomial draw per row, all in f32 on the stored logits of columns [0, V)
+ * (columns V .. ld are never read).  temperature > 0; top_k: 0 = off, else 1 .. 1024; top_p: >= 1 = off, else in (0, 1).
+ * Supported: top_k on (top_p on or off), and both off; top_p on without top_k needs a sort of the whole vocabulary:
+ * P2T_ERR_UNSUPPORTED.  Per row r:
+ *   x_c = float(logit_c) / temperature (a division).  kth = the min(top_k, V)-th largest x; every c with x_c >= kth survives,
+ *   ties at kth included.  The survivor table holds 2048: beyond that, all x_c > kth and the ties at kth in ascending column order
+ *   until it is full, and bit 0 of *flags is set (>= 1025 exact ties).  Ranks: value descending, column ascending among equal
+ *   values.  e_j = exp(x_j - x_0); rank j is kept iff sum_{i >= j} e_i > (1 - top_p) sum_i e_i, rank 0 always (min_tokens_to_keep
+ *   1).  Draw: h = mix64(mix64(mix64(seed + 0x9E3779B97F4A7C15) ^ (uint64)(row0 + r)) ^ (uint64)(int64)step[0]) (mix64: the
+ *   splitmix64 finaliser of p2t_fill_hash), hash24 = h >> 40, u = (hash24 + 0.5) * 2^-24 rounded to f32; the token is the kept
+ *   rank with the smallest j such that sum_{i <= j} e_i > u * (sum of the kept e_i), the last kept rank if rounding leaves none.
+ *   Both filters off: the same rule over all V columns in ascending column order.
+ * p2t_hip.synth.sample_uniform(seed, row, step) restates the chain.  Rows r of a call draw as global rows row0 + r, and step[0] is
+ * the draw's counter: a replayed graph draws fresh numbers.  scores (or NULL): f32 [BB, ld_scores >= V], x_c on the kept columns and
+ * -inf elsewhere (HF's processed scores), finished rows included.  flags: one device word, OR-ed into.  No float atomics, fixed
+ * reduction orders: the same inputs give the same bits.  Rows holding +inf or NaN in [0, V), or -inf everywhere, are unspecified
+ * (the token still lies in [0, V)).  Does not allocate, copy or synchronise: it can be captured into a HIP graph. */
+int p2t_sample_select(const void* logits, int dtype, int64_t ld, int V, int BB, const int64_t* eos_ids, int n_eos,
+                      int64_t pad_id, int32_t* finished, int64_t* next_tokens, int64_t* out_tokens, int64_t ld_tokens,
+                      const int32_t* step, int G, float temperature, int top_k, float top_p, uint64_t seed, int64_t row0,
+                      float* scores, int64_t ld_scores, int32_t* flags, p2t_stream stream);
 /* The decode step's projections on their own: out[M, N] = A[M, K] . W[N, K]^T for M <= 64 rows of bf16 -- a weight stream (every
  * byte of W read once, 8 waves split K per 16 output features, partial sums added in wave order; HBM-bound, not MFMA-bound).
  * K % 32 == 0, lda / ldw multiples of 8, no bias.  epilogue: P2T_EPI_STORE (out_dtype P2T_BF16 or P2T_F32), P2T_EPI_STORE_F32,

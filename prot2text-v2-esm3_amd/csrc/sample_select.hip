@@ -1,0 +1,424 @@
+// Token selection by sampling (p2t_sample_select): HF's TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper
+// (transformers/generation/logits_process.py) and the multinomial draw of GenerationMixin._sample, one 1024-thread block per
+// row, with greedy_select_kernel's step bookkeeping (llama_decode.hip).  The contract, every tie-break included, is the comment
+// on p2t_sample_select in include/p2t_hip.h; tests/sampling_reference.py restates it in fp64.
+//
+// The draw of row r (global row row0 + r) at step[0]:
+//     h = mix64(mix64(mix64(seed + 0x9E3779B97F4A7C15) ^ (uint64)(row0 + r)) ^ (uint64)(int64)step[0])      (mix64: common.h)
+//     hash24 = h >> 40,   u = (hash24 + 0.5) * 2^-24,   used as the nearest f32 (= float(2 hash24 + 1) * 2^-25)
+// p2t_hip/synth.py sample_uniform(seed, row, step) is the same chain on the host.
+//
+// Filtered form (top_k on), sample_topk_kernel:
+//   1. kth = the k-th largest STORED logit by a radix select over an order-preserving integer key, 8 bits per pass (two passes
+//      for bf16, four for f32), integer histograms in LDS, one per wave.  x -> x / temperature is monotone, so the k-th largest
+//      x is kth / temperature, also where the division makes two different logits equal.  The select runs twice: first over the
+//      1024 per-thread maxima (one pass over the row, no atomics), whose k-th largest is a lower bound of kth (at least k <= 1024
+//      of the row's values are that large); then over the row, counting only the values at or above the bound -- some 60 of
+//      128 256 at k = 50, a few thousand at k = 1024 -- so the histograms' same-address atomics stay few.  The row is read with
+//      16-byte loads where its pitch and base allow.
+//   2. every column with x >= that is a survivor: collected into an LDS table of kCap (value, index) pairs through an integer
+//      slot counter (any order), its score written.  More than kCap survivors (>= 1025 exact ties): collected again, the
+//      strictly greater ones first, then the ties in ascending index order by a ballot + per-wave-count scan, until full.
+//   3. the table is sorted bitonically by (value descending, index ascending): a total order, so the slot order of 2. is gone.
+//   4. wave 0: e_j = exp(x_j - x_0), a fixed-order scan (per-lane runs of consecutive ranks, then a shuffle scan of the lane
+//      totals), the top-p cut on the tail mass, the inverse CDF at u over the kept ranks.
+// Unfiltered form (top_k off, top_p off), sample_full_kernel: the row maximum, then every wave scans one contiguous segment of
+// columns in ascending order (64 columns per step, shuffle scan), the 16 segment sums are added in wave order, and the wave whose
+// segment holds u * S walks it again with the same arithmetic to find the column.
+// No float atomics; every float reduction has a fixed order: the same inputs give the same bits.  Every LDS index is bounded by
+// kCap / 256 / 16 whatever the counts say, step[0] is clamped, and the token is clamped to [0, V).
+#include "common.h"
+
+namespace p2t {
+namespace {
+
+constexpr int kCap = 2048;                  // survivor table
+constexpr int kNoIndex = 0x7fffffff;
+
+// order-preserving key of a stored logit: a < b as numbers => key(a) < key(b) (-0 below +0: equal as numbers, harmless, the survivor
+// test is on the float).  A bf16 value's key is decided by its upper 16 bits (the lower 16 are all 0 or all 1 with the sign).
+template <typename T> struct KeyBits { static constexpr int N = sizeof(T) == 2 ? 16 : 32; };
+__device__ __forceinline__ uint32_t key_of(float v) {
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_value(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// f(value, column) for the columns of this thread: 16-byte pieces where `vec` says the row allows them, then the tail one by one
+template <typename T, typename F>
+__device__ __forceinline__ void for_each_column(const T* __restrict__ row, int V, bool vec, int tid, F f) {
+    constexpr int PN = sizeof(T) == 2 ? 8 : 4;
+    const int Vv = vec ? V / PN * PN : 0;
+    for (int c = tid * PN; c < Vv; c += 1024 * PN) {
+        float v[PN];
+        if constexpr (PN == 8) load8(row + c, v);
+        else load4(row + c, v);
+#pragma unroll
+        for (int e = 0; e < PN; ++e) f(v[e], c + e);
+    }
+    for (int c = Vv + tid; c < V; c += 1024) f(to_f32(row[c]), c);
+}
+
+// The k-th largest of the keys `each` hands to its callback (every thread its own share; at least k keys in all), by their upper
+// BITS bits, 8 per pass from the top: per-wave integer histograms, a suffix count over the 256 digits by wave 0.  Block-wide call
+// (barriers inside); hist and s_sel are free again on return.
+template <int BITS, typename Each>
+__device__ __forceinline__ uint32_t radix_select(int k, int (*hist)[256], int* s_sel, Each each) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    uint32_t prefix = 0;
+    int k_rem = k;
+    for (int shift = 24; shift >= 32 - BITS; shift -= 8) {
+        for (int i = tid; i < 16 * 256; i += 1024) (&hist[0][0])[i] = 0;
+        if (tid == 0) { s_sel[0] = 0; s_sel[1] = 1; }
+        __syncthreads();
+        const uint32_t above = shift == 24 ? 0u : (0xffffffffu << (shift + 8));          // the digits already fixed
+        each([&](uint32_t key) {
+            if ((key & above) == prefix) atomicAdd(&hist[w][(key >> shift) & 255u], 1);
+        });
+        __syncthreads();
+        if (tid < 256) {
+            int t = 0;
+#pragma unroll
+            for (int ww = 0; ww < 16; ++ww) t += hist[ww][tid];
+            hist[0][tid] = t;                                 // column tid of the table is this thread's alone
+        }
+        __syncthreads();
+        if (w == 0) {                                         // lane l: digits 255 - 4 l .. 252 - 4 l; counts from the top down
+            int cnt[4], tot = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { cnt[i] = hist[0][255 - (4 * lane + i)]; tot += cnt[i]; }
+            int incl = tot;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int t = __shfl_up(incl, o, 64);
+                if (lane >= o) incl += t;
+            }
+            int run = incl - tot;                             // keys in digits above this lane's
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (run < k_rem && k_rem <= run + cnt[i]) { s_sel[0] = 255 - (4 * lane + i); s_sel[1] = k_rem - run; }
+                run += cnt[i];
+            }
+        }
+        __syncthreads();
+        prefix |= (uint32_t)(s_sel[0] & 255) << shift;
+        k_rem = s_sel[1];
+        __syncthreads();
+    }
+    if (BITS == 16 && !(prefix & 0x80000000u)) prefix |= 0xffffu;       // a negative bf16 value: the lower key bits are ones
+    return prefix;
+}
+
+__device__ __forceinline__ float draw_uniform(uint64_t seed, int64_t row, int step) {
+    uint64_t h = mix64(seed + 0x9E3779B97F4A7C15ull);
+    h = mix64(h ^ (uint64_t)row);
+    h = mix64(h ^ (uint64_t)(int64_t)step);
+    return (float)(int)(2u * (uint32_t)(h >> 40) + 1u) * 0x1p-25f;
+}
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ int wave_min_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    return v;
+}
+// inclusive scan over the 64 lanes in a fixed order
+__device__ __forceinline__ float wave_scan(float v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float t = __shfl_up(v, o, 64);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+
+// greedy_select_kernel's rule (llama_decode.hip): a finished row emits pad, the token goes to column clamp(step[0]) of out_tokens,
+// a row finishes once it emits an eos id
+__device__ __forceinline__ void emit_token(int bb, int tok_in, int V, const int64_t* __restrict__ eos, int n_eos, int64_t pad,
+                                           int32_t* __restrict__ finished, int64_t* __restrict__ next, int64_t* __restrict__ out_tokens,
+                                           int64_t ld_tok, int step, int Gcap) {
+    int64_t tok = min(max(tok_in, 0), V - 1);
+    const int fin = finished[bb];
+    if (fin) tok = pad;
+    next[bb] = tok;
+    const int st = min(max(step, 0), Gcap - 1);
+    out_tokens[(int64_t)bb * ld_tok + st] = tok;
+    if (!fin) {
+        for (int e = 0; e < n_eos; ++e)
+            if (tok == eos[e]) finished[bb] = 1;
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(1024) sample_topk_kernel(const T* __restrict__ logits, int64_t ld, int V, const int64_t* __restrict__ eos,
+                                                           int n_eos, int64_t pad, int32_t* __restrict__ finished, int64_t* __restrict__ next,
+                                                           int64_t* __restrict__ out_tokens, int64_t ld_tok, const int32_t* __restrict__ step_ptr,
+                                                           int Gcap, float temperature, int top_k, float top_p, uint64_t seed, int64_t row0,
+                                                           float* __restrict__ scores, int64_t ld_scores, int32_t* __restrict__ flags) {
+    __shared__ int hist[16][256];
+    __shared__ float sv[kCap];            // survivors: x
+    __shared__ int si[kCap];              //            column
+    __shared__ float se[kCap];            //            exp(x - max)
+    __shared__ int s_sel[2], s_cnt, s_wc[16], s_kept, s_tok;
+    const int bb = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const T* row = logits + (int64_t)bb * ld;
+    float* srow = scores ? scores + (int64_t)bb * ld_scores : nullptr;
+    const int k = min(top_k, V);
+
+    // ---- 1. the k-th largest stored logit ------------------------------------------------------------------------------
+    const bool vec = ld % (16 / sizeof(T)) == 0 && ((uintptr_t)logits & 15u) == 0;
+    uint32_t tmax = 0;                                        // below every key of a number (a thread without a column keeps it)
+    for_each_column(row, V, vec, tid, [&](float v, int) { tmax = max(tmax, key_of(v)); });
+    const uint32_t floor_key = radix_select<KeyBits<T>::N>(k, hist, s_sel, [&](auto count) { count(tmax); });      // k <= 1024 keys
+    const uint32_t kth_key = radix_select<KeyBits<T>::N>(k, hist, s_sel, [&](auto count) {
+        for_each_column(row, V, vec, tid, [&](float v, int) {
+            const uint32_t key = key_of(v);
+            if (key >= floor_key) count(key);
+        });
+    });
+    const float xk = key_value(kth_key) / temperature;
+
+    // ---- 2. survivors ----------------------------------------------------------------------------------------------------
+    if (tid == 0) s_cnt = 0;
+    __syncthreads();
+    for_each_column(row, V, vec, tid, [&](float v, int c) {
+        const float x = v / temperature;
+        const bool keep = x >= xk;
+        if (keep) {
+            const int slot = atomicAdd(&s_cnt, 1);
+            if (slot < kCap) { sv[slot] = x; si[slot] = c; }
+        }
+        if (srow) srow[c] = keep ? x : -INFINITY;
+    });
+    __syncthreads();
+    int n = s_cnt;
+    if (n > kCap) {                                           // block-uniform: >= 1025 exact ties at the k-th value
+        __syncthreads();
+        if (tid == 0) { s_cnt = 0; atomicOr(flags, 1); }
+        __syncthreads();
+        for (int c = tid; c < V; c += 1024) {
+            const float x = to_f32(row[c]) / temperature;
+            if (x > xk) {                                     // fewer than k <= 1024 of them
+                const int slot = atomicAdd(&s_cnt, 1);
+                if (slot < kCap) { sv[slot] = x; si[slot] = c; }
+            }
+        }
+        __syncthreads();
+        int base = min(s_cnt, kCap);
+        for (int c0 = 0; c0 < V; c0 += 1024) {                // the ties, ascending column, until the table is full
+            const int c = c0 + tid;
+            const bool eq = c < V && to_f32(row[c]) / temperature == xk;
+            const unsigned long long b = __ballot(eq);
+            if (lane == 0) s_wc[w] = __popcll(b);
+            __syncthreads();
+            int off = base, tot = 0;
+#pragma unroll
+            for (int ww = 0; ww < 16; ++ww) {
+                const int t = s_wc[ww];
+                if (ww < w) off += t;
+                tot += t;
+            }
+            if (eq) {
+                const int slot = off + __popcll(b & ((1ull << lane) - 1ull));
+                if (slot < kCap) { sv[slot] = xk; si[slot] = c; }
+                else if (srow) srow[c] = -INFINITY;
+            }
+            base = min(base + tot, 2 * kCap);                 // saturated: only "full or not" matters from kCap on
+            __syncthreads();
+        }
+        n = min(base, kCap);
+    }
+    if (n < 1) {                                              // only a row outside the contract (NaN) has no survivor
+        if (tid == 0) { sv[0] = -INFINITY; si[0] = 0; }
+        n = 1;
+    }
+    // ---- 3. total order: value descending, column ascending ----------------------------------------------------------------
+    int P = 64;
+    while (P < n) P <<= 1;                                    // <= kCap
+    for (int i = n + tid; i < P; i += 1024) { sv[i] = -INFINITY; si[i] = kNoIndex; }
+    __syncthreads();
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            if (tid < (P >> 1)) {
+                const int i = ((tid / stride) * 2 * stride + (tid % stride)) & (kCap - 1), j = (i + stride) & (kCap - 1);
+                const float va = sv[i], vb = sv[j];
+                const int ia = si[i], ib = si[j];
+                const bool b_first = vb > va || (vb == va && ib < ia);
+                const bool a_first = va > vb || (va == vb && ia < ib);
+                if (((i & size) == 0) ? b_first : a_first) { sv[i] = vb; sv[j] = va; si[i] = ib; si[j] = ia; }
+            }
+            __syncthreads();
+        }
+    }
+    // ---- 4. top-p and the draw, one wave ---------------------------------------------------------------------------------
+    const int step = step_ptr[0];
+    if (w == 0) {
+        const int per = P >> 6, j0 = lane * per;              // lane l: ranks l * per .. l * per + per - 1
+        const float mx = sv[0];
+        float loc = 0.f;
+        for (int i = 0; i < per; ++i) {
+            const int j = j0 + i;
+            const float e = j < n ? expf(sv[j] - mx) : 0.f;
+            se[j] = e;
+            loc += e;
+        }
+        const float incl = wave_scan(loc, lane);
+        const float S = __shfl(incl, 63, 64);
+        float excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 0.f;
+        int m = n;
+        if (top_p < 1.f) {                                    // rank j stays iff sum_{i >= j} e_i > (1 - top_p) S; rank 0 always
+            const float cut = (1.f - top_p) * S;
+            float run = excl;
+            int cnt = 0;
+            for (int i = 0; i < per; ++i) {
+                const int j = j0 + i;
+                if (j < n) {
+                    cnt += (j == 0 || S - run > cut) ? 1 : 0;
+                    run += se[j];
+                }
+            }
+            m = min(max(wave_sum_int(cnt), 1), n);
+        }
+        float run = excl, at_last = 0.f;
+        for (int i = 0; i < per; ++i) {
+            const int j = j0 + i;
+            if (j < m) {
+                run += se[j];
+                if (j == m - 1) at_last = run;
+            }
+        }
+        const float target = draw_uniform(seed, row0 + bb, step) * __shfl(at_last, (m - 1) / per, 64);
+        int cand = kNoIndex;
+        run = excl;
+        for (int i = 0; i < per; ++i) {
+            const int j = j0 + i;
+            if (j < m) {
+                run += se[j];
+                if (run > target && cand == kNoIndex) cand = j;
+            }
+        }
+        cand = wave_min_int(cand);
+        if (cand >= m) cand = m - 1;                          // rounding left none: the last kept rank
+        if (lane == 0) { s_kept = m; s_tok = si[cand & (kCap - 1)]; }
+    }
+    __syncthreads();
+    if (srow) {
+        const int m = s_kept;
+        for (int j = m + tid; j < n; j += 1024) {
+            const int c = si[j];
+            if (c >= 0 && c < V) srow[c] = -INFINITY;
+        }
+    }
+    if (tid == 0) emit_token(bb, s_tok, V, eos, n_eos, pad, finished, next, out_tokens, ld_tok, step, Gcap);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(1024) sample_full_kernel(const T* __restrict__ logits, int64_t ld, int V, const int64_t* __restrict__ eos,
+                                                           int n_eos, int64_t pad, int32_t* __restrict__ finished, int64_t* __restrict__ next,
+                                                           int64_t* __restrict__ out_tokens, int64_t ld_tok, const int32_t* __restrict__ step_ptr,
+                                                           int Gcap, float temperature, uint64_t seed, int64_t row0, float* __restrict__ scores,
+                                                           int64_t ld_scores) {
+    __shared__ float s_max[16], s_sum[16];
+    __shared__ int s_tok;
+    const int bb = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const T* row = logits + (int64_t)bb * ld;
+    float* srow = scores ? scores + (int64_t)bb * ld_scores : nullptr;
+    float mx = -INFINITY;
+    for (int c = tid; c < V; c += 1024) mx = fmaxf(mx, to_f32(row[c]) / temperature);
+    mx = wave_max(mx);
+    if (lane == 0) s_max[w] = mx;
+    if (tid == 0) s_tok = V - 1;                              // rounding left none: the last column
+    __syncthreads();
+    mx = s_max[0];
+#pragma unroll
+    for (int ww = 1; ww < 16; ++ww) mx = fmaxf(mx, s_max[ww]);
+    // wave w: columns [lo, hi), 64 per step in ascending order; cumulative mass of a column = base_w + (run + scan)
+    const int seg = ((V + 15) / 16 + 63) / 64 * 64, lo = min(w * seg, V), hi = min(lo + seg, V);
+    float run = 0.f;
+    for (int c0 = lo; c0 < hi; c0 += 64) {
+        const int c = c0 + lane;
+        float e = 0.f;
+        if (c < hi) {
+            const float x = to_f32(row[c]) / temperature;
+            e = expf(x - mx);
+            if (srow) srow[c] = x;
+        }
+        run = run + __shfl(wave_scan(e, lane), 63, 64);
+    }
+    if (lane == 0) s_sum[w] = run;
+    __syncthreads();
+    float base = 0.f, S = 0.f;
+#pragma unroll
+    for (int ww = 0; ww < 16; ++ww) {
+        if (ww == w) base = S;
+        S += s_sum[ww];
+    }
+    const int step = step_ptr[0];
+    const float target = draw_uniform(seed, row0 + bb, step) * S;
+    // the wave whose segment holds the target: the cumulative mass before it does not pass the target, that of its last column does
+    // (the running sums never decrease, so at most one wave; each wave judges for itself, on its own two numbers.  A block-uniform
+    // "first ww with b + s_sum[ww] > target" loop over the 16 sums was miscompiled by hipcc: the v_cmp of its first round was followed
+    // by an s_cselect on a stale SCC, and a target inside wave 0's segment was given to wave 2)
+    if (!(base > target) && base + s_sum[w] > target) {       // wave-uniform
+        run = 0.f;
+        for (int c0 = lo; c0 < hi; c0 += 64) {
+            const int c = c0 + lane;
+            const float e = c < hi ? expf(to_f32(row[c]) / temperature - mx) : 0.f;
+            const float sc = wave_scan(e, lane);
+            const unsigned long long over = __ballot(c < hi && base + (run + sc) > target);
+            if (over) {
+                if (lane == 0) s_tok = c0 + (__ffsll((long long)over) - 1);
+                break;
+            }
+            run = run + __shfl(sc, 63, 64);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) emit_token(bb, s_tok, V, eos, n_eos, pad, finished, next, out_tokens, ld_tok, step, Gcap);
+}
+
+}  // namespace
+}  // namespace p2t
+
+using namespace p2t;
+
+extern "C" int p2t_sample_select(const void* logits, int dtype, int64_t ld, int V, int BB, const int64_t* eos_ids, int n_eos, int64_t pad_id,
+                                 int32_t* finished, int64_t* next_tokens, int64_t* out_tokens, int64_t ld_tokens, const int32_t* step, int G,
+                                 float temperature, int top_k, float top_p, uint64_t seed, int64_t row0, float* scores, int64_t ld_scores,
+                                 int32_t* flags, p2t_stream stream) {
+    P2T_REQUIRE(logits && finished && next_tokens && out_tokens && step && flags, "p2t_sample_select: null argument");
+    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_sample_select: dtype %d is neither P2T_F32 nor P2T_BF16", dtype);
+    P2T_REQUIRE(BB > 0 && V > 0 && ld >= V, "p2t_sample_select: BB = %d, V = %d, ld = %lld: needs BB > 0, V > 0, ld >= V", BB, V, (long long)ld);
+    P2T_REQUIRE(G > 0 && ld_tokens >= G && n_eos >= 0 && (n_eos == 0 || eos_ids),
+                "p2t_sample_select: G = %d, ld_tokens = %lld, n_eos = %d: needs G > 0, ld_tokens >= G, eos_ids for n_eos > 0", G, (long long)ld_tokens,
+                n_eos);
+    P2T_REQUIRE(temperature > 0.f && temperature < INFINITY, "p2t_sample_select: temperature %g is not a positive finite number", (double)temperature);
+    P2T_REQUIRE(top_k >= 0 && top_k <= 1024, "p2t_sample_select: top_k = %d: 0 (off) or 1 .. 1024", top_k);
+    P2T_REQUIRE(top_p > 0.f, "p2t_sample_select: top_p = %g: in (0, 1), or >= 1 for off", (double)top_p);
+    P2T_REQUIRE(!scores || ld_scores >= V, "p2t_sample_select: ld_scores = %lld < V = %d", (long long)ld_scores, V);
+    if (top_k == 0 && top_p < 1.f) {
+        set_error("p2t_sample_select: top_p = %g without top_k needs a sort of the whole vocabulary: supported are top_k 1 .. 1024 (top_p on or off) "
+                  "and both filters off", (double)top_p);
+        return P2T_ERR_UNSUPPORTED;
+    }
+    hipStream_t s = (hipStream_t)stream;
+#define P2T_SAMPLE_LAUNCH(T)                                                                                                                  \
+    do {                                                                                                                                      \
+        if (top_k > 0)                                                                                                                        \
+            sample_topk_kernel<T><<<BB, 1024, 0, s>>>((const T*)logits, ld, V, eos_ids, n_eos, pad_id, finished, next_tokens, out_tokens,     \
+                                                      ld_tokens, step, G, temperature, top_k, top_p, seed, row0, scores, ld_scores, flags);   \
+        else                                                                                                                                  \
+            sample_full_kernel<T><<<BB, 1024, 0, s>>>((const T*)logits, ld, V, eos_ids, n_eos, pad_id, finished, next_tokens, out_tokens,     \
+                                                      ld_tokens, step, G, temperature, seed, row0, scores, ld_scores);                        \
+    } while (0)
+    if (dtype == P2T_BF16) P2T_SAMPLE_LAUNCH(bf16_t);
+    else P2T_SAMPLE_LAUNCH(float);
+#undef P2T_SAMPLE_LAUNCH
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}

@@ -6,15 +6,18 @@ temperature, do_sample, top_p, top_k, return_dict_in_generate=False).
 What runs where: the prompt compaction, the prefill (all decoder layers + KV-cache write), every decode step (RMSNorm, the
 projections, rotation + cache append, single-query attention over the cache, LM head) and the greedy choice are kernels of
 libp2t_hip (csrc/llama_decode.hip).  After the first step the greedy loop replays ONE captured HIP graph per token (every length
-lives in device memory), and the host looks at the finished flags only every `sync_every` tokens.  Sampling (temperature / top-k /
-top-p filters + multinomial) and the beam bookkeeping (log-softmax, top-k over beams x vocabulary, gathers of the token tables) are
-torch device ops on the [rows, vocab] logits -- selection bookkeeping, restated from transformers/generation/utils.py (`_sample`,
-`_beam_search` and its helpers) and transformers/generation/logits_process.py; the decoder arithmetic never goes through torch.
+lives in device memory), and the host looks at the finished flags only every `sync_every` tokens.  Sampling with `seed=` is the same
+loop with p2t_sample_select (csrc/sample_select.hip: temperature / top-k / top-p and a counter-hashed draw per row and step) in the
+place of the greedy choice, captured and replayed alike.  Sampling with a torch `generator` (temperature / top-k / top-p filters +
+multinomial) and the beam bookkeeping (log-softmax, top-k over beams x vocabulary, gathers of the token tables) are torch device ops
+on the [rows, vocab] logits -- selection bookkeeping, restated from transformers/generation/utils.py (`_sample`, `_beam_search` and
+its helpers) and transformers/generation/logits_process.py; the decoder arithmetic never goes through torch.
 
 Like HF with `inputs_embeds` only, the returned ids hold the NEW tokens only ([batch, <= max_new_tokens])."""
 from __future__ import annotations
 
 import ctypes as C
+import warnings
 from typing import Optional, Sequence
 
 import torch
@@ -132,6 +135,7 @@ class DecodeEngine:
         self.x = torch.zeros((self.BB, s.hidden_size), dtype=torch.float32, device=self.dev)
         self.next_tokens = torch.zeros((self.BB,), dtype=torch.int64, device=self.dev)
         self.finished = torch.zeros((self.BB,), dtype=torch.int32, device=self.dev)
+        self.sample_flags = torch.zeros((1,), dtype=torch.int32, device=self.dev)      # p2t_sample_select ORs into it (bit 0: table full)
         self.out_tokens = torch.zeros((self.BB, self.G), dtype=torch.int64, device=self.dev)
         self.ws = torch.empty((call("p2t_llama_decode_workspace_bytes", C.byref(self.e["cfg"]), self.BB, self.Tp, self.G),), dtype=torch.uint8,
                               device=self.dev)
@@ -190,6 +194,14 @@ class DecodeEngine:
         call("p2t_greedy_select", ptr(logits), ops.dt_of(logits), logits.stride(0), self.spec.vocab_size, self.BB, ptr(eos) if eos.numel() else None,
              eos.numel(), int(pad_id), ptr(self.finished), ptr(self.next_tokens), ptr(self.out_tokens), self.G, ptr(self.step), self.G, stream())
 
+    def sample_select(self, logits: torch.Tensor, eos: torch.Tensor, pad_id: int, temperature: float, top_k: int, top_p: float, seed: int,
+                      scores: Optional[torch.Tensor] = None, row0: int = 0):
+        """The sampled choice in the greedy one's place: row r draws as row0 + r at the device step counter (include/p2t_hip.h)."""
+        call("p2t_sample_select", ptr(logits), ops.dt_of(logits), logits.stride(0), self.spec.vocab_size, self.BB, ptr(eos) if eos.numel() else None,
+             eos.numel(), int(pad_id), ptr(self.finished), ptr(self.next_tokens), ptr(self.out_tokens), self.G, ptr(self.step), self.G,
+             float(temperature), int(top_k), float(top_p), int(seed) & (2 ** 64 - 1), int(row0), ptr(scores) if scores is not None else None,
+             scores.stride(0) if scores is not None else 0, ptr(self.sample_flags), stream())
+
     def reorder(self, src_rows: torch.Tensor):
         """Generated segment row r <- row src_rows[r] (beam re-ordering; the prompt segment is shared by a prompt's beams)."""
         if self.k_alt is None:
@@ -219,9 +231,14 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
              top_k: Optional[int] = 50, top_p: Optional[float] = 1.0, num_beams: int = 1, length_penalty: float = 1.0,
              early_stopping=False, num_return_sequences: int = 1, return_dict_in_generate: bool = False, output_scores: bool = False,
              output_logits: bool = False, use_graph: bool = True, sync_every: int = 16, generator: Optional[torch.Generator] = None,
-             stream_copy: bool = True, fuse_rope: bool = True, **unused):
+             stream_copy: bool = True, fuse_rope: bool = True, seed: Optional[int] = None, **unused):
     """`LlamaForCausalLM.generate` for prompts given as embeddings (or ids): greedy, sampling (temperature / top-k / top-p) and beam
-    search with length penalty.  Returns the new token ids i64 [batch * num_return_sequences, n] (or a GenerateOutput)."""
+    search with length penalty.  Returns the new token ids i64 [batch * num_return_sequences, n] (or a GenerateOutput).
+
+    Sampling draws from torch's `generator` stream with torch ops on the logits (`seed=None`), or, with `seed=int`, on the device
+    (p2t_sample_select) inside the replayed step graph: row b * num_return_sequences + r at step n draws
+    synth.sample_uniform(seed, row, n), whatever else the batch holds.  The device path serves top_k 1 .. 1024 with top_p on or off, and
+    both filters off; it also returns the processed scores (`output_scores=True`).  `seed` is ignored under greedy decoding."""
     if (inputs_embeds is None) == (input_ids is None):
         raise ValueError("pass exactly one of inputs_embeds / input_ids")
     if unused:
@@ -267,15 +284,43 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
         logits = logits.repeat_interleave(R, dim=0)
     V = decoder.spec.vocab_size
     eos = torch.tensor(eos_ids, dtype=torch.int64, device=eng.dev)
-    if do_sample and return_dict_in_generate and output_scores:
+    on_device = bool(do_sample) and seed is not None
+    if on_device:
+        if generator is not None:
+            raise ValueError("generate: pass `seed` (the device sampler) or `generator` (the torch path), not both")
+        temperature = 1.0 if temperature is None else float(temperature)
+        k = 0 if top_k is None or int(top_k) <= 0 else int(top_k)
+        p = 1.0 if top_p is None or float(top_p) >= 1.0 else float(top_p)
+        if not (temperature > 0 and temperature < float("inf")):
+            raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
+        if not p > 0:
+            raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
+        if k > 1024 or (k == 0 and p < 1.0):
+            raise ValueError(f"generate(seed=): the device sampler serves top_k 1 .. 1024 with top_p on or off, and both filters off (got top_k={top_k}, "
+                             f"top_p={top_p}); sample with `generator=` for anything else")
+    if do_sample and return_dict_in_generate and output_scores and not on_device:
         # HF returns the PROCESSED scores (after temperature / top-k / top-p) under sampling; nothing here is pinned on that
         # (the goldens cover greedy and beam search), so the combination is refused rather than answered with the raw logits
         raise NotImplementedError("generate: output_scores with do_sample is not supported (ask for output_logits: the raw LM-head rows)")
-    keep_logits = [] if (return_dict_in_generate and (output_logits or output_scores)) else None
+    keep_scores = [] if (on_device and return_dict_in_generate and output_scores) else None
+    keep_logits = [] if (return_dict_in_generate and (output_logits or (output_scores and not on_device))) else None
+    scores_buf = torch.empty((eng.BB, V), dtype=torch.float32, device=eng.dev) if keep_scores is not None else None
     pad = int(pad_token_id)
+    warned = []
+
+    def table_full() -> None:                             # the sampler's flags word, read where the finished flags are
+        if on_device and not warned and int(eng.sample_flags.item()) & 1:
+            warned.append(True)
+            warnings.warn("generate(seed=): more than 2048 logits tied at the top-k boundary of a row; the ties beyond the table were dropped "
+                          "in ascending column order (HF would keep them all)", RuntimeWarning, stacklevel=3)
+
+    def sample(lg: torch.Tensor):
+        eng.sample_select(lg, eos, pad, temperature, k, p, seed, scores_buf)
 
     def choose(lg: torch.Tensor, col: int):
-        if do_sample:
+        if on_device:
+            sample(lg)                                   # writes column step[0] == col; step[0] is the draw's counter
+        elif do_sample:
             scores = filter_logits(lg[:, :V].float(), temperature, top_k, top_p)
             nxt = torch.multinomial(scores.softmax(dim=-1), num_samples=1, generator=generator).squeeze(1)
             nxt = torch.where(eng.finished.bool(), torch.full_like(nxt, pad), nxt)
@@ -289,17 +334,23 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     def advance():                                        # chosen tokens -> embeddings -> all layers over the cache -> logits -> choice
         eng.feed(eng.next_tokens)
         eng.decode_step()
-        if not do_sample:
+        if on_device:
+            sample(eng.logits)
+        elif not do_sample:
             eng.greedy_select(eng.logits, eos, pad)
 
     choose(logits, 0)
     if keep_logits is not None:
         keep_logits.append(logits[:, :V].float().clone())
+    if keep_scores is not None:
+        keep_scores.append(scores_buf.clone())
     graph, n = None, 1
     while n < max_new_tokens:
-        if eos_ids and (n == 1 or n % sync_every == 0) and bool(eng.finished.all().item()):
-            break
-        if use_graph and not do_sample and n >= 2:        # the first step ran eagerly (lazy one-time initialisation inside the library)
+        if eos_ids and (n == 1 or n % sync_every == 0):
+            table_full()
+            if bool(eng.finished.all().item()):
+                break
+        if use_graph and (on_device or not do_sample) and n >= 2:        # the first step ran eagerly (lazy one-time initialisation inside the library)
             if graph is None:
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph, capture_error_mode="thread_local"):
@@ -307,15 +358,20 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
             graph.replay()
         else:
             advance()
-        if do_sample:
+        if do_sample and not on_device:
             choose(eng.logits, n)
         if keep_logits is not None:
             keep_logits.append(eng.logits[:, :V].float().clone())
+        if keep_scores is not None:
+            keep_scores.append(scores_buf.clone())
         n += 1
+    table_full()
     seqs = _trim(eng.out_tokens, eos_ids, n)
     if not return_dict_in_generate:
         return seqs
     keep = tuple(keep_logits[: seqs.shape[1]]) if keep_logits is not None else None
+    if keep_scores is not None:
+        return GenerateOutput(seqs, scores=tuple(keep_scores[: seqs.shape[1]]), logits=keep if output_logits else None)
     return GenerateOutput(seqs, scores=keep if output_scores else None, logits=keep if output_logits else None)
 
 

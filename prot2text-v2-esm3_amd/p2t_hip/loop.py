@@ -199,6 +199,13 @@ def iterative_generation_loop(rank, model, data_batch: Dict[str, Any], max_gener
                           temperature=temperature, do_sample=do_sample, top_p=top_p, top_k=top_k, **generate_kwargs)
 
 
+def generation_seed(seed: int, rank: int, batch_index: int) -> int:
+    """The 64-bit seed `inference_epoch` hands to generate(seed=) for batch `batch_index` of rank `rank`: the splitmix64 chain of the
+    draw itself (synth.sample_uniform) over (seed, rank, batch index)."""
+    from .synth import mix64
+    return mix64(mix64(mix64((int(seed) + 0x9E3779B97F4A7C15) & (2 ** 64 - 1)) ^ (int(rank) & (2 ** 64 - 1))) ^ (int(batch_index) & (2 ** 64 - 1)))
+
+
 def inference_epoch(rank, model, dataloader: Iterable[Dict[str, Any]], llama_tokenizer, args: Dict[str, Any],
                     progress: Optional[Callable] = None) -> Optional[str]:
     """scripts/generate_instruct.py:90-147: generate for every batch of this rank's shard, decode predictions and labels with the
@@ -209,11 +216,15 @@ def inference_epoch(rank, model, dataloader: Iterable[Dict[str, Any]], llama_tok
     import os
     model.eval()
     names, preds, labels = [], [], []
+    r = rank if isinstance(rank, int) else (torch.device(rank).index or 0)
     for i, data_batch in enumerate(dataloader):
+        # args["seed"] (optional): the device sampler's seed of this call, mixed from (seed, rank, batch index) so that neither two ranks
+        # nor two successive batches draw from one stream (generate(seed=): row and step are the stream's other two coordinates)
+        kw = {} if args.get("seed") is None else {"seed": generation_seed(args["seed"], r, i)}
         with torch.no_grad():
             out = iterative_generation_loop(rank, model, data_batch, args["max_generation_length"], args.get("num_beams", 1),
                                             args.get("length_penalty", 1.0), args.get("temperature", 1.0), args.get("do_sample", False),
-                                            args.get("top_p", 1.0), args.get("top_k", 50))
+                                            args.get("top_p", 1.0), args.get("top_k", 50), **kw)
         names.extend(data_batch["name"])
         preds.extend(llama_tokenizer.batch_decode(out.cpu(), skip_special_tokens=True))
         labels.extend(llama_tokenizer.batch_decode(data_batch["description_input_ids"], skip_special_tokens=True))
@@ -221,7 +232,6 @@ def inference_epoch(rank, model, dataloader: Iterable[Dict[str, Any]], llama_tok
             progress(i, {"mode": "inference", "batch_maxlen_gen": out.shape[1], "device": f"rank:{rank}"})
     if not args.get("save_generation_dir"):
         return None
-    r = rank if isinstance(rank, int) else (torch.device(rank).index or 0)
     path = os.path.join(args["save_generation_dir"], f"generation_{args['save_generation_postfix_identifier']}_rank{r}.json")
     with open(path, "w") as f:
         json.dump({n: {"true": t, "pred": p} for n, t, p in zip(names, labels, preds)}, f, indent=4)

@@ -51,6 +51,26 @@ def _mix(x: np.ndarray) -> np.ndarray:
     return x
 
 
+def mix64(x: int) -> int:
+    """The splitmix64 finaliser on one Python int (csrc/common.h mix64)."""
+    x &= _MASK64
+    x ^= x >> 30
+    x = (x * int(_M1)) & _MASK64
+    x ^= x >> 27
+    x = (x * int(_M2)) & _MASK64
+    return x ^ (x >> 31)
+
+
+def sample_uniform(seed: int, row: int, step: int) -> float:
+    """The uniform number p2t_sample_select draws for global row `row` at step counter `step` under `seed` (csrc/sample_select.hip):
+    h = mix64(mix64(mix64(seed + GOLDEN) ^ row) ^ step), u = ((h >> 40) + 0.5) * 2^-24: exact as a Python float, in (0, 1).  The
+    kernel uses it rounded to fp32."""
+    h = mix64((int(seed) + int(_GOLDEN)) & _MASK64)
+    h = mix64(h ^ (int(row) & _MASK64))
+    h = mix64(h ^ (int(step) & _MASK64))
+    return ((h >> 40) + 0.5) * 2.0 ** -24
+
+
 def hash_u24(seed: int, name: str, start: int, count: int) -> np.ndarray:
     add, xor = stream_key(seed, name)
     idx = np.arange(start, start + count, dtype=np.uint64)

@@ -3,7 +3,10 @@ decoding): B prompts of 1024 residues + 64 prompt tokens, N new tokens.  Prints 
 HBM roofline of the step: every decoder weight is read once per step (bf16: 2 bytes x (32 layers x (qkv + o + gate/up + down) + LM
 head)) plus the keys / values of the cache -- the algorithmic bytes of a step; frac = (bytes / step time) / 8 TB/s.
 python tools/generate_bench.py [B] [N] [beams] [fp8] > gpurun_out/generate_bench.log      (fp8: set_gemm_dtype("fp8"): e4m3 decoder weights,
-half the projection bytes of a step; the LM head stays bf16)"""
+half the projection bytes of a step; the LM head stays bf16)
+python tools/generate_bench.py [B] [N] sample: the three ways of choosing a token in one process, top_k=50, top_p=0.9, temperature=0.7: ms per
+decode step of greedy decoding, of sampling with torch ops on the logits (`generator=`: no graph) and of the device sampler (`seed=`: graph
+replay), and p2t_sample_select's own time on [B, vocab] bf16 logits (HIP events around 200 launches)."""
 import os
 import sys
 import time
@@ -17,11 +20,58 @@ import p2t_hip as P                                             # noqa: E402
 from p2t_hip import generation, specs, synth                    # noqa: E402
 
 
+def sampler_alone(B: int, V: int, dev, iters: int = 200) -> float:
+    """-> microseconds per p2t_sample_select launch on randn * 3 bf16 logits (top_k 50, top_p 0.9, temperature 0.7)."""
+    from p2t_hip import _lib
+    from p2t_hip.ops import ptr, stream
+    ld = (V + 63) // 64 * 64
+    lg = (torch.randn((B, ld), device=dev, generator=torch.Generator(device=dev).manual_seed(0)) * 3).to(torch.bfloat16)
+    fin, nxt = torch.zeros((B,), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int64, device=dev)
+    out, flags, step = torch.zeros((B, 64), dtype=torch.int64, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev)
+    go = lambda: _lib.call("p2t_sample_select", ptr(lg), _lib.BF16, ld, V, B, None, 0, 0, ptr(fin), ptr(nxt), ptr(out), 64, ptr(step), 64, 0.7, 50, 0.9, 1, 0,
+                           None, 0, ptr(flags), stream())
+    for _ in range(10):
+        go()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        go()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / iters
+
+
+def sample_mode(model, kw, B: int, N: int, V: int, dev):
+    gen = torch.Generator(device=dev)
+    sampling = dict(do_sample=True, top_k=50, top_p=0.9, temperature=0.7)
+    cases = [("greedy (graph replay)", dict(do_sample=False)),
+             ("sampling, torch ops on the logits (generator=; eager launches)", dict(**sampling, generator=gen.manual_seed(1))),
+             ("sampling, p2t_sample_select (seed=; graph replay)", dict(**sampling, seed=1))]
+    for _, extra in cases:                                       # warm-up of each path
+        model.generate(**{**kw, **extra, "max_new_tokens": 4})
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    model.generate(**{**kw, "max_new_tokens": 1})
+    torch.cuda.synchronize()
+    t_prompt = time.perf_counter() - t0
+    for name, extra in cases:
+        best = None
+        for _ in range(2):
+            t0 = time.perf_counter()
+            model.generate(**{**kw, **extra})
+            torch.cuda.synchronize()
+            dt = (time.perf_counter() - t0 - t_prompt) / (N - 1)
+            best = dt if best is None else min(best, dt)
+        print(f"generate cfg3: B={B}, {N} new tokens, {name}: {best * 1e3:.3f} ms/step", flush=True)
+    print(f"p2t_sample_select alone, [{B}, {V}] bf16 logits, top_k=50 top_p=0.9 temperature=0.7: {sampler_alone(B, V, dev):.1f} us per launch", flush=True)
+
+
 def main():
     dev = torch.device("cuda:0")
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
     N = int(sys.argv[2]) if len(sys.argv) > 2 else 128
-    beams = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+    sample = len(sys.argv) > 3 and sys.argv[3] == "sample"
+    beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample else 1
     fp8 = len(sys.argv) > 4 and sys.argv[4] == "fp8"
     esm_name, llama_name, _, _, Tp, _ = specs.CONFIGS["cfg3"]
     esm, llama = specs.esm_spec(esm_name), specs.llama_spec(llama_name)
@@ -39,6 +89,8 @@ def main():
     t = lambda a: torch.from_numpy(a).to(dev)
     kw = dict(inputs=t(ids), attention_mask=torch.ones((B, T), dtype=torch.int64, device=dev), protein_input_ids=t(pid),
               protein_attention_mask=t(pmask), max_new_tokens=N, eos_token_id=None, pad_token_id=128002, do_sample=False, num_beams=beams)
+    if sample:
+        return sample_mode(model, kw, B, N, llama.vocab_size, dev)
     out = model.generate(**{**kw, "max_new_tokens": 4})          # warm-up: engines, workspaces, lazy initialisation
     torch.cuda.synchronize()
     # prompt phase alone
