@@ -650,6 +650,57 @@ int p2t_sample_select(const void* logits, int dtype, int64_t ld, int V, int BB, 
                       int64_t pad_id, int32_t* finished, int64_t* next_tokens, int64_t* out_tokens, int64_t ld_tokens,
                       const int32_t* step, int G, float temperature, int top_k, float top_p, uint64_t seed, int64_t row0,
                       float* scores, int64_t ld_scores, int32_t* flags, p2t_stream stream);
+/* Choice by beam search: one step of transformers' `_beam_search` (5.x, generation/utils.py) with an empty id prompt
+ * (decoder_prompt_len 0, max_length = max_new_tokens), for B0 prompts of nb = num_beams rows each (row b nb + j = beam j of prompt b).
+ * State, all on the device and the caller's.  Tables and per-beam vectors have TWO halves: a step at cur = step[0] reads half cur & 1
+ * and writes half (cur + 1) & 1 (rows move between beams, so they are never updated in place); a fresh state lies in half 0. */
+typedef struct {
+    int64_t* run_seq;        /* i64 [2][B0][nb][G]  running sequences; columns the search has not reached hold the caller's fill (pad_id) */
+    int32_t* run_idx;        /* i32 [2][B0][nb][G]  the global row (b nb + beam) every token of them was continued from; fill -1 */
+    float* run_scores;       /* f32 [2][B0][nb]     running scores; fresh: 0 for beam 0, -1e9 for the others */
+    int64_t* fin_seq;        /* i64 [2][B0][nb][G]  finished hypotheses, best first */
+    int32_t* fin_idx;        /* i32 [2][B0][nb][G]  their beam indices */
+    float* fin_scores;       /* f32 [2][B0][nb]     their length-normalised scores; fresh: -1e9 */
+    int32_t* is_finished;    /* i32 [2][B0][nb]     1 where a slot holds a finished hypothesis; fresh: 0 */
+    int32_t* heuristic_open; /* i32 [B0]            1 while a running beam of the prompt can still beat its worst finished one; fresh: 1 */
+    int32_t* done;           /* i32 [2]             {1 once the search has stopped, the number of steps it took}; fresh: 0, 0.  The final
+                                                    tables lie in half done[1] & 1 */
+    int32_t* sync;           /* i32 [1 + B0]        ticket and per-prompt flags of the stop condition; zeroed once by the caller */
+    float* workspace;        /* p2t_beam_workspace_bytes(B0, nb) bytes, carries the candidates from the first launch to the second */
+} p2t_beam_state;
+size_t p2t_beam_workspace_bytes(int B0, int num_beams);
+/* logits: `dtype` (F32 | BF16) [B0 nb, ld >= V], the rows' next-token logits (columns V .. ld are never read).  With cur = step[0],
+ * keep = max(2, 1 + n_eos) nb, and every value an f32:
+ *   1. per row r: mx = the largest stored logit; S = sum over c < V of expf(x_c - mx), added in a fixed order (1024 threads take the
+ *      columns in 16-byte pieces, each adds its own in ascending order; 64 lanes by a butterfly; 16 waves in order); lse = logf(S);
+ *      lp_c = (x_c - mx) - lse  (two subtractions, in this order).  scores (or NULL): f32 [B0 nb, ld_scores >= V] = lp, which is what HF
+ *      returns as the step's `scores` under beam search.
+ *   2. per prompt, candidates (beam j, column c) with acc = lp_c + run_scores[j] (one addition).  The keep best by acc, ranked by
+ *      (acc descending, beam ascending, then inside a beam stored logit descending, column ascending): x -> acc is monotone, so this
+ *      is the rank key (acc descending, flat index j V + c ascending) wherever two different logits of a beam do not round to the
+ *      same acc.  Candidate k of the ranked list: token t_k, beam j_k, acc a_k.
+ *   3. hit_k = (cur + 1 >= max_length) or t_k in eos_ids.  live_k = a_k + (hit_k ? -1e9 : -0).  The nb best by (live descending, k
+ *      ascending) go on: running row i <- row j_k of half cur & 1 with t_k at column cur, run_idx[.., cur] = b nb + j_k, run_scores[i]
+ *      = live_k; next_tokens[b nb + i] = t_k and src_rows[b nb + i] = b nb + j_k (what p2t_kv_reorder takes).
+ *   4. just_k = hit_k and k < nb.  fin_k = a_k / float(pow(double(cur + 1), double(length_penalty)))  (an IEEE f32 division), then
+ *      fin_k += (all nb slots finished before the step and early_stopping == 1) ? -1e9 : -0; += heuristic_open ? -0 : -1e9;
+ *      += just_k ? -0 : -1e9, in this order.  The nb old finished slots followed by the keep candidates are ranked by (score
+ *      descending, position ascending); the nb best become the finished slots (sequence, beam indices, score, flag = old flag or
+ *      just_k).
+ *   5. heuristic_open &= any over finished slots i of run_scores[0] / float(pow(double(len), double(length_penalty))) > (is_finished[i] ?
+ *      min over all nb slots of fin_scores : -1e9), len = max_length if early_stopping == 2 ("never") and length_penalty > 0, else cur + 1.
+ *   6. the search goes on iff any prompt is open, and not (every slot of every prompt finished and early_stopping == 1), and not every
+ *      candidate k of every prompt a hit; otherwise, or when cur + 1 >= max_length, done = {1, cur + 1}.
+ * Once done[0] is set (or with cur outside [0, max_length)) a call leaves the state untouched, writes pad_id to next_tokens and the
+ * identity to src_rows: replayed steps past the end are harmless.  Supported: 1 <= nb <= 16, keep <= 64, V >= keep, B0 nb V < 2^31;
+ * otherwise P2T_ERR_UNSUPPORTED.  Malformed arguments (null pointers, ld < V, non-positive counts, G not a multiple of 64, max_length
+ * > G, NaN penalty, early_stopping outside 0 .. 2): P2T_ERR_ARG before any GPU call.  G is the row length of the tables.  Rows holding
+ * +inf or NaN in [0, V) are unspecified (every index stays in range).  Two launches, no float atomics, fixed reduction orders: the same
+ * inputs give the same bits.  Does not allocate, copy or synchronise: it can be captured into a HIP graph. */
+int p2t_beam_select(const void* logits, int dtype, int64_t ld, int B0, int num_beams, int V, const int64_t* eos_ids, int n_eos,
+                    int64_t pad_id, float length_penalty, int early_stopping, int max_length, int G, const int32_t* step,
+                    const p2t_beam_state* state, int64_t* next_tokens, int64_t* src_rows, float* scores, int64_t ld_scores,
+                    p2t_stream stream);
 /* The decode step's projections on their own: out[M, N] = A[M, K] . W[N, K]^T for M <= 64 rows of bf16 -- a weight stream (every
  * byte of W read once, 8 waves split K per 16 output features, partial sums added in wave order; HBM-bound, not MFMA-bound).
  * K % 32 == 0, lda / ldw multiples of 8, no bias.  epilogue: P2T_EPI_STORE (out_dtype P2T_BF16 or P2T_F32), P2T_EPI_STORE_F32,

@@ -87,6 +87,11 @@ class KvCacheC(C.Structure):
                 ("B0", C.c_int32), ("group", C.c_int32), ("Tp", C.c_int32), ("G", C.c_int32)]
 
 
+class BeamStateC(C.Structure):
+    _fields_ = [(n, vp) for n in ("run_seq", "run_idx", "run_scores", "fin_seq", "fin_idx", "fin_scores", "is_finished", "heuristic_open", "done",
+                                  "sync", "workspace")]
+
+
 class LlamaLayerStreamC(C.Structure):
     _fields_ = [(n, vp) for n in ("qkv_w", "o_w", "gu_w", "down_w")]
 
@@ -103,7 +108,7 @@ class FlatChunkC(C.Structure):
 FLAT_NORM_BLOCKS, FLAT_CHUNK = 1024, 4096            # P2T_FLAT_NORM_BLOCKS, P2T_FLAT_CHUNK
 
 _STRUCTS = [EsmConfigC, EsmLayerC, EsmWeightsC, LlamaConfigC, LlamaLayerC, LlamaWeightsC, AdapterConfigC,
-            AdapterWeightsC, AdapterSavedC, LlamaLayerTC, KvCacheC, LlamaLayerStreamC, FlatSegmentC, FlatChunkC]
+            AdapterWeightsC, AdapterSavedC, LlamaLayerTC, KvCacheC, LlamaLayerStreamC, FlatSegmentC, FlatChunkC, BeamStateC]
 
 # name -> (restype, argtypes); every symbol include/p2t_hip.h declares
 SIGNATURES = {
@@ -154,6 +159,8 @@ SIGNATURES = {
                               i32, vp, sz, vp]),
     "p2t_greedy_select": (i32, [vp, i32, i64, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, i32, vp]),
     "p2t_sample_select": (i32, [vp, i32, i64, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, i32, f32, i32, f32, u64, i64, vp, i64, vp, vp]),
+    "p2t_beam_workspace_bytes": (sz, [i32, i32]),
+    "p2t_beam_select": (i32, [vp, i32, i64, i32, i32, i32, vp, i32, i64, f32, i32, i32, i32, vp, C.POINTER(BeamStateC), vp, vp, vp, i64, vp]),
     "p2t_attention_decode": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp, i64, vp]),
     "p2t_gemm_nt_skinny": (i32, [vp, i64, vp, i64, i32, vp, i64, i64, i64, i64, i32, i32, vp]),
     "p2t_preshuffle_w": (i32, [vp, i64, i64, i64, vp, vp]),
@@ -224,7 +231,7 @@ for _i, _s in enumerate(_STRUCTS):
         raise ImportError(f"ABI mismatch: {_s.__name__} is {C.sizeof(_s)} bytes here, {lib.p2t_struct_size(_i)} in the library")
 
 _NO_RC = {"p2t_gemm_fix_workspace_bytes", "p2t_version", "p2t_is_lab_build", "p2t_last_error", "p2t_struct_size", "p2t_esm2_workspace_bytes", "p2t_llama_workspace_bytes", "p2t_llama_tape_bytes", "p2t_llama_train_workspace_bytes", "p2t_llama_prefill_workspace_bytes", "p2t_llama_decode_workspace_bytes",
-          "p2t_adapter_backward_workspace_bytes", "p2t_adapter_backward_dx_workspace_bytes", "p2t_lora_wgrad_workspace_bytes"}
+          "p2t_adapter_backward_workspace_bytes", "p2t_adapter_backward_dx_workspace_bytes", "p2t_lora_wgrad_workspace_bytes", "p2t_beam_workspace_bytes"}
 
 
 def call(name: str, *args):

@@ -8,10 +8,13 @@ projections, rotation + cache append, single-query attention over the cache, LM 
 libp2t_hip (csrc/llama_decode.hip).  After the first step the greedy loop replays ONE captured HIP graph per token (every length
 lives in device memory), and the host looks at the finished flags only every `sync_every` tokens.  Sampling with `seed=` is the same
 loop with p2t_sample_select (csrc/sample_select.hip: temperature / top-k / top-p and a counter-hashed draw per row and step) in the
-place of the greedy choice, captured and replayed alike.  Sampling with a torch `generator` (temperature / top-k / top-p filters +
-multinomial) and the beam bookkeeping (log-softmax, top-k over beams x vocabulary, gathers of the token tables) are torch device ops
-on the [rows, vocab] logits -- selection bookkeeping, restated from transformers/generation/utils.py (`_sample`, `_beam_search` and
-its helpers) and transformers/generation/logits_process.py; the decoder arithmetic never goes through torch.
+place of the greedy choice, captured and replayed alike.  Beam search selects with p2t_beam_select (csrc/beam_select.hip: log-softmax,
+the cut to max(2, 1 + n_eos) * beams candidates, the finished slots, the stop condition and the token tables, all in device memory)
+and replays a graph of two steps, since the beam re-ordering swaps two cache buffers.  Sampling with a torch `generator` (temperature /
+top-k / top-p filters + multinomial) and the beam bookkeeping under `beam_select="torch"` or outside the kernel's range (log-softmax,
+top-k over beams x vocabulary, gathers of the token tables) are torch device ops on the [rows, vocab] logits -- selection bookkeeping,
+restated from transformers/generation/utils.py (`_sample`, `_beam_search` and its helpers) and transformers/generation/
+logits_process.py; the decoder arithmetic never goes through torch.
 
 Like HF with `inputs_embeds` only, the returned ids hold the NEW tokens only ([batch, <= max_new_tokens])."""
 from __future__ import annotations
@@ -231,14 +234,20 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
              top_k: Optional[int] = 50, top_p: Optional[float] = 1.0, num_beams: int = 1, length_penalty: float = 1.0,
              early_stopping=False, num_return_sequences: int = 1, return_dict_in_generate: bool = False, output_scores: bool = False,
              output_logits: bool = False, use_graph: bool = True, sync_every: int = 16, generator: Optional[torch.Generator] = None,
-             stream_copy: bool = True, fuse_rope: bool = True, seed: Optional[int] = None, **unused):
+             stream_copy: bool = True, fuse_rope: bool = True, seed: Optional[int] = None, beam_select: Optional[str] = None, **unused):
     """`LlamaForCausalLM.generate` for prompts given as embeddings (or ids): greedy, sampling (temperature / top-k / top-p) and beam
     search with length penalty.  Returns the new token ids i64 [batch * num_return_sequences, n] (or a GenerateOutput).
 
     Sampling draws from torch's `generator` stream with torch ops on the logits (`seed=None`), or, with `seed=int`, on the device
     (p2t_sample_select) inside the replayed step graph: row b * num_return_sequences + r at step n draws
     synth.sample_uniform(seed, row, n), whatever else the batch holds.  The device path serves top_k 1 .. 1024 with top_p on or off, and
-    both filters off; it also returns the processed scores (`output_scores=True`).  `seed` is ignored under greedy decoding."""
+    both filters off; it also returns the processed scores (`output_scores=True`).  `seed` is ignored under greedy decoding.
+
+    Beam search (`num_beams > 1`) selects on the device as well (p2t_beam_select, two launches per token) and, with `use_graph`, replays
+    a captured graph of two steps; the host reads the search's `done` word every `sync_every` tokens.  `beam_select`: None (default) =
+    the device path wherever it applies (num_beams <= 16, max(2, 1 + number of eos ids) * num_beams <= 64), the torch bookkeeping
+    otherwise; "device" = required (ValueError outside that range); "torch" = the torch bookkeeping, one host read per token.  Ties
+    rank by (score descending, candidate index ascending) on the device path; torch.topk leaves them unspecified."""
     if (inputs_embeds is None) == (input_ids is None):
         raise ValueError("pass exactly one of inputs_embeds / input_ids")
     if unused:
@@ -272,7 +281,8 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
         if do_sample:
             raise NotImplementedError("beam sampling (num_beams > 1 with do_sample=True) is not built")
         return _beam_search(decoder, inputs_embeds, attention_mask, max_new_tokens, eos_ids, int(pad_token_id), num_beams, float(length_penalty),
-                            early_stopping, num_return_sequences, return_dict_in_generate, output_scores, output_logits, stream_copy)
+                            early_stopping, num_return_sequences, return_dict_in_generate, output_scores, output_logits, stream_copy,
+                            beam_select, use_graph, sync_every)
     R = int(num_return_sequences)
     if R != 1 and not do_sample:
         raise ValueError("greedy decoding returns one sequence per prompt: num_return_sequences > 1 needs do_sample=True or num_beams > 1")
@@ -384,81 +394,83 @@ def _gather_beams(t: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return torch.take_along_dim(t, idx, dim=1)
 
 
-def _beam_search(decoder, inputs_embeds, attention_mask, max_length: int, eos_ids, pad_id: int, nb: int, length_penalty: float, early_stopping,
-                 num_return_sequences: int, return_dict: bool, output_scores: bool, output_logits: bool, stream_copy: bool = True):
-    B = inputs_embeds.shape[0]
-    eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, stream_copy)
-    dev, V = eng.dev, decoder.spec.vocab_size
-    embeds, mask = eng.compact(inputs_embeds, attention_mask)
-    first_logits = eng.prefill(embeds, mask)                                 # [B, ld]: the beams of a prompt start from the same state
-    eos = torch.tensor(eos_ids, dtype=torch.int64, device=dev)
-    keep = max(2, 1 + len(eos_ids)) * nb
-    top_mask = torch.cat((torch.ones(nb, dtype=torch.bool), torch.zeros(keep - nb, dtype=torch.bool))).to(dev)
-    fill = pad_id
-    running = torch.full((B, nb, max_length), fill, dtype=torch.int64, device=dev)
-    sequences = running.clone()
+BEAMS_MAX, KEEP_MAX = 16, 64                  # p2t_beam_select's supported range (include/p2t_hip.h)
+
+
+def beam_keep(nb: int, n_eos: int) -> int:
+    return max(2, 1 + n_eos) * nb
+
+
+def beam_select_supported(B: int, nb: int, n_eos: int, V: int) -> bool:
+    keep = beam_keep(nb, n_eos)
+    return 1 <= nb <= BEAMS_MAX and keep <= KEEP_MAX and V >= keep and B * nb * V < 2 ** 31
+
+
+def beam_state_init(B: int, nb: int, max_length: int, pad_id: int, dev) -> dict:
+    """The state `_beam_search` starts from (HF: running_sequences, running_beam_scores, sequences, beam_scores, is_sent_finished,
+    next_token_hits_stopping_criteria's open flag, running_beam_indices, beam_indices)."""
+    running = torch.full((B, nb, max_length), pad_id, dtype=torch.int64, device=dev)
     running_scores = torch.zeros((B, nb), dtype=torch.float32, device=dev)
     running_scores[:, 1:] = -1e9
-    beam_scores = torch.full((B, nb), -1e9, dtype=torch.float32, device=dev)
-    is_finished = torch.zeros((B, nb), dtype=torch.bool, device=dev)
-    heuristic_open = torch.ones((B, 1), dtype=torch.bool, device=dev)
     running_idx = torch.full((B, nb, max_length), -1, dtype=torch.int32, device=dev)
-    beam_idx_tab = running_idx.clone()
-    all_scores, all_logits = [], []
-    cur = 0
-    while True:
-        if cur == 0:
-            logits = first_logits[:, :V].float().repeat_interleave(nb, dim=0)     # HF expands the prompt nb times before its prefill
-        else:
-            logits = eng.logits[:, :V].float()
-        log_probs = torch.log_softmax(logits, dim=-1)
-        if return_dict and output_logits:
-            all_logits.append(logits.clone())
-        if return_dict and output_scores:
-            all_scores.append(log_probs.clone())
-        acc = (log_probs.view(B, nb, V) + running_scores[:, :, None]).reshape(B, nb * V)
-        topk_lp, topk_i = torch.topk(acc, k=keep)
-        src_beam = topk_i // V
-        topk_idx = _gather_beams(running_idx, src_beam)
-        topk_seq = _gather_beams(running, src_beam)
-        topk_seq[:, :, cur] = topk_i % V
-        topk_idx[:, :, cur] = (src_beam + torch.arange(B, device=dev).view(-1, 1) * nb).to(torch.int32)
-        # stopping criteria on the candidates: max length, eos
-        hits = torch.full((B, keep), cur + 1 >= max_length, dtype=torch.bool, device=dev)
-        if eos_ids:
-            hits |= torch.isin(topk_seq[:, :, cur], eos)
-        # beams that go on
-        live_lp = topk_lp + hits.float() * -1.0e9
-        nxt = torch.topk(live_lp, k=nb)[1]
-        running = _gather_beams(topk_seq, nxt)
-        running_scores = _gather_beams(live_lp, nxt)
-        running_idx = _gather_beams(topk_idx, nxt)
-        # finished hypotheses
-        just_done = hits & top_mask[None, :]
-        fin_lp = topk_lp / ((cur + 1) ** length_penalty)
-        full = torch.all(is_finished, dim=-1, keepdim=True) & (early_stopping is True)
-        fin_lp = fin_lp + full.float() * -1.0e9 + (~heuristic_open).float() * -1.0e9 + (~just_done).float() * -1.0e9
-        m_seq, m_sc = torch.cat((sequences, topk_seq), 1), torch.cat((beam_scores, fin_lp), 1)
-        m_idx, m_fin = torch.cat((beam_idx_tab, topk_idx), 1), torch.cat((is_finished, just_done), 1)
-        sel = torch.topk(m_sc, k=nb)[1]
-        sequences, beam_scores = _gather_beams(m_seq, sel), _gather_beams(m_sc, sel)
-        beam_idx_tab, is_finished = _gather_beams(m_idx, sel), _gather_beams(m_fin, sel)
-        # the rows the next step continues from
-        src_rows = running_idx[:, :, cur].reshape(-1).to(torch.int64)
-        cur += 1
-        best_len = max_length if (early_stopping == "never" and length_penalty > 0.0) else cur
-        best_running = running_scores[:, :1] / (best_len ** length_penalty)
-        worst_done = torch.where(is_finished, torch.min(beam_scores, dim=1, keepdim=True)[0], torch.full_like(beam_scores, -1.0e9))
-        heuristic_open = heuristic_open & torch.any(best_running > worst_done, dim=-1, keepdim=True)
-        go_on = torch.any(heuristic_open) & ~(torch.all(is_finished) & (early_stopping is True)) & ~torch.all(hits)
-        if not bool(go_on.item()) or cur >= max_length:
-            break
-        if cur > 1:
-            eng.reorder(src_rows)                       # generated keys / values follow their beams (nothing is cached before step 1)
-        eng.next_tokens.copy_(running[:, :, cur - 1].reshape(-1))
-        eng.feed(eng.next_tokens)
-        eng.decode_step()
-    R = num_return_sequences
+    return dict(running=running, sequences=running.clone(), running_scores=running_scores,
+                beam_scores=torch.full((B, nb), -1e9, dtype=torch.float32, device=dev),
+                is_finished=torch.zeros((B, nb), dtype=torch.bool, device=dev), heuristic_open=torch.ones((B, 1), dtype=torch.bool, device=dev),
+                running_idx=running_idx, beam_idx_tab=running_idx.clone())
+
+
+def beam_step_torch(st: dict, logits: torch.Tensor, cur: int, nb: int, eos: torch.Tensor, length_penalty: float, early_stopping,
+                    max_length: int):
+    """One step of the torch path on f32 logits [B * nb, V] (any device): -> (new state, log_probs, src_rows i64 [B * nb], hits, go_on)."""
+    dev, V = logits.device, logits.shape[1]
+    B = logits.shape[0] // nb
+    keep = beam_keep(nb, eos.numel())
+    top_mask = torch.cat((torch.ones(nb, dtype=torch.bool), torch.zeros(keep - nb, dtype=torch.bool))).to(dev)
+    running, running_scores, running_idx = st["running"], st["running_scores"], st["running_idx"]
+    sequences, beam_scores, beam_idx_tab = st["sequences"], st["beam_scores"], st["beam_idx_tab"]
+    is_finished, heuristic_open = st["is_finished"], st["heuristic_open"]
+    log_probs = torch.log_softmax(logits, dim=-1)
+    acc = (log_probs.view(B, nb, V) + running_scores[:, :, None]).reshape(B, nb * V)
+    topk_lp, topk_i = torch.topk(acc, k=keep)
+    src_beam = topk_i // V
+    topk_idx = _gather_beams(running_idx, src_beam)
+    topk_seq = _gather_beams(running, src_beam)
+    topk_seq[:, :, cur] = topk_i % V
+    topk_idx[:, :, cur] = (src_beam + torch.arange(B, device=dev).view(-1, 1) * nb).to(torch.int32)
+    # stopping criteria on the candidates: max length, eos
+    hits = torch.full((B, keep), cur + 1 >= max_length, dtype=torch.bool, device=dev)
+    if eos.numel():
+        hits |= torch.isin(topk_seq[:, :, cur], eos)
+    # beams that go on
+    live_lp = topk_lp + hits.float() * -1.0e9
+    nxt = torch.topk(live_lp, k=nb)[1]
+    running = _gather_beams(topk_seq, nxt)
+    running_scores = _gather_beams(live_lp, nxt)
+    running_idx = _gather_beams(topk_idx, nxt)
+    # finished hypotheses
+    just_done = hits & top_mask[None, :]
+    fin_lp = topk_lp / ((cur + 1) ** length_penalty)
+    full = torch.all(is_finished, dim=-1, keepdim=True) & (early_stopping is True)
+    fin_lp = fin_lp + full.float() * -1.0e9 + (~heuristic_open).float() * -1.0e9 + (~just_done).float() * -1.0e9
+    m_seq, m_sc = torch.cat((sequences, topk_seq), 1), torch.cat((beam_scores, fin_lp), 1)
+    m_idx, m_fin = torch.cat((beam_idx_tab, topk_idx), 1), torch.cat((is_finished, just_done), 1)
+    sel = torch.topk(m_sc, k=nb)[1]
+    sequences, beam_scores = _gather_beams(m_seq, sel), _gather_beams(m_sc, sel)
+    beam_idx_tab, is_finished = _gather_beams(m_idx, sel), _gather_beams(m_fin, sel)
+    # the rows the next step continues from
+    src_rows = running_idx[:, :, cur].reshape(-1).to(torch.int64)
+    cur += 1
+    best_len = max_length if (early_stopping == "never" and length_penalty > 0.0) else cur
+    best_running = running_scores[:, :1] / (best_len ** length_penalty)
+    worst_done = torch.where(is_finished, torch.min(beam_scores, dim=1, keepdim=True)[0], torch.full_like(beam_scores, -1.0e9))
+    heuristic_open = heuristic_open & torch.any(best_running > worst_done, dim=-1, keepdim=True)
+    go_on = torch.any(heuristic_open) & ~(torch.all(is_finished) & (early_stopping is True)) & ~torch.all(hits)
+    new = dict(running=running, sequences=sequences, running_scores=running_scores, beam_scores=beam_scores, is_finished=is_finished,
+               heuristic_open=heuristic_open, running_idx=running_idx, beam_idx_tab=beam_idx_tab)
+    return new, log_probs, src_rows, hits, go_on
+
+
+def _beam_output(sequences, beam_scores, beam_idx_tab, B, R, return_dict, output_scores, output_logits, all_scores, all_logits):
     sequences, beam_scores, beam_idx_tab = sequences[:, :R].reshape(B * R, -1), beam_scores[:, :R].reshape(-1), beam_idx_tab[:, :R].reshape(B * R, -1)
     n = int(((beam_idx_tab + 1).bool()).sum(dim=1).max().item())
     sequences = sequences[:, :n]
@@ -466,3 +478,142 @@ def _beam_search(decoder, inputs_embeds, attention_mask, max_length: int, eos_id
         return sequences
     return GenerateOutput(sequences, scores=tuple(all_scores) if output_scores else None, logits=tuple(all_logits) if output_logits else None,
                           sequences_scores=beam_scores if output_scores else None, beam_indices=beam_idx_tab[:, :n])
+
+
+def _beam_search(decoder, inputs_embeds, attention_mask, max_length: int, eos_ids, pad_id: int, nb: int, length_penalty: float, early_stopping,
+                 num_return_sequences: int, return_dict: bool, output_scores: bool, output_logits: bool, stream_copy: bool = True,
+                 beam_select: Optional[str] = None, use_graph: bool = True, sync_every: int = 16):
+    if beam_select not in (None, "device", "torch"):
+        raise ValueError(f"generate: beam_select = {beam_select!r}: 'device', 'torch' or None")
+    B, V = inputs_embeds.shape[0], decoder.spec.vocab_size
+    if beam_select != "torch":
+        if beam_select_supported(B, nb, len(eos_ids), V):
+            return _beam_search_device(decoder, inputs_embeds, attention_mask, max_length, eos_ids, pad_id, nb, length_penalty, early_stopping,
+                                       num_return_sequences, return_dict, output_scores, output_logits, stream_copy, use_graph, sync_every)
+        if beam_select == "device":
+            raise ValueError(f"generate(beam_select='device'): p2t_beam_select serves 1 <= num_beams <= {BEAMS_MAX} with max(2, 1 + number of eos ids) * "
+                             f"num_beams <= {KEEP_MAX} <= vocabulary (got num_beams = {nb}, {len(eos_ids)} eos ids); the torch path serves the rest")
+    eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, stream_copy)
+    dev = eng.dev
+    embeds, mask = eng.compact(inputs_embeds, attention_mask)
+    first_logits = eng.prefill(embeds, mask)                                 # [B, ld]: the beams of a prompt start from the same state
+    eos = torch.tensor(eos_ids, dtype=torch.int64, device=dev)
+    st = beam_state_init(B, nb, max_length, pad_id, dev)
+    all_scores, all_logits = [], []
+    cur = 0
+    while True:
+        if cur == 0:
+            logits = first_logits[:, :V].float().repeat_interleave(nb, dim=0)     # HF expands the prompt nb times before its prefill
+        else:
+            logits = eng.logits[:, :V].float()
+        if return_dict and output_logits:
+            all_logits.append(logits.clone())
+        st, log_probs, src_rows, _, go_on = beam_step_torch(st, logits, cur, nb, eos, length_penalty, early_stopping, max_length)
+        if return_dict and output_scores:
+            all_scores.append(log_probs)
+        cur += 1
+        if not bool(go_on.item()) or cur >= max_length:
+            break
+        if cur > 1:
+            eng.reorder(src_rows)                       # generated keys / values follow their beams (nothing is cached before step 1)
+        eng.next_tokens.copy_(st["running"][:, :, cur - 1].reshape(-1))
+        eng.feed(eng.next_tokens)
+        eng.decode_step()
+    return _beam_output(st["sequences"], st["beam_scores"], st["beam_idx_tab"], B, num_return_sequences, return_dict, output_scores, output_logits,
+                        all_scores, all_logits)
+
+
+class BeamState:
+    """p2t_beam_state of one generate() call (include/p2t_hip.h): double-buffered tables, a fresh state in half 0."""
+
+    def __init__(self, B: int, nb: int, G: int, pad_id: int, dev):
+        self.B, self.nb, self.G = B, nb, G
+        self.run_seq = torch.full((2, B, nb, G), pad_id, dtype=torch.int64, device=dev)
+        self.fin_seq = self.run_seq.clone()
+        self.run_idx = torch.full((2, B, nb, G), -1, dtype=torch.int32, device=dev)
+        self.fin_idx = self.run_idx.clone()
+        self.run_scores = torch.zeros((2, B, nb), dtype=torch.float32, device=dev)
+        self.run_scores[:, :, 1:] = -1e9
+        self.fin_scores = torch.full((2, B, nb), -1e9, dtype=torch.float32, device=dev)
+        self.is_finished = torch.zeros((2, B, nb), dtype=torch.int32, device=dev)
+        self.heuristic_open = torch.ones((B,), dtype=torch.int32, device=dev)
+        self.done = torch.zeros((2,), dtype=torch.int32, device=dev)
+        self.sync = torch.zeros((1 + B,), dtype=torch.int32, device=dev)
+        self.workspace = torch.zeros((call("p2t_beam_workspace_bytes", B, nb) // 4,), dtype=torch.float32, device=dev)
+        self.c = _lib.BeamStateC(**{n: getattr(self, n).data_ptr() for n, _ in _lib.BeamStateC._fields_})
+
+
+def beam_select(logits: torch.Tensor, V: int, state: BeamState, eos: torch.Tensor, pad_id: int, length_penalty: float, early_stopping,
+                max_length: int, step: torch.Tensor, next_tokens: torch.Tensor, src_rows: torch.Tensor, scores: Optional[torch.Tensor] = None):
+    """One p2t_beam_select call: logits `dtype` [B nb, ld >= V] -> next_tokens, src_rows i64 [B nb] and the state's other half."""
+    es = 1 if early_stopping is True else (2 if early_stopping == "never" else 0)
+    call("p2t_beam_select", ptr(logits), ops.dt_of(logits), logits.stride(0), state.B, state.nb, V, ptr(eos) if eos.numel() else None, eos.numel(),
+         int(pad_id), float(length_penalty), es, int(max_length), state.G, ptr(step), C.byref(state.c), ptr(next_tokens), ptr(src_rows),
+         ptr(scores) if scores is not None else None, scores.stride(0) if scores is not None else 0, stream())
+
+
+def _beam_search_device(decoder, inputs_embeds, attention_mask, max_length: int, eos_ids, pad_id: int, nb: int, length_penalty: float,
+                        early_stopping, num_return_sequences: int, return_dict: bool, output_scores: bool, output_logits: bool,
+                        stream_copy: bool, use_graph: bool, sync_every: int):
+    """The same search with p2t_beam_select in the torch bookkeeping's place: the first token from the prefill logits, one eager step, then
+    a replayed graph of TWO steps (reorder, feed, decode, select, twice: the engine's cache buffers are back where the capture found
+    them), an odd remainder eagerly.  The host reads `done` every `sync_every` tokens and at the end; steps run past the stop leave
+    the state as it is."""
+    B, V = inputs_embeds.shape[0], decoder.spec.vocab_size
+    eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, stream_copy)
+    dev = eng.dev
+    embeds, mask = eng.compact(inputs_embeds, attention_mask)
+    first = eng.prefill(embeds, mask).repeat_interleave(nb, dim=0).contiguous()     # HF expands the prompt nb times before its prefill
+    eos = torch.tensor(eos_ids, dtype=torch.int64, device=dev)
+    st = BeamState(B, nb, eng.G, pad_id, dev)
+    src_rows = torch.zeros((eng.BB,), dtype=torch.int64, device=dev)
+    keep_scores, keep_logits = return_dict and output_scores, return_dict and output_logits
+    # two step slots: a replayed pair leaves the logits / log-probabilities of both its steps to be cloned afterwards
+    lslots = [eng.logits, torch.zeros_like(eng.logits)] if keep_logits else [eng.logits, eng.logits]
+    sslots = [torch.empty((eng.BB, V), dtype=torch.float32, device=dev) for _ in range(2)] if keep_scores else [None, None]
+    all_scores, all_logits = [], []
+
+    def select(lg, slot):
+        beam_select(lg, V, st, eos, pad_id, length_penalty, early_stopping, max_length, eng.step, eng.next_tokens, src_rows, sslots[slot])
+
+    def keep(lg, slot):
+        if keep_logits:
+            all_logits.append(lg[:, :V].float().clone())
+        if keep_scores:
+            all_scores.append(sslots[slot].clone())
+
+    def advance(slot):
+        eng.logits = lslots[slot]
+        eng.reorder(src_rows)                           # generated keys / values follow their beams (a no-op while nothing is cached)
+        eng.feed(eng.next_tokens)
+        eng.decode_step()
+        select(eng.logits, slot)
+
+    select(first, 0)
+    keep(first, 0)
+    graph, n, read_at = None, 1, 0
+    while n < max_length:
+        if n == 1 or n - read_at >= sync_every:
+            read_at = n
+            if bool(st.done[0].item()):
+                break
+        if use_graph and n >= 2 and max_length - n >= 2:                  # the first step ran eagerly (lazy one-time initialisation inside the library)
+            if graph is None:
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    advance(0)
+                    advance(1)
+            graph.replay()
+            keep(lslots[0], 0)
+            keep(lslots[1], 1)
+            n += 2
+        else:
+            advance(0)
+            keep(lslots[0], 0)
+            n += 1
+    done, steps = (int(v) for v in st.done.tolist())
+    if not done:
+        raise RuntimeError("generate: the beam search ran its max_new_tokens steps and p2t_beam_select did not raise `done`")
+    half = steps & 1
+    return _beam_output(st.fin_seq[half], st.fin_scores[half], st.fin_idx[half], B, num_return_sequences, return_dict, output_scores, output_logits,
+                        all_scores[:steps], all_logits[:steps])

@@ -221,6 +221,8 @@ def inference_epoch(rank, model, dataloader: Iterable[Dict[str, Any]], llama_tok
         # args["seed"] (optional): the device sampler's seed of this call, mixed from (seed, rank, batch index) so that neither two ranks
         # nor two successive batches draw from one stream (generate(seed=): row and step are the stream's other two coordinates)
         kw = {} if args.get("seed") is None else {"seed": generation_seed(args["seed"], r, i)}
+        if args.get("beam_select") is not None:              # "device" | "torch": generate(beam_select=), the default picks by range
+            kw["beam_select"] = args["beam_select"]
         with torch.no_grad():
             out = iterative_generation_loop(rank, model, data_batch, args["max_generation_length"], args.get("num_beams", 1),
                                             args.get("length_penalty", 1.0), args.get("temperature", 1.0), args.get("do_sample", False),

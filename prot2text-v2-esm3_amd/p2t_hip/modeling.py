@@ -852,7 +852,8 @@ class LlamaDecoder(nn.Module):
     def generate(self, inputs=None, attention_mask=None, inputs_embeds=None, **kwargs):
         """`LlamaForCausalLM.generate` over the KV-cache decode path (p2t_hip/generation.py): prompts as `inputs_embeds` (what
         Esm2LlamaInstructForCausalLM.generate passes, reference :246-250) or as ids (`inputs` / `input_ids`); greedy, sampling
-        (temperature / top_k / top_p) and beam search (num_beams, length_penalty).  The result holds the NEW tokens only (HF does
+        (temperature / top_k / top_p) and beam search (num_beams, length_penalty, early_stopping; `beam_select="device" | "torch" | None`
+        chooses between the device kernel under graph replay and the torch bookkeeping).  The result holds the NEW tokens only (HF does
         the same for `inputs_embeds`; for id prompts HF prepends the prompt, this path does not)."""
         from . import generation
         ids = kwargs.pop("input_ids", inputs)

@@ -6,7 +6,10 @@ python tools/generate_bench.py [B] [N] [beams] [fp8] > gpurun_out/generate_bench
 half the projection bytes of a step; the LM head stays bf16)
 python tools/generate_bench.py [B] [N] sample: the three ways of choosing a token in one process, top_k=50, top_p=0.9, temperature=0.7: ms per
 decode step of greedy decoding, of sampling with torch ops on the logits (`generator=`: no graph) and of the device sampler (`seed=`: graph
-replay), and p2t_sample_select's own time on [B, vocab] bf16 logits (HIP events around 200 launches)."""
+replay), and p2t_sample_select's own time on [B, vocab] bf16 logits (HIP events around 200 launches).
+python tools/generate_bench.py [B] [N] [beams > 1]: beam search three ways, interleaved, three runs each (median and min .. max): the torch
+bookkeeping (`beam_select="torch"`: one host read per token), p2t_beam_select with eager launches and under replay of the two-step graph;
+then B * beams greedy rows under replay, p2t_beam_select's two launches alone, and p2t_kv_reorder at 30 and at 250 generated tokens."""
 import os
 import sys
 import time
@@ -66,6 +69,72 @@ def sample_mode(model, kw, B: int, N: int, V: int, dev):
     print(f"p2t_sample_select alone, [{B}, {V}] bf16 logits, top_k=50 top_p=0.9 temperature=0.7: {sampler_alone(B, V, dev):.1f} us per launch", flush=True)
 
 
+def _events(go, iters: int) -> float:
+    """-> microseconds per call of go(), HIP events around `iters` calls after 10 warm-up calls."""
+    for _ in range(10):
+        go()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        go()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / iters
+
+
+def beam_mode(model, kw, B: int, N: int, beams: int, V: int, dev):
+    cases = [("torch bookkeeping (beam_select=\"torch\"; eager launches, one host read per token)", dict(beam_select="torch")),
+             ("p2t_beam_select, eager launches", dict(beam_select="device", use_graph=False)),
+             ("p2t_beam_select, two-step graph replay", dict(beam_select="device", use_graph=True))]
+    for _, extra in cases:
+        model.generate(**{**kw, **extra, "max_new_tokens": 6})
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    model.generate(**{**kw, "max_new_tokens": 1, "beam_select": "device"})
+    torch.cuda.synchronize()
+    t_prompt = time.perf_counter() - t0
+    runs = {name: [] for name, _ in cases}
+    for _ in range(3):                                           # interleaved: a drift of the box hits all three alike
+        for name, extra in cases:
+            t0 = time.perf_counter()
+            model.generate(**{**kw, **extra})
+            torch.cuda.synchronize()
+            runs[name].append((time.perf_counter() - t0 - t_prompt) / (N - 1) * 1e3)
+    for name, r in runs.items():
+        print(f"generate cfg3: B={B} beams={beams}, {N} new tokens, {name}: median {np.median(r):.3f} ms/step (min {min(r):.3f}, max {max(r):.3f}; 3 runs)", flush=True)
+    # the same number of rows, greedy, under replay
+    rows = B * beams
+    gkw = {k: (v.repeat_interleave(beams, dim=0) if isinstance(v, torch.Tensor) else v) for k, v in kw.items()}
+    gkw["num_beams"] = 1
+    model.generate(**{**gkw, "max_new_tokens": 4})
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    model.generate(**{**gkw, "max_new_tokens": 1})
+    torch.cuda.synchronize()
+    tg = time.perf_counter() - t0
+    r = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        model.generate(**gkw)
+        torch.cuda.synchronize()
+        r.append((time.perf_counter() - t0 - tg) / (N - 1) * 1e3)
+    print(f"generate cfg3: {rows} greedy rows, {N} new tokens, graph replay: median {np.median(r):.3f} ms/step (min {min(r):.3f}, max {max(r):.3f}; 3 runs)", flush=True)
+    # the two select launches alone: a fresh state at step 0, nothing finishes, so every call does the full work
+    ld = (V + 63) // 64 * 64
+    lg = (torch.randn((rows, ld), device=dev, generator=torch.Generator(device=dev).manual_seed(0)) * 3).to(torch.bfloat16)
+    st = generation.BeamState(B, beams, 256, 0, dev)
+    step, nxt, src = (torch.zeros((n,), dtype=dt, device=dev) for n, dt in ((1, torch.int32), (rows, torch.int64), (rows, torch.int64)))
+    eos = torch.zeros((0,), dtype=torch.int64, device=dev)
+    us = _events(lambda: generation.beam_select(lg, V, st, eos, 0, 1.0, False, 256, step, nxt, src), 200)
+    print(f"p2t_beam_select alone (both launches), [{rows}, {V}] bf16 logits, {beams} beams: {us:.1f} us per call", flush=True)
+    # the beam re-ordering copy of the generated cache segment at two lengths
+    eng = generation.DecodeEngine(model.llama_decoder, B, beams, 64, 256)
+    ident = torch.arange(rows, dtype=torch.int64, device=dev)
+    for at in (30, 250):
+        eng.step.fill_(at)
+        print(f"p2t_kv_reorder, {rows} rows, {at} generated tokens: {_events(lambda: eng.reorder(ident), 50):.1f} us per call", flush=True)
+
+
 def main():
     dev = torch.device("cuda:0")
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
@@ -91,6 +160,8 @@ def main():
               protein_attention_mask=t(pmask), max_new_tokens=N, eos_token_id=None, pad_token_id=128002, do_sample=False, num_beams=beams)
     if sample:
         return sample_mode(model, kw, B, N, llama.vocab_size, dev)
+    if beams > 1:
+        return beam_mode(model, kw, B, N, beams, llama.vocab_size, dev)
     out = model.generate(**{**kw, "max_new_tokens": 4})          # warm-up: engines, workspaces, lazy initialisation
     torch.cuda.synchronize()
     # prompt phase alone
