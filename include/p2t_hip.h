@@ -701,6 +701,46 @@ int p2t_beam_select(const void* logits, int dtype, int64_t ld, int B0, int num_b
                     int64_t pad_id, float length_penalty, int early_stopping, int max_length, int G, const int32_t* step,
                     const p2t_beam_state* state, int64_t* next_tokens, int64_t* src_rows, float* scores, int64_t ld_scores,
                     p2t_stream stream);
+/* Choice by beam sampling: one step of `_beam_search` with do_sample=True (HF's beam-search multinomial sampling), with
+ * p2t_beam_select's arguments, state (the same p2t_beam_state, halves and `done`; the workspace holds
+ * p2t_beam_sample_workspace_bytes(B0, nb) bytes) and bookkeeping, and the sampler's temperature / top_k / top_p / seed.  HF draws keep
+ * continuations per prompt without replacement from softmax(processed log-probabilities + running scores) over nb V candidates
+ * (`_get_top_k_continuations`); a draw without replacement is the descending order of score + Gumbel noise, and the noise here is a
+ * counter hash per candidate.  With cur = step[0], keep = max(2, 1 + n_eos) nb, and every value an f32:
+ *   1. per row: mx, S, lse, lp_c = (x_c - mx) - lse: step 1 of p2t_beam_select, the same fixed summation order.
+ *   2. the warpers in HF's order, on the log-probabilities.  y_c = lp_c / temperature (an IEEE division).  top_k: the survivors are the
+ *      columns whose STORED logit is >= the min(top_k, V)-th largest stored logit, ties included; x -> y is monotone, so this is HF's
+ *      set wherever two different logits do not round to one y.  The table holds 2048: beyond that, all logits above the threshold and
+ *      the ties in ascending column order until it is full, and bit 0 of *flags is set.  Ranks: (stored logit descending, column
+ *      ascending).  top_p: e_j = expf(y_j - y_0); rank j is kept iff sum_{i >= j} e_i > (1 - top_p) sum_i e_i (ranks added in
+ *      ascending order), rank 0 always.  Both filters off: every column is kept.  scores (or NULL): f32 [B0 nb, ld_scores >= V], y_c on
+ *      the kept columns and -inf elsewhere: HF's processed scores of the step.
+ *   3. a kept candidate (beam j, column c) of prompt b: acc = y_c + run_scores[j] (one addition);
+ *      h = mix64(mix64(mix64(mix64(seed + 0x9E3779B97F4A7C15) ^ (uint64)(prompt0 + b)) ^ (uint64)(int64)cur) ^ (uint64)(j V + c));
+ *      u = (2 (h >> 41) + 1) * 2^-24 (an odd 24-bit integer times 2^-24: exact, strictly inside (0, 1));  g = -logf(-logf(u));
+ *      key = acc + g (one addition).  p2t_hip.synth.beam_sample_uniform(seed, prompt, step, flat_index) restates u.
+ *   4. the prompt's kept candidates are ranked by (key descending, flat index j V + c ascending); the first keep of them IN THAT ORDER
+ *      are HF's keep draws in draw order.  Candidate k of the list: token t_k, beam j_k and a_k = acc, the UNPERTURBED score (HF
+ *      gathers the accumulated log-probabilities at the drawn indices).
+ *   5. steps 3 - 6 of p2t_beam_select on that list, unchanged: hits and live, the nb best live rows by (live descending, k ascending),
+ *      just_k = hit_k and k < nb, the length-normalised merge into the finished slots, the open / closed heuristic, the stop condition,
+ *      `done`, pad_id and the identity once stopped (the state is then left alone).
+ *   6. bit 1 of *flags is set when a prompt has fewer than keep kept candidates over all its beams, or when a_(keep-1) is not within 100
+ *      of the prompt's best acc (max over its beams of y_0 + run_scores[j]): HF's f32 softmax gives such a candidate probability 0
+ *      and torch.multinomial fails there.  The results are then unspecified, but every index stays in range and the tables hold no NaN
+ *      (-inf scores are possible).
+ * temperature > 0 and finite; top_k 0 (off) or 1 .. 1024; top_p >= 1 (off) or in (0, 1); flags: one device word, OR-ed into -- else
+ * P2T_ERR_ARG, like p2t_beam_select's malformed arguments, before any GPU call.  top_p on without top_k, and anything outside
+ * p2t_beam_select's range (nb <= 16, keep <= 64, V >= keep, B0 nb V < 2^31): P2T_ERR_UNSUPPORTED.  step[0] is the draw's counter: a
+ * replayed graph draws fresh numbers.  Rows holding +inf or NaN in [0, V) are unspecified (every index stays in range).  Two launches,
+ * no float atomics, fixed reduction orders: the same inputs give the same bits.  Does not allocate, copy or synchronise: it can be
+ * captured into a HIP graph. */
+size_t p2t_beam_sample_workspace_bytes(int B0, int num_beams);
+int p2t_beam_sample_select(const void* logits, int dtype, int64_t ld, int B0, int num_beams, int V, const int64_t* eos_ids, int n_eos,
+                           int64_t pad_id, float length_penalty, int early_stopping, int max_length, int G, const int32_t* step,
+                           const p2t_beam_state* state, int64_t* next_tokens, int64_t* src_rows, float* scores, int64_t ld_scores,
+                           float temperature, int top_k, float top_p, uint64_t seed, int64_t prompt0, int32_t* flags,
+                           p2t_stream stream);
 /* The decode step's projections on their own: out[M, N] = A[M, K] . W[N, K]^T for M <= 64 rows of bf16 -- a weight stream (every
  * byte of W read once, 8 waves split K per 16 output features, partial sums added in wave order; HBM-bound, not MFMA-bound).
  * K % 32 == 0, lda / ldw multiples of 8, no bias.  epilogue: P2T_EPI_STORE (out_dtype P2T_BF16 or P2T_F32), P2T_EPI_STORE_F32,

@@ -161,6 +161,9 @@ SIGNATURES = {
     "p2t_sample_select": (i32, [vp, i32, i64, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, i32, f32, i32, f32, u64, i64, vp, i64, vp, vp]),
     "p2t_beam_workspace_bytes": (sz, [i32, i32]),
     "p2t_beam_select": (i32, [vp, i32, i64, i32, i32, i32, vp, i32, i64, f32, i32, i32, i32, vp, C.POINTER(BeamStateC), vp, vp, vp, i64, vp]),
+    "p2t_beam_sample_workspace_bytes": (sz, [i32, i32]),
+    "p2t_beam_sample_select": (i32, [vp, i32, i64, i32, i32, i32, vp, i32, i64, f32, i32, i32, i32, vp, C.POINTER(BeamStateC), vp, vp, vp, i64, f32, i32, f32,
+                                     u64, i64, vp, vp]),
     "p2t_attention_decode": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp, i64, vp]),
     "p2t_gemm_nt_skinny": (i32, [vp, i64, vp, i64, i32, vp, i64, i64, i64, i64, i32, i32, vp]),
     "p2t_preshuffle_w": (i32, [vp, i64, i64, i64, vp, vp]),
@@ -231,7 +234,8 @@ for _i, _s in enumerate(_STRUCTS):
         raise ImportError(f"ABI mismatch: {_s.__name__} is {C.sizeof(_s)} bytes here, {lib.p2t_struct_size(_i)} in the library")
 
 _NO_RC = {"p2t_gemm_fix_workspace_bytes", "p2t_version", "p2t_is_lab_build", "p2t_last_error", "p2t_struct_size", "p2t_esm2_workspace_bytes", "p2t_llama_workspace_bytes", "p2t_llama_tape_bytes", "p2t_llama_train_workspace_bytes", "p2t_llama_prefill_workspace_bytes", "p2t_llama_decode_workspace_bytes",
-          "p2t_adapter_backward_workspace_bytes", "p2t_adapter_backward_dx_workspace_bytes", "p2t_lora_wgrad_workspace_bytes", "p2t_beam_workspace_bytes"}
+          "p2t_adapter_backward_workspace_bytes", "p2t_adapter_backward_dx_workspace_bytes", "p2t_lora_wgrad_workspace_bytes", "p2t_beam_workspace_bytes",
+          "p2t_beam_sample_workspace_bytes"}
 
 
 def call(name: str, *args):

@@ -10,7 +10,9 @@ lives in device memory), and the host looks at the finished flags only every `sy
 loop with p2t_sample_select (csrc/sample_select.hip: temperature / top-k / top-p and a counter-hashed draw per row and step) in the
 place of the greedy choice, captured and replayed alike.  Beam search selects with p2t_beam_select (csrc/beam_select.hip: log-softmax,
 the cut to max(2, 1 + n_eos) * beams candidates, the finished slots, the stop condition and the token tables, all in device memory)
-and replays a graph of two steps, since the beam re-ordering swaps two cache buffers.  Sampling with a torch `generator` (temperature /
+and replays a graph of two steps, since the beam re-ordering swaps two cache buffers.  Beam sampling (`num_beams > 1, do_sample=True`
+with `seed=` and `beam_select="device"`) is that loop with p2t_beam_sample_select (csrc/beam_sample_select.hip: the warpers on the
+log-probabilities and keep draws without replacement as the descending order of score + counter-hashed Gumbel noise).  Sampling with a torch `generator` (temperature /
 top-k / top-p filters + multinomial) and the beam bookkeeping under `beam_select="torch"` or outside the kernel's range (log-softmax,
 top-k over beams x vocabulary, gathers of the token tables) are torch device ops on the [rows, vocab] logits -- selection bookkeeping,
 restated from transformers/generation/utils.py (`_sample`, `_beam_search` and its helpers) and transformers/generation/
@@ -243,6 +245,12 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     synth.sample_uniform(seed, row, n), whatever else the batch holds.  The device path serves top_k 1 .. 1024 with top_p on or off, and
     both filters off; it also returns the processed scores (`output_scores=True`).  `seed` is ignored under greedy decoding.
 
+    Beam sampling (`num_beams > 1, do_sample=True`: HF's beam-search multinomial sampling) is opt-in: `seed=int` with
+    `beam_select="device"` runs p2t_beam_sample_select in the beam search's loop and graph (prompt b draws as prompt b at the device step
+    counter: synth.beam_sample_uniform; top_k 0 or max(2, 1 + number of eos ids) * num_beams .. 1024, top_p only with top_k), and
+    `generator=` with `beam_select="torch"` runs the torch restatement of HF's two lines (torch.multinomial without replacement).  Every
+    other form of that call raises NotImplementedError.
+
     Beam search (`num_beams > 1`) selects on the device as well (p2t_beam_select, two launches per token) and, with `use_graph`, replays
     a captured graph of two steps; the host reads the search's `done` word every `sync_every` tokens.  `beam_select`: None (default) =
     the device path wherever it applies (num_beams <= 16, max(2, 1 + number of eos ids) * num_beams <= 64), the torch bookkeeping
@@ -278,11 +286,12 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     if num_beams < 1 or num_return_sequences < 1 or num_return_sequences > num_beams and num_beams > 1:
         raise ValueError("num_beams >= 1 and 1 <= num_return_sequences <= num_beams")
     if num_beams > 1:
+        sampling = None
         if do_sample:
-            raise NotImplementedError("beam sampling (num_beams > 1 with do_sample=True) is not built")
+            sampling = _beam_sampling_args(num_beams, len(eos_ids), temperature, top_k, top_p, seed, generator, beam_select)
         return _beam_search(decoder, inputs_embeds, attention_mask, max_new_tokens, eos_ids, int(pad_token_id), num_beams, float(length_penalty),
                             early_stopping, num_return_sequences, return_dict_in_generate, output_scores, output_logits, stream_copy,
-                            beam_select, use_graph, sync_every)
+                            beam_select, use_graph, sync_every, sampling)
     R = int(num_return_sequences)
     if R != 1 and not do_sample:
         raise ValueError("greedy decoding returns one sequence per prompt: num_return_sequences > 1 needs do_sample=True or num_beams > 1")
@@ -394,6 +403,31 @@ def _gather_beams(t: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return torch.take_along_dim(t, idx, dim=1)
 
 
+def _beam_sampling_args(nb: int, n_eos: int, temperature, top_k, top_p, seed, generator, beam_select) -> dict:
+    """The sampling side of `num_beams > 1, do_sample=True`: which path, and its filters checked up front."""
+    if seed is not None and generator is not None:
+        raise ValueError("generate: pass `seed` (the device sampler) or `generator` (the torch path), not both")
+    device = seed is not None and beam_select == "device"
+    if not device and not (generator is not None and beam_select == "torch"):
+        raise NotImplementedError("beam sampling (num_beams > 1 with do_sample=True) is opt-in: pass seed=int together with beam_select='device' "
+                                  "(p2t_beam_sample_select), or generator= together with beam_select='torch'")
+    temperature = 1.0 if temperature is None else float(temperature)
+    k = 0 if top_k is None or int(top_k) <= 0 else int(top_k)
+    p = 1.0 if top_p is None or float(top_p) >= 1.0 else float(top_p)
+    if not (temperature > 0 and temperature < float("inf")):
+        raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
+    if not p > 0:
+        raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
+    keep = beam_keep(nb, n_eos)
+    if device and (k > 1024 or (k == 0 and p < 1.0)):
+        raise ValueError(f"generate(seed=): the device sampler serves top_k 1 .. 1024 with top_p on or off, and both filters off (got top_k={top_k}, "
+                         f"top_p={top_p}); sample with `generator=` for anything else")
+    if 0 < k < keep:
+        raise ValueError(f"generate: beam sampling draws max(2, 1 + number of eos ids) * num_beams = {keep} continuations per prompt, and the first "
+                         f"step has one live beam: top_k = {k} cannot supply them (needs top_k >= {keep}, or 0)")
+    return dict(device=device, temperature=temperature, top_k=k, top_p=p, seed=seed, generator=generator)
+
+
 BEAMS_MAX, KEEP_MAX = 16, 64                  # p2t_beam_select's supported range (include/p2t_hip.h)
 
 
@@ -420,8 +454,11 @@ def beam_state_init(B: int, nb: int, max_length: int, pad_id: int, dev) -> dict:
 
 
 def beam_step_torch(st: dict, logits: torch.Tensor, cur: int, nb: int, eos: torch.Tensor, length_penalty: float, early_stopping,
-                    max_length: int):
-    """One step of the torch path on f32 logits [B * nb, V] (any device): -> (new state, log_probs, src_rows i64 [B * nb], hits, go_on)."""
+                    max_length: int, do_sample: bool = False, generator: Optional[torch.Generator] = None, temperature: float = 1.0,
+                    top_k: Optional[int] = None, top_p: Optional[float] = None):
+    """One step of the torch path on f32 logits [B * nb, V] (any device): -> (new state, log_probs, src_rows i64 [B * nb], hits, go_on).
+    do_sample: the warpers run on the log-probabilities (HF appends the processed rows as the step's scores) and the keep continuations
+    are torch.multinomial draws without replacement, HF's two lines; the new state then also holds them as "drawn" [B, keep]."""
     dev, V = logits.device, logits.shape[1]
     B = logits.shape[0] // nb
     keep = beam_keep(nb, eos.numel())
@@ -430,8 +467,14 @@ def beam_step_torch(st: dict, logits: torch.Tensor, cur: int, nb: int, eos: torc
     sequences, beam_scores, beam_idx_tab = st["sequences"], st["beam_scores"], st["beam_idx_tab"]
     is_finished, heuristic_open = st["is_finished"], st["heuristic_open"]
     log_probs = torch.log_softmax(logits, dim=-1)
+    if do_sample:
+        log_probs = filter_logits(log_probs, temperature, top_k, top_p)
     acc = (log_probs.view(B, nb, V) + running_scores[:, :, None]).reshape(B, nb * V)
-    topk_lp, topk_i = torch.topk(acc, k=keep)
+    if do_sample:
+        topk_i = torch.multinomial(torch.softmax(acc, dim=-1), num_samples=keep, generator=generator)
+        topk_lp = torch.gather(acc, 1, topk_i)
+    else:
+        topk_lp, topk_i = torch.topk(acc, k=keep)
     src_beam = topk_i // V
     topk_idx = _gather_beams(running_idx, src_beam)
     topk_seq = _gather_beams(running, src_beam)
@@ -467,6 +510,8 @@ def beam_step_torch(st: dict, logits: torch.Tensor, cur: int, nb: int, eos: torc
     go_on = torch.any(heuristic_open) & ~(torch.all(is_finished) & (early_stopping is True)) & ~torch.all(hits)
     new = dict(running=running, sequences=sequences, running_scores=running_scores, beam_scores=beam_scores, is_finished=is_finished,
                heuristic_open=heuristic_open, running_idx=running_idx, beam_idx_tab=beam_idx_tab)
+    if do_sample:
+        new["drawn"] = topk_i
     return new, log_probs, src_rows, hits, go_on
 
 
@@ -482,14 +527,14 @@ def _beam_output(sequences, beam_scores, beam_idx_tab, B, R, return_dict, output
 
 def _beam_search(decoder, inputs_embeds, attention_mask, max_length: int, eos_ids, pad_id: int, nb: int, length_penalty: float, early_stopping,
                  num_return_sequences: int, return_dict: bool, output_scores: bool, output_logits: bool, stream_copy: bool = True,
-                 beam_select: Optional[str] = None, use_graph: bool = True, sync_every: int = 16):
+                 beam_select: Optional[str] = None, use_graph: bool = True, sync_every: int = 16, sampling: Optional[dict] = None):
     if beam_select not in (None, "device", "torch"):
         raise ValueError(f"generate: beam_select = {beam_select!r}: 'device', 'torch' or None")
     B, V = inputs_embeds.shape[0], decoder.spec.vocab_size
     if beam_select != "torch":
         if beam_select_supported(B, nb, len(eos_ids), V):
             return _beam_search_device(decoder, inputs_embeds, attention_mask, max_length, eos_ids, pad_id, nb, length_penalty, early_stopping,
-                                       num_return_sequences, return_dict, output_scores, output_logits, stream_copy, use_graph, sync_every)
+                                       num_return_sequences, return_dict, output_scores, output_logits, stream_copy, use_graph, sync_every, sampling)
         if beam_select == "device":
             raise ValueError(f"generate(beam_select='device'): p2t_beam_select serves 1 <= num_beams <= {BEAMS_MAX} with max(2, 1 + number of eos ids) * "
                              f"num_beams <= {KEEP_MAX} <= vocabulary (got num_beams = {nb}, {len(eos_ids)} eos ids); the torch path serves the rest")
@@ -500,6 +545,8 @@ def _beam_search(decoder, inputs_embeds, attention_mask, max_length: int, eos_id
     eos = torch.tensor(eos_ids, dtype=torch.int64, device=dev)
     st = beam_state_init(B, nb, max_length, pad_id, dev)
     all_scores, all_logits = [], []
+    draw = {} if sampling is None else dict(do_sample=True, generator=sampling["generator"], temperature=sampling["temperature"],
+                                            top_k=sampling["top_k"], top_p=sampling["top_p"])
     cur = 0
     while True:
         if cur == 0:
@@ -508,7 +555,7 @@ def _beam_search(decoder, inputs_embeds, attention_mask, max_length: int, eos_id
             logits = eng.logits[:, :V].float()
         if return_dict and output_logits:
             all_logits.append(logits.clone())
-        st, log_probs, src_rows, _, go_on = beam_step_torch(st, logits, cur, nb, eos, length_penalty, early_stopping, max_length)
+        st, log_probs, src_rows, _, go_on = beam_step_torch(st, logits, cur, nb, eos, length_penalty, early_stopping, max_length, **draw)
         if return_dict and output_scores:
             all_scores.append(log_probs)
         cur += 1
@@ -526,7 +573,7 @@ def _beam_search(decoder, inputs_embeds, attention_mask, max_length: int, eos_id
 class BeamState:
     """p2t_beam_state of one generate() call (include/p2t_hip.h): double-buffered tables, a fresh state in half 0."""
 
-    def __init__(self, B: int, nb: int, G: int, pad_id: int, dev):
+    def __init__(self, B: int, nb: int, G: int, pad_id: int, dev, sample: bool = False):
         self.B, self.nb, self.G = B, nb, G
         self.run_seq = torch.full((2, B, nb, G), pad_id, dtype=torch.int64, device=dev)
         self.fin_seq = self.run_seq.clone()
@@ -539,7 +586,9 @@ class BeamState:
         self.heuristic_open = torch.ones((B,), dtype=torch.int32, device=dev)
         self.done = torch.zeros((2,), dtype=torch.int32, device=dev)
         self.sync = torch.zeros((1 + B,), dtype=torch.int32, device=dev)
-        self.workspace = torch.zeros((call("p2t_beam_workspace_bytes", B, nb) // 4,), dtype=torch.float32, device=dev)
+        self.workspace = torch.zeros((call("p2t_beam_sample_workspace_bytes" if sample else "p2t_beam_workspace_bytes", B, nb) // 4,),
+                                     dtype=torch.float32, device=dev)
+        self.flags = torch.zeros((1,), dtype=torch.int32, device=dev)      # p2t_beam_sample_select ORs into it (bit 0: table full, bit 1: ran dry)
         self.c = _lib.BeamStateC(**{n: getattr(self, n).data_ptr() for n, _ in _lib.BeamStateC._fields_})
 
 
@@ -552,10 +601,22 @@ def beam_select(logits: torch.Tensor, V: int, state: BeamState, eos: torch.Tenso
          ptr(scores) if scores is not None else None, scores.stride(0) if scores is not None else 0, stream())
 
 
+def beam_sample_select(logits: torch.Tensor, V: int, state: BeamState, eos: torch.Tensor, pad_id: int, length_penalty: float, early_stopping,
+                       max_length: int, step: torch.Tensor, next_tokens: torch.Tensor, src_rows: torch.Tensor, temperature: float, top_k: int,
+                       top_p: float, seed: int, scores: Optional[torch.Tensor] = None, prompt0: int = 0):
+    """One p2t_beam_sample_select call (`state` built with sample=True): beam_select's arguments plus the sampler's; prompt b draws as
+    prompt0 + b at the device step counter.  The flags word is state.flags."""
+    es = 1 if early_stopping is True else (2 if early_stopping == "never" else 0)
+    call("p2t_beam_sample_select", ptr(logits), ops.dt_of(logits), logits.stride(0), state.B, state.nb, V, ptr(eos) if eos.numel() else None,
+         eos.numel(), int(pad_id), float(length_penalty), es, int(max_length), state.G, ptr(step), C.byref(state.c), ptr(next_tokens), ptr(src_rows),
+         ptr(scores) if scores is not None else None, scores.stride(0) if scores is not None else 0, float(temperature), int(top_k), float(top_p),
+         int(seed) & (2 ** 64 - 1), int(prompt0), ptr(state.flags), stream())
+
+
 def _beam_search_device(decoder, inputs_embeds, attention_mask, max_length: int, eos_ids, pad_id: int, nb: int, length_penalty: float,
                         early_stopping, num_return_sequences: int, return_dict: bool, output_scores: bool, output_logits: bool,
-                        stream_copy: bool, use_graph: bool, sync_every: int):
-    """The same search with p2t_beam_select in the torch bookkeeping's place: the first token from the prefill logits, one eager step, then
+                        stream_copy: bool, use_graph: bool, sync_every: int, sampling: Optional[dict] = None):
+    """The same search with p2t_beam_select (`sampling`: p2t_beam_sample_select) in the torch bookkeeping's place: the first token from the prefill logits, one eager step, then
     a replayed graph of TWO steps (reorder, feed, decode, select, twice: the engine's cache buffers are back where the capture found
     them), an odd remainder eagerly.  The host reads `done` every `sync_every` tokens and at the end; steps run past the stop leave
     the state as it is."""
@@ -565,7 +626,7 @@ def _beam_search_device(decoder, inputs_embeds, attention_mask, max_length: int,
     embeds, mask = eng.compact(inputs_embeds, attention_mask)
     first = eng.prefill(embeds, mask).repeat_interleave(nb, dim=0).contiguous()     # HF expands the prompt nb times before its prefill
     eos = torch.tensor(eos_ids, dtype=torch.int64, device=dev)
-    st = BeamState(B, nb, eng.G, pad_id, dev)
+    st = BeamState(B, nb, eng.G, pad_id, dev, sample=sampling is not None)
     src_rows = torch.zeros((eng.BB,), dtype=torch.int64, device=dev)
     keep_scores, keep_logits = return_dict and output_scores, return_dict and output_logits
     # two step slots: a replayed pair leaves the logits / log-probabilities of both its steps to be cloned afterwards
@@ -573,8 +634,27 @@ def _beam_search_device(decoder, inputs_embeds, attention_mask, max_length: int,
     sslots = [torch.empty((eng.BB, V), dtype=torch.float32, device=dev) for _ in range(2)] if keep_scores else [None, None]
     all_scores, all_logits = [], []
 
+    warned = set()
+
+    def read_done() -> bool:                              # one host read: `done` and, under sampling, the flags word next to it
+        if sampling is not None:
+            bits = int(st.flags.item())
+            if bits & 1 and 1 not in warned:
+                warned.add(1)
+                warnings.warn("generate(seed=): more than 2048 logits tied at the top-k boundary of a row; the ties beyond the table were dropped "
+                              "in ascending column order (HF would keep them all)", RuntimeWarning, stacklevel=4)
+            if bits & 2 and 2 not in warned:
+                warned.add(2)
+                warnings.warn("generate(seed=): a prompt ran out of continuations with positive probability under beam sampling (HF's "
+                              "torch.multinomial fails there); its results are unspecified", RuntimeWarning, stacklevel=4)
+        return bool(st.done[0].item())
+
     def select(lg, slot):
-        beam_select(lg, V, st, eos, pad_id, length_penalty, early_stopping, max_length, eng.step, eng.next_tokens, src_rows, sslots[slot])
+        if sampling is None:
+            beam_select(lg, V, st, eos, pad_id, length_penalty, early_stopping, max_length, eng.step, eng.next_tokens, src_rows, sslots[slot])
+        else:
+            beam_sample_select(lg, V, st, eos, pad_id, length_penalty, early_stopping, max_length, eng.step, eng.next_tokens, src_rows,
+                               sampling["temperature"], sampling["top_k"], sampling["top_p"], sampling["seed"], sslots[slot])
 
     def keep(lg, slot):
         if keep_logits:
@@ -595,7 +675,7 @@ def _beam_search_device(decoder, inputs_embeds, attention_mask, max_length: int,
     while n < max_length:
         if n == 1 or n - read_at >= sync_every:
             read_at = n
-            if bool(st.done[0].item()):
+            if read_done():
                 break
         if use_graph and n >= 2 and max_length - n >= 2:                  # the first step ran eagerly (lazy one-time initialisation inside the library)
             if graph is None:
@@ -611,6 +691,7 @@ def _beam_search_device(decoder, inputs_embeds, attention_mask, max_length: int,
             advance(0)
             keep(lslots[0], 0)
             n += 1
+    read_done()
     done, steps = (int(v) for v in st.done.tolist())
     if not done:
         raise RuntimeError("generate: the beam search ran its max_new_tokens steps and p2t_beam_select did not raise `done`")

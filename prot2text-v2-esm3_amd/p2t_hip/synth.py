@@ -71,6 +71,27 @@ def sample_uniform(seed: int, row: int, step: int) -> float:
     return ((h >> 40) + 0.5) * 2.0 ** -24
 
 
+def beam_sample_uniform(seed: int, prompt: int, step: int, flat_index: int) -> float:
+    """The uniform number behind the Gumbel noise of candidate `flat_index` (= beam * V + column) of global prompt `prompt` at step
+    counter `step` under `seed` in p2t_beam_sample_select (csrc/beam_sample_select.hip): the sampler's chain with one more link,
+    h = mix64(mix64(mix64(mix64(seed + GOLDEN) ^ prompt) ^ step) ^ flat_index), u = (2 (h >> 41) + 1) * 2^-24: an odd 24-bit integer
+    times 2^-24, exact in fp32 and strictly inside (0, 1)."""
+    h = mix64((int(seed) + int(_GOLDEN)) & _MASK64)
+    h = mix64(h ^ (int(prompt) & _MASK64))
+    h = mix64(h ^ (int(step) & _MASK64))
+    h = mix64(h ^ (int(flat_index) & _MASK64))
+    return (2 * (h >> 41) + 1) * 2.0 ** -24
+
+
+def beam_sample_uniforms(seed: int, prompt: int, step: int, flat_indices) -> np.ndarray:
+    """beam_sample_uniform over an array of flat indices (uint64 arithmetic in numpy)."""
+    h = mix64((int(seed) + int(_GOLDEN)) & _MASK64)
+    h = mix64(h ^ (int(prompt) & _MASK64))
+    h = mix64(h ^ (int(step) & _MASK64))
+    x = _mix(np.asarray(flat_indices, dtype=np.uint64) ^ np.uint64(h))
+    return (2.0 * (x >> np.uint64(41)).astype(np.float64) + 1.0) * 2.0 ** -24
+
+
 def hash_u24(seed: int, name: str, start: int, count: int) -> np.ndarray:
     add, xor = stream_key(seed, name)
     idx = np.arange(start, start + count, dtype=np.uint64)

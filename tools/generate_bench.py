@@ -9,7 +9,11 @@ decode step of greedy decoding, of sampling with torch ops on the logits (`gener
 replay), and p2t_sample_select's own time on [B, vocab] bf16 logits (HIP events around 200 launches).
 python tools/generate_bench.py [B] [N] [beams > 1]: beam search three ways, interleaved, three runs each (median and min .. max): the torch
 bookkeeping (`beam_select="torch"`: one host read per token), p2t_beam_select with eager launches and under replay of the two-step graph;
-then B * beams greedy rows under replay, p2t_beam_select's two launches alone, and p2t_kv_reorder at 30 and at 250 generated tokens."""
+then B * beams greedy rows under replay, p2t_beam_select's two launches alone, and p2t_kv_reorder at 30 and at 250 generated tokens.
+python tools/generate_bench.py [B] [N] [beams > 1] sample: beam sampling (top_k=50, top_p=0.9, temperature=0.7) four ways, interleaved, three
+runs each: beam search with p2t_beam_select under graph replay (the yardstick: the same work without the noise), torch beam sampling
+(`beam_select="torch"`, `generator=`), p2t_beam_sample_select with eager launches and under graph replay; then the two select entry
+points' launches alone, back to back."""
 import os
 import sys
 import time
@@ -135,6 +139,52 @@ def beam_mode(model, kw, B: int, N: int, beams: int, V: int, dev):
         print(f"p2t_kv_reorder, {rows} rows, {at} generated tokens: {_events(lambda: eng.reorder(ident), 50):.1f} us per call", flush=True)
 
 
+def beam_sample_mode(model, kw, B: int, N: int, beams: int, V: int, dev):
+    sampling = dict(do_sample=True, top_k=50, top_p=0.9, temperature=0.7)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    cases = [("beam search, p2t_beam_select, two-step graph replay", dict(beam_select="device")),
+             ("beam sampling, torch (beam_select=\"torch\", generator=; eager launches, one host read per token)",
+              dict(**sampling, beam_select="torch", generator=gen)),
+             ("beam sampling, p2t_beam_sample_select, eager launches", dict(**sampling, beam_select="device", seed=1, use_graph=False)),
+             ("beam sampling, p2t_beam_sample_select, two-step graph replay", dict(**sampling, beam_select="device", seed=1))]
+    for _, extra in cases:
+        model.generate(**{**kw, **extra, "max_new_tokens": 6})
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    model.generate(**{**kw, "max_new_tokens": 1, "beam_select": "device"})
+    torch.cuda.synchronize()
+    t_prompt = time.perf_counter() - t0
+    runs = {name: [] for name, _ in cases}
+    for _ in range(3):                                           # interleaved: a drift of the box hits all four alike
+        for name, extra in cases:
+            t0 = time.perf_counter()
+            model.generate(**{**kw, **extra})
+            torch.cuda.synchronize()
+            runs[name].append((time.perf_counter() - t0 - t_prompt) / (N - 1) * 1e3)
+    for name, r in runs.items():
+        print(f"generate cfg3: B={B} beams={beams}, {N} new tokens, {name}: median {np.median(r):.3f} ms/step (min {min(r):.3f}, max {max(r):.3f}; 3 runs)", flush=True)
+    # the select launches alone, back to back: a fresh state at step 0, nothing finishes, so every call does the full work
+    rows, ld = B * beams, (V + 63) // 64 * 64
+    lg = (torch.randn((rows, ld), device=dev, generator=torch.Generator(device=dev).manual_seed(0)) * 3).to(torch.bfloat16)
+    step, nxt, src = (torch.zeros((n,), dtype=dt, device=dev) for n, dt in ((1, torch.int32), (rows, torch.int64), (rows, torch.int64)))
+    eos = torch.zeros((0,), dtype=torch.int64, device=dev)
+    st, sst = generation.BeamState(B, beams, 256, 0, dev), generation.BeamState(B, beams, 256, 0, dev, sample=True)
+    live = generation.BeamState(B, beams, 256, 0, dev, sample=True)        # every beam live, as from the second step on: a fresh state's beams 1 ..
+    live.run_scores[:] = -1.0 - 0.25 * torch.arange(beams, device=dev)     # score -1e9, and with both filters off all V keys of such a row tie
+    for _ in range(2):
+        us = _events(lambda: generation.beam_select(lg, V, st, eos, 0, 1.0, False, 256, step, nxt, src), 200)
+        print(f"p2t_beam_select alone (both launches), [{rows}, {V}] bf16 logits, {beams} beams: {us:.1f} us per call", flush=True)
+        us = _events(lambda: generation.beam_sample_select(lg, V, sst, eos, 0, 1.0, False, 256, step, nxt, src, 0.7, 50, 0.9, 1), 200)
+        print(f"p2t_beam_sample_select alone (both launches), top_k=50 top_p=0.9 temperature=0.7: {us:.1f} us per call", flush=True)
+        us = _events(lambda: generation.beam_sample_select(lg, V, sst, eos, 0, 1.0, False, 256, step, nxt, src, 1.0, 0, 1.0, 1), 200)
+        print(f"p2t_beam_sample_select alone (both launches), both filters off, fresh state (3 of 4 beams at -1e9): {us:.1f} us per call", flush=True)
+        us = _events(lambda: generation.beam_sample_select(lg, V, live, eos, 0, 1.0, False, 256, step, nxt, src, 0.7, 50, 0.9, 1), 200)
+        print(f"p2t_beam_sample_select alone (both launches), top_k=50 top_p=0.9 temperature=0.7, every beam live: {us:.1f} us per call", flush=True)
+        us = _events(lambda: generation.beam_sample_select(lg, V, live, eos, 0, 1.0, False, 256, step, nxt, src, 1.0, 0, 1.0, 1), 200)
+        print(f"p2t_beam_sample_select alone (both launches), both filters off, every beam live: {us:.1f} us per call", flush=True)
+    print(f"flags after these calls: {int(sst.flags.item())} (fresh state), {int(live.flags.item())} (every beam live)", flush=True)
+
+
 def main():
     dev = torch.device("cuda:0")
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
@@ -142,6 +192,7 @@ def main():
     sample = len(sys.argv) > 3 and sys.argv[3] == "sample"
     beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample else 1
     fp8 = len(sys.argv) > 4 and sys.argv[4] == "fp8"
+    beam_sample = beams > 1 and len(sys.argv) > 4 and sys.argv[4] == "sample"
     esm_name, llama_name, _, _, Tp, _ = specs.CONFIGS["cfg3"]
     esm, llama = specs.esm_spec(esm_name), specs.llama_spec(llama_name)
     ad = specs.adapter_spec(esm, llama)
@@ -160,6 +211,8 @@ def main():
               protein_attention_mask=t(pmask), max_new_tokens=N, eos_token_id=None, pad_token_id=128002, do_sample=False, num_beams=beams)
     if sample:
         return sample_mode(model, kw, B, N, llama.vocab_size, dev)
+    if beam_sample:
+        return beam_sample_mode(model, kw, B, N, beams, llama.vocab_size, dev)
     if beams > 1:
         return beam_mode(model, kw, B, N, beams, llama.vocab_size, dev)
     out = model.generate(**{**kw, "max_new_tokens": 4})          # warm-up: engines, workspaces, lazy initialisation
