@@ -11,6 +11,8 @@
 // kSample = true: {perturbed key [BB][64], column [BB][64], accumulated score [BB][64], the row's best accumulated score [BB]}; the
 // rank key is the perturbed key, the score that goes on is the unperturbed one, and bit 1 of *flags is raised when the keep-th
 // candidate is absent or more than 100 below the prompt's best accumulated score.
+// The host half of both entry points is here too (beam_step_setup, at the end): the argument checks, keep, the supported range and the
+// workspace planes they have in common.
 #pragma once
 #include "common.h"
 
@@ -207,6 +209,46 @@ __device__ __forceinline__ void beam_merge_body(const MergeArgs& a, int32_t* __r
             }
         }
     }
+}
+
+// ---- host: what the two entry points check and set up alike ----------------------------------------------------------------------
+struct BeamStep {
+    int BB, keep;
+    float *plane0, *plane2;                                   // workspace planes [BB][64]: candidate keys; (mx, lse) [BB][2] or acc [BB][64]
+    int32_t* cand_col;                                        // plane 1: candidate columns
+    MergeArgs merge;
+};
+
+// The argument checks of entry point `name` (P2T_ERR_ARG), its supported range (P2T_ERR_UNSUPPORTED), keep and the workspace's common part.
+inline int beam_step_setup(const char* name, const void* logits, int dtype, int64_t ld, int B0, int num_beams, int V, const int64_t* eos_ids,
+                           int n_eos, int64_t pad_id, float length_penalty, int early_stopping, int max_length, int G, const int32_t* step,
+                           const p2t_beam_state* state, int64_t* next_tokens, int64_t* src_rows, const float* scores, int64_t ld_scores,
+                           BeamStep* out) {
+    P2T_REQUIRE(logits && step && state && next_tokens && src_rows, "%s: null argument", name);
+    P2T_REQUIRE(state->run_seq && state->run_idx && state->run_scores && state->fin_seq && state->fin_idx && state->fin_scores &&
+                    state->is_finished && state->heuristic_open && state->done && state->sync && state->workspace,
+                "%s: null pointer in the state", name);
+    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "%s: dtype %d is neither P2T_F32 nor P2T_BF16", name, dtype);
+    P2T_REQUIRE(B0 > 0 && num_beams > 0 && V > 0 && ld >= V, "%s: B0 = %d, num_beams = %d, V = %d, ld = %lld: needs positive counts, ld >= V", name,
+                B0, num_beams, V, (long long)ld);
+    P2T_REQUIRE(n_eos >= 0 && (n_eos == 0 || eos_ids), "%s: n_eos = %d: needs n_eos >= 0 and eos_ids for n_eos > 0", name, n_eos);
+    P2T_REQUIRE(G > 0 && G % 64 == 0 && max_length > 0 && max_length <= G,
+                "%s: G = %d, max_length = %d: needs G a positive multiple of 64 and 1 <= max_length <= G", name, G, max_length);
+    P2T_REQUIRE(length_penalty == length_penalty, "%s: length_penalty is NaN", name);
+    P2T_REQUIRE(early_stopping >= 0 && early_stopping <= 2, "%s: early_stopping = %d: 0 (False), 1 (True) or 2 (\"never\")", name, early_stopping);
+    P2T_REQUIRE(!scores || ld_scores >= V, "%s: ld_scores = %lld < V = %d", name, (long long)ld_scores, V);
+    const int64_t keep = (int64_t)(n_eos + 1 > 2 ? n_eos + 1 : 2) * num_beams;
+    if (num_beams > kBeamsMax || keep > kKeepMax || V < keep || (int64_t)B0 * num_beams * V > 0x7fffffffll) {
+        set_error("%s: num_beams = %d, keep = max(2, 1 + n_eos) * num_beams = %lld, V = %d, B0 = %d: supported are 1 <= num_beams <= %d, "
+                  "keep <= %d, V >= keep, B0 * num_beams * V < 2^31", name, num_beams, (long long)keep, V, B0, kBeamsMax, kKeepMax);
+        return P2T_ERR_UNSUPPORTED;
+    }
+    const int BB = B0 * num_beams;
+    float* ws = state->workspace;
+    *out = BeamStep{BB, (int)keep, ws, ws + 2 * (int64_t)BB * kKeepMax, reinterpret_cast<int32_t*>(ws + (int64_t)BB * kKeepMax),
+                    MergeArgs{*state, step, eos_ids, next_tokens, src_rows, pad_id, B0, num_beams, V, (int)keep, n_eos, G, max_length, early_stopping,
+                              length_penalty}};
+    return P2T_OK;
 }
 
 }  // namespace

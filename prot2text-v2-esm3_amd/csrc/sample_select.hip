@@ -8,20 +8,18 @@
 //     hash24 = h >> 40,   u = (hash24 + 0.5) * 2^-24,   used as the nearest f32 (= float(2 hash24 + 1) * 2^-25)
 // p2t_hip/synth.py sample_uniform(seed, row, step) is the same chain on the host.
 //
-// Filtered form (top_k on), sample_topk_kernel:
-//   1. kth = the k-th largest STORED logit by a radix select over an order-preserving integer key, 8 bits per pass (two passes
-//      for bf16, four for f32), integer histograms in LDS, one per wave.  x -> x / temperature is monotone, so the k-th largest
-//      x is kth / temperature, also where the division makes two different logits equal.  The select runs twice: first over the
-//      1024 per-thread maxima (one pass over the row, no atomics), whose k-th largest is a lower bound of kth (at least k <= 1024
-//      of the row's values are that large); then over the row, counting only the values at or above the bound -- some 60 of
-//      128 256 at k = 50, a few thousand at k = 1024 -- so the histograms' same-address atomics stay few.  The row is read with
-//      16-byte loads where its pitch and base allow.
-//   2. every column with x >= that is a survivor: collected into an LDS table of kCap (value, index) pairs through an integer
-//      slot counter (any order), its score written.  More than kCap survivors (>= 1025 exact ties): collected again, the
-//      strictly greater ones first, then the ties in ascending index order by a ballot + per-wave-count scan, until full.
-//   3. the table is sorted bitonically by (value descending, index ascending): a total order, so the slot order of 2. is gone.
-//   4. wave 0: e_j = exp(x_j - x_0), a fixed-order scan (per-lane runs of consecutive ranks, then a shuffle scan of the lane
-//      totals), the top-p cut on the tail mass, the inverse CDF at u over the kept ranks.
+// Filtered form (top_k on), sample_topk_kernel: the table pipeline of select_common.h, with x = stored logit / temperature as the
+// value a column stores and its score written as it is seen; the draw is this file's own.
+//   1. kth = the k-th largest STORED logit (thread_max_key, kth_largest_stored: a radix select over an order-preserving integer key,
+//      8 bits per pass, first over the 1024 per-thread maxima, then over the row above that bound).  x -> x / temperature is
+//      monotone, so the k-th largest x is kth / temperature, also where the division makes two different logits equal.  The row is
+//      read with 16-byte loads where its pitch and base allow.
+//   2. every column with x >= that is a survivor (collect_survivors): an LDS table of kCap (value, index) pairs.  More than kCap
+//      survivors (>= 1025 exact ties): the ordered path (collect_in_order), bit 0 of the flags word, -inf as the score of a tie
+//      that found no slot.
+//   3. the table is sorted by (value descending, index ascending) (pad_and_sort_table): a total order, so the slot order is gone.
+//   4. wave 0: e_j = exp(x_j - x_0), the fixed-order scan and the top-p cut on the tail mass (top_p_cut), then here the inverse CDF
+//      at u over the kept ranks, on the se[] and the lane prefix the cut left.
 // Unfiltered form (top_k off, top_p off), sample_full_kernel: the row maximum, then every wave scans one contiguous segment of
 // columns in ascending order (64 columns per step, shuffle scan), the 16 segment sums are added in wave order, and the wave whose
 // segment holds u * S walks it again with the same arithmetic to find the column.
@@ -74,119 +72,33 @@ __global__ void __launch_bounds__(1024) sample_topk_kernel(const T* __restrict__
 
     // ---- 1. the k-th largest stored logit ------------------------------------------------------------------------------
     const bool vec = ld % (16 / sizeof(T)) == 0 && ((uintptr_t)logits & 15u) == 0;
-    uint32_t tmax = 0;                                        // below every key of a number (a thread without a column keeps it)
-    for_each_column(row, V, vec, tid, [&](float v, int) { tmax = max(tmax, key_of(v)); });
-    const uint32_t floor_key = radix_select<KeyBits<T>::N>(k, hist, s_sel, [&](auto count) { count(tmax); });      // k <= 1024 keys
-    const uint32_t kth_key = radix_select<KeyBits<T>::N>(k, hist, s_sel, [&](auto count) {
-        for_each_column(row, V, vec, tid, [&](float v, int) {
-            const uint32_t key = key_of(v);
-            if (key >= floor_key) count(key);
-        });
-    });
+    const uint32_t kth_key = kth_largest_stored(row, V, vec, k, thread_max_key(row, V, vec, tid), hist, s_sel);
     const float xk = key_value(kth_key) / temperature;
 
-    // ---- 2. survivors ----------------------------------------------------------------------------------------------------
-    if (tid == 0) s_cnt = 0;
-    __syncthreads();
-    for_each_column(row, V, vec, tid, [&](float v, int c) {
-        const float x = v / temperature;
-        const bool keep = x >= xk;
-        if (keep) {
-            const int slot = atomicAdd(&s_cnt, 1);
-            if (slot < kCap) { sv[slot] = x; si[slot] = c; }
-        }
+    // ---- 2. survivors: x and its score; a tie the full table drops scores -inf ---------------------------------------------------
+    auto x_of = [&](float v, int) { return v / temperature; };
+    int n = collect_survivors(row, V, vec, xk, sv, si, &s_cnt, x_of, [&](int c, float x, bool keep) {
         if (srow) srow[c] = keep ? x : -INFINITY;
     });
-    __syncthreads();
-    int n = s_cnt;
     if (n > kCap) {                                           // block-uniform: >= 1025 exact ties at the k-th value
-        __syncthreads();
-        if (tid == 0) { s_cnt = 0; atomicOr(flags, 1); }
-        __syncthreads();
-        for (int c = tid; c < V; c += 1024) {
-            const float x = to_f32(row[c]) / temperature;
-            if (x > xk) {                                     // fewer than k <= 1024 of them
-                const int slot = atomicAdd(&s_cnt, 1);
-                if (slot < kCap) { sv[slot] = x; si[slot] = c; }
-            }
-        }
-        __syncthreads();
-        int base = min(s_cnt, kCap);
-        for (int c0 = 0; c0 < V; c0 += 1024) {                // the ties, ascending column, until the table is full
-            const int c = c0 + tid;
-            const bool eq = c < V && to_f32(row[c]) / temperature == xk;
-            const unsigned long long b = __ballot(eq);
-            if (lane == 0) s_wc[w] = __popcll(b);
-            __syncthreads();
-            int off = base, tot = 0;
-#pragma unroll
-            for (int ww = 0; ww < 16; ++ww) {
-                const int t = s_wc[ww];
-                if (ww < w) off += t;
-                tot += t;
-            }
-            if (eq) {
-                const int slot = off + __popcll(b & ((1ull << lane) - 1ull));
-                if (slot < kCap) { sv[slot] = xk; si[slot] = c; }
-                else if (srow) srow[c] = -INFINITY;
-            }
-            base = min(base + tot, 2 * kCap);                 // saturated: only "full or not" matters from kCap on
-            __syncthreads();
-        }
-        n = min(base, kCap);
+        if (tid == 0) atomicOr(flags, 1);
+        n = collect_in_order(row, V, xk, sv, si, &s_cnt, s_wc, x_of, [&](int c) {
+            if (srow) srow[c] = -INFINITY;
+        });
     }
     if (n < 1) {                                              // only a row outside the contract (NaN) has no survivor
         if (tid == 0) { sv[0] = -INFINITY; si[0] = 0; }
         n = 1;
     }
     // ---- 3. total order: value descending, column ascending ----------------------------------------------------------------
-    int P = 64;
-    while (P < n) P <<= 1;                                    // <= kCap
-    for (int i = n + tid; i < P; i += 1024) { sv[i] = -INFINITY; si[i] = kNoIndex; }
-    __syncthreads();
-    for (int size = 2; size <= P; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            if (tid < (P >> 1)) {
-                const int i = ((tid / stride) * 2 * stride + (tid % stride)) & (kCap - 1), j = (i + stride) & (kCap - 1);
-                const float va = sv[i], vb = sv[j];
-                const int ia = si[i], ib = si[j];
-                const bool b_first = vb > va || (vb == va && ib < ia);
-                const bool a_first = va > vb || (va == vb && ia < ib);
-                if (((i & size) == 0) ? b_first : a_first) { sv[i] = vb; sv[j] = va; si[i] = ib; si[j] = ia; }
-            }
-            __syncthreads();
-        }
-    }
+    const int P = pad_and_sort_table(sv, si, n, tid);
     // ---- 4. top-p and the draw, one wave ---------------------------------------------------------------------------------
     const int step = step_ptr[0];
     if (w == 0) {
         const int per = P >> 6, j0 = lane * per;              // lane l: ranks l * per .. l * per + per - 1
         const float mx = sv[0];
-        float loc = 0.f;
-        for (int i = 0; i < per; ++i) {
-            const int j = j0 + i;
-            const float e = j < n ? expf(sv[j] - mx) : 0.f;
-            se[j] = e;
-            loc += e;
-        }
-        const float incl = wave_scan(loc, lane);
-        const float S = __shfl(incl, 63, 64);
-        float excl = __shfl_up(incl, 1, 64);
-        if (lane == 0) excl = 0.f;
-        int m = n;
-        if (top_p < 1.f) {                                    // rank j stays iff sum_{i >= j} e_i > (1 - top_p) S; rank 0 always
-            const float cut = (1.f - top_p) * S;
-            float run = excl;
-            int cnt = 0;
-            for (int i = 0; i < per; ++i) {
-                const int j = j0 + i;
-                if (j < n) {
-                    cnt += (j == 0 || S - run > cut) ? 1 : 0;
-                    run += se[j];
-                }
-            }
-            m = min(max(wave_sum_int(cnt), 1), n);
-        }
+        float excl;
+        const int m = top_p_cut(n, P, top_p, se, lane, excl, [&](int j) { return expf(sv[j] - mx); });
         float run = excl, at_last = 0.f;
         for (int i = 0; i < per; ++i) {
             const int j = j0 + i;

@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import ctypes as C
 import warnings
+from types import SimpleNamespace
 from typing import Optional, Sequence
 
 import torch
@@ -78,6 +79,40 @@ def filter_logits(scores: torch.Tensor, temperature: float = 1.0, top_k: Optiona
         remove[..., -min_tokens_to_keep:] = False
         scores = scores.masked_fill(remove.scatter(1, sorted_indices, remove), -float("inf"))
     return scores
+
+
+def _sampler_args(temperature, top_k, top_p, seed, generator, device: bool = True):
+    """generate()'s (temperature, top_k, top_p) -> the (temperature, k, p) of p2t_sample_select / p2t_beam_sample_select (k = 0 and
+    p = 1.0: off), checked up front; `device`: held to the device sampler's range."""
+    if seed is not None and generator is not None:
+        raise ValueError("generate: pass `seed` (the device sampler) or `generator` (the torch path), not both")
+    temperature = 1.0 if temperature is None else float(temperature)
+    k = 0 if top_k is None or int(top_k) <= 0 else int(top_k)
+    p = 1.0 if top_p is None or float(top_p) >= 1.0 else float(top_p)
+    if not (temperature > 0 and temperature < float("inf")):
+        raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
+    if not p > 0:
+        raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
+    if device and (k > 1024 or (k == 0 and p < 1.0)):
+        raise ValueError(f"generate(seed=): the device sampler serves top_k 1 .. 1024 with top_p on or off, and both filters off (got top_k={top_k}, "
+                         f"top_p={top_p}); sample with `generator=` for anything else")
+    return temperature, k, p
+
+
+_FLAG_WARNINGS = ((1, "generate(seed=): more than 2048 logits tied at the top-k boundary of a row; the ties beyond the table were dropped in "
+                      "ascending column order (HF would keep them all)"),
+                  (2, "generate(seed=): a prompt ran out of continuations with positive probability under beam sampling (HF's torch.multinomial "
+                      "fails there); its results are unspecified"))
+
+
+def _warn_flags(flags: torch.Tensor, warned: set, stacklevel: int) -> None:
+    """One host read of a device sampler's flags word; each bit's warning at most once per generate() call (`warned`: the bits already
+    reported).  stacklevel: the caller of generate(), counted from the function that calls this one as 2."""
+    bits = int(flags.item())
+    for bit, message in _FLAG_WARNINGS:
+        if bits & bit and bit not in warned:
+            warned.add(bit)
+            warnings.warn(message, RuntimeWarning, stacklevel=stacklevel)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -289,9 +324,11 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
         sampling = None
         if do_sample:
             sampling = _beam_sampling_args(num_beams, len(eos_ids), temperature, top_k, top_p, seed, generator, beam_select)
-        return _beam_search(decoder, inputs_embeds, attention_mask, max_new_tokens, eos_ids, int(pad_token_id), num_beams, float(length_penalty),
-                            early_stopping, num_return_sequences, return_dict_in_generate, output_scores, output_logits, stream_copy,
-                            beam_select, use_graph, sync_every, sampling)
+        return _beam_search(decoder, inputs_embeds, attention_mask, SimpleNamespace(
+            max_length=max_new_tokens, eos_ids=eos_ids, pad_id=int(pad_token_id), nb=num_beams, length_penalty=float(length_penalty),
+            early_stopping=early_stopping, num_return_sequences=num_return_sequences, return_dict=return_dict_in_generate,
+            output_scores=output_scores, output_logits=output_logits, stream_copy=stream_copy, beam_select=beam_select, use_graph=use_graph,
+            sync_every=sync_every, sampling=sampling))
     R = int(num_return_sequences)
     if R != 1 and not do_sample:
         raise ValueError("greedy decoding returns one sequence per prompt: num_return_sequences > 1 needs do_sample=True or num_beams > 1")
@@ -305,18 +342,7 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     eos = torch.tensor(eos_ids, dtype=torch.int64, device=eng.dev)
     on_device = bool(do_sample) and seed is not None
     if on_device:
-        if generator is not None:
-            raise ValueError("generate: pass `seed` (the device sampler) or `generator` (the torch path), not both")
-        temperature = 1.0 if temperature is None else float(temperature)
-        k = 0 if top_k is None or int(top_k) <= 0 else int(top_k)
-        p = 1.0 if top_p is None or float(top_p) >= 1.0 else float(top_p)
-        if not (temperature > 0 and temperature < float("inf")):
-            raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
-        if not p > 0:
-            raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
-        if k > 1024 or (k == 0 and p < 1.0):
-            raise ValueError(f"generate(seed=): the device sampler serves top_k 1 .. 1024 with top_p on or off, and both filters off (got top_k={top_k}, "
-                             f"top_p={top_p}); sample with `generator=` for anything else")
+        temperature, k, p = _sampler_args(temperature, top_k, top_p, seed, generator)
     if do_sample and return_dict_in_generate and output_scores and not on_device:
         # HF returns the PROCESSED scores (after temperature / top-k / top-p) under sampling; nothing here is pinned on that
         # (the goldens cover greedy and beam search), so the combination is refused rather than answered with the raw logits
@@ -325,13 +351,7 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     keep_logits = [] if (return_dict_in_generate and (output_logits or (output_scores and not on_device))) else None
     scores_buf = torch.empty((eng.BB, V), dtype=torch.float32, device=eng.dev) if keep_scores is not None else None
     pad = int(pad_token_id)
-    warned = []
-
-    def table_full() -> None:                             # the sampler's flags word, read where the finished flags are
-        if on_device and not warned and int(eng.sample_flags.item()) & 1:
-            warned.append(True)
-            warnings.warn("generate(seed=): more than 2048 logits tied at the top-k boundary of a row; the ties beyond the table were dropped "
-                          "in ascending column order (HF would keep them all)", RuntimeWarning, stacklevel=3)
+    warned = set()
 
     def sample(lg: torch.Tensor):
         eng.sample_select(lg, eos, pad, temperature, k, p, seed, scores_buf)
@@ -366,7 +386,8 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     graph, n = None, 1
     while n < max_new_tokens:
         if eos_ids and (n == 1 or n % sync_every == 0):
-            table_full()
+            if on_device and not warned:                  # the sampler's flags word (bit 0 only), read where the finished flags are
+                _warn_flags(eng.sample_flags, warned, 3)
             if bool(eng.finished.all().item()):
                 break
         if use_graph and (on_device or not do_sample) and n >= 2:        # the first step ran eagerly (lazy one-time initialisation inside the library)
@@ -384,7 +405,8 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
         if keep_scores is not None:
             keep_scores.append(scores_buf.clone())
         n += 1
-    table_full()
+    if on_device and not warned:
+        _warn_flags(eng.sample_flags, warned, 3)
     seqs = _trim(eng.out_tokens, eos_ids, n)
     if not return_dict_in_generate:
         return seqs
@@ -405,23 +427,13 @@ def _gather_beams(t: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
 
 def _beam_sampling_args(nb: int, n_eos: int, temperature, top_k, top_p, seed, generator, beam_select) -> dict:
     """The sampling side of `num_beams > 1, do_sample=True`: which path, and its filters checked up front."""
-    if seed is not None and generator is not None:
-        raise ValueError("generate: pass `seed` (the device sampler) or `generator` (the torch path), not both")
     device = seed is not None and beam_select == "device"
-    if not device and not (generator is not None and beam_select == "torch"):
+    opted_in = device or (generator is not None and beam_select == "torch")
+    if not opted_in and (seed is None or generator is None):          # both given: _sampler_args refuses that first, as ever
         raise NotImplementedError("beam sampling (num_beams > 1 with do_sample=True) is opt-in: pass seed=int together with beam_select='device' "
                                   "(p2t_beam_sample_select), or generator= together with beam_select='torch'")
-    temperature = 1.0 if temperature is None else float(temperature)
-    k = 0 if top_k is None or int(top_k) <= 0 else int(top_k)
-    p = 1.0 if top_p is None or float(top_p) >= 1.0 else float(top_p)
-    if not (temperature > 0 and temperature < float("inf")):
-        raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float")
-    if not p > 0:
-        raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
+    temperature, k, p = _sampler_args(temperature, top_k, top_p, seed, generator, device)
     keep = beam_keep(nb, n_eos)
-    if device and (k > 1024 or (k == 0 and p < 1.0)):
-        raise ValueError(f"generate(seed=): the device sampler serves top_k 1 .. 1024 with top_p on or off, and both filters off (got top_k={top_k}, "
-                         f"top_p={top_p}); sample with `generator=` for anything else")
     if 0 < k < keep:
         raise ValueError(f"generate: beam sampling draws max(2, 1 + number of eos ids) * num_beams = {keep} continuations per prompt, and the first "
                          f"step has one live beam: top_k = {k} cannot supply them (needs top_k >= {keep}, or 0)")
@@ -515,48 +527,46 @@ def beam_step_torch(st: dict, logits: torch.Tensor, cur: int, nb: int, eos: torc
     return new, log_probs, src_rows, hits, go_on
 
 
-def _beam_output(sequences, beam_scores, beam_idx_tab, B, R, return_dict, output_scores, output_logits, all_scores, all_logits):
+def _beam_output(o, sequences, beam_scores, beam_idx_tab, B, all_scores, all_logits):
+    R = o.num_return_sequences
     sequences, beam_scores, beam_idx_tab = sequences[:, :R].reshape(B * R, -1), beam_scores[:, :R].reshape(-1), beam_idx_tab[:, :R].reshape(B * R, -1)
     n = int(((beam_idx_tab + 1).bool()).sum(dim=1).max().item())
     sequences = sequences[:, :n]
-    if not return_dict:
+    if not o.return_dict:
         return sequences
-    return GenerateOutput(sequences, scores=tuple(all_scores) if output_scores else None, logits=tuple(all_logits) if output_logits else None,
-                          sequences_scores=beam_scores if output_scores else None, beam_indices=beam_idx_tab[:, :n])
+    return GenerateOutput(sequences, scores=tuple(all_scores) if o.output_scores else None, logits=tuple(all_logits) if o.output_logits else None,
+                          sequences_scores=beam_scores if o.output_scores else None, beam_indices=beam_idx_tab[:, :n])
 
 
-def _beam_search(decoder, inputs_embeds, attention_mask, max_length: int, eos_ids, pad_id: int, nb: int, length_penalty: float, early_stopping,
-                 num_return_sequences: int, return_dict: bool, output_scores: bool, output_logits: bool, stream_copy: bool = True,
-                 beam_select: Optional[str] = None, use_graph: bool = True, sync_every: int = 16, sampling: Optional[dict] = None):
-    if beam_select not in (None, "device", "torch"):
-        raise ValueError(f"generate: beam_select = {beam_select!r}: 'device', 'torch' or None")
-    B, V = inputs_embeds.shape[0], decoder.spec.vocab_size
-    if beam_select != "torch":
-        if beam_select_supported(B, nb, len(eos_ids), V):
-            return _beam_search_device(decoder, inputs_embeds, attention_mask, max_length, eos_ids, pad_id, nb, length_penalty, early_stopping,
-                                       num_return_sequences, return_dict, output_scores, output_logits, stream_copy, use_graph, sync_every, sampling)
-        if beam_select == "device":
+def _beam_search(decoder, inputs_embeds, attention_mask, o):
+    """`o`: what generate() decided for the search, under the names of its one call site (max_length counts the new tokens)."""
+    if o.beam_select not in (None, "device", "torch"):
+        raise ValueError(f"generate: beam_select = {o.beam_select!r}: 'device', 'torch' or None")
+    B, V, nb, max_length = inputs_embeds.shape[0], decoder.spec.vocab_size, o.nb, o.max_length
+    if o.beam_select != "torch":
+        if beam_select_supported(B, nb, len(o.eos_ids), V):
+            return _beam_search_device(decoder, inputs_embeds, attention_mask, o)
+        if o.beam_select == "device":
             raise ValueError(f"generate(beam_select='device'): p2t_beam_select serves 1 <= num_beams <= {BEAMS_MAX} with max(2, 1 + number of eos ids) * "
-                             f"num_beams <= {KEEP_MAX} <= vocabulary (got num_beams = {nb}, {len(eos_ids)} eos ids); the torch path serves the rest")
-    eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, stream_copy)
+                             f"num_beams <= {KEEP_MAX} <= vocabulary (got num_beams = {nb}, {len(o.eos_ids)} eos ids); the torch path serves the rest")
+    eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy)
     dev = eng.dev
     embeds, mask = eng.compact(inputs_embeds, attention_mask)
     first_logits = eng.prefill(embeds, mask)                                 # [B, ld]: the beams of a prompt start from the same state
-    eos = torch.tensor(eos_ids, dtype=torch.int64, device=dev)
-    st = beam_state_init(B, nb, max_length, pad_id, dev)
+    eos = torch.tensor(o.eos_ids, dtype=torch.int64, device=dev)
+    st = beam_state_init(B, nb, max_length, o.pad_id, dev)
     all_scores, all_logits = [], []
-    draw = {} if sampling is None else dict(do_sample=True, generator=sampling["generator"], temperature=sampling["temperature"],
-                                            top_k=sampling["top_k"], top_p=sampling["top_p"])
+    draw = {} if o.sampling is None else dict(do_sample=True, **{k: o.sampling[k] for k in ("generator", "temperature", "top_k", "top_p")})
     cur = 0
     while True:
         if cur == 0:
             logits = first_logits[:, :V].float().repeat_interleave(nb, dim=0)     # HF expands the prompt nb times before its prefill
         else:
             logits = eng.logits[:, :V].float()
-        if return_dict and output_logits:
+        if o.return_dict and o.output_logits:
             all_logits.append(logits.clone())
-        st, log_probs, src_rows, _, go_on = beam_step_torch(st, logits, cur, nb, eos, length_penalty, early_stopping, max_length, **draw)
-        if return_dict and output_scores:
+        st, log_probs, src_rows, _, go_on = beam_step_torch(st, logits, cur, nb, eos, o.length_penalty, o.early_stopping, max_length, **draw)
+        if o.return_dict and o.output_scores:
             all_scores.append(log_probs)
         cur += 1
         if not bool(go_on.item()) or cur >= max_length:
@@ -566,8 +576,7 @@ def _beam_search(decoder, inputs_embeds, attention_mask, max_length: int, eos_id
         eng.next_tokens.copy_(st["running"][:, :, cur - 1].reshape(-1))
         eng.feed(eng.next_tokens)
         eng.decode_step()
-    return _beam_output(st["sequences"], st["beam_scores"], st["beam_idx_tab"], B, num_return_sequences, return_dict, output_scores, output_logits,
-                        all_scores, all_logits)
+    return _beam_output(o, st["sequences"], st["beam_scores"], st["beam_idx_tab"], B, all_scores, all_logits)
 
 
 class BeamState:
@@ -592,13 +601,18 @@ class BeamState:
         self.c = _lib.BeamStateC(**{n: getattr(self, n).data_ptr() for n, _ in _lib.BeamStateC._fields_})
 
 
+def _beam_call(name: str, logits, V, state, eos, pad_id, length_penalty, early_stopping, max_length, step, next_tokens, src_rows, scores, *more):
+    """Entry point `name` on p2t_beam_select's argument list, then `more`, then the stream."""
+    es = 1 if early_stopping is True else (2 if early_stopping == "never" else 0)
+    call(name, ptr(logits), ops.dt_of(logits), logits.stride(0), state.B, state.nb, V, ptr(eos) if eos.numel() else None, eos.numel(),
+         int(pad_id), float(length_penalty), es, int(max_length), state.G, ptr(step), C.byref(state.c), ptr(next_tokens), ptr(src_rows),
+         ptr(scores) if scores is not None else None, scores.stride(0) if scores is not None else 0, *more, stream())
+
+
 def beam_select(logits: torch.Tensor, V: int, state: BeamState, eos: torch.Tensor, pad_id: int, length_penalty: float, early_stopping,
                 max_length: int, step: torch.Tensor, next_tokens: torch.Tensor, src_rows: torch.Tensor, scores: Optional[torch.Tensor] = None):
     """One p2t_beam_select call: logits `dtype` [B nb, ld >= V] -> next_tokens, src_rows i64 [B nb] and the state's other half."""
-    es = 1 if early_stopping is True else (2 if early_stopping == "never" else 0)
-    call("p2t_beam_select", ptr(logits), ops.dt_of(logits), logits.stride(0), state.B, state.nb, V, ptr(eos) if eos.numel() else None, eos.numel(),
-         int(pad_id), float(length_penalty), es, int(max_length), state.G, ptr(step), C.byref(state.c), ptr(next_tokens), ptr(src_rows),
-         ptr(scores) if scores is not None else None, scores.stride(0) if scores is not None else 0, stream())
+    _beam_call("p2t_beam_select", logits, V, state, eos, pad_id, length_penalty, early_stopping, max_length, step, next_tokens, src_rows, scores)
 
 
 def beam_sample_select(logits: torch.Tensor, V: int, state: BeamState, eos: torch.Tensor, pad_id: int, length_penalty: float, early_stopping,
@@ -606,55 +620,41 @@ def beam_sample_select(logits: torch.Tensor, V: int, state: BeamState, eos: torc
                        top_p: float, seed: int, scores: Optional[torch.Tensor] = None, prompt0: int = 0):
     """One p2t_beam_sample_select call (`state` built with sample=True): beam_select's arguments plus the sampler's; prompt b draws as
     prompt0 + b at the device step counter.  The flags word is state.flags."""
-    es = 1 if early_stopping is True else (2 if early_stopping == "never" else 0)
-    call("p2t_beam_sample_select", ptr(logits), ops.dt_of(logits), logits.stride(0), state.B, state.nb, V, ptr(eos) if eos.numel() else None,
-         eos.numel(), int(pad_id), float(length_penalty), es, int(max_length), state.G, ptr(step), C.byref(state.c), ptr(next_tokens), ptr(src_rows),
-         ptr(scores) if scores is not None else None, scores.stride(0) if scores is not None else 0, float(temperature), int(top_k), float(top_p),
-         int(seed) & (2 ** 64 - 1), int(prompt0), ptr(state.flags), stream())
+    _beam_call("p2t_beam_sample_select", logits, V, state, eos, pad_id, length_penalty, early_stopping, max_length, step, next_tokens, src_rows,
+               scores, float(temperature), int(top_k), float(top_p), int(seed) & (2 ** 64 - 1), int(prompt0), ptr(state.flags))
 
 
-def _beam_search_device(decoder, inputs_embeds, attention_mask, max_length: int, eos_ids, pad_id: int, nb: int, length_penalty: float,
-                        early_stopping, num_return_sequences: int, return_dict: bool, output_scores: bool, output_logits: bool,
-                        stream_copy: bool, use_graph: bool, sync_every: int, sampling: Optional[dict] = None):
-    """The same search with p2t_beam_select (`sampling`: p2t_beam_sample_select) in the torch bookkeeping's place: the first token from the prefill logits, one eager step, then
-    a replayed graph of TWO steps (reorder, feed, decode, select, twice: the engine's cache buffers are back where the capture found
-    them), an odd remainder eagerly.  The host reads `done` every `sync_every` tokens and at the end; steps run past the stop leave
-    the state as it is."""
-    B, V = inputs_embeds.shape[0], decoder.spec.vocab_size
-    eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, stream_copy)
+def _beam_search_device(decoder, inputs_embeds, attention_mask, o):
+    """The same search with p2t_beam_select (`o.sampling`: p2t_beam_sample_select) in the torch bookkeeping's place: the first token from
+    the prefill logits, one eager step, then a replayed graph of TWO steps (reorder, feed, decode, select, twice: the engine's cache
+    buffers are back where the capture found them), an odd remainder eagerly.  The host reads `done` every `sync_every` tokens and at
+    the end; steps run past the stop leave the state as it is."""
+    B, V, nb, max_length, sampling = inputs_embeds.shape[0], decoder.spec.vocab_size, o.nb, o.max_length, o.sampling
+    eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy)
     dev = eng.dev
     embeds, mask = eng.compact(inputs_embeds, attention_mask)
     first = eng.prefill(embeds, mask).repeat_interleave(nb, dim=0).contiguous()     # HF expands the prompt nb times before its prefill
-    eos = torch.tensor(eos_ids, dtype=torch.int64, device=dev)
-    st = BeamState(B, nb, eng.G, pad_id, dev, sample=sampling is not None)
+    eos = torch.tensor(o.eos_ids, dtype=torch.int64, device=dev)
+    st = BeamState(B, nb, eng.G, o.pad_id, dev, sample=sampling is not None)
     src_rows = torch.zeros((eng.BB,), dtype=torch.int64, device=dev)
-    keep_scores, keep_logits = return_dict and output_scores, return_dict and output_logits
+    keep_scores, keep_logits = o.return_dict and o.output_scores, o.return_dict and o.output_logits
     # two step slots: a replayed pair leaves the logits / log-probabilities of both its steps to be cloned afterwards
     lslots = [eng.logits, torch.zeros_like(eng.logits)] if keep_logits else [eng.logits, eng.logits]
     sslots = [torch.empty((eng.BB, V), dtype=torch.float32, device=dev) for _ in range(2)] if keep_scores else [None, None]
     all_scores, all_logits = [], []
-
     warned = set()
 
     def read_done() -> bool:                              # one host read: `done` and, under sampling, the flags word next to it
         if sampling is not None:
-            bits = int(st.flags.item())
-            if bits & 1 and 1 not in warned:
-                warned.add(1)
-                warnings.warn("generate(seed=): more than 2048 logits tied at the top-k boundary of a row; the ties beyond the table were dropped "
-                              "in ascending column order (HF would keep them all)", RuntimeWarning, stacklevel=4)
-            if bits & 2 and 2 not in warned:
-                warned.add(2)
-                warnings.warn("generate(seed=): a prompt ran out of continuations with positive probability under beam sampling (HF's "
-                              "torch.multinomial fails there); its results are unspecified", RuntimeWarning, stacklevel=4)
+            _warn_flags(st.flags, warned, 6)              # this closure, this function, _beam_search, generate(), its caller
         return bool(st.done[0].item())
 
     def select(lg, slot):
+        common = (lg, V, st, eos, o.pad_id, o.length_penalty, o.early_stopping, max_length, eng.step, eng.next_tokens, src_rows)
         if sampling is None:
-            beam_select(lg, V, st, eos, pad_id, length_penalty, early_stopping, max_length, eng.step, eng.next_tokens, src_rows, sslots[slot])
+            beam_select(*common, sslots[slot])
         else:
-            beam_sample_select(lg, V, st, eos, pad_id, length_penalty, early_stopping, max_length, eng.step, eng.next_tokens, src_rows,
-                               sampling["temperature"], sampling["top_k"], sampling["top_p"], sampling["seed"], sslots[slot])
+            beam_sample_select(*common, sampling["temperature"], sampling["top_k"], sampling["top_p"], sampling["seed"], sslots[slot])
 
     def keep(lg, slot):
         if keep_logits:
@@ -673,11 +673,11 @@ def _beam_search_device(decoder, inputs_embeds, attention_mask, max_length: int,
     keep(first, 0)
     graph, n, read_at = None, 1, 0
     while n < max_length:
-        if n == 1 or n - read_at >= sync_every:
+        if n == 1 or n - read_at >= o.sync_every:
             read_at = n
             if read_done():
                 break
-        if use_graph and n >= 2 and max_length - n >= 2:                  # the first step ran eagerly (lazy one-time initialisation inside the library)
+        if o.use_graph and n >= 2 and max_length - n >= 2:                # the first step ran eagerly (lazy one-time initialisation inside the library)
             if graph is None:
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph, capture_error_mode="thread_local"):
@@ -696,5 +696,4 @@ def _beam_search_device(decoder, inputs_embeds, attention_mask, max_length: int,
     if not done:
         raise RuntimeError("generate: the beam search ran its max_new_tokens steps and p2t_beam_select did not raise `done`")
     half = steps & 1
-    return _beam_output(st.fin_seq[half], st.fin_scores[half], st.fin_idx[half], B, num_return_sequences, return_dict, output_scores, output_logits,
-                        all_scores[:steps], all_logits[:steps])
+    return _beam_output(o, st.fin_seq[half], st.fin_scores[half], st.fin_idx[half], B, all_scores[:steps], all_logits[:steps])

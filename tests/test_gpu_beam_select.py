@@ -139,6 +139,22 @@ def test_exact_bf16_ties_across_the_keep_cut_follow_the_column_rule():
     assert _compare(ref, _read(st, 1, L), nxt, src, None, 0, nb, "ties") == 1
 
 
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_a_plateau_wider_than_the_table_keeps_its_first_columns(dtype):
+    """3000 columns at or above the keep-th value, kCap = 2048 slots: the ordered collection takes the one value above the plateau,
+    then the plateau in ascending column order."""
+    V, ld, nb, L = 3000, 3008, 2, 8
+    vals = np.full((nb, V), 1.25, dtype=np.float32)
+    vals[0, 2999] = vals[1, 5] = 2.5
+    st = G.BeamState(1, nb, GCAP, PAD, dev())
+    ref = BR.step(vals, BR.fresh_state(1, nb, L, PAD), 0, nb, [], 1.0, False, L, PAD)
+    assert ref["decidable"].all() and ref["running_decidable"].all()
+    assert list(ref["next_tokens"]) == [2999, 0] and list(ref["src_rows"]) == [0, 0]
+    nxt, src = _call(st, _tensor(vals, ld, dtype), V, 0, [], 1.0, False, L)
+    assert list(nxt) == [2999, 0] and list(src) == [0, 0]
+    assert _compare(ref, _read(st, 1, L), nxt, src, None, 0, nb, "plateau " + dtype) == 1
+
+
 def test_eos_enters_the_finished_slots_only_from_a_rank_below_nb():
     V, nb, L, eos = 257, 2, 8, 256
     vals = BR.case_logits(6, 0, 2 * nb, V, "f32", [])
