@@ -650,6 +650,33 @@ int p2t_sample_select(const void* logits, int dtype, int64_t ld, int V, int BB, 
                       int64_t pad_id, int32_t* finished, int64_t* next_tokens, int64_t* out_tokens, int64_t ld_tokens,
                       const int32_t* step, int G, float temperature, int top_k, float top_p, uint64_t seed, int64_t row0,
                       float* scores, int64_t ld_scores, int32_t* flags, p2t_stream stream);
+/* Logits processors in front of p2t_greedy_select / p2t_sample_select: HF's RepetitionPenaltyLogitsProcessor ->
+ * NoRepeatNGramLogitsProcessor -> NoBadWordsLogitsProcessor (SuppressTokensLogitsProcessor as words of one token) ->
+ * MinNewTokensLengthLogitsProcessor (transformers 5.15, the order of generation/utils.py `_get_logits_processor`), for prompts given as
+ * embeddings: HF's input_ids then hold the generated tokens only, and so does the history here.  logits: `dtype` (F32 | BF16)
+ * [BB, ld >= V], never written (HF up-casts the last position to f32 before any processor runs); out: f32 [BB, ld_out >= V], which the
+ * selectors then read with dtype F32; it must not overlap logits.  Columns V .. ld are never read, columns V .. ld_out never written.
+ * Per row r, with cur = clamp(step[0], 0, G) and the history h = out_tokens[r, 0 .. cur) (i64 [BB, ld_tokens >= G]: the columns the
+ * selectors wrote, the pad tokens of a finished row included -- harmless, a finished row emits pad whatever its scores are); every
+ * value an f32, every stage strictly after the one before, so a later -inf wins; a history or word token outside [0, V) is compared
+ * like any other and never written to:
+ *   1. y_c = float(logit_c) for c < V.
+ *   2. repetition_penalty != 1: for every history token t, y_t = x_t < 0 ? x_t * penalty : x_t / penalty (one IEEE multiplication or
+ *      division), x_t the STORED logit: duplicates in the history write the same bits.
+ *   3. n = no_repeat_ngram_size > 0 and cur >= n: for every i in [0, cur - n] with h[i .. i + n - 2] equal to the last n - 1 history tokens
+ *      h[cur - n + 1 .. cur), y[h[i + n - 1]] = -inf.  n = 1: every history token.
+ *   4. word w = word_ids[word_offsets[w] .. word_offsets[w + 1]) of length L (word_ids i64 [n_word_ids], word_offsets i32 [n_words + 1],
+ *      ascending; a word whose offsets leave [0, n_word_ids] or are not ascending is skipped): L = 1: y[word] = -inf, always.  L > 1:
+ *      applied once cur >= L (HF skips a word "longer than the context", although its L - 1 leading tokens would fit): if they equal the
+ *      last L - 1 history tokens, y[last token of w] = -inf.  HF drops a word equal to [eos]; that is the caller's to do.
+ *   5. cur < min_new_tokens: y[e] = -inf for each of the n_eos ids (no eos ids: nothing, HF does not install the processor).
+ * HF's NoBadWordsLogitsProcessor adds a bias row (0 or -inf) and so turns a stored -0.0 into +0.0; here every column no stage names
+ * keeps its stored bits.  One 1024-thread block per row, barriers between the stages, no atomics: the same inputs give the same bits.
+ * Does not allocate, copy or synchronise: it can be captured into a HIP graph. */
+int p2t_logits_process(const void* logits, int dtype, int64_t ld, int V, int BB, const int64_t* out_tokens, int64_t ld_tokens,
+                       const int32_t* step, int G, float* out, int64_t ld_out, float repetition_penalty, int no_repeat_ngram_size,
+                       int min_new_tokens, const int64_t* eos_ids, int n_eos, const int64_t* word_ids, const int32_t* word_offsets,
+                       int n_words, int n_word_ids, p2t_stream stream);
 /* Choice by beam search: one step of transformers' `_beam_search` (5.x, generation/utils.py) with an empty id prompt
  * (decoder_prompt_len 0, max_length = max_new_tokens), for B0 prompts of nb = num_beams rows each (row b nb + j = beam j of prompt b).
  * State, all on the device and the caller's.  Tables and per-beam vectors have TWO halves: a step at cur = step[0] reads half cur & 1

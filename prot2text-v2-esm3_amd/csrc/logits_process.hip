@@ -1,0 +1,153 @@
+// Logits processors in front of the token selectors (p2t_logits_process): HF's RepetitionPenaltyLogitsProcessor ->
+// NoRepeatNGramLogitsProcessor -> NoBadWordsLogitsProcessor (SuppressTokensLogitsProcessor folded in as one-token words) ->
+// MinNewTokensLengthLogitsProcessor (transformers/generation/logits_process.py, in the order of GenerationMixin._get_logits_processor),
+// one 1024-thread block per row.  The contract is the comment on p2t_logits_process in include/p2t_hip.h;
+// tests/logits_process_reference.py restates it in numpy float32.
+//
+// The row's history is out_tokens[r, 0 .. cur), cur = clamp(step[0], 0, G): the tokens the selectors wrote, read on the device, so
+// the launch can sit inside the captured step graph.  The stored logits are never edited: the block writes an f32 row of its own
+// and the selectors read that.
+//   1. copy: y_c = float(logit_c), 16-byte loads and stores where pitch and base of both rows allow them.
+//   2. penalty: thread i of the history writes y_t = x_t < 0 ? x_t * penalty : x_t / penalty with x_t read from the SOURCE row, so two
+//      threads holding the same token write the same bits (no de-duplication, no atomics).
+//   3. n-gram: thread i compares history[i .. i + n - 1) with the last n - 1 tokens and writes -inf at history[i + n - 1].
+//   4. bad words: thread w compares all but the last token of word w with the end of the history and writes -inf at its last token.
+//   5. min new tokens: thread e writes -inf at eos id e while cur < min_new_tokens.
+// Stages 3 - 5 only ever write -inf, stage 2 writes one value per column: whatever the thread order, the same inputs give the same
+// bits.  A barrier separates the stages (one block owns the row, so the block's own order is all that is needed).  Every column
+// written is checked against [0, V), every history index against [0, cur), every word offset against [0, n_word_ids].
+#include "common.h"
+
+namespace p2t {
+namespace {
+
+template <typename T>
+__global__ void __launch_bounds__(1024) logits_process_kernel(const T* __restrict__ logits, int64_t ld, int V, const int64_t* __restrict__ out_tokens,
+                                                              int64_t ld_tok, const int32_t* __restrict__ step_ptr, int G, float* __restrict__ out,
+                                                              int64_t ld_out, float penalty, int ngram, int min_new, const int64_t* __restrict__ eos,
+                                                              int n_eos, const int64_t* __restrict__ words, const int32_t* __restrict__ offsets,
+                                                              int n_words, int n_word_ids) {
+    const int bb = blockIdx.x, tid = threadIdx.x;
+    const T* row = logits + (int64_t)bb * ld;
+    float* y = out + (int64_t)bb * ld_out;
+    const int64_t* hist = out_tokens + (int64_t)bb * ld_tok;
+    const int cur = min(max(step_ptr[0], 0), G);
+    const float ninf = -INFINITY;
+
+    // ---- 1. copy ----------------------------------------------------------------------------------------------------------
+    constexpr int PN = sizeof(T) == 2 ? 8 : 4;
+    const bool vec = ld % PN == 0 && ((uintptr_t)logits & 15u) == 0 && ld_out % 4 == 0 && ((uintptr_t)out & 15u) == 0;
+    const int nvec = vec ? V / PN : 0, Vv = nvec * PN;           // 16-byte pieces of the source row
+    // one block streams the whole row, so the copy is bound by load latency, not bandwidth: kUnroll loads per thread are in flight
+    // before the first store (128 256 columns in bf16: 16 pieces per thread, two rounds)
+    constexpr int kUnroll = 8;
+    const uint4* src = reinterpret_cast<const uint4*>(row);
+    for (int p0 = tid; p0 < nvec; p0 += 1024 * kUnroll) {
+        uint4 t[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int p = p0 + u * 1024;
+            t[u] = p < nvec ? src[p] : make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int p = p0 + u * 1024;
+            if (p >= nvec) continue;
+            float* d = y + (int64_t)p * PN;
+            if constexpr (PN == 8) {                              // bf16 -> f32: the 16 bits above 16 zeros
+                *reinterpret_cast<float4*>(d) = make_float4(__uint_as_float(t[u].x << 16), __uint_as_float(t[u].x & 0xFFFF0000u),
+                                                            __uint_as_float(t[u].y << 16), __uint_as_float(t[u].y & 0xFFFF0000u));
+                *reinterpret_cast<float4*>(d + 4) = make_float4(__uint_as_float(t[u].z << 16), __uint_as_float(t[u].z & 0xFFFF0000u),
+                                                                __uint_as_float(t[u].w << 16), __uint_as_float(t[u].w & 0xFFFF0000u));
+            } else {
+                *reinterpret_cast<uint4*>(d) = t[u];
+            }
+        }
+    }
+    for (int c = Vv + tid; c < V; c += 1024) y[c] = to_f32(row[c]);
+    __syncthreads();
+
+    // ---- 2. repetition penalty ----------------------------------------------------------------------------------------------
+    if (penalty != 1.f) {
+        for (int i = tid; i < cur; i += 1024) {
+            const int64_t t = hist[i];
+            if (t >= 0 && t < V) {
+                const float x = to_f32(row[t]);
+                y[t] = x < 0.f ? x * penalty : x / penalty;
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- 3. no repeated n-gram: windows i .. i + n - 1 inside the history, i <= cur - n ---------------------------------------------
+    if (ngram > 0 && cur >= ngram) {
+        const int64_t* last = hist + (cur - (ngram - 1));         // the last n - 1 tokens
+        for (int i = tid; i <= cur - ngram; i += 1024) {
+            bool same = true;
+            for (int j = 0; j < ngram - 1 && same; ++j) same = hist[i + j] == last[j];
+            if (same) {
+                const int64_t t = hist[i + ngram - 1];
+                if (t >= 0 && t < V) y[t] = ninf;
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- 4. bad words (a suppressed token is a word of one token) ----------------------------------------------------------------------
+    for (int w = tid; w < n_words; w += 1024) {
+        const int lo = offsets[w], hi = offsets[w + 1];
+        if (lo < 0 || hi <= lo || hi > n_word_ids) continue;
+        const int L = hi - lo;
+        if (L > 1 && L > cur) continue;                           // HF: "the sequence is longer than the context, ignore"
+        bool same = true;
+        for (int j = 0; j < L - 1 && same; ++j) same = words[lo + j] == hist[cur - (L - 1) + j];
+        if (same) {
+            const int64_t t = words[hi - 1];
+            if (t >= 0 && t < V) y[t] = ninf;
+        }
+    }
+    __syncthreads();
+
+    // ---- 5. no eos before min_new_tokens -----------------------------------------------------------------------------------------
+    if (cur < min_new) {
+        for (int e = tid; e < n_eos; e += 1024) {
+            const int64_t t = eos[e];
+            if (t >= 0 && t < V) y[t] = ninf;
+        }
+    }
+}
+
+}  // namespace
+}  // namespace p2t
+
+using namespace p2t;
+
+extern "C" int p2t_logits_process(const void* logits, int dtype, int64_t ld, int V, int BB, const int64_t* out_tokens, int64_t ld_tokens,
+                                  const int32_t* step, int G, float* out, int64_t ld_out, float repetition_penalty, int no_repeat_ngram_size,
+                                  int min_new_tokens, const int64_t* eos_ids, int n_eos, const int64_t* word_ids, const int32_t* word_offsets,
+                                  int n_words, int n_word_ids, p2t_stream stream) {
+    P2T_REQUIRE(logits && out_tokens && step && out, "p2t_logits_process: null argument");
+    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_logits_process: dtype %d is neither P2T_F32 nor P2T_BF16", dtype);
+    P2T_REQUIRE(BB > 0 && V > 0 && ld >= V && ld_out >= V,
+                "p2t_logits_process: BB = %d, V = %d, ld = %lld, ld_out = %lld: needs BB > 0, V > 0, ld >= V, ld_out >= V", BB, V, (long long)ld,
+                (long long)ld_out);
+    P2T_REQUIRE(G > 0 && ld_tokens >= G, "p2t_logits_process: G = %d, ld_tokens = %lld: needs G > 0, ld_tokens >= G", G, (long long)ld_tokens);
+    P2T_REQUIRE(repetition_penalty > 0.f && repetition_penalty < INFINITY, "p2t_logits_process: repetition_penalty %g is not a positive finite number",
+                (double)repetition_penalty);
+    P2T_REQUIRE(no_repeat_ngram_size >= 0 && min_new_tokens >= 0,
+                "p2t_logits_process: no_repeat_ngram_size = %d, min_new_tokens = %d: needs both >= 0 (0: off)", no_repeat_ngram_size, min_new_tokens);
+    P2T_REQUIRE(n_eos >= 0 && (n_eos == 0 || eos_ids), "p2t_logits_process: n_eos = %d: needs n_eos >= 0, eos_ids for n_eos > 0", n_eos);
+    P2T_REQUIRE(n_words >= 0 && n_word_ids >= 0 && (n_words == 0 || (word_ids && word_offsets && n_word_ids > 0)),
+                "p2t_logits_process: n_words = %d, n_word_ids = %d: needs both >= 0, word_ids, word_offsets and n_word_ids > 0 for n_words > 0", n_words,
+                n_word_ids);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == P2T_BF16)
+        logits_process_kernel<bf16_t><<<BB, 1024, 0, s>>>((const bf16_t*)logits, ld, V, out_tokens, ld_tokens, step, G, out, ld_out, repetition_penalty,
+                                                          no_repeat_ngram_size, min_new_tokens, eos_ids, n_eos, word_ids, word_offsets, n_words,
+                                                          n_word_ids);
+    else
+        logits_process_kernel<float><<<BB, 1024, 0, s>>>((const float*)logits, ld, V, out_tokens, ld_tokens, step, G, out, ld_out, repetition_penalty,
+                                                         no_repeat_ngram_size, min_new_tokens, eos_ids, n_eos, word_ids, word_offsets, n_words, n_word_ids);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}

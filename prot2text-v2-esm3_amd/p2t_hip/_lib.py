@@ -159,6 +159,7 @@ SIGNATURES = {
                               i32, vp, sz, vp]),
     "p2t_greedy_select": (i32, [vp, i32, i64, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, i32, vp]),
     "p2t_sample_select": (i32, [vp, i32, i64, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, i32, f32, i32, f32, u64, i64, vp, i64, vp, vp]),
+    "p2t_logits_process": (i32, [vp, i32, i64, i32, i32, vp, i64, vp, i32, vp, i64, f32, i32, i32, vp, i32, vp, vp, i32, i32, vp]),
     "p2t_beam_workspace_bytes": (sz, [i32, i32]),
     "p2t_beam_select": (i32, [vp, i32, i64, i32, i32, i32, vp, i32, i64, f32, i32, i32, i32, vp, C.POINTER(BeamStateC), vp, vp, vp, i64, vp]),
     "p2t_beam_sample_workspace_bytes": (sz, [i32, i32]),

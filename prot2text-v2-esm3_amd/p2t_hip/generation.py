@@ -12,7 +12,10 @@ place of the greedy choice, captured and replayed alike.  Beam search selects wi
 the cut to max(2, 1 + n_eos) * beams candidates, the finished slots, the stop condition and the token tables, all in device memory)
 and replays a graph of two steps, since the beam re-ordering swaps two cache buffers.  Beam sampling (`num_beams > 1, do_sample=True`
 with `seed=` and `beam_select="device"`) is that loop with p2t_beam_sample_select (csrc/beam_sample_select.hip: the warpers on the
-log-probabilities and keep draws without replacement as the descending order of score + counter-hashed Gumbel noise).  Sampling with a torch `generator` (temperature /
+log-probabilities and keep draws without replacement as the descending order of score + counter-hashed Gumbel noise).  The logits
+processors of `num_beams == 1` (repetition penalty, n-gram, bad-word / suppressed-token and min-new-token bans) are p2t_logits_process
+(csrc/logits_process.hip), one launch in front of the greedy / sampled choice inside the same graph: it reads the step's logits and the
+rows' own generated history on the device and writes the f32 scores the selector then reads.  Sampling with a torch `generator` (temperature /
 top-k / top-p filters + multinomial) and the beam bookkeeping under `beam_select="torch"` or outside the kernel's range (log-softmax,
 top-k over beams x vocabulary, gathers of the token tables) are torch device ops on the [rows, vocab] logits -- selection bookkeeping,
 restated from transformers/generation/utils.py (`_sample`, `_beam_search` and its helpers) and transformers/generation/
@@ -99,6 +102,38 @@ def _sampler_args(temperature, top_k, top_p, seed, generator, device: bool = Tru
     return temperature, k, p
 
 
+def _processor_args(V: int, eos_ids: Sequence[int], repetition_penalty, no_repeat_ngram_size, min_new_tokens, bad_words_ids, suppress_tokens):
+    """generate()'s logits-processor keywords -> the settings of p2t_logits_process (None: no processor is active), checked up front with
+    HF's wording where HF has one (transformers/generation/logits_process.py).  Words: the bad words without any equal to [eos] (HF drops
+    them), then every suppressed id as a word of one token."""
+    penalty = 1.0 if repetition_penalty is None else repetition_penalty
+    if isinstance(penalty, bool) or not isinstance(penalty, (int, float)) or not (penalty > 0 and penalty < float("inf")):
+        raise ValueError(f"`penalty` has to be a strictly positive float, but is {repetition_penalty}")
+    ngram = 0 if no_repeat_ngram_size is None else no_repeat_ngram_size
+    if isinstance(ngram, bool) or not isinstance(ngram, int) or ngram < 0:
+        raise ValueError(f"`ngram_size` has to be a strictly positive integer, but is {no_repeat_ngram_size}")
+    min_new = 0 if min_new_tokens is None else min_new_tokens
+    if isinstance(min_new, bool) or not isinstance(min_new, int) or min_new < 0:
+        raise ValueError(f"`min_new_tokens` has to be a positive integer, but is {min_new_tokens}")
+    words = []
+    if bad_words_ids is not None:
+        if not isinstance(bad_words_ids, list) or len(bad_words_ids) == 0:
+            raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bad_words_ids}.")
+        if any(not isinstance(w, list) for w in bad_words_ids):
+            raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bad_words_ids}.")
+        if any(len(w) == 0 or any(isinstance(t, bool) or not isinstance(t, int) or t < 0 for t in w) for w in bad_words_ids):
+            raise ValueError(f"Each list in `bad_words_ids` has to be a non-empty list of positive integers, but is {bad_words_ids}.")
+        beyond = [t for w in bad_words_ids for t in w if t >= V]
+        if beyond:
+            raise ValueError(f"The model vocabulary size is {V}, but the following tokens were being biased: {beyond}")
+        words = [list(w) for w in bad_words_ids if all(list(w) != [e] for e in eos_ids)]
+    words += [[t] for t in _as_id_list(suppress_tokens)]          # ids outside the vocabulary name no column (HF: torch.isin over arange(V))
+    min_new = min_new if eos_ids else 0                           # HF installs MinNewTokensLengthLogitsProcessor only with an eos id
+    if float(penalty) == 1.0 and ngram == 0 and min_new == 0 and not words:
+        return None
+    return dict(penalty=float(penalty), ngram=int(ngram), min_new=int(min_new), words=words)
+
+
 _FLAG_WARNINGS = ((1, "generate(seed=): more than 2048 logits tied at the top-k boundary of a row; the ties beyond the table were dropped in "
                       "ascending column order (HF would keep them all)"),
                   (2, "generate(seed=): a prompt ran out of continuations with positive probability under beam sampling (HF's torch.multinomial "
@@ -153,7 +188,8 @@ def stream_weights(decoder):
 class DecodeEngine:
     """Cache + buffers of ONE generate() call: B0 prompts, `group` rows per prompt (beams), capacities Tp / G (multiples of 64)."""
 
-    def __init__(self, decoder, B0: int, group: int, T: int, max_new_tokens: int, stream_copy: bool = True, fuse_rope: bool = True):
+    def __init__(self, decoder, B0: int, group: int, T: int, max_new_tokens: int, stream_copy: bool = True, fuse_rope: bool = True,
+                 processors: Optional[dict] = None, eos_ids: Sequence[int] = ()):
         m, s = decoder.model, decoder.spec
         self.flags = 0 if fuse_rope else 1          # P2T_DECODE_NO_ROPE_FUSION
         if s.hidden_size % 64:
@@ -184,6 +220,14 @@ class DecodeEngine:
         # run on the row-major weights (the LM head had no row-major fallback and returned wrong logits)
         self.stream = stream_weights(decoder) if (stream_copy and self.dtype == torch.bfloat16 and B0 * group <= 64) else None
         self._cache_struct()
+        self.processors = processors                                      # _processor_args' settings, or None: nothing allocated, nothing launched
+        if processors is not None:
+            i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=self.dev)
+            lens = [len(w) for w in processors["words"]]
+            self.processed = torch.zeros((self.BB, self.ld_logits), dtype=torch.float32, device=self.dev)
+            self.proc_eos = i64(list(eos_ids)) if processors["min_new"] > 0 else i64([])
+            self.word_ids = i64([t for w in processors["words"] for t in w])
+            self.word_offsets = torch.tensor([sum(lens[:i]) for i in range(len(lens) + 1)], dtype=torch.int32, device=self.dev)
 
     def _cache_struct(self):
         self.cache = _lib.KvCacheC(k_prompt=self.k_prompt.data_ptr(), vt_prompt=self.vt_prompt.data_ptr(), k_gen=self.k_gen.data_ptr(),
@@ -242,6 +286,16 @@ class DecodeEngine:
              float(temperature), int(top_k), float(top_p), int(seed) & (2 ** 64 - 1), int(row0), ptr(scores) if scores is not None else None,
              scores.stride(0) if scores is not None else 0, ptr(self.sample_flags), stream())
 
+    def process(self, logits: torch.Tensor) -> torch.Tensor:
+        """The logits processors on the step's logits and the rows' own history out_tokens[:, : step[0]] (p2t_logits_process, inside the
+        step graph like the selectors) -> the processed f32 buffer the selectors then read; `logits` stays as it is."""
+        pr, opt = self.processors, lambda t: ptr(t) if t.numel() else None
+        call("p2t_logits_process", ptr(logits), ops.dt_of(logits), logits.stride(0), self.spec.vocab_size, self.BB, ptr(self.out_tokens),
+             self.out_tokens.stride(0), ptr(self.step), self.G, ptr(self.processed), self.processed.stride(0), pr["penalty"], pr["ngram"],
+             pr["min_new"], opt(self.proc_eos), self.proc_eos.numel(), opt(self.word_ids), opt(self.word_offsets), len(pr["words"]),
+             self.word_ids.numel(), stream())
+        return self.processed
+
     def reorder(self, src_rows: torch.Tensor):
         """Generated segment row r <- row src_rows[r] (beam re-ordering; the prompt segment is shared by a prompt's beams)."""
         if self.k_alt is None:
@@ -271,7 +325,9 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
              top_k: Optional[int] = 50, top_p: Optional[float] = 1.0, num_beams: int = 1, length_penalty: float = 1.0,
              early_stopping=False, num_return_sequences: int = 1, return_dict_in_generate: bool = False, output_scores: bool = False,
              output_logits: bool = False, use_graph: bool = True, sync_every: int = 16, generator: Optional[torch.Generator] = None,
-             stream_copy: bool = True, fuse_rope: bool = True, seed: Optional[int] = None, beam_select: Optional[str] = None, **unused):
+             stream_copy: bool = True, fuse_rope: bool = True, seed: Optional[int] = None, beam_select: Optional[str] = None,
+             repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
+             bad_words_ids: Optional[list] = None, suppress_tokens=None, **unused):
     """`LlamaForCausalLM.generate` for prompts given as embeddings (or ids): greedy, sampling (temperature / top-k / top-p) and beam
     search with length penalty.  Returns the new token ids i64 [batch * num_return_sequences, n] (or a GenerateOutput).
 
@@ -290,7 +346,13 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     a captured graph of two steps; the host reads the search's `done` word every `sync_every` tokens.  `beam_select`: None (default) =
     the device path wherever it applies (num_beams <= 16, max(2, 1 + number of eos ids) * num_beams <= 64), the torch bookkeeping
     otherwise; "device" = required (ValueError outside that range); "torch" = the torch bookkeeping, one host read per token.  Ties
-    rank by (score descending, candidate index ascending) on the device path; torch.topk leaves them unspecified."""
+    rank by (score descending, candidate index ascending) on the device path; torch.topk leaves them unspecified.
+
+    Logits processors (`num_beams == 1`): `repetition_penalty` (off: None, 1.0), `no_repeat_ngram_size` (off: None, 0), `min_new_tokens`
+    (off: None, 0, or no eos id), `bad_words_ids` and `suppress_tokens`, with HF's semantics for prompts given as embeddings: the history
+    is the generated tokens only.  One kernel (p2t_logits_process) in front of the greedy / sampled choice, inside the replayed step graph,
+    and in front of the torch filters under `generator=`; `output_scores` then returns the processed scores, `output_logits` the raw rows.
+    With none of them active nothing is launched or allocated.  Under beam search they raise NotImplementedError."""
     if (inputs_embeds is None) == (input_ids is None):
         raise ValueError("pass exactly one of inputs_embeds / input_ids")
     if unused:
@@ -318,8 +380,14 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
             pad_token_id = 0
         else:
             pad_token_id = eos_ids[0]                                        # HF's fallback (with a warning)
+    V = decoder.spec.vocab_size
+    proc = _processor_args(V, eos_ids, repetition_penalty, no_repeat_ngram_size, min_new_tokens, bad_words_ids, suppress_tokens)
     if num_beams < 1 or num_return_sequences < 1 or num_return_sequences > num_beams and num_beams > 1:
         raise ValueError("num_beams >= 1 and 1 <= num_return_sequences <= num_beams")
+    if num_beams > 1 and proc is not None:
+        raise NotImplementedError("generate(): repetition_penalty / no_repeat_ngram_size / min_new_tokens / bad_words_ids / suppress_tokens are not "
+                                  "supported with num_beams > 1: HF applies the processors to the log-softmax inside the beam step, and "
+                                  "p2t_beam_select computes that log-softmax itself from the logits; they are served with num_beams == 1")
     if num_beams > 1:
         sampling = None
         if do_sample:
@@ -333,12 +401,11 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     if R != 1 and not do_sample:
         raise ValueError("greedy decoding returns one sequence per prompt: num_return_sequences > 1 needs do_sample=True or num_beams > 1")
     # R samples per prompt (HF repeats the prompt R times): R rows that SHARE the prompt segment of the cache, like the beams of a prompt
-    eng = DecodeEngine(decoder, B, R, T, max_new_tokens, stream_copy, fuse_rope)
+    eng = DecodeEngine(decoder, B, R, T, max_new_tokens, stream_copy, fuse_rope, processors=proc, eos_ids=eos_ids)
     embeds, mask = eng.compact(inputs_embeds, attention_mask)
     logits = eng.prefill(embeds, mask)
     if R > 1:
         logits = logits.repeat_interleave(R, dim=0)
-    V = decoder.spec.vocab_size
     eos = torch.tensor(eos_ids, dtype=torch.int64, device=eng.dev)
     on_device = bool(do_sample) and seed is not None
     if on_device:
@@ -348,7 +415,9 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
         # (the goldens cover greedy and beam search), so the combination is refused rather than answered with the raw logits
         raise NotImplementedError("generate: output_scores with do_sample is not supported (ask for output_logits: the raw LM-head rows)")
     keep_scores = [] if (on_device and return_dict_in_generate and output_scores) else None
-    keep_logits = [] if (return_dict_in_generate and (output_logits or (output_scores and not on_device))) else None
+    # greedy with processors: the step's scores are the processed rows (a clone of the engine's buffer), not the raw logits
+    keep_processed = [] if (proc is not None and return_dict_in_generate and output_scores and not do_sample) else None
+    keep_logits = [] if (return_dict_in_generate and (output_logits or (output_scores and not on_device and keep_processed is None))) else None
     scores_buf = torch.empty((eng.BB, V), dtype=torch.float32, device=eng.dev) if keep_scores is not None else None
     pad = int(pad_token_id)
     warned = set()
@@ -357,6 +426,8 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
         eng.sample_select(lg, eos, pad, temperature, k, p, seed, scores_buf)
 
     def choose(lg: torch.Tensor, col: int):
+        if proc is not None:
+            lg = eng.process(lg)                         # history: out_tokens[:, : step[0]], step[0] == col
         if on_device:
             sample(lg)                                   # writes column step[0] == col; step[0] is the draw's counter
         elif do_sample:
@@ -373,16 +444,21 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     def advance():                                        # chosen tokens -> embeddings -> all layers over the cache -> logits -> choice
         eng.feed(eng.next_tokens)
         eng.decode_step()
+        if do_sample and not on_device:
+            return                                        # the torch path chooses outside (choose)
+        lg = eng.process(eng.logits) if proc is not None else eng.logits
         if on_device:
-            sample(eng.logits)
-        elif not do_sample:
-            eng.greedy_select(eng.logits, eos, pad)
+            sample(lg)
+        else:
+            eng.greedy_select(lg, eos, pad)
 
     choose(logits, 0)
     if keep_logits is not None:
         keep_logits.append(logits[:, :V].float().clone())
     if keep_scores is not None:
         keep_scores.append(scores_buf.clone())
+    if keep_processed is not None:
+        keep_processed.append(eng.processed[:, :V].clone())
     graph, n = None, 1
     while n < max_new_tokens:
         if eos_ids and (n == 1 or n % sync_every == 0):
@@ -404,6 +480,8 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
             keep_logits.append(eng.logits[:, :V].float().clone())
         if keep_scores is not None:
             keep_scores.append(scores_buf.clone())
+        if keep_processed is not None:
+            keep_processed.append(eng.processed[:, :V].clone())
         n += 1
     if on_device and not warned:
         _warn_flags(eng.sample_flags, warned, 3)
@@ -411,6 +489,8 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     if not return_dict_in_generate:
         return seqs
     keep = tuple(keep_logits[: seqs.shape[1]]) if keep_logits is not None else None
+    if keep_processed is not None:
+        keep_scores = keep_processed
     if keep_scores is not None:
         return GenerateOutput(seqs, scores=tuple(keep_scores[: seqs.shape[1]]), logits=keep if output_logits else None)
     return GenerateOutput(seqs, scores=keep if output_scores else None, logits=keep if output_logits else None)

@@ -13,7 +13,10 @@ then B * beams greedy rows under replay, p2t_beam_select's two launches alone, a
 python tools/generate_bench.py [B] [N] [beams > 1] sample: beam sampling (top_k=50, top_p=0.9, temperature=0.7) four ways, interleaved, three
 runs each: beam search with p2t_beam_select under graph replay (the yardstick: the same work without the noise), torch beam sampling
 (`beam_select="torch"`, `generator=`), p2t_beam_sample_select with eager launches and under graph replay; then the two select entry
-points' launches alone, back to back."""
+points' launches alone, back to back.
+python tools/generate_bench.py [B] [N] process: the logits processors (repetition_penalty 1.3, no_repeat_ngram_size 3; then those plus
+min_new_tokens, bad_words_ids and suppress_tokens) in front of the greedy choice, under graph replay, against plain greedy decoding,
+interleaved, three runs each; then p2t_logits_process alone on [B, vocab] bf16 logits at histories of 0, 64 and 255 tokens."""
 import os
 import sys
 import time
@@ -139,6 +142,41 @@ def beam_mode(model, kw, B: int, N: int, beams: int, V: int, dev):
         print(f"p2t_kv_reorder, {rows} rows, {at} generated tokens: {_events(lambda: eng.reorder(ident), 50):.1f} us per call", flush=True)
 
 
+def process_mode(model, kw, B: int, N: int, V: int, dev):
+    rp = dict(repetition_penalty=1.3, no_repeat_ngram_size=3)
+    every = dict(rp, min_new_tokens=N // 2, eos_token_id=[128001, 128009], bad_words_ids=[[11, 12], [13, 14, 15], [16]] * 8, suppress_tokens=list(range(100, 132)))
+    cases = [("greedy (graph replay)", dict()),
+             ("greedy + repetition_penalty 1.3, no_repeat_ngram_size 3 (p2t_logits_process in the graph)", rp),
+             ("greedy + penalty, n-gram, min_new_tokens, 24 bad words, 32 suppressed ids (two eos ids: a host read per 16 tokens)", every)]
+    for _, extra in cases:
+        model.generate(**{**kw, **extra, "max_new_tokens": 4})
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    model.generate(**{**kw, "max_new_tokens": 1})
+    torch.cuda.synchronize()
+    t_prompt = time.perf_counter() - t0
+    runs = {name: [] for name, _ in cases}
+    for _ in range(3):                                           # interleaved: a drift of the box hits all three alike
+        for name, extra in cases:
+            t0 = time.perf_counter()
+            out = model.generate(**{**kw, **extra})
+            torch.cuda.synchronize()
+            runs[name].append((time.perf_counter() - t0 - t_prompt) / (out.shape[1] - 1) * 1e3)
+    for name, r in runs.items():
+        print(f"generate cfg3: B={B}, {N} new tokens, {name}: median {np.median(r):.3f} ms/step (min {min(r):.3f}, max {max(r):.3f}; 3 runs)", flush=True)
+    # the kernel alone: every processor on, random histories from 1000 ids (repeats for certain)
+    eng = generation.DecodeEngine(model.llama_decoder, B, 1, 64, 256, processors=generation._processor_args(
+        V, [128001, 128009], 1.3, 3, 256, every["bad_words_ids"], every["suppress_tokens"]), eos_ids=[128001, 128009])
+    g = torch.Generator(device=dev).manual_seed(0)
+    eng.logits.copy_((torch.randn(eng.logits.shape, device=dev, generator=g) * 3).to(torch.bfloat16))
+    eng.out_tokens.copy_(torch.randint(0, 1000, eng.out_tokens.shape, device=dev, generator=g))
+    for at in (0, 64, 255):
+        eng.step.fill_(at)
+        us = _events(lambda: eng.process(eng.logits), 200)
+        print(f"p2t_logits_process alone, [{B}, {V}] bf16 logits -> f32, every processor on, {at} history tokens: {us:.1f} us per launch "
+              f"({B * V * 6 / us / 1e6:.2f} TB/s of row traffic)", flush=True)
+
+
 def beam_sample_mode(model, kw, B: int, N: int, beams: int, V: int, dev):
     sampling = dict(do_sample=True, top_k=50, top_p=0.9, temperature=0.7)
     gen = torch.Generator(device=dev).manual_seed(1)
@@ -190,7 +228,8 @@ def main():
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
     N = int(sys.argv[2]) if len(sys.argv) > 2 else 128
     sample = len(sys.argv) > 3 and sys.argv[3] == "sample"
-    beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample else 1
+    process = len(sys.argv) > 3 and sys.argv[3] == "process"
+    beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample and not process else 1
     fp8 = len(sys.argv) > 4 and sys.argv[4] == "fp8"
     beam_sample = beams > 1 and len(sys.argv) > 4 and sys.argv[4] == "sample"
     esm_name, llama_name, _, _, Tp, _ = specs.CONFIGS["cfg3"]
@@ -211,6 +250,8 @@ def main():
               protein_attention_mask=t(pmask), max_new_tokens=N, eos_token_id=None, pad_token_id=128002, do_sample=False, num_beams=beams)
     if sample:
         return sample_mode(model, kw, B, N, llama.vocab_size, dev)
+    if process:
+        return process_mode(model, kw, B, N, llama.vocab_size, dev)
     if beam_sample:
         return beam_sample_mode(model, kw, B, N, beams, llama.vocab_size, dev)
     if beams > 1:
