@@ -728,6 +728,44 @@ int p2t_beam_select(const void* logits, int dtype, int64_t ld, int B0, int num_b
                     int64_t pad_id, float length_penalty, int early_stopping, int max_length, int G, const int32_t* step,
                     const p2t_beam_state* state, int64_t* next_tokens, int64_t* src_rows, float* scores, int64_t ld_scores,
                     p2t_stream stream);
+/* Logits processors under beam search: HF's `_beam_search` (transformers 5.15, generation/utils.py) takes log_softmax of the step's
+ * logits, runs the processors on THOSE rows with the beam's running sequence as the history, returns the processed rows as the step's
+ * `scores` and adds the running scores without renormalising.  This call writes the processed rows; p2t_beam_select_logprobs ranks
+ * them.  logits: `dtype` (F32 | BF16) [B0 nb, ld >= V], never written; lp: f32 [B0 nb, ld_lp >= V], must not overlap logits (columns
+ * V .. ld are never read, columns V .. ld_lp never written).  Of the state only run_seq and done are read.  The processor settings are
+ * p2t_logits_process's.  With cur = step[0]: done[0] != 0 or cur outside [0, max_length): nothing is written.  Otherwise per row r,
+ * every value an f32, every stage strictly after the one before:
+ *   1. mx, S, lse and lp_c = (x_c - mx) - lse for c < V: step 1 of p2t_beam_select, the same fixed summation order, so the row has the
+ *      bits p2t_beam_select writes to its `scores`.
+ *   2. - 5.  stages 2 - 5 of p2t_logits_process on that row with the history h = run_seq[cur & 1][r][0 .. cur) (the half is chosen on
+ *      the device from step[0]); for prompts given as embeddings that is the generated tokens only.  The penalty's x_t is
+ *      (float(logit_t) - mx) - lse, recomputed from the stored logit: y_t = x_t < 0 ? x_t * penalty : x_t / penalty (log-probabilities
+ *      are <= 0, so in practice the product), duplicates in the history write the same bits.  A history or word token outside [0, V) is
+ *      compared like any other and never written to.
+ * Malformed arguments (null pointers, ld < V, ld_lp < V, non-positive counts, G not a multiple of 64, max_length outside 1 .. G, a
+ * penalty that is not positive and finite, negative sizes, counts without their arrays): P2T_ERR_ARG before any GPU call; nb > 16 or
+ * B0 nb V >= 2^31: P2T_ERR_UNSUPPORTED.  One 1024-thread block per row, barriers between the stages, no atomics: the same inputs give
+ * the same bits.  Rows holding +inf or NaN in [0, V) are unspecified (every index stays in range).  Does not allocate, copy or
+ * synchronise: it can be captured into a HIP graph. */
+int p2t_beam_logprobs_process(const void* logits, int dtype, int64_t ld, int B0, int num_beams, int V, const int32_t* step, int G,
+                              int max_length, const p2t_beam_state* state, float repetition_penalty, int no_repeat_ngram_size,
+                              int min_new_tokens, const int64_t* eos_ids, int n_eos, const int64_t* word_ids, const int32_t* word_offsets,
+                              int n_words, int n_word_ids, float* lp, int64_t ld_lp, p2t_stream stream);
+/* p2t_beam_select for rows that ALREADY hold log-probabilities (processed ones: p2t_beam_logprobs_process): lp f32 [B0 nb, ld >= V],
+ * never written; state, halves, workspace (p2t_beam_workspace_bytes), `done` behaviour, supported range and argument checks are
+ * p2t_beam_select's.  With cur = step[0], keep = max(2, 1 + n_eos) nb, and every value an f32:
+ *   2. per prompt, candidates (beam j, column c) with acc = lp_c + run_scores[j] (one addition), lp_c READ from the row.  A processed
+ *      row is not a monotone image of the logits, so the rows themselves are ranked: inside a beam by (lp descending, column ascending),
+ *      of which the first keep are the beam's candidates; the prompt's keep best of those by (acc descending, beam ascending, then
+ *      rank inside the beam ascending).  Candidate k of the ranked list: token t_k, beam j_k, acc a_k.
+ *   3. - 6.  steps 3 - 6 of p2t_beam_select on that list, unchanged.
+ * Rows may hold -inf (banned columns): they rank like any value, ties by column ascending, whatever their number.  A prompt with fewer
+ * than nb finite candidates gets -inf running scores, as in HF; no NaN arises from them (-inf + -1e9 and -inf / len_pow are -inf).
+ * Rows holding +inf or NaN in [0, V) are unspecified (every index stays in range).  Two launches, no float atomics: the same inputs
+ * give the same bits.  Does not allocate, copy or synchronise: it can be captured into a HIP graph. */
+int p2t_beam_select_logprobs(const float* lp, int64_t ld, int B0, int num_beams, int V, const int64_t* eos_ids, int n_eos, int64_t pad_id,
+                             float length_penalty, int early_stopping, int max_length, int G, const int32_t* step,
+                             const p2t_beam_state* state, int64_t* next_tokens, int64_t* src_rows, p2t_stream stream);
 /* Choice by beam sampling: one step of `_beam_search` with do_sample=True (HF's beam-search multinomial sampling), with
  * p2t_beam_select's arguments, state (the same p2t_beam_state, halves and `done`; the workspace holds
  * p2t_beam_sample_workspace_bytes(B0, nb) bytes) and bookkeeping, and the sampler's temperature / top_k / top_p / seed.  HF draws keep

@@ -7,7 +7,8 @@
 // The stop condition spans the prompts: every block leaves its three flags in sync[1 + b] and takes a ticket from sync[0] (an integer
 // atomic); the block that takes the last one combines them in prompt order, raises done and resets the ticket.
 // kSample = false: the workspace holds {stored logit [BB][64], column [BB][64], (mx, lse) [BB][2]}; a candidate's rank key is its
-// accumulated score ((x - mx) - lse) + running.
+// accumulated score ((x - mx) - lse) + running.  p2t_beam_select_logprobs leaves log-probabilities and (mx, lse) = (0, 0) there: the
+// same expression is then exactly x + running.
 // kSample = true: {perturbed key [BB][64], column [BB][64], accumulated score [BB][64], the row's best accumulated score [BB]}; the
 // rank key is the perturbed key, the score that goes on is the unperturbed one, and bit 1 of *flags is raised when the keep-th
 // candidate is absent or more than 100 below the prompt's best accumulated score.

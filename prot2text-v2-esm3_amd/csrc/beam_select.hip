@@ -1,6 +1,7 @@
-// Beam-search selection (p2t_beam_select): one step of transformers' `_beam_search` (5.x, vectorised form; generation/utils.py) with an
-// empty id prompt, as two launches that read every length on the device.  The contract, every tie-break included, is the comment on
-// p2t_beam_select in include/p2t_hip.h; tests/beam_reference.py restates it in fp64.
+// Beam-search selection (p2t_beam_select; p2t_beam_select_logprobs on rows that already hold processed log-probabilities, at the end):
+// one step of transformers' `_beam_search` (5.x, vectorised form; generation/utils.py) with an empty id prompt, as two launches that
+// read every length on the device.  The contract, every tie-break included, is the comment on p2t_beam_select in include/p2t_hip.h;
+// tests/beam_reference.py restates it in fp64 (tests/beam_logprobs_reference.py: p2t_beam_select_logprobs in f32).
 //
 // beam_rows_kernel, one 1024-thread block per row (beam): the table pipeline of select_common.h on the stored logits -- the `keep`-th
 // largest by two radix selects, the survivors at or above it, their sort by (value descending, column ascending) -- then max = rank 0
@@ -18,7 +19,9 @@
 namespace p2t {
 namespace {
 
-template <typename T>
+// kLogprobs (p2t_beam_select_logprobs): the row already holds log-probabilities, so it is ranked as it stands: no row_lse, no scores
+// write-out, and (mx, lse) = (0, 0), with which the merge's ((x - 0) - 0) + run is exactly x + run (for -inf and -0 as well).
+template <typename T, bool kLogprobs = false>
 __global__ void __launch_bounds__(1024) beam_rows_kernel(const T* __restrict__ logits, int64_t ld, int V, int keep, int max_length,
                                                          const int32_t* __restrict__ step_ptr, const int32_t* __restrict__ done,
                                                          float* __restrict__ cand_val, int32_t* __restrict__ cand_col,
@@ -47,11 +50,15 @@ __global__ void __launch_bounds__(1024) beam_rows_kernel(const T* __restrict__ l
         cand_val[(int64_t)bb * kKeepMax + tid] = sv[tid];
         cand_col[(int64_t)bb * kKeepMax + tid] = min(max(si[tid], 0), V - 1);
     }
-    const float lse = row_lse(row, V, vec, mx, s_sum);
-    if (tid == 0) { row_stat[2 * bb] = mx; row_stat[2 * bb + 1] = lse; }
-    if (scores) {
-        float* srow = scores + (int64_t)bb * ld_scores;
-        for (int c = tid; c < V; c += 1024) srow[c] = (to_f32(row[c]) - mx) - lse;
+    if constexpr (kLogprobs) {
+        if (tid == 0) { row_stat[2 * bb] = 0.f; row_stat[2 * bb + 1] = 0.f; }
+    } else {
+        const float lse = row_lse(row, V, vec, mx, s_sum);
+        if (tid == 0) { row_stat[2 * bb] = mx; row_stat[2 * bb + 1] = lse; }
+        if (scores) {
+            float* srow = scores + (int64_t)bb * ld_scores;
+            for (int c = tid; c < V; c += 1024) srow[c] = (to_f32(row[c]) - mx) - lse;
+        }
     }
 }
 
@@ -84,6 +91,20 @@ extern "C" int p2t_beam_select(const void* logits, int dtype, int64_t ld, int B0
                                                       row_stat, scores, ld_scores);
     P2T_LAUNCH_CHECK();
     beam_merge_kernel<<<B0, 256, 0, s>>>(b.merge);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
+extern "C" int p2t_beam_select_logprobs(const float* lp, int64_t ld, int B0, int num_beams, int V, const int64_t* eos_ids, int n_eos, int64_t pad_id,
+                                        float length_penalty, int early_stopping, int max_length, int G, const int32_t* step,
+                                        const p2t_beam_state* state, int64_t* next_tokens, int64_t* src_rows, p2t_stream stream) {
+    BeamStep b;
+    P2T_TRY(beam_step_setup("p2t_beam_select_logprobs", lp, P2T_F32, ld, B0, num_beams, V, eos_ids, n_eos, pad_id, length_penalty, early_stopping,
+                            max_length, G, step, state, next_tokens, src_rows, nullptr, 0, &b));
+    hipStream_t s = (hipStream_t)stream;
+    beam_rows_kernel<float, true><<<b.BB, 1024, 0, s>>>(lp, ld, V, b.keep, max_length, step, state->done, b.plane0, b.cand_col, b.plane2, nullptr, 0);
+    P2T_LAUNCH_CHECK();
+    beam_merge_kernel<<<B0, 256, 0, s>>>(b.merge);                 // unchanged: the candidates' keys are lp + running
     P2T_LAUNCH_CHECK();
     return P2T_OK;
 }

@@ -13,10 +13,11 @@
 //   3. n-gram: thread i compares history[i .. i + n - 1) with the last n - 1 tokens and writes -inf at history[i + n - 1].
 //   4. bad words: thread w compares all but the last token of word w with the end of the history and writes -inf at its last token.
 //   5. min new tokens: thread e writes -inf at eos id e while cur < min_new_tokens.
-// Stages 3 - 5 only ever write -inf, stage 2 writes one value per column: whatever the thread order, the same inputs give the same
-// bits.  A barrier separates the stages (one block owns the row, so the block's own order is all that is needed).  Every column
-// written is checked against [0, V), every history index against [0, cur), every word offset against [0, n_word_ids].
-#include "common.h"
+// Stages 2 - 5 are logits_process_stages.h, shared with p2t_beam_logprobs_process (beam_process.hip).  Stages 3 - 5 only ever write
+// -inf, stage 2 writes one value per column: whatever the thread order, the same inputs give the same bits.  A barrier separates the
+// stages (one block owns the row, so the block's own order is all that is needed).  Every column written is checked against [0, V),
+// every history index against [0, cur), every word offset against [0, n_word_ids].
+#include "logits_process_stages.h"
 
 namespace p2t {
 namespace {
@@ -32,7 +33,6 @@ __global__ void __launch_bounds__(1024) logits_process_kernel(const T* __restric
     float* y = out + (int64_t)bb * ld_out;
     const int64_t* hist = out_tokens + (int64_t)bb * ld_tok;
     const int cur = min(max(step_ptr[0], 0), G);
-    const float ninf = -INFINITY;
 
     // ---- 1. copy ----------------------------------------------------------------------------------------------------------
     constexpr int PN = sizeof(T) == 2 ? 8 : 4;
@@ -65,56 +65,10 @@ __global__ void __launch_bounds__(1024) logits_process_kernel(const T* __restric
         }
     }
     for (int c = Vv + tid; c < V; c += 1024) y[c] = to_f32(row[c]);
-    __syncthreads();
 
-    // ---- 2. repetition penalty ----------------------------------------------------------------------------------------------
-    if (penalty != 1.f) {
-        for (int i = tid; i < cur; i += 1024) {
-            const int64_t t = hist[i];
-            if (t >= 0 && t < V) {
-                const float x = to_f32(row[t]);
-                y[t] = x < 0.f ? x * penalty : x / penalty;
-            }
-        }
-    }
-    __syncthreads();
-
-    // ---- 3. no repeated n-gram: windows i .. i + n - 1 inside the history, i <= cur - n ---------------------------------------------
-    if (ngram > 0 && cur >= ngram) {
-        const int64_t* last = hist + (cur - (ngram - 1));         // the last n - 1 tokens
-        for (int i = tid; i <= cur - ngram; i += 1024) {
-            bool same = true;
-            for (int j = 0; j < ngram - 1 && same; ++j) same = hist[i + j] == last[j];
-            if (same) {
-                const int64_t t = hist[i + ngram - 1];
-                if (t >= 0 && t < V) y[t] = ninf;
-            }
-        }
-    }
-    __syncthreads();
-
-    // ---- 4. bad words (a suppressed token is a word of one token) ----------------------------------------------------------------------
-    for (int w = tid; w < n_words; w += 1024) {
-        const int lo = offsets[w], hi = offsets[w + 1];
-        if (lo < 0 || hi <= lo || hi > n_word_ids) continue;
-        const int L = hi - lo;
-        if (L > 1 && L > cur) continue;                           // HF: "the sequence is longer than the context, ignore"
-        bool same = true;
-        for (int j = 0; j < L - 1 && same; ++j) same = words[lo + j] == hist[cur - (L - 1) + j];
-        if (same) {
-            const int64_t t = words[hi - 1];
-            if (t >= 0 && t < V) y[t] = ninf;
-        }
-    }
-    __syncthreads();
-
-    // ---- 5. no eos before min_new_tokens -----------------------------------------------------------------------------------------
-    if (cur < min_new) {
-        for (int e = tid; e < n_eos; e += 1024) {
-            const int64_t t = eos[e];
-            if (t >= 0 && t < V) y[t] = ninf;
-        }
-    }
+    // ---- 2 - 5. penalty (x_t the STORED logit), n-gram, bad words, min new tokens: logits_process_stages.h -----------------------------
+    const ProcessorArgs p{penalty, ngram, min_new, eos, n_eos, words, offsets, n_words, n_word_ids};
+    processor_stages(y, V, hist, cur, p, tid, [&](int t) { return to_f32(row[t]); });
 }
 
 }  // namespace
@@ -132,14 +86,8 @@ extern "C" int p2t_logits_process(const void* logits, int dtype, int64_t ld, int
                 "p2t_logits_process: BB = %d, V = %d, ld = %lld, ld_out = %lld: needs BB > 0, V > 0, ld >= V, ld_out >= V", BB, V, (long long)ld,
                 (long long)ld_out);
     P2T_REQUIRE(G > 0 && ld_tokens >= G, "p2t_logits_process: G = %d, ld_tokens = %lld: needs G > 0, ld_tokens >= G", G, (long long)ld_tokens);
-    P2T_REQUIRE(repetition_penalty > 0.f && repetition_penalty < INFINITY, "p2t_logits_process: repetition_penalty %g is not a positive finite number",
-                (double)repetition_penalty);
-    P2T_REQUIRE(no_repeat_ngram_size >= 0 && min_new_tokens >= 0,
-                "p2t_logits_process: no_repeat_ngram_size = %d, min_new_tokens = %d: needs both >= 0 (0: off)", no_repeat_ngram_size, min_new_tokens);
-    P2T_REQUIRE(n_eos >= 0 && (n_eos == 0 || eos_ids), "p2t_logits_process: n_eos = %d: needs n_eos >= 0, eos_ids for n_eos > 0", n_eos);
-    P2T_REQUIRE(n_words >= 0 && n_word_ids >= 0 && (n_words == 0 || (word_ids && word_offsets && n_word_ids > 0)),
-                "p2t_logits_process: n_words = %d, n_word_ids = %d: needs both >= 0, word_ids, word_offsets and n_word_ids > 0 for n_words > 0", n_words,
-                n_word_ids);
+    P2T_TRY(processor_args_check("p2t_logits_process", repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_ids, n_eos, word_ids, word_offsets,
+                                 n_words, n_word_ids));
     hipStream_t s = (hipStream_t)stream;
     if (dtype == P2T_BF16)
         logits_process_kernel<bf16_t><<<BB, 1024, 0, s>>>((const bf16_t*)logits, ld, V, out_tokens, ld_tokens, step, G, out, ld_out, repetition_penalty,

@@ -15,7 +15,10 @@ with `seed=` and `beam_select="device"`) is that loop with p2t_beam_sample_selec
 log-probabilities and keep draws without replacement as the descending order of score + counter-hashed Gumbel noise).  The logits
 processors of `num_beams == 1` (repetition penalty, n-gram, bad-word / suppressed-token and min-new-token bans) are p2t_logits_process
 (csrc/logits_process.hip), one launch in front of the greedy / sampled choice inside the same graph: it reads the step's logits and the
-rows' own generated history on the device and writes the f32 scores the selector then reads.  Sampling with a torch `generator` (temperature /
+rows' own generated history on the device and writes the f32 scores the selector then reads.  Under beam search (opt-in:
+`beam_select="device"`) HF runs them on the log-softmax inside the beam step with the beam's running sequence as the history:
+p2t_beam_logprobs_process (csrc/beam_process.hip) writes those processed log-probabilities and p2t_beam_select_logprobs ranks them as they
+stand, both inside the two-step graph.  Sampling with a torch `generator` (temperature /
 top-k / top-p filters + multinomial) and the beam bookkeeping under `beam_select="torch"` or outside the kernel's range (log-softmax,
 top-k over beams x vocabulary, gathers of the token tables) are torch device ops on the [rows, vocab] logits -- selection bookkeeping,
 restated from transformers/generation/utils.py (`_sample`, `_beam_search` and its helpers) and transformers/generation/
@@ -286,15 +289,26 @@ class DecodeEngine:
              float(temperature), int(top_k), float(top_p), int(seed) & (2 ** 64 - 1), int(row0), ptr(scores) if scores is not None else None,
              scores.stride(0) if scores is not None else 0, ptr(self.sample_flags), stream())
 
-    def process(self, logits: torch.Tensor) -> torch.Tensor:
+    def process(self, logits: torch.Tensor, history: Optional[torch.Tensor] = None, step: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The logits processors on the step's logits and the rows' own history out_tokens[:, : step[0]] (p2t_logits_process, inside the
-        step graph like the selectors) -> the processed f32 buffer the selectors then read; `logits` stays as it is."""
+        step graph like the selectors) -> the processed f32 buffer the selectors then read; `logits` stays as it is.  `history` (i64
+        [BB, n], contiguous) and `step` (a device word): another token table and counter than the engine's own -- the torch beam path's
+        running sequences, with the f32 log-probabilities as `logits`."""
         pr, opt = self.processors, lambda t: ptr(t) if t.numel() else None
-        call("p2t_logits_process", ptr(logits), ops.dt_of(logits), logits.stride(0), self.spec.vocab_size, self.BB, ptr(self.out_tokens),
-             self.out_tokens.stride(0), ptr(self.step), self.G, ptr(self.processed), self.processed.stride(0), pr["penalty"], pr["ngram"],
+        history, step = self.out_tokens if history is None else history, self.step if step is None else step
+        call("p2t_logits_process", ptr(logits), ops.dt_of(logits), logits.stride(0), self.spec.vocab_size, self.BB, ptr(history),
+             history.stride(0), ptr(step), history.shape[1], ptr(self.processed), self.processed.stride(0), pr["penalty"], pr["ngram"],
              pr["min_new"], opt(self.proc_eos), self.proc_eos.numel(), opt(self.word_ids), opt(self.word_offsets), len(pr["words"]),
              self.word_ids.numel(), stream())
         return self.processed
+
+    def beam_process(self, logits: torch.Tensor, state: "BeamState", max_length: int, lp: torch.Tensor):
+        """The logits processors under beam search (p2t_beam_logprobs_process, inside the step graph): log-softmax of the step's logits,
+        processed with each beam's running sequence state.run_seq[step[0] & 1] as its history, into the f32 rows `lp`."""
+        pr, opt = self.processors, lambda t: ptr(t) if t.numel() else None
+        call("p2t_beam_logprobs_process", ptr(logits), ops.dt_of(logits), logits.stride(0), state.B, state.nb, self.spec.vocab_size, ptr(self.step),
+             state.G, int(max_length), C.byref(state.c), pr["penalty"], pr["ngram"], pr["min_new"], opt(self.proc_eos), self.proc_eos.numel(),
+             opt(self.word_ids), opt(self.word_offsets), len(pr["words"]), self.word_ids.numel(), ptr(lp), lp.stride(0), stream())
 
     def reorder(self, src_rows: torch.Tensor):
         """Generated segment row r <- row src_rows[r] (beam re-ordering; the prompt segment is shared by a prompt's beams)."""
@@ -352,7 +366,14 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     (off: None, 0, or no eos id), `bad_words_ids` and `suppress_tokens`, with HF's semantics for prompts given as embeddings: the history
     is the generated tokens only.  One kernel (p2t_logits_process) in front of the greedy / sampled choice, inside the replayed step graph,
     and in front of the torch filters under `generator=`; `output_scores` then returns the processed scores, `output_logits` the raw rows.
-    With none of them active nothing is launched or allocated.  Under beam search they raise NotImplementedError."""
+    With none of them active nothing is launched or allocated.
+
+    Logits processors under beam search (`num_beams > 1`) are opt-in: HF runs them on the log-softmax inside the beam step, with the
+    beam's running sequence as the history, and ranks the processed rows.  `beam_select="device"` does that with two entry points inside
+    the two-step graph (p2t_beam_logprobs_process, then p2t_beam_select_logprobs on its rows; ValueError outside p2t_beam_select's
+    range), `beam_select="torch"` with p2t_logits_process on the torch path's log-softmax; `output_scores` returns the processed rows,
+    `output_logits` the raw ones.  `beam_select=None` raises NotImplementedError, and so does beam sampling with a processor (HF then
+    runs the warpers after the processors, and the device beam sampler cuts by stored logit)."""
     if (inputs_embeds is None) == (input_ids is None):
         raise ValueError("pass exactly one of inputs_embeds / input_ids")
     if unused:
@@ -385,9 +406,15 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     if num_beams < 1 or num_return_sequences < 1 or num_return_sequences > num_beams and num_beams > 1:
         raise ValueError("num_beams >= 1 and 1 <= num_return_sequences <= num_beams")
     if num_beams > 1 and proc is not None:
-        raise NotImplementedError("generate(): repetition_penalty / no_repeat_ngram_size / min_new_tokens / bad_words_ids / suppress_tokens are not "
-                                  "supported with num_beams > 1: HF applies the processors to the log-softmax inside the beam step, and "
-                                  "p2t_beam_select computes that log-softmax itself from the logits; they are served with num_beams == 1")
+        if do_sample:
+            raise NotImplementedError("generate(): repetition_penalty / no_repeat_ngram_size / min_new_tokens / bad_words_ids / suppress_tokens are not "
+                                      "supported under beam sampling (num_beams > 1 with do_sample=True): HF runs the warpers after the processors, "
+                                      "and p2t_beam_sample_select cuts by stored logit")
+        if beam_select not in ("device", "torch"):
+            raise NotImplementedError("generate(): repetition_penalty / no_repeat_ngram_size / min_new_tokens / bad_words_ids / suppress_tokens with "
+                                      "num_beams > 1 are opt-in: HF applies the processors to the log-softmax inside the beam step, which "
+                                      "p2t_beam_select computes itself from the logits; pass beam_select='device' (p2t_beam_logprobs_process + "
+                                      "p2t_beam_select_logprobs) or beam_select='torch'")
     if num_beams > 1:
         sampling = None
         if do_sample:
@@ -396,7 +423,7 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
             max_length=max_new_tokens, eos_ids=eos_ids, pad_id=int(pad_token_id), nb=num_beams, length_penalty=float(length_penalty),
             early_stopping=early_stopping, num_return_sequences=num_return_sequences, return_dict=return_dict_in_generate,
             output_scores=output_scores, output_logits=output_logits, stream_copy=stream_copy, beam_select=beam_select, use_graph=use_graph,
-            sync_every=sync_every, sampling=sampling))
+            sync_every=sync_every, sampling=sampling, processors=proc))
     R = int(num_return_sequences)
     if R != 1 and not do_sample:
         raise ValueError("greedy decoding returns one sequence per prompt: num_return_sequences > 1 needs do_sample=True or num_beams > 1")
@@ -547,10 +574,12 @@ def beam_state_init(B: int, nb: int, max_length: int, pad_id: int, dev) -> dict:
 
 def beam_step_torch(st: dict, logits: torch.Tensor, cur: int, nb: int, eos: torch.Tensor, length_penalty: float, early_stopping,
                     max_length: int, do_sample: bool = False, generator: Optional[torch.Generator] = None, temperature: float = 1.0,
-                    top_k: Optional[int] = None, top_p: Optional[float] = None):
+                    top_k: Optional[int] = None, top_p: Optional[float] = None, process=None):
     """One step of the torch path on f32 logits [B * nb, V] (any device): -> (new state, log_probs, src_rows i64 [B * nb], hits, go_on).
     do_sample: the warpers run on the log-probabilities (HF appends the processed rows as the step's scores) and the keep continuations
-    are torch.multinomial draws without replacement, HF's two lines; the new state then also holds them as "drawn" [B, keep]."""
+    are torch.multinomial draws without replacement, HF's two lines; the new state then also holds them as "drawn" [B, keep].
+    process(log_probs [B * nb, V], running [B, nb, max_length], cur) -> the rows after the logits processors (HF runs them on the
+    log-softmax, with the beams' running sequences as histories); the returned log_probs are then the processed rows."""
     dev, V = logits.device, logits.shape[1]
     B = logits.shape[0] // nb
     keep = beam_keep(nb, eos.numel())
@@ -559,6 +588,8 @@ def beam_step_torch(st: dict, logits: torch.Tensor, cur: int, nb: int, eos: torc
     sequences, beam_scores, beam_idx_tab = st["sequences"], st["beam_scores"], st["beam_idx_tab"]
     is_finished, heuristic_open = st["is_finished"], st["heuristic_open"]
     log_probs = torch.log_softmax(logits, dim=-1)
+    if process is not None:
+        log_probs = process(log_probs, running, cur)
     if do_sample:
         log_probs = filter_logits(log_probs, temperature, top_k, top_p)
     acc = (log_probs.view(B, nb, V) + running_scores[:, :, None]).reshape(B, nb * V)
@@ -629,7 +660,7 @@ def _beam_search(decoder, inputs_embeds, attention_mask, o):
         if o.beam_select == "device":
             raise ValueError(f"generate(beam_select='device'): p2t_beam_select serves 1 <= num_beams <= {BEAMS_MAX} with max(2, 1 + number of eos ids) * "
                              f"num_beams <= {KEEP_MAX} <= vocabulary (got num_beams = {nb}, {len(o.eos_ids)} eos ids); the torch path serves the rest")
-    eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy)
+    eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy, processors=o.processors, eos_ids=o.eos_ids)
     dev = eng.dev
     embeds, mask = eng.compact(inputs_embeds, attention_mask)
     first_logits = eng.prefill(embeds, mask)                                 # [B, ld]: the beams of a prompt start from the same state
@@ -637,6 +668,14 @@ def _beam_search(decoder, inputs_embeds, attention_mask, o):
     st = beam_state_init(B, nb, max_length, o.pad_id, dev)
     all_scores, all_logits = [], []
     draw = {} if o.sampling is None else dict(do_sample=True, **{k: o.sampling[k] for k in ("generator", "temperature", "top_k", "top_p")})
+    if o.processors is not None:
+        cur_word = torch.zeros((1,), dtype=torch.int32, device=dev)
+
+        def process(log_probs, running, cur):               # p2t_logits_process on the f32 log-probabilities, history = the running sequences
+            cur_word.fill_(cur)
+            return eng.process(log_probs.contiguous(), running.reshape(B * nb, max_length).contiguous(), cur_word)[:, :V].clone()
+
+        draw["process"] = process
     cur = 0
     while True:
         if cur == 0:
@@ -695,6 +734,14 @@ def beam_select(logits: torch.Tensor, V: int, state: BeamState, eos: torch.Tenso
     _beam_call("p2t_beam_select", logits, V, state, eos, pad_id, length_penalty, early_stopping, max_length, step, next_tokens, src_rows, scores)
 
 
+def beam_select_logprobs(lp: torch.Tensor, V: int, state: BeamState, eos: torch.Tensor, pad_id: int, length_penalty: float, early_stopping,
+                         max_length: int, step: torch.Tensor, next_tokens: torch.Tensor, src_rows: torch.Tensor):
+    """One p2t_beam_select_logprobs call: beam_select on f32 rows [B nb, ld >= V] that already hold (processed) log-probabilities."""
+    es = 1 if early_stopping is True else (2 if early_stopping == "never" else 0)
+    call("p2t_beam_select_logprobs", ptr(lp), lp.stride(0), state.B, state.nb, V, ptr(eos) if eos.numel() else None, eos.numel(), int(pad_id),
+         float(length_penalty), es, int(max_length), state.G, ptr(step), C.byref(state.c), ptr(next_tokens), ptr(src_rows), stream())
+
+
 def beam_sample_select(logits: torch.Tensor, V: int, state: BeamState, eos: torch.Tensor, pad_id: int, length_penalty: float, early_stopping,
                        max_length: int, step: torch.Tensor, next_tokens: torch.Tensor, src_rows: torch.Tensor, temperature: float, top_k: int,
                        top_p: float, seed: int, scores: Optional[torch.Tensor] = None, prompt0: int = 0):
@@ -705,12 +752,13 @@ def beam_sample_select(logits: torch.Tensor, V: int, state: BeamState, eos: torc
 
 
 def _beam_search_device(decoder, inputs_embeds, attention_mask, o):
-    """The same search with p2t_beam_select (`o.sampling`: p2t_beam_sample_select) in the torch bookkeeping's place: the first token from
+    """The same search with p2t_beam_select (`o.sampling`: p2t_beam_sample_select; `o.processors`: p2t_beam_logprobs_process +
+    p2t_beam_select_logprobs) in the torch bookkeeping's place: the first token from
     the prefill logits, one eager step, then a replayed graph of TWO steps (reorder, feed, decode, select, twice: the engine's cache
     buffers are back where the capture found them), an odd remainder eagerly.  The host reads `done` every `sync_every` tokens and at
     the end; steps run past the stop leave the state as it is."""
     B, V, nb, max_length, sampling = inputs_embeds.shape[0], decoder.spec.vocab_size, o.nb, o.max_length, o.sampling
-    eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy)
+    eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy, processors=o.processors, eos_ids=o.eos_ids)
     dev = eng.dev
     embeds, mask = eng.compact(inputs_embeds, attention_mask)
     first = eng.prefill(embeds, mask).repeat_interleave(nb, dim=0).contiguous()     # HF expands the prompt nb times before its prefill
@@ -721,6 +769,9 @@ def _beam_search_device(decoder, inputs_embeds, attention_mask, o):
     # two step slots: a replayed pair leaves the logits / log-probabilities of both its steps to be cloned afterwards
     lslots = [eng.logits, torch.zeros_like(eng.logits)] if keep_logits else [eng.logits, eng.logits]
     sslots = [torch.empty((eng.BB, V), dtype=torch.float32, device=dev) for _ in range(2)] if keep_scores else [None, None]
+    # the rows of processed log-probabilities (HF's scores of the step): the two score slots, or, when nobody asks for the scores, the
+    # engine's one f32 buffer for both steps of the graph
+    lp_slots = sslots if keep_scores else [eng.processed, eng.processed] if o.processors is not None else None
     all_scores, all_logits = [], []
     warned = set()
 
@@ -731,7 +782,10 @@ def _beam_search_device(decoder, inputs_embeds, attention_mask, o):
 
     def select(lg, slot):
         common = (lg, V, st, eos, o.pad_id, o.length_penalty, o.early_stopping, max_length, eng.step, eng.next_tokens, src_rows)
-        if sampling is None:
+        if o.processors is not None:                    # the processed log-probabilities, then their ranking as they stand
+            eng.beam_process(lg, st, max_length, lp_slots[slot])
+            beam_select_logprobs(lp_slots[slot], *common[1:])
+        elif sampling is None:
             beam_select(*common, sslots[slot])
         else:
             beam_sample_select(*common, sampling["temperature"], sampling["top_k"], sampling["top_p"], sampling["seed"], sslots[slot])

@@ -16,7 +16,11 @@ runs each: beam search with p2t_beam_select under graph replay (the yardstick: t
 points' launches alone, back to back.
 python tools/generate_bench.py [B] [N] process: the logits processors (repetition_penalty 1.3, no_repeat_ngram_size 3; then those plus
 min_new_tokens, bad_words_ids and suppress_tokens) in front of the greedy choice, under graph replay, against plain greedy decoding,
-interleaved, three runs each; then p2t_logits_process alone on [B, vocab] bf16 logits at histories of 0, 64 and 255 tokens."""
+interleaved, three runs each; then p2t_logits_process alone on [B, vocab] bf16 logits at histories of 0, 64 and 255 tokens.
+python tools/generate_bench.py [B] [N] [beams > 1] process: the logits processors under beam search (`beam_select="device"`), under replay of
+the two-step graph, interleaved, three runs each: plain beam search (p2t_beam_select: nothing new is launched or allocated), the same with
+repetition_penalty 1.3 + no_repeat_ngram_size 3, the same with all five processors; then p2t_beam_logprobs_process alone on
+[B * beams, vocab] bf16 logits at histories of 0 and 64 tokens, p2t_beam_select_logprobs alone on its rows, and p2t_beam_select alone."""
 import os
 import sys
 import time
@@ -177,6 +181,54 @@ def process_mode(model, kw, B: int, N: int, V: int, dev):
               f"({B * V * 6 / us / 1e6:.2f} TB/s of row traffic)", flush=True)
 
 
+def beam_process_mode(model, kw, B: int, N: int, beams: int, V: int, dev):
+    rp = dict(repetition_penalty=1.3, no_repeat_ngram_size=3)
+    every = dict(rp, min_new_tokens=N // 2, eos_token_id=[128001, 128009], bad_words_ids=[[11, 12], [13, 14, 15], [16]] * 8, suppress_tokens=list(range(100, 132)))
+    cases = [("beam search, p2t_beam_select, two-step graph replay", dict()),
+             ("beam search + repetition_penalty 1.3, no_repeat_ngram_size 3 (p2t_beam_logprobs_process + p2t_beam_select_logprobs in the graph)", rp),
+             ("beam search + penalty, n-gram, min_new_tokens, 24 bad words, 32 suppressed ids (two eos ids)", every)]
+    kw = {**kw, "beam_select": "device"}
+    for _, extra in cases:
+        model.generate(**{**kw, **extra, "max_new_tokens": 6})
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    model.generate(**{**kw, "max_new_tokens": 1})
+    torch.cuda.synchronize()
+    t_prompt = time.perf_counter() - t0
+    runs = {name: [] for name, _ in cases}
+    for _ in range(3):                                           # interleaved: a drift of the box hits all three alike
+        for name, extra in cases:
+            t0 = time.perf_counter()
+            out = model.generate(**{**kw, **extra})
+            torch.cuda.synchronize()
+            runs[name].append((time.perf_counter() - t0 - t_prompt) / (N - 1) * 1e3)
+            assert out.shape[1] == N, (name, out.shape)          # nothing finished early: every run is N steps
+    for name, r in runs.items():
+        print(f"generate cfg3: B={B} beams={beams}, {N} new tokens, {name}: median {np.median(r):.3f} ms/step (min {min(r):.3f}, max {max(r):.3f}; 3 runs)", flush=True)
+    # the entry points alone: every processor on, random histories from 1000 ids (repeats for certain); the selections on a fresh state at
+    # step 0, where nothing finishes, so every call does the full work
+    rows = B * beams
+    eng = generation.DecodeEngine(model.llama_decoder, B, beams, 64, 256, processors=generation._processor_args(
+        V, [128001, 128009], 1.3, 3, 256, every["bad_words_ids"], every["suppress_tokens"]), eos_ids=[128001, 128009])
+    g = torch.Generator(device=dev).manual_seed(0)
+    eng.logits.copy_((torch.randn(eng.logits.shape, device=dev, generator=g) * 3).to(torch.bfloat16))
+    hist = generation.BeamState(B, beams, 256, 0, dev)
+    hist.run_seq.copy_(torch.randint(0, 1000, hist.run_seq.shape, device=dev, generator=g))
+    for at in (0, 64):
+        eng.step.fill_(at)
+        us = _events(lambda: eng.beam_process(eng.logits, hist, 256, eng.processed), 200)
+        print(f"p2t_beam_logprobs_process alone, [{rows}, {V}] bf16 logits -> f32, every processor on, {at} history tokens: {us:.1f} us per launch",
+              flush=True)
+    st = generation.BeamState(B, beams, 256, 0, dev)
+    step, nxt, src = (torch.zeros((n,), dtype=dt, device=dev) for n, dt in ((1, torch.int32), (rows, torch.int64), (rows, torch.int64)))
+    eos = torch.zeros((0,), dtype=torch.int64, device=dev)
+    us = _events(lambda: generation.beam_select_logprobs(eng.processed, V, st, eos, 0, 1.0, False, 256, step, nxt, src), 200)
+    print(f"p2t_beam_select_logprobs alone (both launches), [{rows}, {V}] f32 processed log-probabilities, {beams} beams: {us:.1f} us per call", flush=True)
+    st = generation.BeamState(B, beams, 256, 0, dev)
+    us = _events(lambda: generation.beam_select(eng.logits, V, st, eos, 0, 1.0, False, 256, step, nxt, src), 200)
+    print(f"p2t_beam_select alone (both launches), [{rows}, {V}] bf16 logits, {beams} beams: {us:.1f} us per call", flush=True)
+
+
 def beam_sample_mode(model, kw, B: int, N: int, beams: int, V: int, dev):
     sampling = dict(do_sample=True, top_k=50, top_p=0.9, temperature=0.7)
     gen = torch.Generator(device=dev).manual_seed(1)
@@ -232,6 +284,7 @@ def main():
     beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample and not process else 1
     fp8 = len(sys.argv) > 4 and sys.argv[4] == "fp8"
     beam_sample = beams > 1 and len(sys.argv) > 4 and sys.argv[4] == "sample"
+    beam_process = beams > 1 and len(sys.argv) > 4 and sys.argv[4] == "process"
     esm_name, llama_name, _, _, Tp, _ = specs.CONFIGS["cfg3"]
     esm, llama = specs.esm_spec(esm_name), specs.llama_spec(llama_name)
     ad = specs.adapter_spec(esm, llama)
@@ -252,6 +305,8 @@ def main():
         return sample_mode(model, kw, B, N, llama.vocab_size, dev)
     if process:
         return process_mode(model, kw, B, N, llama.vocab_size, dev)
+    if beam_process:
+        return beam_process_mode(model, kw, B, N, beams, llama.vocab_size, dev)
     if beam_sample:
         return beam_sample_mode(model, kw, B, N, beams, llama.vocab_size, dev)
     if beams > 1:
