@@ -55,7 +55,8 @@ typedef void* p2t_stream;
 int p2t_version(void);
 const char* p2t_last_error(void);
 /* sizeof() of the ABI structs, for bindings to self-check: 0 esm2_config, 1 esm2_layer, 2 esm2_weights,
- * 3 llama_config, 4 llama_layer, 5 llama_weights, 6 adapter_config, 7 adapter_weights, 8 adapter_saved, 9 llama_layer_t. */
+ * 3 llama_config, 4 llama_layer, 5 llama_weights, 6 adapter_config, 7 adapter_weights, 8 adapter_saved, 9 llama_layer_t,
+ * 10 kv_cache, 11 llama_layer_stream, 12 flat_segment, 13 flat_chunk, 14 beam_state, 15 llama_layer_mxfp4. */
 size_t p2t_struct_size(int which);
 
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
@@ -825,6 +826,61 @@ int p2t_gemm_nt_skinny_fp8(const void* A, int64_t lda, const uint8_t* a_scale, c
                            int w_preshuffled, void* out, int64_t ldc, int64_t M, int64_t N, int64_t K, int out_dtype, int epilogue,
                            p2t_stream stream);
 int p2t_preshuffle_w_fp8(const void* W, int64_t ldw, int64_t N, int64_t K, void* out, p2t_stream stream);
+
+/* ---------------------------------------------------------------- MXFP4 decoder weights (decode step only; DESIGN.md sections 9, 11)
+ * Storage (OCP MXFP4): e2m1 codes, two per byte -- the even column in the low nibble -- row-major [N][ld_codes >= Kq / 2] bytes, and one
+ * E8M0 scale byte per block of 32 consecutive K columns, dense [N][Kq / 32].  Kq = K rounded up to 128; columns >= K count as zeros.
+ * A code is sign (bit 3) | magnitude index into {0, 0.5, 1, 1.5, 2, 3, 4, 6}; the value is that times 2^(scale byte - 127).
+ *
+ * Scale rule (this project's fp8 rule, not OCP's floor rule: nothing saturates).  For block j of a row, e_j = the smallest integer with
+ * amax_j / 2^e_j <= 6; E_row = max_j e_j; then the CLAMP e_j <- max(e_j, E_row - 8).  A zero block gets E_row - 8, an all-zero row the
+ * byte 127 everywhere.  The stored byte is 127 + e_j.  (Inputs are finite and, where non-zero, normal f32 magnitudes.)
+ * Codes: round-to-nearest onto the grid times 2^e_j, ties to the even code (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2,
+ * 3.5 -> 4, 5 -> 4); the sign bit is the input's sign (so the sign of a value that rounds to zero is unspecified for a reader).
+ *
+ * Why the clamp: with it every value of a row is a multiple of 2^(E_row - 9) below 2^(E_row + 3), i.e. e4m3-representable under the
+ * ONE row scale p2t_quant_rows_fp8 picks -- p2t_quant_rows_fp8(dequantised row) returns the row bit for bit.  That is what lets the
+ * prefill, the cache-less forward and decode beyond 64 rows run the e4m3 kernels on the SAME weights W~ the decode step streams in
+ * 4.25 bits.  Without the clamp a block 2^-9 or more below the row maximum falls under the e4m3 grid of the row scale and is rounded.
+ * Re-quantising W~ gives W~ back (values; a block whose maximum rounded down to 3 * 2^e may re-quantise at e - 1 to the same values).
+ * |w - w~| <= 2^e_j per element (half the widest grid step, 2 * 2^e_j between 4 and 6).
+ *
+ * p2t_quant_rows_mxfp4: x F32 / BF16 [rows, ld_x] (ld_x % 8 == 0) -> codes [rows, ld_codes] (ld_codes % 16 == 0; bytes [0, Kq / 2) of
+ * every row written, nothing behind them) + scales [rows, Kq / 32].  One block per row, two passes.
+ * p2t_dequant_rows_mxfp4: -> out bf16 [rows, ld_out], columns [0, cols): exact (two significant bits).
+ * p2t_preshuffle_w_mxfp4: the stream copy of the decode GEMM, ONE buffer of round_up(N, 16) / 16 * (K / 128) chunks of 1088 bytes,
+ * chunk (t, s) = what one MFMA consumes: byte 16 lane + b = codes[16 t + lane % 16][64 s + 16 (lane / 16) + b] (1024 bytes), then byte
+ * 1024 + lane = scales[16 t + lane % 16][4 s + lane / 16] (64 bytes); rows >= N: zero codes, byte 127.  K % 128 == 0 (K = Kq here).
+ * p2t_gemm_nt_skinny_mxfp4: p2t_gemm_nt_skinny_fp8 with W in this format -- A e4m3 [M <= 64, lda] + a_scale as there, W codes [N, ldw
+ * bytes] + w_block_scale [N, K / 32], or w_preshuffled: W = the stream copy (ldw, w_block_scale ignored).  K % 128 == 0, K >= 128,
+ * lda % 16 == 0, ldw % 16 == 0, ldw >= K / 2; same epilogues.  v_mfma_scale_f32_16x16x128_f8f6f4 with an fp4 A operand: lane (r, g)
+ * takes the code bytes of the K columns 128 s + 32 g .. + 31, one MX block per lane and step (its scale byte is that lane's scale
+ * operand); the e4m3 operand keeps the fp8 form's lane map.  Anything else: P2T_ERR_UNSUPPORTED. */
+int p2t_quant_rows_mxfp4(const void* x, int dtype, int64_t ld_x, int64_t rows, int64_t cols, void* codes, int64_t ld_codes,
+                         uint8_t* scales, p2t_stream stream);
+int p2t_dequant_rows_mxfp4(const void* codes, int64_t ld_codes, const uint8_t* scales, int64_t rows, int64_t cols, void* out,
+                           int64_t ld_out, p2t_stream stream);
+int p2t_preshuffle_w_mxfp4(const void* codes, int64_t ld_codes, const uint8_t* scales, int64_t N, int64_t K, void* out,
+                           p2t_stream stream);
+int p2t_gemm_nt_skinny_mxfp4(const void* A, int64_t lda, const uint8_t* a_scale, const void* W, int64_t ldw,
+                             const uint8_t* w_block_scale, int w_preshuffled, void* out, int64_t ldc, int64_t M, int64_t N, int64_t K,
+                             int out_dtype, int epilogue, p2t_stream stream);
+/* The four projections of a layer in that format, in the row order and K padding of p2t_llama_layer's matrices (K = hidden / heads *
+ * head_dim / ffn rounded up to 128; codes with ld = K / 2).  stream_order != 0: the *_w are p2t_preshuffle_w_mxfp4 copies and the *_bs
+ * are ignored (the same value in every layer). */
+typedef struct {
+    const void* qkv_w; const void* o_w; const void* gu_w; const void* down_w;
+    const uint8_t* qkv_bs; const uint8_t* o_bs; const uint8_t* gu_bs; const uint8_t* down_bs;
+    int32_t stream_order; int32_t reserved;
+} p2t_llama_layer_mxfp4;
+/* p2t_llama_decode_step for a gemm_fp8 configuration (bf16 activations) with at most 64 rows, whose four projections per layer stream
+ * `layers` (HOST array of n_layers entries) instead of the e4m3 matrices of `w`; norms, row quantisers, attention, the fused rotation
+ * epilogue (or the two-launch path where it does not apply) and the bf16 LM head are that function's.  `w` is the gemm_fp8 weight set
+ * whose e4m3 matrices hold the same W~ (the prefill reads those). */
+int p2t_llama_decode_step_mxfp4(const p2t_llama_config* cfg, const p2t_llama_weights* w, const p2t_llama_layer_mxfp4* layers,
+                                const void* lm_head, int64_t ld_head, int lm_head_preshuffled, const p2t_kv_cache* cache,
+                                const float* x, void* logits, int64_t ld_logits, int flags, void* workspace, size_t workspace_bytes,
+                                p2t_stream stream);
 /* The decode step's attention on its own (exposed so that it can be checked against the plain arithmetic): ONE query token per
  * row, q `dtype` [BB, nh, dp], over prompt_len[row / group] keys of the prompt segment and step[0] + 1 keys of the generated
  * segment (the layouts of ONE layer of p2t_kv_cache), GQA; softmax((scale) q k^T) v with f32 statistics -- log2_scores: q holds

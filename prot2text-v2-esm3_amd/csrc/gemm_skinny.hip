@@ -347,6 +347,163 @@ __global__ void __launch_bounds__(256) preshuffle_fp8_kernel(const uint8_t* __re
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The same stream on MXFP4 weights (include/p2t_hip.h, "MXFP4 decoder weights"): e2m1 codes, two per byte, and one E8M0 scale byte per
+// block of 32 K columns, against the e4m3 activation rows of the fp8 form -- the same instruction with A's format field = 4
+// (cbsz: fp4, four A registers).  A K step is 128 columns = 64 code bytes of a row.  Lane maps, found with one-hot operands on the
+// hardware and pinned by the exact-integer witness of tests/test_gpu_mxfp4.py: nibble j of the fp4 operand of lane (r16, g) is K column
+// 32 g + j of row r16 -- one load of 16 code bytes, one MX block per lane and step, and the scale byte of lane (r16, g) applies to
+// exactly that block (it changes every step) -- while the e4m3 operand keeps the fp8 form's map (registers 0..3: columns 16 g ..,
+// registers 4..7: columns 64 + 16 g ..).  So fp4 lane group g meets the low (g < 2) or high registers of the fp8 lane groups 2 (g & 1)
+// and 2 (g & 1) + 1; the MFMA pairs them by column.  The activation row scale rides in byte j of one register as in the fp8 form.
+// Stream copy (launch_preshuffle_mxfp4): [tile][step] chunks of 1088 bytes = 1024 code bytes [lane][16] + 64 scale bytes [lane].
+constexpr int kMxChunk = 1088;
+
+template <int MT, int NT, int EPI, bool PRE>
+__global__ void __launch_bounds__(kSkWaves * 64) gemm_skinny_mxfp4_kernel(const uint8_t* __restrict__ x, int64_t lda, const uint8_t* __restrict__ xs,
+                                                                         const uint8_t* __restrict__ W, int64_t ldw, const uint8_t* __restrict__ wbs,
+                                                                         void* __restrict__ out, int64_t ldc, int M, int N, int K, SkinnyRope ra) {
+    __shared__ float red[kSkWaves][NT][MT][64][4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r16 = lane & 15, g = lane >> 4;
+    int row0[NT];
+    if constexpr (EPI == SK_SWIGLU || EPI == SK_QKV_ROPE) {
+        const int j = blockIdx.x >> 1, q = blockIdx.x & 1;
+        row0[0] = 64 * j + 16 * q;
+        row0[1] = row0[0] + 32;
+    } else {
+#pragma unroll
+        for (int i = 0; i < NT; ++i) row0[i] = (blockIdx.x * NT + i) * 16;
+    }
+    const int steps = K >> 7;                                       // 128 columns of K per MFMA
+    constexpr int kStep = PRE ? kMxChunk : 64;                      // bytes between the code fragments of consecutive K steps
+    const uint8_t* wp[NT];
+    const uint8_t* sp[NT];                                          // the lane's scale byte of step 0; + kStep (stream) / + 4 (row-major) per step
+    bool wok[NT];
+    int sx = 0;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        if constexpr (PRE) {
+            wok[i] = row0[i] < N;                                   // rows are padded to whole tiles with zero codes
+            wp[i] = W + (int64_t)(wok[i] ? row0[i] >> 4 : 0) * steps * kMxChunk + lane * 16;
+            sp[i] = W + (int64_t)(wok[i] ? row0[i] >> 4 : 0) * steps * kMxChunk + 1024 + lane;
+        } else {
+            wok[i] = row0[i] + r16 < N;
+            wp[i] = W + (int64_t)(wok[i] ? row0[i] + r16 : 0) * ldw + g * 16;
+            sp[i] = wbs + (int64_t)(wok[i] ? row0[i] + r16 : 0) * (steps * 4) + g;
+        }
+    }
+    const uint8_t* xp[MT];
+    bool xok[MT];
+#pragma unroll
+    for (int j = 0; j < MT; ++j) {
+        xok[j] = j * 16 + r16 < M;
+        xp[j] = x + (int64_t)(xok[j] ? j * 16 + r16 : 0) * lda + g * 16;
+        sx |= (int)xs[xok[j] ? j * 16 + r16 : 0] << (8 * j);
+    }
+    const int s0 = (int)((int64_t)steps * w / kSkWaves), s1 = (int)((int64_t)steps * (w + 1) / kSkWaves);
+    f32x4 acc[NT][MT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int j = 0; j < MT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const v4i zero4 = {0, 0, 0, 0};
+    auto ld16 = [](const uint8_t* p) { return *reinterpret_cast<const v4i*>(p); };
+    auto ld16s = [](const uint8_t* p) {
+        if constexpr (PRE) return __builtin_nontemporal_load(reinterpret_cast<const v4i*>(p));
+        else return *reinterpret_cast<const v4i*>(p);
+    };
+    constexpr int kScaleStep = PRE ? kMxChunk : 4;
+    int s = s0;
+    auto batch = [&](auto uu) {
+        constexpr int UU = decltype(uu)::value;
+        v4i a[UU][NT];
+        int sa[UU][NT];
+        v8i b[UU][MT];
+#pragma unroll
+        for (int u = 0; u < UU; ++u) {
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                a[u][i] = wok[i] ? ld16s(wp[i] + (int64_t)(s + u) * kStep) : zero4;
+                sa[u][i] = wok[i] ? (int)sp[i][(int64_t)(s + u) * kScaleStep] : 127;
+            }
+#pragma unroll
+            for (int j = 0; j < MT; ++j) {
+                const uint8_t* p = xp[j] + (int64_t)(s + u) * 128;
+                const v4i lo = xok[j] ? ld16(p) : zero4, hi = xok[j] ? ld16(p + 64) : zero4;
+                b[u][j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UU; ++u)
+            static_for<0, NT>([&](auto ii) {
+                static_for<0, MT>([&](auto jj) {
+                    constexpr int I = decltype(ii)::value, J = decltype(jj)::value;
+                    const v8i a8 = __builtin_shufflevector(a[u][I], zero4, 0, 1, 2, 3, 4, 5, 6, 7);
+                    acc[I][J] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8, b[u][J], acc[I][J], 4, 0, 0, sa[u][I], J, sx);
+                });
+            });
+        s += UU;
+    };
+    // the fp8 form's steps per batch.  Twice as many (the same weight bytes in flight per lane) was measured and dropped: a wave of the
+    // Llama-8B projections has 4 (K = 4096) or 14 (K = 14336) steps, so the deeper batch never ran there and its registers (144-236
+    // VGPRs against 94-149) only cost the second block per CU: gate/up 18.5 -> 14.0 us
+    constexpr int U = NT * MT >= 4 ? 2 : (NT * MT == 1 ? 8 : 4);
+    while (s + U <= s1) batch(std::integral_constant<int, U>{});
+    if constexpr (U >= 8) { if (s + 4 <= s1) batch(std::integral_constant<int, 4>{}); }
+    if constexpr (U >= 4) { if (s + 2 <= s1) batch(std::integral_constant<int, 2>{}); }
+    if (s < s1) batch(std::integral_constant<int, 1>{});
+    if (s < s1) batch(std::integral_constant<int, 1>{});
+    skinny_finish<MT, NT, EPI>(red, acc, row0, w, lane, out, ldc, M, N, ra);
+}
+
+template <int MT, int EPI, bool PRE>
+int launch_mt_mxfp4(const uint8_t* x, int64_t lda, const uint8_t* xs, const uint8_t* W, int64_t ldw, const uint8_t* wbs, void* out, int64_t ldc, int M, int N,
+                    int K, const SkinnyRope& ra, hipStream_t s) {
+    if constexpr (EPI == SK_SWIGLU || EPI == SK_QKV_ROPE) {
+        gemm_skinny_mxfp4_kernel<MT, 2, EPI, PRE><<<(unsigned)(N / 32), kSkWaves * 64, 0, s>>>(x, lda, xs, W, ldw, wbs, out, ldc, M, N, K, ra);
+    } else {
+        const int tiles = (N + 15) / 16;                            // the fp8 form's thresholds
+        if (tiles >= 1024 || (MT >= 2 && tiles >= 384))
+            gemm_skinny_mxfp4_kernel<MT, 2, EPI, PRE><<<(unsigned)((tiles + 1) / 2), kSkWaves * 64, 0, s>>>(x, lda, xs, W, ldw, wbs, out, ldc, M, N, K, ra);
+        else
+            gemm_skinny_mxfp4_kernel<MT, 1, EPI, PRE><<<(unsigned)tiles, kSkWaves * 64, 0, s>>>(x, lda, xs, W, ldw, wbs, out, ldc, M, N, K, ra);
+    }
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+template <int EPI>
+int launch_epi_mxfp4(const uint8_t* x, int64_t lda, const uint8_t* xs, const uint8_t* W, int64_t ldw, const uint8_t* wbs, void* out, int64_t ldc, int M,
+                     int N, int K, int pre, hipStream_t s, const SkinnyRope& ra = SkinnyRope{}) {
+#define P2T_SKM(MTV)                                                                                                              \
+    (pre ? launch_mt_mxfp4<MTV, EPI, true>(x, lda, xs, W, ldw, wbs, out, ldc, M, N, K, ra, s)                                      \
+         : launch_mt_mxfp4<MTV, EPI, false>(x, lda, xs, W, ldw, wbs, out, ldc, M, N, K, ra, s))
+    if (M <= 16) return P2T_SKM(1);
+    if (M <= 32) return P2T_SKM(2);
+    return P2T_SKM(4);
+#undef P2T_SKM
+}
+
+// chunk (tile, step) of the stream copy: byte 16 lane + b = codes[16 tile + lane % 16][64 step + 16 (lane / 16) + b], byte 1024 + lane =
+// scales[16 tile + lane % 16][4 step + lane / 16]; rows >= N: zero codes, scale byte 127.  One thread per (chunk, lane).
+__global__ void __launch_bounds__(256) preshuffle_mxfp4_kernel(const uint8_t* __restrict__ codes, int64_t ldw, const uint8_t* __restrict__ bs, int N, int K,
+                                                               uint8_t* __restrict__ out, int64_t items) {
+    const int steps = K >> 7;
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < items; c += (int64_t)gridDim.x * 256) {
+        const int lane = (int)(c & 63);
+        const int64_t ts = c >> 6;
+        const int step = (int)(ts % steps);
+        const int64_t row = (ts / steps) * 16 + (lane & 15);
+        uint4 v = make_uint4(0, 0, 0, 0);
+        uint8_t sc = 127;
+        if (row < N) {
+            v = *reinterpret_cast<const uint4*>(codes + row * ldw + 64 * step + 16 * (lane >> 4));
+            sc = bs[row * (steps * 4) + 4 * step + (lane >> 4)];
+        }
+        *reinterpret_cast<uint4*>(out + ts * kMxChunk + lane * 16) = v;
+        out[ts * kMxChunk + 1024 + lane] = sc;
+    }
+}
+
 template <int MT, int EPI, bool PRE>
 int launch_mt(const bf16_t* x, int64_t lda, const bf16_t* W, int64_t ldw, void* out, int64_t ldc, int M, int N, int K, const SkinnyRope& ra, hipStream_t s) {
     if constexpr (EPI == SK_SWIGLU || EPI == SK_QKV_ROPE) {
@@ -454,6 +611,46 @@ int launch_gemm_skinny_fp8(const void* x, int64_t lda, const uint8_t* xs, const 
                                                                           : P2T_ERR_UNSUPPORTED;
     }
     return P2T_ERR_UNSUPPORTED;
+}
+
+// MXFP4 form: x e4m3 bytes + row scales xs as above; W e2m1 codes [N, ldw bytes >= K / 2] with block scales wbs [N, K / 32] (pre: the
+// interleaved stream copy, ldw and wbs unused).  K % 128 == 0.  Same epilogues; ra != nullptr = the QKV + rotation + cache-append form.
+int launch_gemm_skinny_mxfp4(const void* x, int64_t lda, const uint8_t* xs, const void* W, int64_t ldw, const uint8_t* wbs, void* out, int64_t ldc,
+                             int64_t M, int64_t N, int64_t K, int out_dtype, int epilogue, const SkinnyRope* ra, hipStream_t s, int pre) {
+    if (!xs || (!pre && !wbs) || M < 1 || M > 64 || N < 1 || N >= (1 << 30) || K < 128 || K % 128 || K >= (1 << 30) || lda % 16 || lda < K ||
+        (!pre && (ldw % 16 || ldw < K / 2)))
+        return P2T_ERR_UNSUPPORTED;
+    const uint8_t* xb = (const uint8_t*)x;
+    const uint8_t* wb = (const uint8_t*)W;
+    const int m = (int)M, n = (int)N, k = (int)K;
+    if (ra) {
+        if (N % 64 || (ra->d != 64 && ra->d != 128) || N != (int64_t)(ra->nh + 2 * ra->nkv) * ra->d) return P2T_ERR_UNSUPPORTED;
+        return launch_epi_mxfp4<SK_QKV_ROPE>(xb, lda, xs, wb, ldw, wbs, nullptr, 0, m, n, k, pre, s, *ra);
+    }
+    switch (epilogue) {
+        case P2T_EPI_STORE:
+            if (out_dtype == P2T_BF16 && ldc % 4 == 0) return launch_epi_mxfp4<SK_STORE>(xb, lda, xs, wb, ldw, wbs, out, ldc, m, n, k, pre, s);
+            if (out_dtype == P2T_F32 && ldc % 4 == 0) return launch_epi_mxfp4<SK_STORE_F32>(xb, lda, xs, wb, ldw, wbs, out, ldc, m, n, k, pre, s);
+            return P2T_ERR_UNSUPPORTED;
+        case P2T_EPI_STORE_F32:
+            return ldc % 4 == 0 ? launch_epi_mxfp4<SK_STORE_F32>(xb, lda, xs, wb, ldw, wbs, out, ldc, m, n, k, pre, s) : P2T_ERR_UNSUPPORTED;
+        case P2T_EPI_RESID:
+            return ldc % 4 == 0 ? launch_epi_mxfp4<SK_RESID>(xb, lda, xs, wb, ldw, wbs, out, ldc, m, n, k, pre, s) : P2T_ERR_UNSUPPORTED;
+        case P2T_EPI_SWIGLU:
+            return (out_dtype == P2T_BF16 && n % 64 == 0 && ldc % 4 == 0) ? launch_epi_mxfp4<SK_SWIGLU>(xb, lda, xs, wb, ldw, wbs, out, ldc, m, n, k, pre, s)
+                                                                          : P2T_ERR_UNSUPPORTED;
+    }
+    return P2T_ERR_UNSUPPORTED;
+}
+
+int launch_preshuffle_mxfp4(const void* codes, int64_t ldw, const uint8_t* bs, int64_t N, int64_t K, void* out, hipStream_t s) {
+    P2T_REQUIRE(codes && bs && out && N > 0 && N < (1 << 30) && K >= 128 && K % 128 == 0 && K < (1 << 30) && ldw >= K / 2 && ldw % 16 == 0,
+                "p2t_preshuffle_w_mxfp4: bad arguments (K %% 128, ld_codes %% 16, ld_codes >= K / 2)");
+    const int64_t items = round_up(N, 16) / 16 * (K / 128) * 64;
+    const int64_t blocks = ceil_div(items, 256);
+    preshuffle_mxfp4_kernel<<<(unsigned)(blocks > 65535 ? 65535 : blocks), 256, 0, s>>>((const uint8_t*)codes, ldw, bs, (int)N, (int)K, (uint8_t*)out, items);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
 }
 
 int launch_preshuffle_fp8(const void* W, int64_t ldw, int64_t N, int64_t K, void* out, hipStream_t s) {

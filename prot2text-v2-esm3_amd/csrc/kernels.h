@@ -160,6 +160,11 @@ int launch_preshuffle(const void* W, int64_t ldw, int64_t N, int64_t K, void* ou
 int launch_gemm_skinny_fp8(const void* x, int64_t lda, const uint8_t* xs, const void* W, int64_t ldw, const uint8_t* ws, void* out, int64_t ldc, int64_t M,
                            int64_t N, int64_t K, int out_dtype, int epilogue, const SkinnyRope* ra, hipStream_t s, int pre);
 int launch_preshuffle_fp8(const void* W, int64_t ldw, int64_t N, int64_t K, void* out, hipStream_t s);
+// MXFP4 weights (e2m1 codes [N, ldw bytes] + E8M0 block scales [N, K / 32]) against the same e4m3 rows; pre: the interleaved stream
+// copy of launch_preshuffle_mxfp4 (ldw, wbs unused)
+int launch_gemm_skinny_mxfp4(const void* x, int64_t lda, const uint8_t* xs, const void* W, int64_t ldw, const uint8_t* wbs, void* out, int64_t ldc,
+                             int64_t M, int64_t N, int64_t K, int out_dtype, int epilogue, const SkinnyRope* ra, hipStream_t s, int pre);
+int launch_preshuffle_mxfp4(const void* codes, int64_t ldw, const uint8_t* bs, int64_t N, int64_t K, void* out, hipStream_t s);
 
 int launch_attn_simple(const void* q, const void* k, const void* v, const uint8_t* key_mask, const int32_t* kv_info, void* out,
                        int64_t ld_out, int B, int T, int nh, int nkv, int d, int dp, float scale, int causal, int dtype,

@@ -636,9 +636,10 @@ extern "C" size_t p2t_llama_decode_workspace_bytes(const p2t_llama_config* cfg, 
     return decode_plan(cfg, BB, Tp, G, nullptr, nullptr);
 }
 
-extern "C" int p2t_llama_decode_step(const p2t_llama_config* c, const p2t_llama_weights* w, const p2t_llama_layer_stream* ws_layers,
-                                     const void* lm_head, int64_t ld_head, int lm_head_preshuffled, const p2t_kv_cache* cache, const float* x_in, void* logits, int64_t ld_logits, int flags, void* workspace,
-                                     size_t workspace_bytes, p2t_stream stream) {
+// mx: the MXFP4 form of the projections (p2t_llama_decode_step_mxfp4; a gemm_fp8 model, at most 64 rows) or nullptr
+static int decode_step_impl(const p2t_llama_config* c, const p2t_llama_weights* w, const p2t_llama_layer_stream* ws_layers, const p2t_llama_layer_mxfp4* mx,
+                            const void* lm_head, int64_t ld_head, int lm_head_preshuffled, const p2t_kv_cache* cache, const float* x_in, void* logits,
+                            int64_t ld_logits, int flags, void* workspace, size_t workspace_bytes, p2t_stream stream) {
     P2T_REQUIRE(c && w && w->layers && w->final_norm_w && lm_head && x_in && logits && workspace, "p2t_llama_decode_step: null argument");
     const bool fuse_rope = !(flags & P2T_DECODE_NO_ROPE_FUSION);
     P2T_TRY(check_cache(c, cache, "p2t_llama_decode_step"));
@@ -681,8 +682,11 @@ extern "C" int p2t_llama_decode_step(const p2t_llama_config* c, const p2t_llama_
     // gemm_fp8 models (e4m3 weights AND GEMM operands, bf16 activations elsewhere): the same step with every
     // projection on the e4m3 stream (half the weight bytes of a step); rows are quantised by the RMSNorm / a quantise pass as in the prefill
     const int64_t Hq = round_up(H, 128), Fq = round_up(F, 128), QOq = round_up((int64_t)nh * d, 128);
+    struct MxProj { const void* w; const uint8_t* bs; };   // one projection of p2t_llama_layer_mxfp4; w == nullptr: the e4m3 stream
     auto gemm8 = [&](const uint8_t* A, int64_t lda, const uint8_t* as, const void* W, const uint8_t* wsc, const void* pre, void* out, int64_t ldc,
-                     int64_t N, int64_t K, int out_dtype, int epi, const SkinnyRope* ra, hipStream_t st) {
+                     int64_t N, int64_t K, int out_dtype, int epi, const SkinnyRope* ra, hipStream_t st, MxProj m4 = MxProj{nullptr, nullptr}) {
+        // no general 4-bit GEMM behind this one: only the fused-rotation form may answer UNSUPPORTED (the caller then takes two launches)
+        if (m4.w) return launch_gemm_skinny_mxfp4(A, lda, as, m4.w, K / 2, m4.bs, out, ldc, M, N, K, out_dtype, epi, ra, st, mx->stream_order != 0);
         const int r = launch_gemm_skinny_fp8(A, lda, as, pre ? pre : W, K, wsc, out, ldc, M, N, K, out_dtype, epi, ra, st, pre != nullptr);
         if (r != P2T_ERR_UNSUPPORTED || ra) return r;
         GemmArgs g = gemm_args_fp8(A, lda, as, W, wsc, M, N, K, out, ldc, out_dtype, epi);
@@ -695,6 +699,10 @@ extern "C" int p2t_llama_decode_step(const p2t_llama_config* c, const p2t_llama_
         P2T_REQUIRE(!L.q_norm_w == !L.k_norm_w, "p2t_llama_decode_step: q_norm_w and k_norm_w go together (layer %d)", l);
         const int fused_prefill = !L.q_norm_w && (d == 64 || d == 128);
         const p2t_llama_layer_stream* S = ws_layers ? ws_layers + l : nullptr;
+        const MxProj xq{mx ? mx[l].qkv_w : nullptr, mx ? mx[l].qkv_bs : nullptr}, xo{mx ? mx[l].o_w : nullptr, mx ? mx[l].o_bs : nullptr},
+            xg{mx ? mx[l].gu_w : nullptr, mx ? mx[l].gu_bs : nullptr}, xd{mx ? mx[l].down_w : nullptr, mx ? mx[l].down_bs : nullptr};
+        P2T_REQUIRE(!mx || (xq.w && xo.w && xg.w && xd.w && (mx->stream_order || (xq.bs && xo.bs && xg.bs && xd.bs))),
+                    "p2t_llama_decode_step_mxfp4: null codes / block scales in layer %d", l);
         const size_t per_g = (size_t)BB * nkv * cache->G * dp;
         P2T_TRY(launch_rmsnorm_fp8_few(b.x, H, L.ln1_w, c->rms_norm_eps, b.hq, Hq, b.hs, M, H, s));
         bool roped = false;
@@ -703,11 +711,11 @@ extern "C" int p2t_llama_decode_step(const p2t_llama_config* c, const p2t_llama_
             ra.inv_freq = inv_freq; ra.prompt_len = cache->prompt_len; ra.step = cache->step; ra.group = cache->group;
             ra.nh = nh; ra.nkv = nkv; ra.d = d; ra.G = cache->G; ra.q_scale = q_fold;
             ra.q = b.qb; ra.k = (bf16_t*)cache->k_gen + per_g * l; ra.vt = (bf16_t*)cache->vt_gen + per_g * l;
-            const int r = gemm8(b.hq, Hq, b.hs, L.qkv_w, L.qkv_ws, S ? S->qkv_w : nullptr, nullptr, 0, NQKV, Hq, dt, 0, &ra, s);
+            const int r = gemm8(b.hq, Hq, b.hs, L.qkv_w, L.qkv_ws, S ? S->qkv_w : nullptr, nullptr, 0, NQKV, Hq, dt, 0, &ra, s, xq);
             if (r != P2T_ERR_UNSUPPORTED) { P2T_TRY(r); roped = true; }
         }
         if (!roped) {
-            P2T_TRY(gemm8(b.hq, Hq, b.hs, L.qkv_w, L.qkv_ws, S ? S->qkv_w : nullptr, b.qkv, NQKV, NQKV, Hq, P2T_F32, P2T_EPI_STORE_F32, nullptr, s));
+            P2T_TRY(gemm8(b.hq, Hq, b.hs, L.qkv_w, L.qkv_ws, S ? S->qkv_w : nullptr, b.qkv, NQKV, NQKV, Hq, P2T_F32, P2T_EPI_STORE_F32, nullptr, s, xq));
             const unsigned grid = (unsigned)ceil_div((int64_t)BB * (nh + 2 * nkv), 4);
             rope_append_kernel<bf16_t><<<grid, 256, 0, s>>>(b.qkv, NQKV, inv_freq, L.q_norm_w, L.k_norm_w, c->rms_norm_eps, cache->prompt_len, cache->step,
                                                             cache->group, (bf16_t*)b.qb, (bf16_t*)cache->k_gen + per_g * l, (bf16_t*)cache->vt_gen + per_g * l,
@@ -716,11 +724,11 @@ extern "C" int p2t_llama_decode_step(const p2t_llama_config* c, const p2t_llama_
         }
         P2T_TRY(launch_attn_decode_t<bf16_t>(b, cache, l, BB, nh, nkv, d, dp, c_exp, 1, QO, s));
         P2T_TRY(launch_quant_rows_few(b.ao, dt, QO, M, (int64_t)nh * d, b.aoq, QOq, b.aos, s));
-        P2T_TRY(gemm8(b.aoq, QOq, b.aos, L.o_w, L.o_ws, S ? S->o_w : nullptr, b.x, H, H, QOq, P2T_F32, P2T_EPI_RESID, nullptr, s));
+        P2T_TRY(gemm8(b.aoq, QOq, b.aos, L.o_w, L.o_ws, S ? S->o_w : nullptr, b.x, H, H, QOq, P2T_F32, P2T_EPI_RESID, nullptr, s, xo));
         P2T_TRY(launch_rmsnorm_fp8_few(b.x, H, L.ln2_w, c->rms_norm_eps, b.hq, Hq, b.hs, M, H, s));
-        P2T_TRY(gemm8(b.hq, Hq, b.hs, L.gu_w, L.gu_ws, S ? S->gu_w : nullptr, b.act, Fp, 2 * F, Hq, dt, P2T_EPI_SWIGLU, nullptr, s));
+        P2T_TRY(gemm8(b.hq, Hq, b.hs, L.gu_w, L.gu_ws, S ? S->gu_w : nullptr, b.act, Fp, 2 * F, Hq, dt, P2T_EPI_SWIGLU, nullptr, s, xg));
         P2T_TRY(launch_quant_rows_few(b.act, dt, Fp, M, F, b.actq, Fq, b.acts, s));
-        P2T_TRY(gemm8(b.actq, Fq, b.acts, L.down_w, L.down_ws, S ? S->down_w : nullptr, b.x, H, H, Fq, P2T_F32, P2T_EPI_RESID, nullptr, s));
+        P2T_TRY(gemm8(b.actq, Fq, b.acts, L.down_w, L.down_ws, S ? S->down_w : nullptr, b.x, H, H, Fq, P2T_F32, P2T_EPI_RESID, nullptr, s, xd));
     }
     for (int l = 0; !c->gemm_fp8 && l < c->n_layers; ++l) {
         const p2t_llama_layer& L = w->layers[l];
@@ -778,6 +786,28 @@ extern "C" int p2t_llama_decode_step(const p2t_llama_config* c, const p2t_llama_
     advance_kernel<<<1, 1, 0, s>>>(cache->step);
     P2T_LAUNCH_CHECK();
     return P2T_OK;
+}
+
+extern "C" int p2t_llama_decode_step(const p2t_llama_config* c, const p2t_llama_weights* w, const p2t_llama_layer_stream* ws_layers,
+                                     const void* lm_head, int64_t ld_head, int lm_head_preshuffled, const p2t_kv_cache* cache, const float* x_in, void* logits, int64_t ld_logits, int flags, void* workspace,
+                                     size_t workspace_bytes, p2t_stream stream) {
+    return decode_step_impl(c, w, ws_layers, nullptr, lm_head, ld_head, lm_head_preshuffled, cache, x_in, logits, ld_logits, flags, workspace, workspace_bytes,
+                            stream);
+}
+
+// The step of a gemm_fp8 model whose four projections per layer stream MXFP4 weights (include/p2t_hip.h): everything else -- the
+// row quantisers, the attention, the bf16 LM head -- is p2t_llama_decode_step's.
+extern "C" int p2t_llama_decode_step_mxfp4(const p2t_llama_config* c, const p2t_llama_weights* w, const p2t_llama_layer_mxfp4* mx_layers,
+                                           const void* lm_head, int64_t ld_head, int lm_head_preshuffled, const p2t_kv_cache* cache, const float* x_in,
+                                           void* logits, int64_t ld_logits, int flags, void* workspace, size_t workspace_bytes, p2t_stream stream) {
+    P2T_REQUIRE(c && mx_layers && cache, "p2t_llama_decode_step_mxfp4: null argument");
+    P2T_REQUIRE(c->gemm_fp8 && c->dtype == P2T_BF16, "p2t_llama_decode_step_mxfp4: needs a gemm_fp8 configuration with bf16 activations");
+    P2T_REQUIRE((int64_t)cache->B0 * cache->group <= 64, "p2t_llama_decode_step_mxfp4: at most 64 rows (got %lld): beyond that the e4m3 weights serve",
+                (long long)cache->B0 * cache->group);
+    for (int l = 1; l < c->n_layers; ++l)
+        P2T_REQUIRE(!mx_layers[l].stream_order == !mx_layers[0].stream_order, "p2t_llama_decode_step_mxfp4: layers differ in stream_order");
+    return decode_step_impl(c, w, nullptr, mx_layers, lm_head, ld_head, lm_head_preshuffled, cache, x_in, logits, ld_logits, flags, workspace,
+                            workspace_bytes, stream);
 }
 
 extern "C" int p2t_greedy_select(const void* logits, int dtype, int64_t ld, int V, int BB, const int64_t* eos_ids, int n_eos, int64_t pad_id,

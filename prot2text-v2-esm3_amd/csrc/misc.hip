@@ -248,6 +248,7 @@ extern "C" size_t p2t_struct_size(int which) {
         case 12: return sizeof(p2t_flat_segment);
         case 13: return sizeof(p2t_flat_chunk);
         case 14: return sizeof(p2t_beam_state);
+        case 15: return sizeof(p2t_llama_layer_mxfp4);
     }
     return 0;
 }

@@ -113,9 +113,122 @@ int launch_quant_rows_few(const void* x, int dtype, int64_t ld_x, int64_t rows, 
     return P2T_OK;
 }
 
+// ---- MXFP4 weights (include/p2t_hip.h, "MXFP4 decoder weights"): e2m1 codes + one E8M0 byte per block of 32 columns ----
+// e of a block from its absolute maximum: the smallest integer with amax / 2^e <= 6 = 1.5 * 2^2 (the integer rule of e8m0_of_amax):
+// amax = (1 + f) 2^ea  ->  e = ea - 2 + (f > 0.5)
+__device__ __forceinline__ int mx_e_of_amax(float amax) {
+    const unsigned u = __float_as_uint(amax);
+    return (int)((u >> 23) & 0xFF) - 127 - 2 + ((u & 0x7FFFFF) > 0x400000 ? 1 : 0);
+}
+// round-to-nearest onto {0, 0.5, 1, 1.5, 2, 3, 4, 6}, ties to the even code; v in [0, 6]
+__device__ __forceinline__ unsigned mx_code(float v) {
+    return (unsigned)(v > 0.25f) + (v >= 0.75f) + (v > 1.25f) + (v >= 1.75f) + (v > 2.5f) + (v >= 3.5f) + (v > 5.0f);
+}
+
+// One block per row, one thread per MX block of 32 columns (blocks tid, tid + 256, ..), two passes over the row: block maxima and the
+// row maximum first, then the clamped scale bytes and the codes (the second pass hits L1 / L2).
+template <typename Tin>
+__global__ void __launch_bounds__(256) quant_rows_mxfp4_kernel(const Tin* __restrict__ x, int64_t ld_x, int cols, uint8_t* __restrict__ codes,
+                                                               int64_t ld_codes, uint8_t* __restrict__ scales) {
+    __shared__ float red[4];
+    const int nb = (cols + 127) / 128 * 4;
+    const Tin* xr = x + (int64_t)blockIdx.x * ld_x;
+    float emax = -INFINITY;                                         // exponents are small integers: exact as floats
+    for (int j = threadIdx.x; j < nb; j += 256) {
+        float amax = 0.f;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            float v[8];
+            load_block8(xr, 32 * j + 8 * p, cols, v);
+#pragma unroll
+            for (int t = 0; t < 8; ++t) amax = fmaxf(amax, fabsf(v[t]));
+        }
+        if (amax > 0.f) emax = fmaxf(emax, (float)mx_e_of_amax(amax));
+    }
+    emax = block_max4(emax, red);
+    const bool zero_row = !(emax > -INFINITY);
+    const int e_floor = zero_row ? 0 : (int)emax - 8;
+    for (int j = threadIdx.x; j < nb; j += 256) {
+        float v[32];
+        float amax = 0.f;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            float t8[8];
+            load_block8(xr, 32 * j + 8 * p, cols, t8);
+#pragma unroll
+            for (int t = 0; t < 8; ++t) { v[8 * p + t] = t8[t]; amax = fmaxf(amax, fabsf(t8[t])); }
+        }
+        int e = amax > 0.f ? max(mx_e_of_amax(amax), e_floor) : e_floor;
+        const int E = min(max(e + 127, 1), 253);
+        const float inv = pow2_neg(E);
+        unsigned wds[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            unsigned wd = 0;
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                const float f = v[8 * p + t];
+                wd |= (mx_code(fabsf(f) * inv) | (f < 0.f ? 8u : 0u)) << (4 * t);
+            }
+            wds[p] = wd;
+        }
+        *reinterpret_cast<uint4*>(codes + (int64_t)blockIdx.x * ld_codes + 16 * j) = make_uint4(wds[0], wds[1], wds[2], wds[3]);
+        scales[(int64_t)blockIdx.x * nb + j] = (uint8_t)E;
+    }
+}
+
+// out[r, c] = grid[code & 7] * 2^(scale byte - 127), signed: at most two significant bits, exact in bf16.  One thread per 8 columns.
+__global__ void __launch_bounds__(256) dequant_rows_mxfp4_kernel(const uint8_t* __restrict__ codes, int64_t ld_codes, const uint8_t* __restrict__ scales,
+                                                                 int64_t rows, int cols, bf16_t* __restrict__ out, int64_t ld_out) {
+    const int per = (cols + 7) / 8, nb = (cols + 127) / 128 * 4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < rows * per; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / per;
+        const int c0 = (int)(i - r * per) * 8;
+        const unsigned wd = *reinterpret_cast<const unsigned*>(codes + r * ld_codes + c0 / 2);
+        const int e = (int)scales[r * nb + c0 / 32] - 127;
+        for (int t = 0; t < 8 && c0 + t < cols; ++t) {
+            const unsigned cd = (wd >> (4 * t)) & 15u, ex = (cd >> 1) & 3u, mn = cd & 1u;
+            const float mag = ex == 0 ? 0.5f * (float)mn : ldexpf(1.0f + 0.5f * (float)mn, (int)ex - 1);
+            const float val = ldexpf(mag, e);
+            out[r * ld_out + c0 + t] = from_f32<bf16_t>((cd & 8u) ? -val : val);
+        }
+    }
+}
+
 }  // namespace p2t
 
 using namespace p2t;
+
+extern "C" int p2t_quant_rows_mxfp4(const void* x, int dtype, int64_t ld_x, int64_t rows, int64_t cols, void* codes, int64_t ld_codes,
+                                    uint8_t* scales, p2t_stream stream) {
+    P2T_REQUIRE(x && codes && scales && rows >= 0 && cols > 0 && cols < (1 << 30) && (dtype == P2T_F32 || dtype == P2T_BF16),
+                "p2t_quant_rows_mxfp4: bad arguments");
+    P2T_REQUIRE(ld_x % 8 == 0 && ld_x >= cols && ld_codes % 16 == 0 && ld_codes >= round_up(cols, 128) / 2,
+                "p2t_quant_rows_mxfp4: ld_x must be a multiple of 8, ld_codes a multiple of 16 and >= round_up(cols, 128) / 2 (ld_x=%lld ld_codes=%lld)",
+                (long long)ld_x, (long long)ld_codes);
+    if (rows == 0) return P2T_OK;
+    P2T_REQUIRE(rows < (1ll << 31), "p2t_quant_rows_mxfp4: too many rows");
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == P2T_BF16)
+        quant_rows_mxfp4_kernel<bf16_t><<<(unsigned)rows, 256, 0, s>>>((const bf16_t*)x, ld_x, (int)cols, (uint8_t*)codes, ld_codes, scales);
+    else
+        quant_rows_mxfp4_kernel<float><<<(unsigned)rows, 256, 0, s>>>((const float*)x, ld_x, (int)cols, (uint8_t*)codes, ld_codes, scales);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
+extern "C" int p2t_dequant_rows_mxfp4(const void* codes, int64_t ld_codes, const uint8_t* scales, int64_t rows, int64_t cols, void* out,
+                                      int64_t ld_out, p2t_stream stream) {
+    P2T_REQUIRE(codes && scales && out && rows >= 0 && cols > 0 && cols < (1 << 30), "p2t_dequant_rows_mxfp4: bad arguments");
+    P2T_REQUIRE(ld_codes % 16 == 0 && ld_codes >= round_up(cols, 128) / 2 && ld_out >= cols,
+                "p2t_dequant_rows_mxfp4: ld_codes must be a multiple of 16 and >= round_up(cols, 128) / 2, ld_out >= cols");
+    if (rows == 0) return P2T_OK;
+    const int64_t items = rows * ceil_div(cols, 8), blocks = ceil_div(items, 256);
+    dequant_rows_mxfp4_kernel<<<(unsigned)(blocks > 65535 ? 65535 : blocks), 256, 0, (hipStream_t)stream>>>((const uint8_t*)codes, ld_codes, scales, rows,
+                                                                                                           (int)cols, (bf16_t*)out, ld_out);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
 
 extern "C" int p2t_quant_rows_fp8(const void* x, int dtype, int64_t ld_x, int64_t rows, int64_t cols, void* q, int64_t ld_q,
                                   uint8_t* scale, p2t_stream stream) {

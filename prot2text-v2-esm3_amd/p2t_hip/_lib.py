@@ -96,6 +96,11 @@ class LlamaLayerStreamC(C.Structure):
     _fields_ = [(n, vp) for n in ("qkv_w", "o_w", "gu_w", "down_w")]
 
 
+class LlamaLayerMxfp4C(C.Structure):
+    _fields_ = [(n, vp) for n in ("qkv_w", "o_w", "gu_w", "down_w", "qkv_bs", "o_bs", "gu_bs", "down_bs")] + [("stream_order", C.c_int32),
+                                                                                                          ("reserved", C.c_int32)]
+
+
 class FlatSegmentC(C.Structure):
     _fields_ = [("offset", i64), ("numel", i64), ("shadow", vp), ("rows", i64), ("cols", i64), ("ld", i64), ("scale", f32),
                 ("shadow_dtype", C.c_int32)]
@@ -108,7 +113,7 @@ class FlatChunkC(C.Structure):
 FLAT_NORM_BLOCKS, FLAT_CHUNK = 1024, 4096            # P2T_FLAT_NORM_BLOCKS, P2T_FLAT_CHUNK
 
 _STRUCTS = [EsmConfigC, EsmLayerC, EsmWeightsC, LlamaConfigC, LlamaLayerC, LlamaWeightsC, AdapterConfigC,
-            AdapterWeightsC, AdapterSavedC, LlamaLayerTC, KvCacheC, LlamaLayerStreamC, FlatSegmentC, FlatChunkC, BeamStateC]
+            AdapterWeightsC, AdapterSavedC, LlamaLayerTC, KvCacheC, LlamaLayerStreamC, FlatSegmentC, FlatChunkC, BeamStateC, LlamaLayerMxfp4C]
 
 # name -> (restype, argtypes); every symbol include/p2t_hip.h declares
 SIGNATURES = {
@@ -157,6 +162,8 @@ SIGNATURES = {
     "p2t_llama_decode_workspace_bytes": (sz, [C.POINTER(LlamaConfigC), i32, i32, i32]),
     "p2t_llama_decode_step": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), C.POINTER(LlamaLayerStreamC), vp, i64, i32, C.POINTER(KvCacheC), vp, vp, i64,
                               i32, vp, sz, vp]),
+    "p2t_llama_decode_step_mxfp4": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), C.POINTER(LlamaLayerMxfp4C), vp, i64, i32,
+                                    C.POINTER(KvCacheC), vp, vp, i64, i32, vp, sz, vp]),
     "p2t_greedy_select": (i32, [vp, i32, i64, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, i32, vp]),
     "p2t_sample_select": (i32, [vp, i32, i64, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, i32, f32, i32, f32, u64, i64, vp, i64, vp, vp]),
     "p2t_logits_process": (i32, [vp, i32, i64, i32, i32, vp, i64, vp, i32, vp, i64, f32, i32, i32, vp, i32, vp, vp, i32, i32, vp]),
@@ -173,6 +180,10 @@ SIGNATURES = {
     "p2t_preshuffle_w": (i32, [vp, i64, i64, i64, vp, vp]),
     "p2t_preshuffle_w_fp8": (i32, [vp, i64, i64, i64, vp, vp]),
     "p2t_gemm_nt_skinny_fp8": (i32, [vp, i64, vp, vp, i64, vp, i32, vp, i64, i64, i64, i64, i32, i32, vp]),
+    "p2t_quant_rows_mxfp4": (i32, [vp, i32, i64, i64, i64, vp, i64, vp, vp]),
+    "p2t_dequant_rows_mxfp4": (i32, [vp, i64, vp, i64, i64, vp, i64, vp]),
+    "p2t_preshuffle_w_mxfp4": (i32, [vp, i64, vp, i64, i64, vp, vp]),
+    "p2t_gemm_nt_skinny_mxfp4": (i32, [vp, i64, vp, vp, i64, vp, i32, vp, i64, i64, i64, i64, i32, i32, vp]),
     "p2t_kv_reorder": (i32, [C.POINTER(LlamaConfigC), C.POINTER(KvCacheC), vp, vp, vp, vp]),
     "p2t_llama_tape_bytes": (sz, [C.POINTER(LlamaConfigC), i32, i32]),
     "p2t_llama_train_workspace_bytes": (sz, [C.POINTER(LlamaConfigC), i32, i32]),

@@ -163,6 +163,31 @@ def preshuffle(w: torch.Tensor, n: int) -> torch.Tensor:
     return out
 
 
+def preshuffle_mxfp4(codes: torch.Tensor, scales: torch.Tensor, n: int) -> torch.Tensor:
+    """MXFP4 codes [>= n, K / 2] + block scales [>= n, K / 32] -> the interleaved stream copy of the decode GEMM (p2t_preshuffle_w_mxfp4):
+    per 16-row tile and 128-column step the 1 KB of codes one MFMA consumes, then its 64 scale bytes."""
+    K = codes.shape[1] * 2
+    out = torch.empty((round_up(n, 16) // 16 * (K // 128) * 1088,), dtype=torch.uint8, device=codes.device)
+    call("p2t_preshuffle_w_mxfp4", ptr(codes), codes.stride(0), ptr(scales), n, K, ptr(out), stream())
+    return out
+
+
+def mxfp4_layers(e, stream_order: bool):
+    """(host array of p2t_llama_layer_mxfp4, tensors to keep alive) from the engine's MXFP4 codes / block scales: row-major, or their
+    stream copies."""
+    layers, keep = (_lib.LlamaLayerMxfp4C * len(e["mx"]))(), []
+    for i, t in enumerate(e["mx"]):
+        for name in ("qkv", "o", "gu", "down"):
+            codes, bs = t[name + "_w"], t[name + "_bs"]
+            if stream_order:
+                codes = preshuffle_mxfp4(codes, bs, codes.shape[0])
+            keep.append(codes)
+            setattr(layers[i], name + "_w", codes.data_ptr())
+            setattr(layers[i], name + "_bs", None if stream_order else bs.data_ptr())
+        layers[i].stream_order = int(stream_order)
+    return layers, keep
+
+
 def stream_weights(decoder):
     """Second copies of every decoder projection + the LM head in the stream order, built once per model (dropped with the engine
     when weights are loaded): Llama-3.1-8B: 15 GB next to the 15 GB the prefill reads -- HBM is sized for it."""
@@ -170,19 +195,23 @@ def stream_weights(decoder):
     e = m.ensure_engine(s.num_hidden_layers)
     lm = decoder._lm_head_padded()
     # (the engine object is rebuilt when weights are loaded; _version catches an in-place update of the LM head that kept the engine)
-    key = (id(e), lm.data_ptr(), lm._version, decoder.model.embed_tokens.weight._version, bool(m.gemm_fp8))
+    fmt = "mxfp4" if m.gemm_mxfp4 else ("fp8" if m.gemm_fp8 else "model")
+    key = (id(e), lm.data_ptr(), lm._version, decoder.model.embed_tokens.weight._version, fmt)
     st = getattr(m, "_stream_engine", None)
     if st is not None and st["key"] == key:
         return st
     d, nh, nkv = s.head_dim, s.num_attention_heads, s.num_key_value_heads
     rows = dict(qkv_w=(nh + 2 * nkv) * d, o_w=s.hidden_size, gu_w=2 * s.intermediate_size, down_w=s.hidden_size)
-    layers, keep = (_lib.LlamaLayerStreamC * s.num_hidden_layers)(), []
-    for i in range(s.num_hidden_layers):
-        t = e["keep"][i]
-        for name, n in rows.items():
-            w = preshuffle(t[name], n)
-            keep.append(w)
-            setattr(layers[i], name, w.data_ptr())
+    if m.gemm_mxfp4:       # the stream copies serve the decode step alone (<= 64 rows), and that step reads the 4-bit form: no e4m3 copies
+        layers, keep = mxfp4_layers(e, True)
+    else:
+        layers, keep = (_lib.LlamaLayerStreamC * s.num_hidden_layers)(), []
+        for i in range(s.num_hidden_layers):
+            t = e["keep"][i]
+            for name, n in rows.items():
+                w = preshuffle(t[name], n)
+                keep.append(w)
+                setattr(layers[i], name, w.data_ptr())
     st = dict(key=key, layers=layers, keep=keep, lm_head=preshuffle(lm, s.vocab_size))
     m._stream_engine = st
     return st
@@ -222,6 +251,11 @@ class DecodeEngine:
         # the stream-order copies are read by the skinny GEMMs only (<= 64 rows): beyond that every projection and the LM head
         # run on the row-major weights (the LM head had no row-major fallback and returned wrong logits)
         self.stream = stream_weights(decoder) if (stream_copy and self.dtype == torch.bfloat16 and B0 * group <= 64) else None
+        # "mxfp4" decoders: up to 64 rows step on the 4-bit weights (their stream copies, or row-major under stream_copy=False);
+        # beyond that the e4m3 copies of the same values serve, as in "fp8" mode
+        self.mx = None                                                    # (host array of p2t_llama_layer_mxfp4, what it points to)
+        if m.gemm_mxfp4 and B0 * group <= 64:
+            self.mx = (self.stream["layers"], self.stream["keep"]) if self.stream else mxfp4_layers(self.e, False)
         self._cache_struct()
         self.processors = processors                                      # _processor_args' settings, or None: nothing allocated, nothing launched
         if processors is not None:
@@ -272,8 +306,13 @@ class DecodeEngine:
     def decode_step(self):
         """One token per row from self.x -> self.logits; the device step counter advances."""
         st = self.stream
-        layers = C.cast(st["layers"], C.POINTER(_lib.LlamaLayerStreamC)) if st else None
         head = st["lm_head"] if st else self.lm_head
+        if self.mx is not None:
+            call("p2t_llama_decode_step_mxfp4", C.byref(self.e["cfg"]), C.byref(self.e["w"]), C.cast(self.mx[0], C.POINTER(_lib.LlamaLayerMxfp4C)), ptr(head),
+                 self.lm_head.stride(0), int(st is not None), C.byref(self.cache), ptr(self.x), ptr(self.logits), self.ld_logits, self.flags, ptr(self.ws),
+                 self.ws.numel(), stream())
+            return
+        layers = C.cast(st["layers"], C.POINTER(_lib.LlamaLayerStreamC)) if st else None
         call("p2t_llama_decode_step", C.byref(self.e["cfg"]), C.byref(self.e["w"]), layers, ptr(head), self.lm_head.stride(0), int(st is not None),
              C.byref(self.cache), ptr(self.x), ptr(self.logits), self.ld_logits, self.flags, ptr(self.ws), self.ws.numel(), stream())
 

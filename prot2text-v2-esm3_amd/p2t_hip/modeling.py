@@ -423,6 +423,7 @@ class LlamaTextModel(nn.Module):
         self.spec = spec
         self._engine, self._ws = None, _Workspace()
         self.gemm_fp8 = False
+        self.gemm_mxfp4 = False          # with gemm_fp8: the e4m3 weights hold the MXFP4 values W~, the decode step streams their 4-bit form
         self.register_load_state_dict_post_hook(lambda module, _incompatible: module.invalidate_engine())
 
     @property
@@ -440,7 +441,9 @@ class LlamaTextModel(nn.Module):
         if F % 32:
             raise ValueError("Llama intermediate_size must be a multiple of 32")
         Hp, Fp, QO = round_up(H, 64), round_up(F, 64), round_up(s.num_attention_heads * d, 64)
-        keep, layers = [], (_lib.LlamaLayerC * max(n_layers, 1))()
+        keep, layers, mx = [], (_lib.LlamaLayerC * max(n_layers, 1))(), {}
+        if self.gemm_mxfp4 and not (self.gemm_fp8 and dt == torch.bfloat16):
+            raise ValueError("MXFP4 decoder weights ride on the fp8 GEMM path of a bf16 model")
         P = dict(self.named_parameters())
         for i in range(n_layers):
             p = f"layers.{i}."
@@ -456,6 +459,10 @@ class LlamaTextModel(nn.Module):
                 t["q_norm_w"], t["k_norm_w"] = _f32(P[p + "self_attn.q_norm.weight"]), _f32(P[p + "self_attn.k_norm.weight"])
             if self.gemm_fp8:
                 for name, kdim in (("qkv", H), ("o", s.num_attention_heads * d), ("gu", H), ("down", F)):
+                    if self.gemm_mxfp4:      # W -> W~ (e2m1 codes x clamped block scales): e4m3-exact under one row scale, so the fp8 kernels lose nothing
+                        codes, bs = ops.quant_rows_mxfp4(t[name + "_w"].contiguous(), kdim)
+                        mx.setdefault(i, {}).update({name + "_w": codes, name + "_bs": bs})
+                        t[name + "_w"] = ops.dequant_rows_mxfp4(codes, bs, kdim, t[name + "_w"].shape[1])
                     t[name + "_w"], t[name + "_ws"] = _quant_fp8(t[name + "_w"], kdim)
             keep.append(t)
             for k, v in t.items():
@@ -474,7 +481,7 @@ class LlamaTextModel(nn.Module):
                                 gemm_fp8=int(self.gemm_fp8))
         if self.gemm_fp8 and dt != torch.bfloat16:
             raise ValueError("fp8 GEMMs need a bf16 model (activations and attention stay bf16)")
-        self._engine = dict(cfg=cfg, w=w, layers=layers, keep=keep, n=n_layers)
+        self._engine = dict(cfg=cfg, w=w, layers=layers, keep=keep, n=n_layers, mx=[mx[i] for i in range(len(mx))])
         return self._engine
 
     def _inv_freq(self) -> torch.Tensor:
@@ -974,15 +981,21 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
         """"fp8": the eight projections of both frozen towers run on the fp8 MFMA kernel -- weights quantised once to e4m3
         with one power-of-two (E8M0) scale per output channel, activations per token on the fly (BASELINE.json configs[4];
         DESIGN.md section 9).  "model": GEMMs in the model dtype.  The HF-named parameters stay the masters either way
-        (checkpoints are unaffected); the adapter, the only trained block, always stays in the model dtype."""
-        if gemm_dtype not in ("model", "fp8"):
-            raise ValueError("gemm_dtype must be 'model' or 'fp8'")
-        on = gemm_dtype == "fp8"
+        (checkpoints are unaffected); the adapter, the only trained block, always stays in the model dtype.
+        "mxfp4": the encoder as under "fp8"; every decoder projection W is first rounded to its MXFP4 value W~ (e2m1 codes, one
+        power-of-two scale per 32 inputs, include/p2t_hip.h), which its e4m3 copy then holds exactly -- prefill, cache-less forward and
+        decode beyond 64 rows run the fp8 kernels on W~, and the decode step of `generate` streams the 4.25-bit form of the same W~."""
+        if gemm_dtype not in ("model", "fp8", "mxfp4"):
+            raise ValueError("gemm_dtype must be 'model', 'fp8' or 'mxfp4'")
+        on, mx = gemm_dtype in ("fp8", "mxfp4"), gemm_dtype == "mxfp4"
         if on and self.esm_encoder.dtype != torch.bfloat16:
             raise ValueError("fp8 GEMMs need a bf16 model")
         for tower in (self.esm_encoder, self.llama_decoder.model):
-            if tower.gemm_fp8 != on:
+            tower_mx = mx and tower is self.llama_decoder.model
+            if tower.gemm_fp8 != on or getattr(tower, "gemm_mxfp4", False) != tower_mx:
                 tower.gemm_fp8 = on
+                if tower is self.llama_decoder.model:
+                    tower.gemm_mxfp4 = tower_mx
                 tower.invalidate_engine()
         return self
 

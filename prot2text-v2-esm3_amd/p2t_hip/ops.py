@@ -147,6 +147,28 @@ def quant_rows_fp8(x: torch.Tensor, cols: int | None = None, ld_q: int | None = 
     return q, sc
 
 
+def quant_rows_mxfp4(x: torch.Tensor, cols: int | None = None):
+    """Row-wise MXFP4 quantisation (include/p2t_hip.h, "MXFP4 decoder weights") -> (e2m1 codes uint8 [rows, Kq / 2], two per byte,
+    E8M0 block scales uint8 [rows, Kq / 32]); Kq = cols rounded up to 128."""
+    _chk(x.dim() == 2 and x.stride(1) == 1 and x.dtype in (torch.bfloat16, torch.float32), "quant_rows_mxfp4: 2-D row-major bf16 / f32 input")
+    rows = x.shape[0]
+    cols = x.shape[1] if cols is None else cols
+    kq = round_up(cols, 128)
+    codes = torch.empty((rows, kq // 2), dtype=torch.uint8, device=x.device)
+    sc = torch.empty((rows, kq // 32), dtype=torch.uint8, device=x.device)
+    call("p2t_quant_rows_mxfp4", ptr(x), dt_of(x), x.stride(0), rows, cols, ptr(codes), codes.stride(0), ptr(sc), stream())
+    return codes, sc
+
+
+def dequant_rows_mxfp4(codes: torch.Tensor, scales: torch.Tensor, cols: int, ld: int | None = None) -> torch.Tensor:
+    """codes / scales of quant_rows_mxfp4 -> the values they stand for, bf16 [rows, ld] (exact; columns cols .. ld - 1 zero)."""
+    _chk(codes.dtype == torch.uint8 and scales.dtype == torch.uint8 and codes.dim() == 2 and scales.is_contiguous(), "dequant_rows_mxfp4: uint8 operands")
+    _chk(scales.shape == (codes.shape[0], round_up(cols, 128) // 32), "dequant_rows_mxfp4: one scale byte per 32 columns of K rounded up to 128")
+    out = torch.zeros((codes.shape[0], cols if ld is None else ld), dtype=torch.bfloat16, device=codes.device)
+    call("p2t_dequant_rows_mxfp4", ptr(codes), codes.stride(0), ptr(scales), codes.shape[0], cols, ptr(out), out.stride(0), stream())
+    return out
+
+
 def norm_fp8(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None, eps: float, ld_q: int | None = None,
              bound: tuple[float, float] | None = None):
     """LayerNorm (b given) or RMSNorm (b None) of the f32 stream, written as e4m3 + E8M0 row scales.  bound = (w_norm_max,

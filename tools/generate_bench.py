@@ -4,6 +4,8 @@ HBM roofline of the step: every decoder weight is read once per step (bf16: 2 by
 head)) plus the keys / values of the cache -- the algorithmic bytes of a step; frac = (bytes / step time) / 8 TB/s.
 python tools/generate_bench.py [B] [N] [beams] [fp8] > gpurun_out/generate_bench.log      (fp8: set_gemm_dtype("fp8"): e4m3 decoder weights,
 half the projection bytes of a step; the LM head stays bf16)
+python tools/generate_bench.py [B] [N] [beams] mxfp4: the same with set_gemm_dtype("mxfp4"): MXFP4 decoder weights, 4.25 bits per projection
+weight in the decode step
 python tools/generate_bench.py [B] [N] sample: the three ways of choosing a token in one process, top_k=50, top_p=0.9, temperature=0.7: ms per
 decode step of greedy decoding, of sampling with torch ops on the logits (`generator=`: no graph) and of the device sampler (`seed=`: graph
 replay), and p2t_sample_select's own time on [B, vocab] bf16 logits (HIP events around 200 launches).
@@ -282,7 +284,8 @@ def main():
     sample = len(sys.argv) > 3 and sys.argv[3] == "sample"
     process = len(sys.argv) > 3 and sys.argv[3] == "process"
     beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample and not process else 1
-    fp8 = len(sys.argv) > 4 and sys.argv[4] == "fp8"
+    gemm_dtype = sys.argv[4] if len(sys.argv) > 4 and sys.argv[4] in ("fp8", "mxfp4") else "model"
+    fp8 = gemm_dtype != "model"
     beam_sample = beams > 1 and len(sys.argv) > 4 and sys.argv[4] == "sample"
     beam_process = beams > 1 and len(sys.argv) > 4 and sys.argv[4] == "process"
     esm_name, llama_name, _, _, Tp, _ = specs.CONFIGS["cfg3"]
@@ -291,7 +294,7 @@ def main():
     model = P.Esm2LlamaInstructForCausalLM.from_specs(esm, llama, ad, dtype=torch.bfloat16, device=dev, seed=0)
     model.eval()
     if fp8:
-        model.set_gemm_dtype("fp8")
+        model.set_gemm_dtype(gemm_dtype)
     n_prompt = 64
     T = Tp + n_prompt
     rs = np.random.RandomState(0)
@@ -326,12 +329,13 @@ def main():
         res[graph] = (time.perf_counter() - t0 - t_prompt) / (N - 1)
     H, F, L, V = llama.hidden_size, llama.intermediate_size, llama.num_hidden_layers, llama.vocab_size
     nh, nkv, d = llama.num_attention_heads, llama.num_key_value_heads, llama.head_dim
-    w_bytes = (1 if fp8 else 2) * L * ((nh + 2 * nkv) * d * H + nh * d * H + 3 * H * F) + 2 * V * H
+    per_weight = {"model": 2.0, "fp8": 1.0, "mxfp4": 17.0 / 32.0}[gemm_dtype]       # mxfp4: 4 bits + one scale byte per 32 weights
+    w_bytes = per_weight * L * ((nh + 2 * nkv) * d * H + nh * d * H + 3 * H * F) + 2 * V * H
     BB = B * beams
     kv_bytes = 2 * 2 * L * nkv * d * (B * T + BB * N / 2)       # keys + values, bf16, at the mean generated length
     step_bytes = w_bytes + kv_bytes
     for graph, dt in res.items():
-        print(f"generate cfg3{' fp8 GEMMs' if fp8 else ''}: B={B} beams={beams} prompt {T} tokens, {N} new tokens, {'HIP graph' if graph else 'eager launches'}: "
+        print(f"generate cfg3{' ' + gemm_dtype + ' GEMMs' if fp8 else ''}: B={B} beams={beams} prompt {T} tokens, {N} new tokens, {'HIP graph' if graph else 'eager launches'}: "
               f"{dt * 1e3:.3f} ms/step = {BB / dt:.0f} tokens/s ({1 / dt:.1f} steps/s); step bytes {step_bytes / 1e9:.2f} GB (weights {w_bytes / 1e9:.2f}, "
               f"cache {kv_bytes / 1e9:.2f}) -> {step_bytes / dt / 1e12:.2f} TB/s = {step_bytes / dt / 8e12:.3f} of 8 TB/s", flush=True)
     print(f"prompt phase (ESM2-3B + adapter + scatter + compaction + prefill of {B} x {T} tokens + first token): {t_prompt * 1e3:.1f} ms; "

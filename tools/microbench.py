@@ -238,6 +238,35 @@ def bench_skinny():
                 res.append(f"{'stream copy' if pre else 'row-major W'} {ms * 1e3:7.1f} us {N * K * 2 / ms / 1e6:6.0f} GB/s")
             print(f"skinny M={M:2d} {name:8s} N={N:6d} K={K:5d}: " + " | ".join(res), flush=True)
             del ws
+            if name == "lm head":       # stays bf16 in every mode
+                continue
+            # the same projection on quantised weights: e4m3 + row scales (p2t_gemm_nt_skinny_fp8) and MXFP4 codes + block scales
+            # (p2t_gemm_nt_skinny_mxfp4, 4.25 bits per weight), cold weights from a ring of copies as above
+            from p2t_hip.generation import preshuffle_mxfp4
+            w0 = rand((N, K), scale=0.02)
+            a8, sa = ops.quant_rows_fp8(x)
+            w8, sw = ops.quant_rows_fp8(w0)
+            codes, bs = ops.quant_rows_mxfp4(w0)
+            del w0
+            for fmt, wbytes in (("fp8", N * K), ("mxfp4", N * K * 17 // 32)):
+                copies = max(2, min(40, int(1.3e9 // wbytes) + 1))
+                res = []
+                for pre in (0, 1):
+                    if fmt == "fp8":
+                        ring = [(preshuffle(w8, N) if pre else w8.clone(), sw) for _ in range(copies)]
+                    else:
+                        ring = [(preshuffle_mxfp4(codes, bs, N), None) if pre else (codes.clone(), bs.clone()) for _ in range(copies)]
+                    i = [0]
+
+                    def run():
+                        w, sc = ring[i[0] % copies]
+                        i[0] += 1
+                        _lib.call("p2t_gemm_nt_skinny_" + fmt, ptr(a8), K, ptr(sa), ptr(w), K if fmt == "fp8" else K // 2, ptr(sc) if sc is not None else None,
+                                  pre, ptr(out), ldc, M, N, K, odt, epi, stream())
+                    ms = timeit(run, iters=max(20, copies), warm=copies)
+                    res.append(f"{'stream copy' if pre else 'row-major W'} {ms * 1e3:7.1f} us {wbytes / ms / 1e6:6.0f} GB/s")
+                    del ring
+                print(f"skinny M={M:2d} {name:8s} N={N:6d} K={K:5d} {fmt:5s}: " + " | ".join(res), flush=True)
 
 
 def bench_fp8abl():
