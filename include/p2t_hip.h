@@ -590,6 +590,14 @@ typedef struct {
     int32_t* step;                      /* device i32 [1]: generated tokens already in the cache; a decode step appends at
                                            index step[0], attends to prompt_len + step[0] + 1 keys and increments it last */
     int32_t B0, group, Tp, G;
+    /* fp8 prompt segment (bf16 models; opt-in): both NULL = the layouts above.  Both set: k_prompt / vt_prompt hold e4m3 (OCP e4m3fn)
+     * BYTES in the same index order -- K codes [n_layers][B0][kv_heads][Tp][dp], V codes [n_layers][B0][kv_heads][dp][Tp] -- and these are
+     * one E8M0 scale byte per key for K and one for V, [n_layers][B0][kv_heads][Tp] each.  The scale of a key is chosen over that
+     * key's dp features of one kv head by p2t_quant_rows_fp8's rule (the smallest 2^e with amax / 2^e <= 448; byte 127 for an all-zero
+     * key; bytes 1 .. 254) and the codes are e4m3_round(x / 2^e), round to nearest even: what p2t_quant_rows_fp8 gives on the same bf16
+     * row.  Keys are quantised after the rotation; columns head_dim .. dp are zero codes.  The generated segment stays `dtype`.
+     * One set without the other: P2T_ERR_ARG; set on a model that is not bf16: P2T_ERR_UNSUPPORTED. */
+    uint8_t* k_prompt_scale;  uint8_t* v_prompt_scale;
 } p2t_kv_cache;
 
 /* Stable partition of every row by its mask: out[b, r] = x[b, t_r] for the r-th token with mask != 0, rows >= lens[b] zero;
@@ -890,6 +898,22 @@ int p2t_llama_decode_step_mxfp4(const p2t_llama_config* cfg, const p2t_llama_wei
 int p2t_attention_decode(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
                          const int32_t* prompt_len, const int32_t* step, int B0, int group, int nh, int nkv, int head_dim, int Tp,
                          int G, float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out, p2t_stream stream);
+/* p2t_attention_decode over an fp8 prompt segment (p2t_kv_cache with the two scale arrays set; ONE layer's buffers): k_prompt /
+ * vt_prompt are e4m3 bytes, k_prompt_scale / v_prompt_scale their E8M0 bytes per key [B0][kv_heads][Tp] (16-byte aligned, like the
+ * code buffers); the generated segment is bf16.  bf16 only (another dtype, or use_mfma = 0: P2T_ERR_UNSUPPORTED): the matrix-pipe
+ * kernel, whose prompt tiles widen the codes to bf16 exactly (e4m3 is a subset of bf16), multiply a key's f32 score by its K scale
+ * and its probability by its V scale after the row sum took the unscaled one -- powers of two, so the result is the bf16 kernel's
+ * arithmetic on the dequantised operands, with its rounding points.  Keys behind prompt_len are never read into a result. */
+int p2t_attention_decode_prompt_fp8(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
+                                    const int32_t* prompt_len, const int32_t* step, int B0, int group, int nh, int nkv, int head_dim,
+                                    int Tp, int G, float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out,
+                                    const uint8_t* k_prompt_scale, const uint8_t* v_prompt_scale, p2t_stream stream);
+/* The prefill's store into an fp8 prompt segment, ONE layer: k, v bf16 [B][kv_heads][T][dp] (keys after the rotation) -> K codes
+ * [B][kv_heads][Tp][dp], V codes transposed [B][kv_heads][dp][Tp] and the two scale arrays [B][kv_heads][Tp] (p2t_kv_cache's format),
+ * in one launch: one block per (64-key tile, row x kv head), the maximum over a key's features reduced inside a lane group (no
+ * atomics), V transposed through LDS.  Positions < T only: every byte behind them keeps its value.  T <= Tp, Tp % 64 == 0. */
+int p2t_kv_quant_store(const void* k, const void* v, int B, int kv_heads, int T, int head_dim, int Tp, void* k_codes, void* vt_codes,
+                       uint8_t* k_scale, uint8_t* v_scale, p2t_stream stream);
 /* Beam re-ordering of the generated segment: row r of (k_dst, vt_dst) = row src_row[r] of the cache's generated segment, the
  * first step[0] tokens of every layer / head (k_dst, vt_dst: second buffers of the same shape; the caller swaps). */
 int p2t_kv_reorder(const p2t_llama_config* cfg, const p2t_kv_cache* cache, const int64_t* src_row, void* k_dst, void* vt_dst,

@@ -12,9 +12,12 @@
 //     beams per prompt: all beams of a prompt share its prompt segment, beam re-ordering touches the generated segment only);
 //   * every row generates in lock-step: ONE device counter `step` = generated tokens already in the cache.  A decode step reads it on
 //     the device (so the whole step replays as a HIP graph without a host round trip), appends at index `step`, attends to
-//     prompt_len[b0] + step + 1 keys and increments it last.
+//     prompt_len[b0] + step + 1 keys and increments it last;
+//   * opt-in for bf16 models (p2t_kv_cache's scale arrays set): the PROMPT segment as e4m3 codes in the same index order + one E8M0 scale
+//     byte per key for K and for V -- quantised by the prefill's store (kv_quant_store_kernel), read by the F8 tiles of the attention.
 #include "common.h"
 #include "kernels.h"
+#include "quant_fp8.h"
 
 namespace p2t {
 namespace {
@@ -78,6 +81,66 @@ __global__ void __launch_bounds__(256) v_transpose_store_kernel(const T* __restr
     for (int i = threadIdx.x; i < 64 * dp; i += 256) {
         const int c = i >> 6, tl = i & 63;
         if (t0 + tl < Tp) vt[((int64_t)bh * dp + c) * Tp + t0 + tl] = tile[tl][c];
+    }
+}
+
+// fp8 prompt segment (p2t_kv_cache with the scale arrays set): k, v bf16 [BH][seq][DP] -> K codes [BH][Tp][DP], V codes transposed
+// [BH][DP][Tp], one E8M0 byte per key each; quant_rows_kernel's arithmetic on every key row (amax -> e8m0_of_amax -> x * 2^-e ->
+// v_cvt_pk_fp8_f32), columns d .. DP zero.  grid (64-key tiles, BH); DP / 8 lanes share a key (8 features each) and reduce its
+// maximum among themselves; the V codes cross LDS for the transpose.  Positions < seq only.
+template <int DP>
+__global__ void __launch_bounds__(256) kv_quant_store_kernel(const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, uint8_t* __restrict__ kq,
+                                                             uint8_t* __restrict__ vtq, uint8_t* __restrict__ ks, uint8_t* __restrict__ vs, int seq,
+                                                             int d, int Tp) {
+    constexpr int LG = DP / 8, KPP = 256 / LG;                        // lanes per key, keys per pass
+    __shared__ __attribute__((aligned(16))) uint8_t tile[DP][68];     // V codes [feature][key of the tile]
+    const int bh = blockIdx.y, t0 = blockIdx.x * 64;
+    const int sub = threadIdx.x % LG, kl = threadIdx.x / LG;
+    auto quant8 = [&](const bf16_t* src, bool ok, int& E) {           // 8 features of one key -> their codes; E of the whole key
+        float x[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] = 0.f;
+        if (ok) load8(src, x);
+        float amax = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            x[e] = 8 * sub + e < d ? x[e] : 0.f;
+            amax = fmaxf(amax, fabsf(x[e]));
+        }
+#pragma unroll
+        for (int o = LG / 2; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+        E = e8m0_of_amax(amax);
+        const float inv = pow2_neg(E);
+        return make_uint2(pack_fp8x4(x[0] * inv, x[1] * inv, x[2] * inv, x[3] * inv), pack_fp8x4(x[4] * inv, x[5] * inv, x[6] * inv, x[7] * inv));
+    };
+#pragma unroll
+    for (int pass = 0; pass < 64 / KPP; ++pass) {
+        const int tl = pass * KPP + kl, t = t0 + tl;
+        const bool ok = t < seq;                                      // the same for the lanes of a key
+        const int64_t in = ((int64_t)bh * seq + t) * DP + 8 * sub, row = (int64_t)bh * Tp + t;
+        int E;
+        const uint2 kc = quant8(k + in, ok, E);
+        if (ok) {
+            *reinterpret_cast<uint2*>(kq + row * DP + 8 * sub) = kc;
+            if (sub == 0) ks[row] = (uint8_t)E;
+        }
+        const uint2 vc = quant8(v + in, ok, E);
+        if (ok && sub == 0) vs[row] = (uint8_t)E;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) tile[8 * sub + e][tl] = (uint8_t)((e < 4 ? vc.x : vc.y) >> (8 * (e & 3)));
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < DP * 16; i += 256) {
+        const int c = i >> 4, t = t0 + 4 * (i & 15);
+        const unsigned w = *reinterpret_cast<const unsigned*>(&tile[c][4 * (i & 15)]);
+        uint8_t* dst = vtq + ((int64_t)bh * DP + c) * Tp + t;
+        if (t + 4 <= seq) {
+            *reinterpret_cast<unsigned*>(dst) = w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (t + e < seq) dst[e] = (uint8_t)(w >> (8 * e));
+        }
     }
 }
 
@@ -295,43 +358,73 @@ __global__ void __launch_bounds__(512) attn_decode_kernel(const T* __restrict__ 
 //     probabilities a lane holds after two sub-tiles are 8 CONSECUTIVE keys: exactly the B operand of
 //   O[feature, head] += V^T . P: A = 16 features x 32 keys of the transposed value segment (a lane: 16 bytes = 8 consecutive keys of
 //     one feature), no exchange between lanes anywhere.
-template <int DP, int GH, int NW>
-__global__ void __launch_bounds__(NW * 64) attn_decode_mfma_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kp,
-                                                               const bf16_t* __restrict__ vtp, const bf16_t* __restrict__ kg,
-                                                               const bf16_t* __restrict__ vtg, const int32_t* __restrict__ prompt_len,
-                                                               const int32_t* __restrict__ step_ptr, int group, int nh, int nkv, int G, int Tp,
-                                                               int Gcap, float c_exp, bf16_t* __restrict__ out, int64_t ld_out, int d) {
-    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-    constexpr int PW = DP + 2, KK = DP / 32, DT = DP / 16;
-    __shared__ float red[NW][GH][PW];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
-    const int pair = blockIdx.x, bb = pair / nkv, kvh = pair - bb * nkv, b0 = bb / group;
-    const int hc = blockIdx.y;
-    const int h0 = kvh * G + hc * GH, nhead = min(GH, G - hc * GH);
-    const bf16x8 zero8 = {};
-    bf16x8 qf[KK];                                                  // B operand of S: head slot j, features 32 kk + 8 g ..
+//
+// F8 tiles (the fp8 prompt segment: e4m3 codes + one E8M0 byte per key for K and for V) feed the same two products: the codes are widened
+// to bf16 (exact) right in front of the MFMA that takes them, the K scale multiplies the key's f32 score and the V scale the key's
+// probability once the row sum has taken the unscaled one -- powers of two, so nothing rounds differently from the bf16 tile on the
+// dequantised operands.  A lane's loads stay 16 bytes of one row, which now hold 16 elements, so both contraction orders are permuted
+// (any order serves a sum as long as the two operands agree):
+//   S: lane g reads the features 64 (kk / 2) + 16 g + 8 (kk % 2) .. of its key for step kk (DP 32: 8 g ..) -- `qf` is then the query in
+//     that order (the kernel's qp);
+//   A rows: row 4 g + r of sub-tile t <-> key 16 g + 4 t + r, so a lane's sixteen scores are the keys 16 g .. 16 g + 15: one 16-byte
+//     load of each scale array, one 16-byte load per feature of the transposed codes, P in that key order.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ bf16x8 e4m3x8_to_bf16(unsigned lo, unsigned hi) {
+    const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, true);
+    const auto c = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, false), e = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, true);
+    return __builtin_bit_cast(bf16x8, u32x4{pack_bf16x2(a[0], a[1]), pack_bf16x2(b[0], b[1]), pack_bf16x2(c[0], c[1]), pack_bf16x2(e[0], e[1])});
+}
+__device__ __forceinline__ float e8m0_byte_to_f32(unsigned word, int byte) {       // 2^(E - 127) for E = 1 .. 254; E = 0 -> 0
+    return __uint_as_float(((word >> (8 * byte)) & 0xFFu) << 23);
+}
+
+// One 64-key tile `tt` of a segment of `cap` keys, `n` of them valid, into a wave's running (max, sum, output).
+template <int DP, bool F8>
+__device__ __forceinline__ void decode_tile(const void* __restrict__ k_seg, const void* __restrict__ v_seg, const uint8_t* __restrict__ ks_seg,
+                                            const uint8_t* __restrict__ vs_seg, int tt, int n, int cap, const bf16x8 (&qf)[DP / 32], float c_exp, int j,
+                                            int g, float& m_run, float& l_run, f32x4 (&acc)[DP / 16]) {
+    constexpr int KK = DP / 32, DT = DP / 16;
+    const bool full = tt * 64 + 64 <= n;
+    f32x4 sc[4];
+    // all fragments of the tile first (32 loads of 16 bytes in flight per lane for bf16), then the arithmetic
+    bf16x8 kf[F8 ? 1 : 4][F8 ? 1 : KK], vf[F8 ? 1 : 2][F8 ? 1 : DT];
+    unsigned kw[F8 ? 4 : 1][2 * KK];
+    u32x4 vw[F8 ? DT : 1], ksw = {}, vsw = {};
+    if constexpr (F8) {
+        const uint8_t* kb = (const uint8_t*)k_seg + (int64_t)(tt * 64 + 16 * (j >> 2) + (j & 3)) * DP;
+        const uint8_t* vb = (const uint8_t*)v_seg + (int64_t)tt * 64 + 16 * g;
 #pragma unroll
-    for (int kk = 0; kk < KK; ++kk)
-        qf[kk] = j < nhead ? *reinterpret_cast<const bf16x8*>(q + ((int64_t)bb * nh + h0 + j) * DP + 32 * kk + 8 * g) : zero8;
-    const int n0 = min(max(prompt_len[b0], 0), Tp), n1 = min(max(step_ptr[0], 0) + 1, Gcap);
-    const int tiles0 = (n0 + 63) >> 6, tiles = tiles0 + ((n1 + 63) >> 6);
-    const bf16_t* k_seg0 = kp + ((int64_t)b0 * nkv + kvh) * Tp * DP;
-    const bf16_t* k_seg1 = kg + ((int64_t)bb * nkv + kvh) * Gcap * DP;
-    const bf16_t* v_seg0 = vtp + ((int64_t)b0 * nkv + kvh) * DP * Tp;
-    const bf16_t* v_seg1 = vtg + ((int64_t)bb * nkv + kvh) * DP * Gcap;
-    // A rows of S: lane row i = j <-> key offset 8 (i / 4) + (i % 4) inside a 32-key half, + 4 for the odd sub-tile
-    const int krow = 8 * (j >> 2) + (j & 3);
-    float m_run = -INFINITY, l_run = 0.f;
-    f32x4 acc[DT];
+        for (int st = 0; st < 4; ++st) {
+            if constexpr (DP == 32) {
+                const uint2 t2 = *reinterpret_cast<const uint2*>(kb + 4 * st * DP + 8 * g);
+                kw[st][0] = t2.x; kw[st][1] = t2.y;
+            } else {
 #pragma unroll
-    for (int dt = 0; dt < DT; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int t = w; t < tiles; t += NW) {
-        const int sg = t >= tiles0, tt = sg ? t - tiles0 : t, n = sg ? n1 : n0, cap = sg ? Gcap : Tp;
-        const bool full = tt * 64 + 64 <= n;
-        const bf16_t* kb = (sg ? k_seg1 : k_seg0) + (int64_t)tt * 64 * DP + 8 * g;
-        const bf16_t* vb = (sg ? v_seg1 : v_seg0) + (int64_t)tt * 64 + 8 * g;
-        // all fragments of the tile first (32 loads of 16 bytes in flight per lane), then the arithmetic
-        bf16x8 kf[4][KK], vf[2][DT];
+                for (int h = 0; h < KK / 2; ++h) {
+                    const u32x4 t4 = *reinterpret_cast<const u32x4*>(kb + 4 * st * DP + 64 * h + 16 * g);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) kw[st][4 * h + i] = t4[i];
+                }
+            }
+        }
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) vw[dt] = *reinterpret_cast<const u32x4*>(vb + (int64_t)(16 * dt + j) * cap);
+        ksw = *reinterpret_cast<const u32x4*>(ks_seg + tt * 64 + 16 * g);
+        vsw = *reinterpret_cast<const u32x4*>(vs_seg + tt * 64 + 16 * g);
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+            sc[st] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk)
+                sc[st] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(e4m3x8_to_bf16(kw[st][2 * kk], kw[st][2 * kk + 1]), qf[kk], sc[st], 0, 0, 0);
+        }
+    } else {
+        // A rows of S: lane row i = j <-> key offset 8 (i / 4) + (i % 4) inside a 32-key half, + 4 for the odd sub-tile
+        const int krow = 8 * (j >> 2) + (j & 3);
+        const bf16_t* kb = (const bf16_t*)k_seg + (int64_t)tt * 64 * DP + 8 * g;
+        const bf16_t* vb = (const bf16_t*)v_seg + (int64_t)tt * 64 + 8 * g;
 #pragma unroll
         for (int st = 0; st < 4; ++st)
 #pragma unroll
@@ -341,59 +434,127 @@ __global__ void __launch_bounds__(NW * 64) attn_decode_mfma_kernel(const bf16_t*
         for (int hv = 0; hv < 2; ++hv)
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) vf[hv][dt] = *reinterpret_cast<const bf16x8*>(vb + (int64_t)(16 * dt + j) * cap + 32 * hv);
-        f32x4 sc[4];
 #pragma unroll
         for (int st = 0; st < 4; ++st) {
             sc[st] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kk = 0; kk < KK; ++kk) sc[st] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[st][kk], qf[kk], sc[st], 0, 0, 0);
         }
-        // lane (head j, g): sc[st][r] is the key 32 (st / 2) + 8 g + 4 (st % 2) + r of the tile
-        float mx = -INFINITY;
+    }
+    // lane (head j, g): sc[st][r] is the key 32 (st / 2) + 8 g + 4 (st % 2) + r of the tile (F8: 16 g + 4 st + r)
+    float mx = -INFINITY;
 #pragma unroll
-        for (int st = 0; st < 4; ++st)
+    for (int st = 0; st < 4; ++st)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const bool ok = full || tt * 64 + 32 * (st >> 1) + 8 * g + 4 * (st & 1) + r < n;
-                sc[st][r] = ok ? sc[st][r] * c_exp : -INFINITY;
-                mx = fmaxf(mx, sc[st][r]);
+        for (int r = 0; r < 4; ++r) {
+            const int key = F8 ? 16 * g + 4 * st + r : 32 * (st >> 1) + 8 * g + 4 * (st & 1) + r;
+            const bool ok = full || tt * 64 + key < n;
+            float s = sc[st][r];
+            if constexpr (F8) s *= e8m0_byte_to_f32(ksw[st], r);
+            sc[st][r] = ok ? s * c_exp : -INFINITY;                   // a select: what a key behind the prefix holds goes no further
+            mx = fmaxf(mx, sc[st][r]);
+        }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m_run, mx);                          // every tile holds at least one valid key
+    const float alpha = exp2f(m_run - m_new);
+    m_run = m_new;
+    if (F8 && !full) {                                             // code and scale bytes behind the valid prefix -> 0 (0 x garbage must stay 0)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int nv = n - (tt * 64 + 16 * g + 4 * i);         // valid keys among the word's four
+            const unsigned keep = nv >= 4 ? ~0u : (nv <= 0 ? 0u : (1u << (8 * nv)) - 1u);
+            vsw[i] &= keep;
+#pragma unroll
+            for (int dt = 0; dt < (F8 ? DT : 1); ++dt) vw[dt][i] &= keep;
+        }
+    }
+    float psum = 0.f;
+    bf16x8 pf[2];
+#pragma unroll
+    for (int hv = 0; hv < 2; ++hv) {
+        float p[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            p[e] = exp2f(sc[2 * hv + (e >> 2)][e & 3] - m_new);
+            psum += p[e];
+            if constexpr (F8) p[e] *= e8m0_byte_to_f32(vsw[2 * hv + (e >> 2)], e & 3);      // after the sum took the unscaled p
+        }
+        pf[hv] = __builtin_bit_cast(bf16x8, u32x4{pack_bf16x2(p[0], p[1]), pack_bf16x2(p[2], p[3]), pack_bf16x2(p[4], p[5]), pack_bf16x2(p[6], p[7])});
+    }
+    l_run = l_run * alpha + psum;
+    if (!F8 && !full) {                                            // keys behind the valid prefix: 0 x garbage must stay 0
+#pragma unroll
+        for (int hv = 0; hv < 2; ++hv)
+#pragma unroll
+            for (int dt = 0; dt < (F8 ? 1 : DT); ++dt) {
+                typedef short s16x8 __attribute__((ext_vector_type(8)));
+                s16x8 v = __builtin_bit_cast(s16x8, vf[hv][dt]);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = tt * 64 + 32 * hv + 8 * g + e < n ? v[e] : (short)0;
+                vf[hv][dt] = __builtin_bit_cast(bf16x8, v);
             }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);                          // every tile holds at least one valid key
-        const float alpha = exp2f(m_run - m_new);
-        m_run = m_new;
-        float psum = 0.f;
-        bf16x8 pf[2];
+    }
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+        acc[dt] *= alpha;
 #pragma unroll
         for (int hv = 0; hv < 2; ++hv) {
-            float p[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                p[e] = exp2f(sc[2 * hv + (e >> 2)][e & 3] - m_new);
-                psum += p[e];
-            }
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-            pf[hv] = __builtin_bit_cast(bf16x8, u32x4{pack_bf16x2(p[0], p[1]), pack_bf16x2(p[2], p[3]), pack_bf16x2(p[4], p[5]), pack_bf16x2(p[6], p[7])});
+            if constexpr (F8) acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(e4m3x8_to_bf16(vw[dt][2 * hv], vw[dt][2 * hv + 1]), pf[hv], acc[dt], 0, 0, 0);
+            else acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[hv][dt], pf[hv], acc[dt], 0, 0, 0);
         }
-        l_run = l_run * alpha + psum;
-        if (!full) {                                                  // keys behind the valid prefix: 0 x garbage must stay 0
+    }
+}
+
+// P8: the prompt segment is the fp8 form (kp / vtp: e4m3 bytes, kps / vps: their scale bytes [B0][kv heads][Tp]); the generated
+// segment's tiles are the bf16 ones either way.
+template <int DP, int GH, int NW, bool P8>
+__global__ void __launch_bounds__(NW * 64) attn_decode_mfma_kernel(const bf16_t* __restrict__ q, const void* __restrict__ kp,
+                                                               const void* __restrict__ vtp, const bf16_t* __restrict__ kg,
+                                                               const bf16_t* __restrict__ vtg, const uint8_t* __restrict__ kps,
+                                                               const uint8_t* __restrict__ vps, const int32_t* __restrict__ prompt_len,
+                                                               const int32_t* __restrict__ step_ptr, int group, int nh, int nkv, int G, int Tp,
+                                                               int Gcap, float c_exp, bf16_t* __restrict__ out, int64_t ld_out, int d) {
+    constexpr int PW = DP + 2, KK = DP / 32, DT = DP / 16, EP = P8 ? 1 : 2;       // EP: bytes per element of the prompt segment
+    __shared__ float red[NW][GH][PW];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
+    const int pair = blockIdx.x, bb = pair / nkv, kvh = pair - bb * nkv, b0 = bb / group;
+    const int hc = blockIdx.y;
+    const int h0 = kvh * G + hc * GH, nhead = min(GH, G - hc * GH);
+    const bf16x8 zero8 = {};
+    const bf16_t* qrow = q + ((int64_t)bb * nh + h0 + j) * DP;
+    auto load_q = [&](bf16x8 (&qf)[KK], bool f8_order) {            // B operand of S: head slot j, features 32 kk + 8 g .. (or the F8 tiles' order)
 #pragma unroll
-            for (int hv = 0; hv < 2; ++hv)
-#pragma unroll
-                for (int dt = 0; dt < DT; ++dt) {
-                    typedef short s16x8 __attribute__((ext_vector_type(8)));
-                    s16x8 v = __builtin_bit_cast(s16x8, vf[hv][dt]);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = tt * 64 + 32 * hv + 8 * g + e < n ? v[e] : (short)0;
-                    vf[hv][dt] = __builtin_bit_cast(bf16x8, v);
-                }
+        for (int kk = 0; kk < KK; ++kk) {
+            const int f = f8_order && DP > 32 ? 64 * (kk >> 1) + 16 * g + 8 * (kk & 1) : 32 * kk + 8 * g;
+            qf[kk] = j < nhead ? *reinterpret_cast<const bf16x8*>(qrow + f) : zero8;
         }
+    };
+    bf16x8 qf[KK];
+    load_q(qf, P8);
+    const int n0 = min(max(prompt_len[b0], 0), Tp), n1 = min(max(step_ptr[0], 0) + 1, Gcap);
+    const int tiles0 = (n0 + 63) >> 6, tiles = tiles0 + ((n1 + 63) >> 6);
+    const char* k_seg0 = (const char*)kp + ((int64_t)b0 * nkv + kvh) * Tp * DP * EP;
+    const bf16_t* k_seg1 = kg + ((int64_t)bb * nkv + kvh) * Gcap * DP;
+    const char* v_seg0 = (const char*)vtp + ((int64_t)b0 * nkv + kvh) * DP * Tp * EP;
+    const bf16_t* v_seg1 = vtg + ((int64_t)bb * nkv + kvh) * DP * Gcap;
+    const uint8_t* ks_seg0 = P8 ? kps + ((int64_t)b0 * nkv + kvh) * Tp : nullptr;
+    const uint8_t* vs_seg0 = P8 ? vps + ((int64_t)b0 * nkv + kvh) * Tp : nullptr;
+    float m_run = -INFINITY, l_run = 0.f;
+    f32x4 acc[DT];
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            acc[dt] *= alpha;
-#pragma unroll
-            for (int hv = 0; hv < 2; ++hv) acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[hv][dt], pf[hv], acc[dt], 0, 0, 0);
+    for (int dt = 0; dt < DT; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (P8) {
+        // a wave's tiles in the same order as below: its prompt tiles, then (q in the bf16 tiles' feature order) its generated ones
+        int t = w;
+        for (; t < tiles0; t += NW) decode_tile<DP, true>(k_seg0, v_seg0, ks_seg0, vs_seg0, t, n0, Tp, qf, c_exp, j, g, m_run, l_run, acc);
+        if (t < tiles) load_q(qf, false);
+        for (; t < tiles; t += NW) decode_tile<DP, false>(k_seg1, v_seg1, nullptr, nullptr, t - tiles0, n1, Gcap, qf, c_exp, j, g, m_run, l_run, acc);
+    } else {
+        for (int t = w; t < tiles; t += NW) {
+            const int sg = t >= tiles0, tt = sg ? t - tiles0 : t;
+            decode_tile<DP, false>(sg ? (const void*)k_seg1 : (const void*)k_seg0, sg ? (const void*)v_seg1 : (const void*)v_seg0, nullptr, nullptr, tt,
+                                   sg ? n1 : n0, sg ? Gcap : Tp, qf, c_exp, j, g, m_run, l_run, acc);
         }
     }
     l_run += __shfl_xor(l_run, 16, 64);
@@ -535,21 +696,33 @@ int launch_attn_decode_t(const DecodeBuffers& b, const p2t_kv_cache* kc, int lay
     const dim3 grid((unsigned)(BB * nkv), (unsigned)b.ZC);
     if constexpr (sizeof(T) == 2) {
         if (use_mfma) {                      // (0: the lane-per-key kernel below, the form every dtype can run)
-#define P2T_ADM(DPV, GHV)                                                                                                             \
-    attn_decode_mfma_kernel<DPV, GHV, (GHV <= 4 && DPV <= 64 ? 16 : 8)><<<grid, (GHV <= 4 && DPV <= 64 ? 16 : 8) * 64, 0, s>>>(                                  \
-        (const bf16_t*)b.qb, (const bf16_t*)kp, (const bf16_t*)vtp, (const bf16_t*)kg, (const bf16_t*)vtg, kc->prompt_len, kc->step, kc->group, nh, \
-        nkv, G, kc->Tp, kc->G, c_exp, (bf16_t*)b.ao, QO, d)
-#define P2T_ADM_G(DPV)                                                                                                                \
+            // the fp8 prompt segment (the cache carries scales): the same index order in bytes, one scale byte per key
+            const size_t per_s = (size_t)kc->B0 * nkv * kc->Tp;
+            const uint8_t* kp8 = (const uint8_t*)kc->k_prompt + per_p * layer;
+            const uint8_t* vtp8 = (const uint8_t*)kc->vt_prompt + per_p * layer;
+            const uint8_t* kps = kc->k_prompt_scale ? kc->k_prompt_scale + per_s * layer : nullptr;
+            const uint8_t* vps = kc->k_prompt_scale ? kc->v_prompt_scale + per_s * layer : nullptr;
+#define P2T_ADM(DPV, GHV, P8V)                                                                                                        \
+    attn_decode_mfma_kernel<DPV, GHV, (GHV <= 4 && DPV <= 64 ? 16 : 8), P8V><<<grid, (GHV <= 4 && DPV <= 64 ? 16 : 8) * 64, 0, s>>>(    \
+        (const bf16_t*)b.qb, P8V ? (const void*)kp8 : (const void*)kp, P8V ? (const void*)vtp8 : (const void*)vtp, (const bf16_t*)kg,  \
+        (const bf16_t*)vtg, kps, vps, kc->prompt_len, kc->step, kc->group, nh, nkv, G, kc->Tp, kc->G, c_exp, (bf16_t*)b.ao, QO, d)
+#define P2T_ADM_G(DPV, P8V)                                                                                                           \
     do {                                                                                                                              \
-        if (b.GH == 1) P2T_ADM(DPV, 1); else if (b.GH == 2) P2T_ADM(DPV, 2); else if (b.GH == 4) P2T_ADM(DPV, 4); else P2T_ADM(DPV, 8);  \
+        if (b.GH == 1) P2T_ADM(DPV, 1, P8V); else if (b.GH == 2) P2T_ADM(DPV, 2, P8V); else if (b.GH == 4) P2T_ADM(DPV, 4, P8V);       \
+        else P2T_ADM(DPV, 8, P8V);                                                                                                    \
     } while (0)
-            if (dp == 32) P2T_ADM_G(32); else if (dp == 64) P2T_ADM_G(64); else P2T_ADM_G(128);
+            if (kps) {
+                if (dp == 32) P2T_ADM_G(32, true); else if (dp == 64) P2T_ADM_G(64, true); else P2T_ADM_G(128, true);
+            } else {
+                if (dp == 32) P2T_ADM_G(32, false); else if (dp == 64) P2T_ADM_G(64, false); else P2T_ADM_G(128, false);
+            }
 #undef P2T_ADM_G
 #undef P2T_ADM
             P2T_LAUNCH_CHECK();
             return P2T_OK;
         }
     }
+    P2T_REQUIRE(!kc->k_prompt_scale, "attention over an fp8 prompt segment: the matrix-pipe kernel only");
 #define P2T_AD(DPV, GHV)                                                                                                              \
     attn_decode_kernel<T, DPV, GHV><<<grid, 512, 0, s>>>((const T*)b.qb, kp, vtp, kg, vtg, kc->prompt_len, kc->step, kc->group, nh, nkv, G, \
                                                          kc->Tp, kc->G, c_exp, round_p, (T*)b.ao, QO, d)
@@ -569,6 +742,23 @@ int check_cache(const p2t_llama_config* c, const p2t_kv_cache* kc, const char* w
     P2T_REQUIRE(kc->B0 > 0 && kc->group > 0 && kc->Tp > 0 && kc->G > 0 && kc->Tp % 64 == 0 && kc->G % 64 == 0,
                 "%s: cache capacities must be positive multiples of 64 (Tp %d, G %d)", who, kc->Tp, kc->G);
     P2T_REQUIRE(c->heads % c->kv_heads == 0 && c->head_dim % 2 == 0 && c->head_dim <= 128, "%s: unsupported head shape", who);
+    P2T_REQUIRE(!kc->k_prompt_scale == !kc->v_prompt_scale, "%s: k_prompt_scale and v_prompt_scale go together (the fp8 prompt segment)", who);
+    if (kc->k_prompt_scale && c->dtype != P2T_BF16) {
+        set_error("%s: the fp8 prompt segment serves bf16 models only", who);
+        return P2T_ERR_UNSUPPORTED;
+    }
+    P2T_REQUIRE(!kc->k_prompt_scale || (((uintptr_t)kc->k_prompt | (uintptr_t)kc->vt_prompt | (uintptr_t)kc->k_prompt_scale | (uintptr_t)kc->v_prompt_scale) & 15) == 0,
+                "%s: the fp8 prompt segment's buffers must be 16-byte aligned", who);
+    return P2T_OK;
+}
+
+int launch_kv_quant_store(const void* k, const void* v, int BH, int T, int d, int Tp, uint8_t* kq, uint8_t* vtq, uint8_t* ks, uint8_t* vs, hipStream_t s) {
+    const int dp = head_dim_padded(d);
+    const dim3 grid((unsigned)ceil_div(T, 64), (unsigned)BH);
+#define P2T_KVQ(DPV) kv_quant_store_kernel<DPV><<<grid, 256, 0, s>>>((const bf16_t*)k, (const bf16_t*)v, kq, vtq, ks, vs, T, d, Tp)
+    if (dp == 32) P2T_KVQ(32); else if (dp == 64) P2T_KVQ(64); else P2T_KVQ(128);
+#undef P2T_KVQ
+    P2T_LAUNCH_CHECK();
     return P2T_OK;
 }
 
@@ -578,6 +768,11 @@ int check_cache(const p2t_llama_config* c, const p2t_kv_cache* kc, const char* w
 int llama_kv_store(const p2t_llama_config* c, const p2t_kv_cache* kc, int layer, const void* k, const void* v, int B, int T, hipStream_t s) {
     const int dp = head_dim_padded(c->head_dim), nkv = c->kv_heads;
     const size_t e = dtype_size(c->dtype), per = (size_t)kc->B0 * nkv * kc->Tp * dp;
+    if (kc->k_prompt_scale) {                 // fp8 prompt segment: codes + scales of both in one launch (check_cache: a bf16 model)
+        const size_t per_s = (size_t)kc->B0 * nkv * kc->Tp;
+        return launch_kv_quant_store(k, v, B * nkv, T, c->head_dim, kc->Tp, (uint8_t*)kc->k_prompt + per * layer, (uint8_t*)kc->vt_prompt + per * layer,
+                                     kc->k_prompt_scale + per_s * layer, kc->v_prompt_scale + per_s * layer, s);
+    }
     char* kd = (char*)kc->k_prompt + per * layer * e;
     P2T_CHECK_HIP(hipMemcpy2DAsync(kd, (size_t)kc->Tp * dp * e, k, (size_t)T * dp * e, (size_t)T * dp * e, (size_t)B * nkv, hipMemcpyDeviceToDevice, s));
     const dim3 grid((unsigned)ceil_div(T, 64), (unsigned)(B * nkv));
@@ -845,16 +1040,21 @@ extern "C" int p2t_kv_reorder(const p2t_llama_config* c, const p2t_kv_cache* cac
     return P2T_OK;
 }
 
-extern "C" int p2t_attention_decode(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
-                                    const int32_t* prompt_len, const int32_t* step, int B0, int group, int nh, int nkv, int head_dim, int Tp, int G,
-                                    float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out, p2t_stream stream) {
+static int attention_decode_impl(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
+                                 const int32_t* prompt_len, const int32_t* step, int B0, int group, int nh, int nkv, int head_dim, int Tp, int G,
+                                 float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out, const uint8_t* k_prompt_scale,
+                                 const uint8_t* v_prompt_scale, p2t_stream stream) {
     P2T_REQUIRE(q && out && (dtype == P2T_F32 || dtype == P2T_BF16) && nkv > 0 && nh % nkv == 0 && ld_out >= (int64_t)nh * head_dim,
                 "p2t_attention_decode: bad arguments");
     p2t_llama_config c{};
     c.heads = nh; c.kv_heads = nkv; c.head_dim = head_dim; c.dtype = dtype;
     p2t_kv_cache kc{const_cast<void*>(k_prompt), const_cast<void*>(vt_prompt), const_cast<void*>(k_gen), const_cast<void*>(vt_gen), prompt_len,
-                    const_cast<int32_t*>(step), B0, group, Tp, G};
+                    const_cast<int32_t*>(step), B0, group, Tp, G, const_cast<uint8_t*>(k_prompt_scale), const_cast<uint8_t*>(v_prompt_scale)};
     P2T_TRY(check_cache(&c, &kc, "p2t_attention_decode"));
+    if (k_prompt_scale && use_mfma == 0) {
+        set_error("p2t_attention_decode_prompt_fp8: the matrix-pipe kernel only (use_mfma = 0: the lane-per-key kernel reads no fp8 segment)");
+        return P2T_ERR_UNSUPPORTED;
+    }
     const int BB = B0 * group, dp = head_dim_padded(head_dim);
     DecodeBuffers b{};
     attn_decode_plan(nh, nkv, &b.ZC, &b.GH);
@@ -865,4 +1065,30 @@ extern "C" int p2t_attention_decode(const void* q, const void* k_prompt, const v
     if (dtype == P2T_BF16) return launch_attn_decode_t<bf16_t>(b, &kc, 0, BB, nh, nkv, head_dim, dp, c_exp, 1, ld_out, s, use_mfma != 0);
     P2T_REQUIRE(use_mfma <= 0, "p2t_attention_decode: the matrix-pipe kernel is bf16 only");
     return launch_attn_decode_t<float>(b, &kc, 0, BB, nh, nkv, head_dim, dp, c_exp, 0, ld_out, s);
+}
+
+extern "C" int p2t_attention_decode(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
+                                    const int32_t* prompt_len, const int32_t* step, int B0, int group, int nh, int nkv, int head_dim, int Tp, int G,
+                                    float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out, p2t_stream stream) {
+    return attention_decode_impl(q, k_prompt, vt_prompt, k_gen, vt_gen, prompt_len, step, B0, group, nh, nkv, head_dim, Tp, G, scale, log2_scores, dtype,
+                                 use_mfma, out, ld_out, nullptr, nullptr, stream);
+}
+
+extern "C" int p2t_attention_decode_prompt_fp8(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
+                                               const int32_t* prompt_len, const int32_t* step, int B0, int group, int nh, int nkv, int head_dim, int Tp,
+                                               int G, float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out,
+                                               const uint8_t* k_prompt_scale, const uint8_t* v_prompt_scale, p2t_stream stream) {
+    P2T_REQUIRE(!k_prompt_scale == !v_prompt_scale, "p2t_attention_decode_prompt_fp8: k_prompt_scale and v_prompt_scale go together");
+    P2T_REQUIRE(k_prompt_scale, "p2t_attention_decode_prompt_fp8: null scale arrays (p2t_attention_decode serves the bf16 prompt segment)");
+    return attention_decode_impl(q, k_prompt, vt_prompt, k_gen, vt_gen, prompt_len, step, B0, group, nh, nkv, head_dim, Tp, G, scale, log2_scores, dtype,
+                                 use_mfma, out, ld_out, k_prompt_scale, v_prompt_scale, stream);
+}
+
+extern "C" int p2t_kv_quant_store(const void* k, const void* v, int B, int kv_heads, int T, int head_dim, int Tp, void* k_codes, void* vt_codes,
+                                  uint8_t* k_scale, uint8_t* v_scale, p2t_stream stream) {
+    P2T_REQUIRE(k && v && k_codes && vt_codes && k_scale && v_scale && B > 0 && kv_heads > 0 && T > 0, "p2t_kv_quant_store: null/empty argument");
+    P2T_REQUIRE(head_dim > 0 && head_dim % 2 == 0 && head_dim <= 128 && Tp % 64 == 0 && T <= Tp,
+                "p2t_kv_quant_store: head_dim %d must be even and <= 128, Tp %d a multiple of 64 that holds T %d", head_dim, Tp, T);
+    P2T_REQUIRE((((uintptr_t)k | (uintptr_t)v | (uintptr_t)k_codes | (uintptr_t)vt_codes) & 15) == 0, "p2t_kv_quant_store: buffers must be 16-byte aligned");
+    return launch_kv_quant_store(k, v, B * kv_heads, T, head_dim, Tp, (uint8_t*)k_codes, (uint8_t*)vt_codes, k_scale, v_scale, (hipStream_t)stream);
 }

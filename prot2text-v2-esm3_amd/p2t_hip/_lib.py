@@ -84,7 +84,8 @@ class AdapterSavedC(C.Structure):
 
 class KvCacheC(C.Structure):
     _fields_ = [("k_prompt", vp), ("vt_prompt", vp), ("k_gen", vp), ("vt_gen", vp), ("prompt_len", vp), ("step", vp),
-                ("B0", C.c_int32), ("group", C.c_int32), ("Tp", C.c_int32), ("G", C.c_int32)]
+                ("B0", C.c_int32), ("group", C.c_int32), ("Tp", C.c_int32), ("G", C.c_int32),
+                ("k_prompt_scale", vp), ("v_prompt_scale", vp)]          # the fp8 prompt segment's E8M0 bytes, or both NULL
 
 
 class BeamStateC(C.Structure):
@@ -176,6 +177,8 @@ SIGNATURES = {
     "p2t_beam_sample_select": (i32, [vp, i32, i64, i32, i32, i32, vp, i32, i64, f32, i32, i32, i32, vp, C.POINTER(BeamStateC), vp, vp, vp, i64, f32, i32, f32,
                                      u64, i64, vp, vp]),
     "p2t_attention_decode": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp, i64, vp]),
+    "p2t_attention_decode_prompt_fp8": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp, i64, vp, vp, vp]),
+    "p2t_kv_quant_store": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "p2t_gemm_nt_skinny": (i32, [vp, i64, vp, i64, i32, vp, i64, i64, i64, i64, i32, i32, vp]),
     "p2t_preshuffle_w": (i32, [vp, i64, i64, i64, vp, vp]),
     "p2t_preshuffle_w_fp8": (i32, [vp, i64, i64, i64, vp, vp]),

@@ -221,8 +221,12 @@ class DecodeEngine:
     """Cache + buffers of ONE generate() call: B0 prompts, `group` rows per prompt (beams), capacities Tp / G (multiples of 64)."""
 
     def __init__(self, decoder, B0: int, group: int, T: int, max_new_tokens: int, stream_copy: bool = True, fuse_rope: bool = True,
-                 processors: Optional[dict] = None, eos_ids: Sequence[int] = ()):
+                 processors: Optional[dict] = None, eos_ids: Sequence[int] = (), prompt_kv_dtype: Optional[str] = None):
         m, s = decoder.model, decoder.spec
+        if prompt_kv_dtype not in (None, "fp8"):
+            raise ValueError(f"prompt_kv_dtype must be None or 'fp8' (got {prompt_kv_dtype!r})")
+        if prompt_kv_dtype == "fp8" and m.dtype != torch.bfloat16:
+            raise ValueError("prompt_kv_dtype='fp8' (the e4m3 prompt segment of the KV cache) serves bf16 models only")
         self.flags = 0 if fuse_rope else 1          # P2T_DECODE_NO_ROPE_FUSION
         if s.hidden_size % 64:
             raise ValueError("the LM head path needs hidden_size % 64 == 0")
@@ -233,7 +237,15 @@ class DecodeEngine:
         self.Tp, self.G = round_up(max(T, 1), 64), round_up(max(max_new_tokens, 1), 64)
         L, nkv, dp = s.num_hidden_layers, s.num_key_value_heads, ops.head_dim_padded(s.head_dim)
         z = lambda *shape: torch.zeros(shape, dtype=self.dtype, device=self.dev)
-        self.k_prompt, self.vt_prompt = z(L, B0, nkv, self.Tp, dp), z(L, B0, nkv, dp, self.Tp)
+        # the prompt segment: model dtype, or (prompt_kv_dtype="fp8") e4m3 codes in the same index order + one E8M0 byte per key for K and
+        # for V (include/p2t_hip.h, p2t_kv_cache): the prefill quantises on its store, the step's attention reads half the bytes
+        self.k_prompt_scale = self.v_prompt_scale = None
+        if prompt_kv_dtype == "fp8":
+            z8 = lambda *shape: torch.zeros(shape, dtype=torch.uint8, device=self.dev)
+            self.k_prompt, self.vt_prompt = z8(L, B0, nkv, self.Tp, dp), z8(L, B0, nkv, dp, self.Tp)
+            self.k_prompt_scale, self.v_prompt_scale = z8(L, B0, nkv, self.Tp), z8(L, B0, nkv, self.Tp)
+        else:
+            self.k_prompt, self.vt_prompt = z(L, B0, nkv, self.Tp, dp), z(L, B0, nkv, dp, self.Tp)
         self.k_gen, self.vt_gen = z(L, self.BB, nkv, self.G, dp), z(L, self.BB, nkv, dp, self.G)
         self.k_alt = self.vt_alt = None                                  # second generated segment, beam search only
         self.lens = torch.zeros((B0,), dtype=torch.int32, device=self.dev)
@@ -269,7 +281,9 @@ class DecodeEngine:
     def _cache_struct(self):
         self.cache = _lib.KvCacheC(k_prompt=self.k_prompt.data_ptr(), vt_prompt=self.vt_prompt.data_ptr(), k_gen=self.k_gen.data_ptr(),
                                    vt_gen=self.vt_gen.data_ptr(), prompt_len=self.lens.data_ptr(), step=self.step.data_ptr(), B0=self.B0,
-                                   group=self.group, Tp=self.Tp, G=self.G)
+                                   group=self.group, Tp=self.Tp, G=self.G,
+                                   k_prompt_scale=self.k_prompt_scale.data_ptr() if self.k_prompt_scale is not None else None,
+                                   v_prompt_scale=self.v_prompt_scale.data_ptr() if self.v_prompt_scale is not None else None)
 
     # -- prompt -------------------------------------------------------------------------------------------------------------
     def compact(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor):
@@ -380,7 +394,7 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
              output_logits: bool = False, use_graph: bool = True, sync_every: int = 16, generator: Optional[torch.Generator] = None,
              stream_copy: bool = True, fuse_rope: bool = True, seed: Optional[int] = None, beam_select: Optional[str] = None,
              repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
-             bad_words_ids: Optional[list] = None, suppress_tokens=None, **unused):
+             bad_words_ids: Optional[list] = None, suppress_tokens=None, prompt_kv_dtype: Optional[str] = None, **unused):
     """`LlamaForCausalLM.generate` for prompts given as embeddings (or ids): greedy, sampling (temperature / top-k / top-p) and beam
     search with length penalty.  Returns the new token ids i64 [batch * num_return_sequences, n] (or a GenerateOutput).
 
@@ -406,6 +420,11 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     is the generated tokens only.  One kernel (p2t_logits_process) in front of the greedy / sampled choice, inside the replayed step graph,
     and in front of the torch filters under `generator=`; `output_scores` then returns the processed scores, `output_logits` the raw rows.
     With none of them active nothing is launched or allocated.
+
+    `prompt_kv_dtype="fp8"` (bf16 models; ValueError otherwise) keeps the PROMPT segment of the KV cache as e4m3 codes with one
+    power-of-two scale per key and kv head for K and for V (p2t_kv_quant_store on the prefill's store, the attention of
+    p2t_attention_decode_prompt_fp8 in the step): half the cache bytes a step reads; the generated segment stays bf16.  The prefill
+    attends before the store, so the first token's logits do not change; every decoding mode runs unchanged around it.
 
     Logits processors under beam search (`num_beams > 1`) are opt-in: HF runs them on the log-softmax inside the beam step, with the
     beam's running sequence as the history, and ranks the processed rows.  `beam_select="device"` does that with two entry points inside
@@ -462,12 +481,12 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
             max_length=max_new_tokens, eos_ids=eos_ids, pad_id=int(pad_token_id), nb=num_beams, length_penalty=float(length_penalty),
             early_stopping=early_stopping, num_return_sequences=num_return_sequences, return_dict=return_dict_in_generate,
             output_scores=output_scores, output_logits=output_logits, stream_copy=stream_copy, beam_select=beam_select, use_graph=use_graph,
-            sync_every=sync_every, sampling=sampling, processors=proc))
+            sync_every=sync_every, sampling=sampling, processors=proc, prompt_kv_dtype=prompt_kv_dtype))
     R = int(num_return_sequences)
     if R != 1 and not do_sample:
         raise ValueError("greedy decoding returns one sequence per prompt: num_return_sequences > 1 needs do_sample=True or num_beams > 1")
     # R samples per prompt (HF repeats the prompt R times): R rows that SHARE the prompt segment of the cache, like the beams of a prompt
-    eng = DecodeEngine(decoder, B, R, T, max_new_tokens, stream_copy, fuse_rope, processors=proc, eos_ids=eos_ids)
+    eng = DecodeEngine(decoder, B, R, T, max_new_tokens, stream_copy, fuse_rope, processors=proc, eos_ids=eos_ids, prompt_kv_dtype=prompt_kv_dtype)
     embeds, mask = eng.compact(inputs_embeds, attention_mask)
     logits = eng.prefill(embeds, mask)
     if R > 1:
@@ -699,7 +718,8 @@ def _beam_search(decoder, inputs_embeds, attention_mask, o):
         if o.beam_select == "device":
             raise ValueError(f"generate(beam_select='device'): p2t_beam_select serves 1 <= num_beams <= {BEAMS_MAX} with max(2, 1 + number of eos ids) * "
                              f"num_beams <= {KEEP_MAX} <= vocabulary (got num_beams = {nb}, {len(o.eos_ids)} eos ids); the torch path serves the rest")
-    eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy, processors=o.processors, eos_ids=o.eos_ids)
+    eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy, processors=o.processors, eos_ids=o.eos_ids,
+                       prompt_kv_dtype=o.prompt_kv_dtype)
     dev = eng.dev
     embeds, mask = eng.compact(inputs_embeds, attention_mask)
     first_logits = eng.prefill(embeds, mask)                                 # [B, ld]: the beams of a prompt start from the same state
@@ -797,7 +817,8 @@ def _beam_search_device(decoder, inputs_embeds, attention_mask, o):
     buffers are back where the capture found them), an odd remainder eagerly.  The host reads `done` every `sync_every` tokens and at
     the end; steps run past the stop leave the state as it is."""
     B, V, nb, max_length, sampling = inputs_embeds.shape[0], decoder.spec.vocab_size, o.nb, o.max_length, o.sampling
-    eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy, processors=o.processors, eos_ids=o.eos_ids)
+    eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy, processors=o.processors, eos_ids=o.eos_ids,
+                       prompt_kv_dtype=o.prompt_kv_dtype)
     dev = eng.dev
     embeds, mask = eng.compact(inputs_embeds, attention_mask)
     first = eng.prefill(embeds, mask).repeat_interleave(nb, dim=0).contiguous()     # HF expands the prompt nb times before its prefill

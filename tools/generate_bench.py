@@ -22,7 +22,10 @@ interleaved, three runs each; then p2t_logits_process alone on [B, vocab] bf16 l
 python tools/generate_bench.py [B] [N] [beams > 1] process: the logits processors under beam search (`beam_select="device"`), under replay of
 the two-step graph, interleaved, three runs each: plain beam search (p2t_beam_select: nothing new is launched or allocated), the same with
 repetition_penalty 1.3 + no_repeat_ngram_size 3, the same with all five processors; then p2t_beam_logprobs_process alone on
-[B * beams, vocab] bf16 logits at histories of 0 and 64 tokens, p2t_beam_select_logprobs alone on its rows, and p2t_beam_select alone."""
+[B * beams, vocab] bf16 logits at histories of 0 and 64 tokens, p2t_beam_select_logprobs alone on its rows, and p2t_beam_select alone.
+python tools/generate_bench.py [B] [N] [beams] kv8 [fp8 | mxfp4]: the step with the bf16 and with the fp8 prompt segment of the KV cache
+(`prompt_kv_dtype="fp8"`), interleaved in one process, three runs each under graph replay, each next to a run of its prompt phase (beams > 1: beam_select="device", the beams of a
+prompt share its prompt segment): median and min .. max, and the cache bytes a step reads either way."""
 import os
 import sys
 import time
@@ -277,14 +280,50 @@ def beam_sample_mode(model, kw, B: int, N: int, beams: int, V: int, dev):
     print(f"flags after these calls: {int(sst.flags.item())} (fresh state), {int(live.flags.item())} (every beam live)", flush=True)
 
 
+def kv8_mode(model, kw, B: int, N: int, beams: int, T: int, llama, gemm_dtype: str):
+    cases = [("bf16 prompt segment", dict()), ("fp8 prompt segment (prompt_kv_dtype=\"fp8\")", dict(prompt_kv_dtype="fp8"))]
+    if beams > 1:
+        kw = {**kw, "beam_select": "device"}
+    for _, extra in cases:                                       # warm-up of each path
+        model.generate(**{**kw, **extra, "max_new_tokens": 6})
+    torch.cuda.synchronize()
+
+    def timed(**over):
+        t0 = time.perf_counter()
+        model.generate(**{**kw, **over})
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    runs, t_prompt = {name: [] for name, _ in cases}, {name: [] for name, _ in cases}
+    for _ in range(3):                                           # interleaved: a drift of the box hits both alike
+        for name, extra in cases:
+            # the prompt phase (one new token) next to every full run: at 32 prompts it is longer than the 63 steps it is subtracted from
+            t1 = timed(**extra, max_new_tokens=1)
+            runs[name].append((timed(**extra) - t1) / (N - 1) * 1e3)
+            t_prompt[name].append(t1 * 1e3)
+    L, nkv, d = llama.num_hidden_layers, llama.num_key_value_heads, llama.head_dim
+    rows = B * beams
+    gen_bytes = 2 * 2 * L * nkv * d * rows * N / 2               # the generated segment: bf16 either way, at the mean generated length
+    # every row streams its prompt's segment (the beams of a prompt read the same bytes: rows * T keys pass the CUs, B * T are distinct)
+    for (name, _), per_key in zip(cases, (2 * 2 * d, 2 * d + 2)):
+        r = runs[name]
+        print(f"generate cfg3{' ' + gemm_dtype + ' GEMMs' if gemm_dtype != 'model' else ''}: B={B} beams={beams} prompt {T} tokens, {N} new tokens, graph replay, "
+              f"{name}: median {np.median(r):.3f} ms/step (min {min(r):.3f}, max {max(r):.3f}; 3 runs); cache bytes read per step "
+              f"{(L * nkv * per_key * rows * T + gen_bytes) / 1e9:.2f} GB ({L * nkv * per_key * B * T / 1e9:.2f} GB distinct prompt bytes); "
+              f"prompt phase {np.median(t_prompt[name]):.1f} ms", flush=True)
+
+
 def main():
     dev = torch.device("cuda:0")
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
     N = int(sys.argv[2]) if len(sys.argv) > 2 else 128
     sample = len(sys.argv) > 3 and sys.argv[3] == "sample"
     process = len(sys.argv) > 3 and sys.argv[3] == "process"
-    beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample and not process else 1
+    kv8 = "kv8" in sys.argv[3:5]
+    beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample and not process and sys.argv[3] != "kv8" else 1
     gemm_dtype = sys.argv[4] if len(sys.argv) > 4 and sys.argv[4] in ("fp8", "mxfp4") else "model"
+    if kv8:                                                      # [B] [N] [beams] kv8 [fp8 | mxfp4]
+        after = sys.argv[sys.argv.index("kv8") + 1:]
+        gemm_dtype = after[0] if after and after[0] in ("fp8", "mxfp4") else "model"
     fp8 = gemm_dtype != "model"
     beam_sample = beams > 1 and len(sys.argv) > 4 and sys.argv[4] == "sample"
     beam_process = beams > 1 and len(sys.argv) > 4 and sys.argv[4] == "process"
@@ -304,6 +343,8 @@ def main():
     t = lambda a: torch.from_numpy(a).to(dev)
     kw = dict(inputs=t(ids), attention_mask=torch.ones((B, T), dtype=torch.int64, device=dev), protein_input_ids=t(pid),
               protein_attention_mask=t(pmask), max_new_tokens=N, eos_token_id=None, pad_token_id=128002, do_sample=False, num_beams=beams)
+    if kv8:
+        return kv8_mode(model, kw, B, N, beams, T, llama, gemm_dtype)
     if sample:
         return sample_mode(model, kw, B, N, llama.vocab_size, dev)
     if process:

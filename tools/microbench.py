@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks on the GPU box (HIP-event timed, random data): GEMM shapes of the
 cfg-3 towers, attention, norms.  Usage: python tools/microbench.py [gemm] [attn] [norm]
+`attn_decode` [m8] [m32]: the decode step's attention alone over the bf16 and the fp8 prompt segment of the KV cache.
 
 The `gemm` / `cold` / `ksweep` modes force launch forms through p2t_set_gemm_policy, and `fp8abl` runs the fp8 K-loop ablations
 (tile 1001-1003): run them against the LAB build (P2T_HIP_LIB=tools/build/libp2t_lab.so, `make -C prot2text-v2-esm3_amd/csrc lab`);
@@ -269,6 +270,48 @@ def bench_skinny():
                 print(f"skinny M={M:2d} {name:8s} N={N:6d} K={K:5d} {fmt:5s}: " + " | ".join(res), flush=True)
 
 
+def bench_attn_decode():
+    """The decode step's attention alone at Llama-3.1-8B sizes (8 kv heads x 4 query heads x head_dim 128) over 1088 prompt keys + 33
+    generated ones: p2t_attention_decode (bf16 prompt segment) and p2t_attention_decode_prompt_fp8 (e4m3 codes + one scale byte per key)
+    in the same loop, alternating, each on a ring of cache copies so that nothing is served from a cache; five rounds, median and range."""
+    import numpy as np
+    from p2t_hip.ops import ptr, stream
+    nh, nkv, d, T, S = 32, 8, 128, 1088, 32
+    Tp, G, copies, rounds, n = ops.round_up(T, 64), 64, 24, 5, 96
+    for B in [int(a[1:]) for a in sys.argv if a.startswith("m") and a[1:].isdigit()] or [8, 32]:
+        kp, vtp = [rand((B, nkv, Tp, d), scale=0.5) for _ in range(copies)], [rand((B, nkv, d, Tp), scale=0.5) for _ in range(copies)]
+        kg, vtg, q = rand((B, nkv, G, d), scale=0.5), rand((B, nkv, d, G), scale=0.5), rand((B, nh, d), scale=0.5)
+        k8, v8, ks, vs = [], [], [], []
+        for c in range(copies):                                   # the same keys and values through the prefill's store
+            k8.append(torch.empty((B, nkv, Tp, d), dtype=torch.uint8, device=dev)); v8.append(torch.empty((B, nkv, d, Tp), dtype=torch.uint8, device=dev))
+            ks.append(torch.empty((B, nkv, Tp), dtype=torch.uint8, device=dev)); vs.append(torch.empty((B, nkv, Tp), dtype=torch.uint8, device=dev))
+            _lib.call("p2t_kv_quant_store", ptr(kp[c]), ptr(vtp[c].transpose(2, 3).contiguous()), B, nkv, Tp, d, Tp, ptr(k8[c]), ptr(v8[c]), ptr(ks[c]),
+                      ptr(vs[c]), stream())
+        lens = torch.full((B,), T, dtype=torch.int32, device=dev)
+        step = torch.tensor([S], dtype=torch.int32, device=dev)
+        out = torch.zeros((B, nh * d), dtype=torch.bfloat16, device=dev)
+        i = [0]
+
+        def run(fp8):
+            c = i[0] % copies
+            i[0] += 1
+            if fp8:
+                _lib.call("p2t_attention_decode_prompt_fp8", ptr(q), ptr(k8[c]), ptr(v8[c]), ptr(kg), ptr(vtg), ptr(lens), ptr(step), B, 1, nh, nkv, d, Tp, G,
+                          1.0, 1, _lib.BF16, 1, ptr(out), nh * d, ptr(ks[c]), ptr(vs[c]), stream())
+            else:
+                _lib.call("p2t_attention_decode", ptr(q), ptr(kp[c]), ptr(vtp[c]), ptr(kg), ptr(vtg), ptr(lens), ptr(step), B, 1, nh, nkv, d, Tp, G, 1.0, 1,
+                          _lib.BF16, 1, ptr(out), nh * d, stream())
+        res = {0: [], 1: []}
+        for _ in range(rounds):
+            for fp8 in (0, 1):
+                res[fp8].append(timeit(lambda: run(fp8), iters=n, warm=copies) * 1e3)
+        for fp8, name in ((0, "bf16 prompt segment"), (1, "fp8 prompt segment ")):
+            nbytes = 2 * B * nkv * ((d * (1 if fp8 else 2) + fp8) * T + 2 * d * (S + 1))         # keys + values (+ one scale byte per key each)
+            r = res[fp8]
+            print(f"attn_decode B={B:2d} {T}+{S + 1} keys, {name}: median {np.median(r):5.1f} us (min {min(r):.1f}, max {max(r):.1f}; {rounds} rounds of {n}), "
+                  f"{nbytes / np.median(r) / 1e3:5.0f} GB/s of cache bytes ({nbytes / 1e6:.1f} MB)", flush=True)
+
+
 def bench_fp8abl():
     """Lab ablations of the fp8 K loop (per-tile kernel, garbage results; lab build only): full / no DMA / no fragment reloads / neither."""
     for name, M, N, K in (("esm qkv b64", 65536, 7680, 2560), ("esm fc2 b64", 65536, 2560, 10240), ("square 8k", 8192, 8192, 8192)):
@@ -299,5 +342,7 @@ if __name__ == "__main__":
         bench_fp8()
     if "skinny" in which:
         bench_skinny()
+    if "attn_decode" in which:
+        bench_attn_decode()
     if "fp8abl" in which:
         bench_fp8abl()
