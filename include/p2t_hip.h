@@ -56,7 +56,7 @@ int p2t_version(void);
 const char* p2t_last_error(void);
 /* sizeof() of the ABI structs, for bindings to self-check: 0 esm2_config, 1 esm2_layer, 2 esm2_weights,
  * 3 llama_config, 4 llama_layer, 5 llama_weights, 6 adapter_config, 7 adapter_weights, 8 adapter_saved, 9 llama_layer_t,
- * 10 kv_cache, 11 llama_layer_stream, 12 flat_segment, 13 flat_chunk, 14 beam_state, 15 llama_layer_mxfp4. */
+ * 10 kv_cache, 11 llama_layer_stream, 12 flat_segment, 13 flat_chunk, 14 beam_state, 15 llama_layer_mxfp4, 16 lm_head_q. */
 size_t p2t_struct_size(int which);
 
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
@@ -889,6 +889,41 @@ int p2t_llama_decode_step_mxfp4(const p2t_llama_config* cfg, const p2t_llama_wei
                                 const void* lm_head, int64_t ld_head, int lm_head_preshuffled, const p2t_kv_cache* cache,
                                 const float* x, void* logits, int64_t ld_logits, int flags, void* workspace, size_t workspace_bytes,
                                 p2t_stream stream);
+/* ---- The quantised LM head (generate(lm_head_dtype="fp8" | "mxfp4"); bf16 models).  The head W [vocab, hidden] as
+ *   P2T_LM_HEAD_E4M3:  e4m3 codes [vocab, ld >= Kq] + one E8M0 byte per vocabulary row `scales` [vocab]: p2t_quant_rows_fp8 of the head;
+ *   P2T_LM_HEAD_MXFP4: e2m1 codes [vocab, ld >= Kq / 2 bytes] + one E8M0 byte per 32 columns `scales` [vocab, Kq / 32]: p2t_quant_rows_mxfp4
+ * (Kq = hidden rounded up to 128, pad zero, ld % 16 == 0, codes 16-byte aligned).  stream_order != 0: `codes` is the p2t_preshuffle_w_fp8 /
+ * p2t_preshuffle_w_mxfp4 copy (ld ignored; the MXFP4 copy carries its block scales: scales may be NULL; the e4m3 copy keeps `scales`).
+ * A stream copy serves at most 64 rows.  More than 64 rows run the general fp8 GEMM on ROW-MAJOR e4m3 codes at ld = Kq: the e4m3 head's
+ * own, or, for an MXFP4 head, codes_e4m3 / scales_e4m3 = p2t_quant_rows_fp8 of the dequantised head (exact: "MXFP4 decoder weights" above);
+ * both NULL otherwise. */
+enum { P2T_LM_HEAD_E4M3 = 1, P2T_LM_HEAD_MXFP4 = 2 };
+typedef struct {
+    int32_t format; int32_t stream_order;
+    const void* codes; const uint8_t* scales; int64_t ld;
+    const void* codes_e4m3; const uint8_t* scales_e4m3;
+} p2t_lm_head_q;
+size_t p2t_lm_head_q_workspace_bytes(int64_t M, int64_t hidden);
+/* logits bf16 [M, ld_logits] = head(rmsnorm(x) * norm_w): x f32 [M, ld_x] (the residual stream; ld_x % 8 == 0, hidden % 8 == 0) is
+ * normalised and written as e4m3 rows [M, Kq] + one E8M0 byte per row by the rule of the fp8 step's projections (p2t_rmsnorm_fp8), then
+ * multiplied with the head: v_mfma_scale_f32_16x16x128_f8f6f4, f32 accumulation, one rounding to bf16; up to 64 rows on the weight
+ * stream of p2t_gemm_nt_skinny_fp8 / _mxfp4 (columns vocab .. ld_logits are not written), beyond that on p2t_gemm_nt_fp8's kernels.
+ * norm_w == NULL: x holds rows that are normalised already (p2t_llama_prefill's last_hidden) and is quantised by p2t_quant_rows_fp8's
+ * rule.  act_codes [M, Kq] / act_scales [M] (optional, both or neither, 16-byte aligned): receive the e4m3 rows the GEMM read (tests);
+ * NULL: they live in `workspace` (p2t_lm_head_q_workspace_bytes).  out_dtype: P2T_BF16 (anything else: P2T_ERR_UNSUPPORTED, as are a stream
+ * copy with M > 64, an MXFP4 head with M > 64 and no e4m3 copy, an e4m3 head with M > 64 and ld != Kq, and M > 64 with vocab % 16 != 0:
+ * p2t_gemm_nt's own condition).  Enqueues only: capturable. */
+int p2t_lm_head_logits_q(const float* x, int64_t ld_x, const float* norm_w, float eps, const p2t_lm_head_q* head, int64_t M,
+                         int64_t hidden, int64_t vocab, void* logits, int64_t ld_logits, int out_dtype, uint8_t* act_codes,
+                         uint8_t* act_scales, void* workspace, size_t workspace_bytes, p2t_stream stream);
+/* p2t_llama_decode_step and p2t_llama_decode_step_mxfp4 behind one door: w_stream or mx_layers (either may be NULL; both set:
+ * P2T_ERR_ARG; mx_layers under p2t_llama_decode_step_mxfp4's conditions), and head_q: NULL = that step, launch for launch; set = the
+ * final RMSNorm and the LM head run as p2t_lm_head_logits_q on the residual stream (lm_head / ld_head / lm_head_preshuffled are then
+ * ignored and may be NULL / 0) and the workspace holds p2t_llama_decode_workspace_bytes + p2t_lm_head_q_workspace_bytes(BB, hidden). */
+int p2t_llama_decode_step_q(const p2t_llama_config* cfg, const p2t_llama_weights* w, const p2t_llama_layer_stream* w_stream,
+                            const p2t_llama_layer_mxfp4* mx_layers, const void* lm_head, int64_t ld_head, int lm_head_preshuffled,
+                            const p2t_lm_head_q* head_q, const p2t_kv_cache* cache, const float* x, void* logits, int64_t ld_logits,
+                            int flags, void* workspace, size_t workspace_bytes, p2t_stream stream);
 /* The decode step's attention on its own (exposed so that it can be checked against the plain arithmetic): ONE query token per
  * row, q `dtype` [BB, nh, dp], over prompt_len[row / group] keys of the prompt segment and step[0] + 1 keys of the generated
  * segment (the layouts of ONE layer of p2t_kv_cache), GQA; softmax((scale) q k^T) v with f32 statistics -- log2_scores: q holds

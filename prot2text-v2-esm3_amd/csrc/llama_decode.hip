@@ -831,27 +831,98 @@ extern "C" size_t p2t_llama_decode_workspace_bytes(const p2t_llama_config* cfg, 
     return decode_plan(cfg, BB, Tp, G, nullptr, nullptr);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The quantised LM head (include/p2t_hip.h, p2t_lm_head_q): final RMSNorm written as e4m3 rows + E8M0 row scales, then the weight
+// stream of gemm_skinny.hip on e4m3 / MXFP4 codes (<= 64 rows) or the general fp8 GEMM on e4m3 codes (more rows; never a stream copy).
+static int64_t lm_head_q_kq(int64_t H) { return round_up(H, 128); }
+static size_t lm_head_q_ws_bytes(int64_t M, int64_t H) {
+    return M > 0 && H > 0 ? (size_t)round_up(M * lm_head_q_kq(H), 256) + (size_t)round_up(M, 256) + 512 : 0;
+}
+
+// every refusal of a head call, before any launch.  `who`: the entry point's name
+static int lm_head_q_check(const p2t_lm_head_q* h, int64_t M, int64_t H, int64_t V, int64_t ld_logits, int out_dtype, const char* who) {
+    P2T_REQUIRE(h, "%s: null head descriptor", who);
+    P2T_REQUIRE(h->format == P2T_LM_HEAD_E4M3 || h->format == P2T_LM_HEAD_MXFP4, "%s: head format %d is neither P2T_LM_HEAD_E4M3 nor P2T_LM_HEAD_MXFP4", who,
+                h->format);
+    P2T_REQUIRE(M > 0 && H > 0 && H % 8 == 0 && H < (1 << 30) && V > 0 && V < (1 << 30), "%s: bad head shape (rows %lld, hidden %lld %% 8, vocab %lld)", who,
+                (long long)M, (long long)H, (long long)V);
+    P2T_REQUIRE(ld_logits >= V && ld_logits % 4 == 0, "%s: ld_logits %lld must be a multiple of 4 that holds vocab %lld", who, (long long)ld_logits, (long long)V);
+    const int64_t Kq = lm_head_q_kq(H);
+    const bool mx = h->format == P2T_LM_HEAD_MXFP4;
+    P2T_REQUIRE(h->codes && ((uintptr_t)h->codes & 15) == 0, "%s: null or misaligned head codes (16-byte alignment)", who);
+    P2T_REQUIRE(h->scales || (mx && h->stream_order), "%s: null head scales (only an interleaved MXFP4 stream copy carries its own)", who);
+    P2T_REQUIRE(h->stream_order || (h->ld % 16 == 0 && h->ld >= (mx ? Kq / 2 : Kq)), "%s: head ld %lld must be a multiple of 16 and at least %lld bytes", who,
+                (long long)h->ld, (long long)(mx ? Kq / 2 : Kq));
+    P2T_REQUIRE(!h->codes_e4m3 == !h->scales_e4m3, "%s: codes_e4m3 and scales_e4m3 go together", who);
+    P2T_REQUIRE(!h->codes_e4m3 || mx, "%s: codes_e4m3 is the MXFP4 head's copy for more than 64 rows (an e4m3 head serves them itself)", who);
+    if (out_dtype != P2T_BF16) {
+        set_error("%s: the quantised LM head serves bf16 models only", who);
+        return P2T_ERR_UNSUPPORTED;
+    }
+    if (M > 64 && h->stream_order) {
+        set_error("%s: a stream-order LM head serves at most 64 rows (got %lld): pass the row-major one", who, (long long)M);
+        return P2T_ERR_UNSUPPORTED;
+    }
+    if (M > 64 && mx && !h->codes_e4m3) {
+        set_error("%s: an MXFP4 LM head serves more than 64 rows (got %lld) through its e4m3 copy (codes_e4m3, scales_e4m3)", who, (long long)M);
+        return P2T_ERR_UNSUPPORTED;
+    }
+    if (M > 64 && V % 16) {
+        set_error("%s: more than 64 rows run the general GEMM, which takes a vocabulary that is a multiple of 16 (got %lld)", who, (long long)V);
+        return P2T_ERR_UNSUPPORTED;
+    }
+    if (M > 64 && !mx && h->ld != Kq) {
+        set_error("%s: more than 64 rows read the e4m3 head at ld = hidden rounded up to 128 (%lld, got %lld)", who, (long long)Kq, (long long)h->ld);
+        return P2T_ERR_UNSUPPORTED;
+    }
+    return P2T_OK;
+}
+
+// checked arguments only.  norm_w == nullptr: x holds rows that are normalised already (the prefill's last hidden rows)
+static int lm_head_q_run(const float* x, int64_t ld_x, const float* norm_w, float eps, const p2t_lm_head_q* h, int64_t M, int64_t H, int64_t V, void* logits,
+                         int64_t ld_logits, uint8_t* aq, uint8_t* as, hipStream_t s) {
+    const int64_t Kq = lm_head_q_kq(H);
+    if (norm_w) P2T_TRY(launch_rmsnorm_fp8_few(x, ld_x, norm_w, eps, aq, Kq, as, M, H, s));
+    else P2T_TRY(launch_quant_rows_few(x, P2T_F32, ld_x, M, H, aq, Kq, as, s));
+    if (M <= 64) {
+        if (h->format == P2T_LM_HEAD_MXFP4)
+            return launch_gemm_skinny_mxfp4(aq, Kq, as, h->codes, h->ld, h->scales, logits, ld_logits, M, V, Kq, P2T_BF16, P2T_EPI_STORE, nullptr, s,
+                                            h->stream_order != 0);
+        return launch_gemm_skinny_fp8(aq, Kq, as, h->codes, h->ld, h->scales, logits, ld_logits, M, V, Kq, P2T_BF16, P2T_EPI_STORE, nullptr, s,
+                                      h->stream_order != 0);
+    }
+    const bool mx = h->format == P2T_LM_HEAD_MXFP4;
+    return p2t::gemm_nt(gemm_args_fp8(aq, Kq, as, mx ? h->codes_e4m3 : h->codes, mx ? h->scales_e4m3 : h->scales, M, V, Kq, logits, ld_logits, P2T_BF16,
+                                      P2T_EPI_STORE), s);
+}
+
 // mx: the MXFP4 form of the projections (p2t_llama_decode_step_mxfp4; a gemm_fp8 model, at most 64 rows) or nullptr
 static int decode_step_impl(const p2t_llama_config* c, const p2t_llama_weights* w, const p2t_llama_layer_stream* ws_layers, const p2t_llama_layer_mxfp4* mx,
                             const void* lm_head, int64_t ld_head, int lm_head_preshuffled, const p2t_kv_cache* cache, const float* x_in, void* logits,
-                            int64_t ld_logits, int flags, void* workspace, size_t workspace_bytes, p2t_stream stream) {
-    P2T_REQUIRE(c && w && w->layers && w->final_norm_w && lm_head && x_in && logits && workspace, "p2t_llama_decode_step: null argument");
+                            int64_t ld_logits, int flags, void* workspace, size_t workspace_bytes, p2t_stream stream, const p2t_lm_head_q* head_q = nullptr,
+                            const char* who = "p2t_llama_decode_step") {
+    P2T_REQUIRE(c && w && w->layers && w->final_norm_w && (lm_head || head_q) && x_in && logits && workspace, "%s: null argument", who);
     const bool fuse_rope = !(flags & P2T_DECODE_NO_ROPE_FUSION);
-    P2T_TRY(check_cache(c, cache, "p2t_llama_decode_step"));
-    P2T_REQUIRE(!c->gemm_fp8 || c->dtype == P2T_BF16, "p2t_llama_decode_step: gemm_fp8 needs bf16 activations (dtype = P2T_BF16)");
+    P2T_TRY(check_cache(c, cache, who));
+    P2T_REQUIRE(!c->gemm_fp8 || c->dtype == P2T_BF16, "%s: gemm_fp8 needs bf16 activations (dtype = P2T_BF16)", who);
     const int BB = cache->B0 * cache->group;
     const int dt = c->dtype;
     const int64_t H = c->hidden, F = c->ffn, Hp = round_up(H, 64), Fp = round_up(F, 64);
     const int d = c->head_dim, dp = head_dim_padded(d), nh = c->heads, nkv = c->kv_heads;
     const int64_t NQKV = (int64_t)(nh + 2 * nkv) * d, QO = round_up((int64_t)nh * d, 64);
-    P2T_REQUIRE((lm_head_preshuffled || ld_head >= Hp) && ld_logits >= c->vocab, "p2t_llama_decode_step: ld_head %lld < %lld or ld_logits %lld < vocab", (long long)ld_head,
+    P2T_REQUIRE((head_q || lm_head_preshuffled || ld_head >= Hp) && ld_logits >= c->vocab, "%s: ld_head %lld < %lld or ld_logits %lld < vocab", who, (long long)ld_head,
                 (long long)Hp, (long long)ld_logits);
-    P2T_REQUIRE(workspace_bytes >= decode_plan(c, BB, cache->Tp, cache->G, nullptr, nullptr), "p2t_llama_decode_step: workspace too small");
+    // the quantised head: every refusal before the first launch; its e4m3 rows + row scales sit behind the step's own buffers
+    if (head_q) P2T_TRY(lm_head_q_check(head_q, BB, H, c->vocab, ld_logits, dt, who));
+    P2T_REQUIRE(workspace_bytes >= decode_plan(c, BB, cache->Tp, cache->G, nullptr, nullptr) + (head_q ? lm_head_q_ws_bytes(BB, H) : 0),
+                "%s: workspace too small", who);
     hipStream_t s = (hipStream_t)stream;
     Arena ar(workspace, workspace_bytes);
     DecodeBuffers b;
     decode_plan(c, BB, cache->Tp, cache->G, &ar, &b);
-    P2T_REQUIRE(!ar.overflow, "p2t_llama_decode_step: workspace overflow");
+    uint8_t* head_aq = head_q ? (uint8_t*)ar.take((size_t)BB * lm_head_q_kq(H)) : nullptr;
+    uint8_t* head_as = head_q ? (uint8_t*)ar.take((size_t)BB) : nullptr;
+    P2T_REQUIRE(!ar.overflow, "%s: workspace overflow", who);
     const float* inv_freq = w->inv_freq;
     if (!inv_freq) {
         P2T_TRY(launch_inv_freq(b.inv_freq, d / 2, c->rope_theta, c->rope_llama3, c->rope_factor, c->rope_low_freq_factor, c->rope_high_freq_factor,
@@ -890,8 +961,8 @@ static int decode_step_impl(const p2t_llama_config* c, const p2t_llama_weights* 
     };
     for (int l = 0; c->gemm_fp8 && l < c->n_layers; ++l) {
         const p2t_llama_layer& L = w->layers[l];
-        P2T_REQUIRE(L.qkv_ws && L.o_ws && L.gu_ws && L.down_ws, "p2t_llama_decode_step: gemm_fp8 needs the row scales of layer %d", l);
-        P2T_REQUIRE(!L.q_norm_w == !L.k_norm_w, "p2t_llama_decode_step: q_norm_w and k_norm_w go together (layer %d)", l);
+        P2T_REQUIRE(L.qkv_ws && L.o_ws && L.gu_ws && L.down_ws, "%s: gemm_fp8 needs the row scales of layer %d", who, l);
+        P2T_REQUIRE(!L.q_norm_w == !L.k_norm_w, "%s: q_norm_w and k_norm_w go together (layer %d)", who, l);
         const int fused_prefill = !L.q_norm_w && (d == 64 || d == 128);
         const p2t_llama_layer_stream* S = ws_layers ? ws_layers + l : nullptr;
         const MxProj xq{mx ? mx[l].qkv_w : nullptr, mx ? mx[l].qkv_bs : nullptr}, xo{mx ? mx[l].o_w : nullptr, mx ? mx[l].o_bs : nullptr},
@@ -927,7 +998,7 @@ static int decode_step_impl(const p2t_llama_config* c, const p2t_llama_weights* 
     }
     for (int l = 0; !c->gemm_fp8 && l < c->n_layers; ++l) {
         const p2t_llama_layer& L = w->layers[l];
-        P2T_REQUIRE(!L.q_norm_w == !L.k_norm_w, "p2t_llama_decode_step: q_norm_w and k_norm_w go together (layer %d)", l);
+        P2T_REQUIRE(!L.q_norm_w == !L.k_norm_w, "%s: q_norm_w and k_norm_w go together (layer %d)", who, l);
         const int fused_prefill = !L.q_norm_w && (d == 64 || d == 128);
         P2T_TRY(launch_rmsnorm_few_rows(b.x, H, L.ln1_w, c->rms_norm_eps, b.h, Hp, M, H, dt, s));
         bool roped = false;
@@ -970,10 +1041,16 @@ static int decode_step_impl(const p2t_llama_config* c, const p2t_llama_weights* 
         GemmArgs g4(b.act, Fp, L.down_w, Fp, M, H, Fp, dt, b.x, H, P2T_F32, P2T_EPI_RESID);
         P2T_TRY(gemm_nt(g4, s, stream_w ? ws_layers[l].down_w : nullptr));
     }
-    P2T_REQUIRE(!lm_head_preshuffled || dt == P2T_BF16, "p2t_llama_decode_step: pre-shuffled weights are a bf16 layout");
+    if (head_q) {                                        // one more branch after the layer loops: the e4m3 / MXFP4 head on the residual stream
+        P2T_TRY(lm_head_q_run(b.x, H, w->final_norm_w, c->rms_norm_eps, head_q, M, H, c->vocab, logits, ld_logits, head_aq, head_as, s));
+        advance_kernel<<<1, 1, 0, s>>>(cache->step);
+        P2T_LAUNCH_CHECK();
+        return P2T_OK;
+    }
+    P2T_REQUIRE(!lm_head_preshuffled || dt == P2T_BF16, "%s: pre-shuffled weights are a bf16 layout", who);
     // the stream-order copy is only readable by the skinny kernels (<= 64 rows): beyond that the general GEMM would read the
     // shuffled tiles as a row-major [vocab, Hp] matrix and return wrong logits without an error
-    P2T_REQUIRE(!lm_head_preshuffled || M <= 64, "p2t_llama_decode_step: a pre-shuffled LM head serves at most 64 rows (got %lld): pass the row-major one",
+    P2T_REQUIRE(!lm_head_preshuffled || M <= 64, "%s: a pre-shuffled LM head serves at most 64 rows (got %lld): pass the row-major one", who,
                 (long long)M);
     P2T_TRY(launch_rmsnorm_few_rows(b.x, H, w->final_norm_w, c->rms_norm_eps, b.h, Hp, M, H, dt, s));
     GemmArgs gh(b.h, Hp, lm_head, ld_head, M, c->vocab, Hp, dt, logits, ld_logits, dt, P2T_EPI_STORE);
@@ -1003,6 +1080,48 @@ extern "C" int p2t_llama_decode_step_mxfp4(const p2t_llama_config* c, const p2t_
         P2T_REQUIRE(!mx_layers[l].stream_order == !mx_layers[0].stream_order, "p2t_llama_decode_step_mxfp4: layers differ in stream_order");
     return decode_step_impl(c, w, nullptr, mx_layers, lm_head, ld_head, lm_head_preshuffled, cache, x_in, logits, ld_logits, flags, workspace,
                             workspace_bytes, stream);
+}
+
+// Both steps behind one door, plus the quantised LM head: w_stream or mx_layers (either may be NULL, not both set); head_q == NULL is
+// the existing step, launch for launch.
+extern "C" int p2t_llama_decode_step_q(const p2t_llama_config* c, const p2t_llama_weights* w, const p2t_llama_layer_stream* ws_layers,
+                                       const p2t_llama_layer_mxfp4* mx_layers, const void* lm_head, int64_t ld_head, int lm_head_preshuffled,
+                                       const p2t_lm_head_q* head_q, const p2t_kv_cache* cache, const float* x_in, void* logits, int64_t ld_logits, int flags,
+                                       void* workspace, size_t workspace_bytes, p2t_stream stream) {
+    P2T_REQUIRE(!(ws_layers && mx_layers), "p2t_llama_decode_step_q: w_stream and mx_layers are two forms of the same projections: pass one");
+    if (mx_layers) {
+        P2T_REQUIRE(c && cache, "p2t_llama_decode_step_q: null argument");
+        P2T_REQUIRE(c->gemm_fp8 && c->dtype == P2T_BF16, "p2t_llama_decode_step_q: mx_layers need a gemm_fp8 configuration with bf16 activations");
+        P2T_REQUIRE((int64_t)cache->B0 * cache->group <= 64, "p2t_llama_decode_step_q: mx_layers serve at most 64 rows (got %lld): beyond that the e4m3 weights serve",
+                    (long long)cache->B0 * cache->group);
+        for (int l = 1; l < c->n_layers; ++l)
+            P2T_REQUIRE(!mx_layers[l].stream_order == !mx_layers[0].stream_order, "p2t_llama_decode_step_q: layers differ in stream_order");
+    }
+    return decode_step_impl(c, w, ws_layers, mx_layers, lm_head, ld_head, lm_head_preshuffled, cache, x_in, logits, ld_logits, flags, workspace, workspace_bytes,
+                            stream, head_q, "p2t_llama_decode_step_q");
+}
+
+extern "C" size_t p2t_lm_head_q_workspace_bytes(int64_t M, int64_t hidden) { return lm_head_q_ws_bytes(M, hidden); }
+
+extern "C" int p2t_lm_head_logits_q(const float* x, int64_t ld_x, const float* norm_w, float eps, const p2t_lm_head_q* head, int64_t M, int64_t hidden,
+                                    int64_t vocab, void* logits, int64_t ld_logits, int out_dtype, uint8_t* act_codes, uint8_t* act_scales, void* workspace,
+                                    size_t workspace_bytes, p2t_stream stream) {
+    P2T_REQUIRE(x && logits, "p2t_lm_head_logits_q: null x / logits");
+    P2T_TRY(lm_head_q_check(head, M, hidden, vocab, ld_logits, out_dtype, "p2t_lm_head_logits_q"));
+    P2T_REQUIRE(ld_x >= hidden && ld_x % 8 == 0 && ((uintptr_t)x & 15) == 0, "p2t_lm_head_logits_q: ld_x %lld must be a multiple of 8 that holds hidden %lld (x 16-byte aligned)",
+                (long long)ld_x, (long long)hidden);
+    P2T_REQUIRE(!act_codes == !act_scales, "p2t_lm_head_logits_q: act_codes and act_scales go together");
+    P2T_REQUIRE(!act_codes || ((uintptr_t)act_codes & 15) == 0, "p2t_lm_head_logits_q: act_codes must be 16-byte aligned");
+    uint8_t* aq = act_codes;
+    uint8_t* as = act_scales;
+    if (!aq) {
+        P2T_REQUIRE(workspace && workspace_bytes >= lm_head_q_ws_bytes(M, hidden), "p2t_lm_head_logits_q: workspace too small (p2t_lm_head_q_workspace_bytes)");
+        Arena ar(workspace, workspace_bytes);
+        aq = (uint8_t*)ar.take((size_t)M * lm_head_q_kq(hidden));
+        as = (uint8_t*)ar.take((size_t)M);
+        P2T_REQUIRE(!ar.overflow, "p2t_lm_head_logits_q: workspace overflow");
+    }
+    return lm_head_q_run(x, ld_x, norm_w, eps, head, M, hidden, vocab, logits, ld_logits, aq, as, (hipStream_t)stream);
 }
 
 extern "C" int p2t_greedy_select(const void* logits, int dtype, int64_t ld, int V, int BB, const int64_t* eos_ids, int n_eos, int64_t pad_id,

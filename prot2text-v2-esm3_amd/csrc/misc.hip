@@ -249,6 +249,7 @@ extern "C" size_t p2t_struct_size(int which) {
         case 13: return sizeof(p2t_flat_chunk);
         case 14: return sizeof(p2t_beam_state);
         case 15: return sizeof(p2t_llama_layer_mxfp4);
+        case 16: return sizeof(p2t_lm_head_q);
     }
     return 0;
 }

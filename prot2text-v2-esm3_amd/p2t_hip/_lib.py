@@ -102,6 +102,13 @@ class LlamaLayerMxfp4C(C.Structure):
                                                                                                           ("reserved", C.c_int32)]
 
 
+LM_HEAD_E4M3, LM_HEAD_MXFP4 = 1, 2                   # p2t_lm_head_q.format
+
+
+class LmHeadQC(C.Structure):
+    _fields_ = [("format", C.c_int32), ("stream_order", C.c_int32), ("codes", vp), ("scales", vp), ("ld", i64), ("codes_e4m3", vp), ("scales_e4m3", vp)]
+
+
 class FlatSegmentC(C.Structure):
     _fields_ = [("offset", i64), ("numel", i64), ("shadow", vp), ("rows", i64), ("cols", i64), ("ld", i64), ("scale", f32),
                 ("shadow_dtype", C.c_int32)]
@@ -114,7 +121,8 @@ class FlatChunkC(C.Structure):
 FLAT_NORM_BLOCKS, FLAT_CHUNK = 1024, 4096            # P2T_FLAT_NORM_BLOCKS, P2T_FLAT_CHUNK
 
 _STRUCTS = [EsmConfigC, EsmLayerC, EsmWeightsC, LlamaConfigC, LlamaLayerC, LlamaWeightsC, AdapterConfigC,
-            AdapterWeightsC, AdapterSavedC, LlamaLayerTC, KvCacheC, LlamaLayerStreamC, FlatSegmentC, FlatChunkC, BeamStateC, LlamaLayerMxfp4C]
+            AdapterWeightsC, AdapterSavedC, LlamaLayerTC, KvCacheC, LlamaLayerStreamC, FlatSegmentC, FlatChunkC, BeamStateC, LlamaLayerMxfp4C,
+            LmHeadQC]
 
 # name -> (restype, argtypes); every symbol include/p2t_hip.h declares
 SIGNATURES = {
@@ -165,6 +173,10 @@ SIGNATURES = {
                               i32, vp, sz, vp]),
     "p2t_llama_decode_step_mxfp4": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), C.POINTER(LlamaLayerMxfp4C), vp, i64, i32,
                                     C.POINTER(KvCacheC), vp, vp, i64, i32, vp, sz, vp]),
+    "p2t_llama_decode_step_q": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), C.POINTER(LlamaLayerStreamC), C.POINTER(LlamaLayerMxfp4C), vp, i64,
+                                i32, C.POINTER(LmHeadQC), C.POINTER(KvCacheC), vp, vp, i64, i32, vp, sz, vp]),
+    "p2t_lm_head_q_workspace_bytes": (sz, [i64, i64]),
+    "p2t_lm_head_logits_q": (i32, [vp, i64, vp, f32, C.POINTER(LmHeadQC), i64, i64, i64, vp, i64, i32, vp, vp, vp, sz, vp]),
     "p2t_greedy_select": (i32, [vp, i32, i64, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, i32, vp]),
     "p2t_sample_select": (i32, [vp, i32, i64, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, i32, f32, i32, f32, u64, i64, vp, i64, vp, vp]),
     "p2t_logits_process": (i32, [vp, i32, i64, i32, i32, vp, i64, vp, i32, vp, i64, f32, i32, i32, vp, i32, vp, vp, i32, i32, vp]),
@@ -253,7 +265,7 @@ for _i, _s in enumerate(_STRUCTS):
 
 _NO_RC = {"p2t_gemm_fix_workspace_bytes", "p2t_version", "p2t_is_lab_build", "p2t_last_error", "p2t_struct_size", "p2t_esm2_workspace_bytes", "p2t_llama_workspace_bytes", "p2t_llama_tape_bytes", "p2t_llama_train_workspace_bytes", "p2t_llama_prefill_workspace_bytes", "p2t_llama_decode_workspace_bytes",
           "p2t_adapter_backward_workspace_bytes", "p2t_adapter_backward_dx_workspace_bytes", "p2t_lora_wgrad_workspace_bytes", "p2t_beam_workspace_bytes",
-          "p2t_beam_sample_workspace_bytes"}
+          "p2t_beam_sample_workspace_bytes", "p2t_lm_head_q_workspace_bytes"}
 
 
 def call(name: str, *args):

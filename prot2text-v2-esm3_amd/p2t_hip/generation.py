@@ -188,9 +188,11 @@ def mxfp4_layers(e, stream_order: bool):
     return layers, keep
 
 
-def stream_weights(decoder):
+def stream_weights(decoder, lm_head: bool = True):
     """Second copies of every decoder projection + the LM head in the stream order, built once per model (dropped with the engine
-    when weights are loaded): Llama-3.1-8B: 15 GB next to the 15 GB the prefill reads -- HBM is sized for it."""
+    when weights are loaded): Llama-3.1-8B: 15 GB next to the 15 GB the prefill reads -- HBM is sized for it.
+    lm_head=False (a quantised head serves the steps: generate(lm_head_dtype=)): the bf16 head's copy, 1.05 GB there, is not built --
+    st["lm_head"] stays None until a call with lm_head=True wants it."""
     m, s = decoder.model, decoder.spec
     e = m.ensure_engine(s.num_hidden_layers)
     lm = decoder._lm_head_padded()
@@ -199,6 +201,8 @@ def stream_weights(decoder):
     key = (id(e), lm.data_ptr(), lm._version, decoder.model.embed_tokens.weight._version, fmt)
     st = getattr(m, "_stream_engine", None)
     if st is not None and st["key"] == key:
+        if lm_head and st["lm_head"] is None:
+            st["lm_head"] = preshuffle(lm, s.vocab_size)
         return st
     d, nh, nkv = s.head_dim, s.num_attention_heads, s.num_key_value_heads
     rows = dict(qkv_w=(nh + 2 * nkv) * d, o_w=s.hidden_size, gu_w=2 * s.intermediate_size, down_w=s.hidden_size)
@@ -212,21 +216,92 @@ def stream_weights(decoder):
                 w = preshuffle(t[name], n)
                 keep.append(w)
                 setattr(layers[i], name, w.data_ptr())
-    st = dict(key=key, layers=layers, keep=keep, lm_head=preshuffle(lm, s.vocab_size))
+    st = dict(key=key, layers=layers, keep=keep, lm_head=preshuffle(lm, s.vocab_size) if lm_head else None)
     m._stream_engine = st
     return st
+
+
+def lm_head_q(decoder, fmt: str) -> dict:
+    """The quantised LM head of generate(lm_head_dtype=fmt), built once per model and kept beside the bf16 head (which still serves
+    lm_head_dtype=None, training and, with tied embeddings, the embedding lookup): "fp8" = p2t_quant_rows_fp8 of the padded bf16 head
+    (e4m3 codes + one E8M0 byte per vocabulary row), "mxfp4" = p2t_quant_rows_mxfp4 of it (e2m1 codes + one E8M0 byte per 32 columns).
+    Keyed like stream_weights: a weight load (new engine) or an in-place update of the head rebuilds it.  The stream-order copy and, for
+    "mxfp4", the e4m3 copy of the same values W~ that more than 64 rows read are made on first use (head_q_struct)."""
+    m, s = decoder.model, decoder.spec
+    e = m.ensure_engine(s.num_hidden_layers)
+    lm = decoder._lm_head_padded()
+    key = (id(e), lm.data_ptr(), lm._version, decoder.lm_head.weight._version, fmt)
+    cache = getattr(m, "_lm_head_q", None)
+    if cache is None:
+        cache = m._lm_head_q = {}
+    st = cache.get(fmt)
+    if st is not None and st["key"] == key:
+        return st
+    H = s.hidden_size
+    if fmt == "fp8":
+        codes, scales = ops.quant_rows_fp8(lm, H)
+    else:
+        codes, scales = ops.quant_rows_mxfp4(lm, H)
+    st = cache[fmt] = dict(key=key, fmt=fmt, codes=codes, scales=scales, stream=None, e4m3=None)
+    return st
+
+
+def head_q_struct(decoder, st: dict, stream_order: bool, rows: int):
+    """(p2t_lm_head_q, what it points to) over lm_head_q's tensors: the stream-order copy (at most 64 rows, never the general GEMM) or
+    the row-major codes, plus, for an MXFP4 head read by more than 64 rows, the e4m3 codes of the dequantised head."""
+    V, H = decoder.spec.vocab_size, decoder.spec.hidden_size
+    mx = st["fmt"] == "mxfp4"
+    d = _lib.LmHeadQC(format=_lib.LM_HEAD_MXFP4 if mx else _lib.LM_HEAD_E4M3, stream_order=int(stream_order), ld=st["codes"].stride(0))
+    if stream_order:
+        if st["stream"] is None:
+            st["stream"] = preshuffle_mxfp4(st["codes"], st["scales"], V) if mx else preshuffle(st["codes"], V)
+        d.codes, d.scales = st["stream"].data_ptr(), None if mx else st["scales"].data_ptr()
+    else:
+        d.codes, d.scales = st["codes"].data_ptr(), st["scales"].data_ptr()
+    if mx and rows > 64:
+        if st["e4m3"] is None:        # W~ is e4m3-exact under one row scale (include/p2t_hip.h, "MXFP4 decoder weights"): the projections' rule
+            st["e4m3"] = ops.quant_rows_fp8(ops.dequant_rows_mxfp4(st["codes"], st["scales"], H, round_up(H, 64)), H)
+        d.codes_e4m3, d.scales_e4m3 = st["e4m3"][0].data_ptr(), st["e4m3"][1].data_ptr()
+    return d, st
+
+
+def lm_head_logits_q(x: torch.Tensor, norm_w: Optional[torch.Tensor], eps: float, head, vocab: int, ld_logits: Optional[int] = None,
+                     return_act: bool = False, out: Optional[torch.Tensor] = None):
+    """p2t_lm_head_logits_q: x f32 [M, hidden] (the residual stream; norm_w None: rows that are normalised already) -> logits bf16
+    [M, ld_logits] on the quantised head `head` (_lib.LmHeadQC); return_act: also the e4m3 rows [M, Kq] and their E8M0 bytes [M] that
+    the GEMM read.  `out`: write into this buffer (columns vocab .. are left as they are)."""
+    if x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1:
+        raise ValueError("lm_head_logits_q: x must be f32 [rows, hidden], row-major")
+    M, H = x.shape
+    ld = round_up(vocab, 64) if ld_logits is None else ld_logits
+    if out is None:
+        out = torch.zeros((M, ld), dtype=torch.bfloat16, device=x.device)
+    aq = torch.empty((M, round_up(H, 128)), dtype=torch.uint8, device=x.device) if return_act else None
+    asc = torch.empty((M,), dtype=torch.uint8, device=x.device) if return_act else None
+    ws = None if return_act else torch.empty((call("p2t_lm_head_q_workspace_bytes", M, H),), dtype=torch.uint8, device=x.device)
+    call("p2t_lm_head_logits_q", ptr(x), x.stride(0), ptr(norm_w), float(eps), C.byref(head), M, H, int(vocab), ptr(out), out.stride(0), ops.dt_of(out),
+         ptr(aq), ptr(asc), ptr(ws), ws.numel() if ws is not None else 0, stream())
+    return (out, aq, asc) if return_act else out
 
 
 class DecodeEngine:
     """Cache + buffers of ONE generate() call: B0 prompts, `group` rows per prompt (beams), capacities Tp / G (multiples of 64)."""
 
     def __init__(self, decoder, B0: int, group: int, T: int, max_new_tokens: int, stream_copy: bool = True, fuse_rope: bool = True,
-                 processors: Optional[dict] = None, eos_ids: Sequence[int] = (), prompt_kv_dtype: Optional[str] = None):
+                 processors: Optional[dict] = None, eos_ids: Sequence[int] = (), prompt_kv_dtype: Optional[str] = None,
+                 lm_head_dtype: Optional[str] = None):
         m, s = decoder.model, decoder.spec
         if prompt_kv_dtype not in (None, "fp8"):
             raise ValueError(f"prompt_kv_dtype must be None or 'fp8' (got {prompt_kv_dtype!r})")
         if prompt_kv_dtype == "fp8" and m.dtype != torch.bfloat16:
             raise ValueError("prompt_kv_dtype='fp8' (the e4m3 prompt segment of the KV cache) serves bf16 models only")
+        if lm_head_dtype not in (None, "fp8", "mxfp4"):
+            raise ValueError(f"lm_head_dtype must be None, 'fp8' or 'mxfp4' (got {lm_head_dtype!r})")
+        if lm_head_dtype is not None and m.dtype != torch.bfloat16:
+            raise ValueError(f"lm_head_dtype={lm_head_dtype!r} (the quantised LM head of the decode step) serves bf16 models only")
+        if lm_head_dtype is not None and B0 * group > 64 and s.vocab_size % 16:
+            raise ValueError(f"lm_head_dtype={lm_head_dtype!r} with more than 64 rows (got {B0 * group}) runs the general fp8 GEMM, which serves a "
+                             f"vocabulary that is a multiple of 16 only (got {s.vocab_size})")
         self.flags = 0 if fuse_rope else 1          # P2T_DECODE_NO_ROPE_FUSION
         if s.hidden_size % 64:
             raise ValueError("the LM head path needs hidden_size % 64 == 0")
@@ -262,12 +337,21 @@ class DecodeEngine:
         self.lm_head = decoder._lm_head_padded()
         # the stream-order copies are read by the skinny GEMMs only (<= 64 rows): beyond that every projection and the LM head
         # run on the row-major weights (the LM head had no row-major fallback and returned wrong logits)
-        self.stream = stream_weights(decoder) if (stream_copy and self.dtype == torch.bfloat16 and B0 * group <= 64) else None
+        self.stream = stream_weights(decoder, lm_head=lm_head_dtype is None) if (stream_copy and self.dtype == torch.bfloat16 and B0 * group <= 64) else None
         # "mxfp4" decoders: up to 64 rows step on the 4-bit weights (their stream copies, or row-major under stream_copy=False);
         # beyond that the e4m3 copies of the same values serve, as in "fp8" mode
         self.mx = None                                                    # (host array of p2t_llama_layer_mxfp4, what it points to)
         if m.gemm_mxfp4 and B0 * group <= 64:
             self.mx = (self.stream["layers"], self.stream["keep"]) if self.stream else mxfp4_layers(self.e, False)
+        # lm_head_dtype: the final RMSNorm + LM head of the prefill's first token AND of every step on ONE quantised head (p2t_lm_head_q);
+        # its stream-order copy under the bf16 copies' condition (stream_copy, at most 64 rows), row-major e4m3 codes beyond 64 rows.
+        # None: nothing built, nothing allocated, p2t_llama_decode_step[_mxfp4] as ever
+        self.head_q = self.head_q_first = None
+        if lm_head_dtype is not None:
+            st = lm_head_q(decoder, lm_head_dtype)
+            self.head_q = head_q_struct(decoder, st, stream_copy and self.BB <= 64, self.BB)
+            self.head_q_first = head_q_struct(decoder, st, stream_copy and B0 <= 64, B0)      # the prefill's B0 rows
+            self.ws = torch.empty((self.ws.numel() + call("p2t_lm_head_q_workspace_bytes", self.BB, s.hidden_size),), dtype=torch.uint8, device=self.dev)
         self._cache_struct()
         self.processors = processors                                      # _processor_args' settings, or None: nothing allocated, nothing launched
         if processors is not None:
@@ -309,6 +393,8 @@ class DecodeEngine:
         last = torch.empty((B, H), dtype=torch.float32, device=self.dev)
         call("p2t_llama_prefill", C.byref(cfg), C.byref(self.e["w"]), ptr(embeds), ptr(mask), B, T, C.byref(self.cache), ptr(last), ptr(ws),
              ws.numel(), stream())
+        if self.head_q_first is not None:        # token 0 is scored by the matrix that scores token 1: the normalised rows, quantised, on the same head
+            return lm_head_logits_q(last, None, 0.0, self.head_q_first[0], self.spec.vocab_size, self.ld_logits)
         a = last if self.dtype == torch.float32 else ops.cast(last, self.dtype)
         return ops.gemm_nt(a, self.lm_head, None, n=self.spec.vocab_size, k=H, out_dtype=self.dtype)
 
@@ -320,6 +406,12 @@ class DecodeEngine:
     def decode_step(self):
         """One token per row from self.x -> self.logits; the device step counter advances."""
         st = self.stream
+        if self.head_q is not None:
+            layers = C.cast(st["layers"], C.POINTER(_lib.LlamaLayerStreamC)) if (st and self.mx is None) else None
+            mx = C.cast(self.mx[0], C.POINTER(_lib.LlamaLayerMxfp4C)) if self.mx is not None else None
+            call("p2t_llama_decode_step_q", C.byref(self.e["cfg"]), C.byref(self.e["w"]), layers, mx, None, 0, 0, C.byref(self.head_q[0]), C.byref(self.cache),
+                 ptr(self.x), ptr(self.logits), self.ld_logits, self.flags, ptr(self.ws), self.ws.numel(), stream())
+            return
         head = st["lm_head"] if st else self.lm_head
         if self.mx is not None:
             call("p2t_llama_decode_step_mxfp4", C.byref(self.e["cfg"]), C.byref(self.e["w"]), C.cast(self.mx[0], C.POINTER(_lib.LlamaLayerMxfp4C)), ptr(head),
@@ -394,7 +486,8 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
              output_logits: bool = False, use_graph: bool = True, sync_every: int = 16, generator: Optional[torch.Generator] = None,
              stream_copy: bool = True, fuse_rope: bool = True, seed: Optional[int] = None, beam_select: Optional[str] = None,
              repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
-             bad_words_ids: Optional[list] = None, suppress_tokens=None, prompt_kv_dtype: Optional[str] = None, **unused):
+             bad_words_ids: Optional[list] = None, suppress_tokens=None, prompt_kv_dtype: Optional[str] = None,
+             lm_head_dtype: Optional[str] = None, **unused):
     """`LlamaForCausalLM.generate` for prompts given as embeddings (or ids): greedy, sampling (temperature / top-k / top-p) and beam
     search with length penalty.  Returns the new token ids i64 [batch * num_return_sequences, n] (or a GenerateOutput).
 
@@ -425,6 +518,14 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     power-of-two scale per key and kv head for K and for V (p2t_kv_quant_store on the prefill's store, the attention of
     p2t_attention_decode_prompt_fp8 in the step): half the cache bytes a step reads; the generated segment stays bf16.  The prefill
     attends before the store, so the first token's logits do not change; every decoding mode runs unchanged around it.
+
+    `lm_head_dtype="fp8" | "mxfp4"` (bf16 models; ValueError otherwise; independent of `set_gemm_dtype` and `prompt_kv_dtype`) scores every
+    token -- the prefill's first one included -- with a quantised LM head: e4m3 codes + one power-of-two scale per vocabulary row, or
+    MXFP4 codes + one per 32 columns (lm_head_q: p2t_quant_rows_fp8 / p2t_quant_rows_mxfp4 of the bf16 head, built once per model),
+    against the final RMSNorm's row written as e4m3 (p2t_lm_head_logits_q inside p2t_llama_decode_step_q): half / 27 % of the bytes of
+    the step's largest launch.  It changes arithmetic and only which logits the decoding modes read; the bf16 head stays for None (the
+    parent's path, nothing built), for training and, with tied embeddings, for the embedding lookup.  More than 64 rows run the general
+    fp8 GEMM on row-major e4m3 codes of the same values.
 
     Logits processors under beam search (`num_beams > 1`) are opt-in: HF runs them on the log-softmax inside the beam step, with the
     beam's running sequence as the history, and ranks the processed rows.  `beam_select="device"` does that with two entry points inside
@@ -481,12 +582,13 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
             max_length=max_new_tokens, eos_ids=eos_ids, pad_id=int(pad_token_id), nb=num_beams, length_penalty=float(length_penalty),
             early_stopping=early_stopping, num_return_sequences=num_return_sequences, return_dict=return_dict_in_generate,
             output_scores=output_scores, output_logits=output_logits, stream_copy=stream_copy, beam_select=beam_select, use_graph=use_graph,
-            sync_every=sync_every, sampling=sampling, processors=proc, prompt_kv_dtype=prompt_kv_dtype))
+            sync_every=sync_every, sampling=sampling, processors=proc, prompt_kv_dtype=prompt_kv_dtype, lm_head_dtype=lm_head_dtype))
     R = int(num_return_sequences)
     if R != 1 and not do_sample:
         raise ValueError("greedy decoding returns one sequence per prompt: num_return_sequences > 1 needs do_sample=True or num_beams > 1")
     # R samples per prompt (HF repeats the prompt R times): R rows that SHARE the prompt segment of the cache, like the beams of a prompt
-    eng = DecodeEngine(decoder, B, R, T, max_new_tokens, stream_copy, fuse_rope, processors=proc, eos_ids=eos_ids, prompt_kv_dtype=prompt_kv_dtype)
+    eng = DecodeEngine(decoder, B, R, T, max_new_tokens, stream_copy, fuse_rope, processors=proc, eos_ids=eos_ids, prompt_kv_dtype=prompt_kv_dtype,
+                       lm_head_dtype=lm_head_dtype)
     embeds, mask = eng.compact(inputs_embeds, attention_mask)
     logits = eng.prefill(embeds, mask)
     if R > 1:
@@ -719,7 +821,7 @@ def _beam_search(decoder, inputs_embeds, attention_mask, o):
             raise ValueError(f"generate(beam_select='device'): p2t_beam_select serves 1 <= num_beams <= {BEAMS_MAX} with max(2, 1 + number of eos ids) * "
                              f"num_beams <= {KEEP_MAX} <= vocabulary (got num_beams = {nb}, {len(o.eos_ids)} eos ids); the torch path serves the rest")
     eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy, processors=o.processors, eos_ids=o.eos_ids,
-                       prompt_kv_dtype=o.prompt_kv_dtype)
+                       prompt_kv_dtype=o.prompt_kv_dtype, lm_head_dtype=o.lm_head_dtype)
     dev = eng.dev
     embeds, mask = eng.compact(inputs_embeds, attention_mask)
     first_logits = eng.prefill(embeds, mask)                                 # [B, ld]: the beams of a prompt start from the same state
@@ -818,7 +920,7 @@ def _beam_search_device(decoder, inputs_embeds, attention_mask, o):
     the end; steps run past the stop leave the state as it is."""
     B, V, nb, max_length, sampling = inputs_embeds.shape[0], decoder.spec.vocab_size, o.nb, o.max_length, o.sampling
     eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy, processors=o.processors, eos_ids=o.eos_ids,
-                       prompt_kv_dtype=o.prompt_kv_dtype)
+                       prompt_kv_dtype=o.prompt_kv_dtype, lm_head_dtype=o.lm_head_dtype)
     dev = eng.dev
     embeds, mask = eng.compact(inputs_embeds, attention_mask)
     first = eng.prefill(embeds, mask).repeat_interleave(nb, dim=0).contiguous()     # HF expands the prompt nb times before its prefill

@@ -434,6 +434,7 @@ class LlamaTextModel(nn.Module):
         self._engine = None
         self._train_engine = None
         self._stream_engine = None          # generation.stream_weights
+        self._lm_head_q = None              # generation.lm_head_q
 
     def _build_engine(self, n_layers: int):
         s, dt = self.spec, self.dtype
@@ -1088,7 +1089,7 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
         """Reference :217-251: `inputs` is the [prompt] only; the prompt embeddings (placeholders replaced by the adapter rows) come
         from `forward(return_decoder_inputs=True)` and go to `llama_decoder.generate(inputs_embeds=, attention_mask=, **kwargs)`.
         The output does not repeat the prompt (it went in as embeddings).  `prompt_kv_dtype="fp8"` among the kwargs (bf16 models): the
-        e4m3 prompt segment of the KV cache (generation.generate)."""
+        e4m3 prompt segment of the KV cache; `lm_head_dtype="fp8" | "mxfp4"` (bf16 models): the quantised LM head (generation.generate)."""
         if getattr(self.esm_encoder, "lora", None) is not None:
             raise NotImplementedError(_ENCODER_LORA_MSG)
         with torch.no_grad():

@@ -25,7 +25,10 @@ repetition_penalty 1.3 + no_repeat_ngram_size 3, the same with all five processo
 [B * beams, vocab] bf16 logits at histories of 0 and 64 tokens, p2t_beam_select_logprobs alone on its rows, and p2t_beam_select alone.
 python tools/generate_bench.py [B] [N] [beams] kv8 [fp8 | mxfp4]: the step with the bf16 and with the fp8 prompt segment of the KV cache
 (`prompt_kv_dtype="fp8"`), interleaved in one process, three runs each under graph replay, each next to a run of its prompt phase (beams > 1: beam_select="device", the beams of a
-prompt share its prompt segment): median and min .. max, and the cache bytes a step reads either way."""
+prompt share its prompt segment): median and min .. max, and the cache bytes a step reads either way.
+python tools/generate_bench.py [B] [N] [beams] head [fp8 | mxfp4] [kv8] [fp8 | mxfp4]: the step with the bf16 LM head (off) and with the
+quantised one (`lm_head_dtype=`; both formats when none is named), interleaved in one process, three runs each under graph replay, each
+next to a run of its prompt phase; `kv8`: the same again over the fp8 prompt segment; last: the tower GEMM dtype."""
 import os
 import sys
 import time
@@ -312,17 +315,59 @@ def kv8_mode(model, kw, B: int, N: int, beams: int, T: int, llama, gemm_dtype: s
               f"prompt phase {np.median(t_prompt[name]):.1f} ms", flush=True)
 
 
+def head_mode(model, kw, B: int, N: int, beams: int, T: int, llama, gemm_dtype: str, fmts, with_kv8: bool):
+    """The step with the bf16 LM head (off: the parent's arithmetic) and with the quantised one (`lm_head_dtype=`), interleaved in one
+    process, three runs each under graph replay, each next to a run of its prompt phase -- kv8_mode's method; with `kv8` the same again
+    over the fp8 prompt segment of the KV cache."""
+    if beams > 1:
+        kw = {**kw, "beam_select": "device"}
+    H, V = llama.hidden_size, llama.vocab_size
+    head_bytes = {None: 2.0 * V * H, "fp8": 1.0 * V * H + V, "mxfp4": V * H * 17.0 / 32.0}
+
+    def timed(**over):
+        t0 = time.perf_counter()
+        model.generate(**{**kw, **over})
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    for kv in ((None, "fp8") if with_kv8 else (None,)):
+        cases = [("bf16 LM head (off)", None)] + [(f"{f} LM head (lm_head_dtype=\"{f}\")", f) for f in fmts]
+        extra = lambda f: dict(lm_head_dtype=f, prompt_kv_dtype=kv)
+        for _, f in cases:                                       # warm-up of each path: engines, the quantised head and its stream copy
+            model.generate(**{**kw, **extra(f), "max_new_tokens": 6})
+        torch.cuda.synchronize()
+        runs = {name: [] for name, _ in cases}
+        for _ in range(3):                                       # interleaved: a drift of the box hits every case alike
+            for name, f in cases:
+                t1 = timed(**extra(f), max_new_tokens=1)
+                runs[name].append((timed(**extra(f)) - t1) / (N - 1) * 1e3)
+        off = np.median(runs[cases[0][0]])
+        for name, f in cases:
+            r = runs[name]
+            print(f"generate cfg3{' ' + gemm_dtype + ' GEMMs' if gemm_dtype != 'model' else ''}{' kv8' if kv else ''}: B={B} beams={beams} prompt {T} tokens, "
+                  f"{N} new tokens, graph replay, {name}: median {np.median(r):.3f} ms/step (min {min(r):.3f}, max {max(r):.3f}; 3 runs), "
+                  f"{np.median(r) - off:+.3f} ms vs off; head bytes per step {head_bytes[f] / 1e9:.3f} GB", flush=True)
+
+
 def main():
     dev = torch.device("cuda:0")
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
     N = int(sys.argv[2]) if len(sys.argv) > 2 else 128
     sample = len(sys.argv) > 3 and sys.argv[3] == "sample"
     process = len(sys.argv) > 3 and sys.argv[3] == "process"
-    kv8 = "kv8" in sys.argv[3:5]
-    beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample and not process and sys.argv[3] != "kv8" else 1
+    head = "head" in sys.argv[3:5]                               # [B] [N] [beams] head [fp8 | mxfp4] [kv8] [fp8 | mxfp4 weights]
+    kv8 = "kv8" in sys.argv[3:5] and not head
+    beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample and not process and sys.argv[3] not in ("kv8", "head") else 1
     gemm_dtype = sys.argv[4] if len(sys.argv) > 4 and sys.argv[4] in ("fp8", "mxfp4") else "model"
     if kv8:                                                      # [B] [N] [beams] kv8 [fp8 | mxfp4]
         after = sys.argv[sys.argv.index("kv8") + 1:]
+        gemm_dtype = after[0] if after and after[0] in ("fp8", "mxfp4") else "model"
+    head_fmts, head_kv8 = ("fp8", "mxfp4"), False
+    if head:
+        after = sys.argv[sys.argv.index("head") + 1:]
+        if after and after[0] in ("fp8", "mxfp4"):
+            head_fmts, after = (after[0],), after[1:]
+        if after and after[0] == "kv8":
+            head_kv8, after = True, after[1:]
         gemm_dtype = after[0] if after and after[0] in ("fp8", "mxfp4") else "model"
     fp8 = gemm_dtype != "model"
     beam_sample = beams > 1 and len(sys.argv) > 4 and sys.argv[4] == "sample"
@@ -343,6 +388,8 @@ def main():
     t = lambda a: torch.from_numpy(a).to(dev)
     kw = dict(inputs=t(ids), attention_mask=torch.ones((B, T), dtype=torch.int64, device=dev), protein_input_ids=t(pid),
               protein_attention_mask=t(pmask), max_new_tokens=N, eos_token_id=None, pad_token_id=128002, do_sample=False, num_beams=beams)
+    if head:
+        return head_mode(model, kw, B, N, beams, T, llama, gemm_dtype, head_fmts, head_kv8)
     if kv8:
         return kv8_mode(model, kw, B, N, beams, T, llama, gemm_dtype)
     if sample:

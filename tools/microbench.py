@@ -213,6 +213,8 @@ def bench_skinny():
     shapes = [("o-proj", 4096, 4096, _lib.EPI_RESID), ("qkv", 6144, 4096, _lib.EPI_STORE_F32), ("gate/up", 28672, 4096, _lib.EPI_SWIGLU),
               ("down", 4096, 14336, _lib.EPI_RESID), ("lm head", 128256, 4096, _lib.EPI_STORE)]
     Ms = [int(a[1:]) for a in sys.argv if a.startswith("m") and a[1:].isdigit()] or [8, 32]
+    if "head" in sys.argv:              # `skinny head`: the LM head shape alone, bf16 / fp8 / mxfp4 (generate(lm_head_dtype=))
+        shapes = shapes[-1:]
     for M in Ms:
         for name, N, K, epi in shapes:
             copies = max(2, min(40, int(1.3e9 // (N * K * 2)) + 1))
@@ -239,8 +241,6 @@ def bench_skinny():
                 res.append(f"{'stream copy' if pre else 'row-major W'} {ms * 1e3:7.1f} us {N * K * 2 / ms / 1e6:6.0f} GB/s")
             print(f"skinny M={M:2d} {name:8s} N={N:6d} K={K:5d}: " + " | ".join(res), flush=True)
             del ws
-            if name == "lm head":       # stays bf16 in every mode
-                continue
             # the same projection on quantised weights: e4m3 + row scales (p2t_gemm_nt_skinny_fp8) and MXFP4 codes + block scales
             # (p2t_gemm_nt_skinny_mxfp4, 4.25 bits per weight), cold weights from a ring of copies as above
             from p2t_hip.generation import preshuffle_mxfp4
