@@ -949,6 +949,48 @@ int p2t_attention_decode_prompt_fp8(const void* q, const void* k_prompt, const v
  * atomics), V transposed through LDS.  Positions < T only: every byte behind them keeps its value.  T <= Tp, Tp % 64 == 0. */
 int p2t_kv_quant_store(const void* k, const void* v, int B, int kv_heads, int T, int head_dim, int Tp, void* k_codes, void* vt_codes,
                        uint8_t* k_scale, uint8_t* v_scale, p2t_stream stream);
+/* ---- continuous batching: rows that carry their OWN step counters (group == 1).  A finished row's slot is loaded with the next
+ * prompt while the other rows go on; every length lives on the device, so a captured step graph keeps replaying across refills.
+ * p2t_kv_cache keeps its layout: the counters travel beside it (row_step, device i32 [BB]) and cache->step is neither read nor
+ * written by these entry points (it may be NULL). */
+/* p2t_llama_decode_step_q with per-row counters: row r runs at position prompt_len[r] + row_step[r], its keys / values are appended at
+ * index clamp(row_step[r], 0, G - 1), its attention covers prompt_len[r] + row_step[r] + 1 keys, and last of all row_step[r] += 1 where
+ * frozen[r] == 0 (frozen: device i32 [BB], or NULL = no row is frozen).  A frozen row still runs (launch shapes are fixed): it
+ * re-appends at its own index and does not advance -- harmless, and safe for a slot that was never loaded (prompt_len 0, row_step 0,
+ * frozen: it attends to the one key it just wrote).  Every model and weight form of p2t_llama_decode_step_q; group != 1:
+ * P2T_ERR_UNSUPPORTED.  Equal counters and frozen == NULL: the logits and cache contents of p2t_llama_decode_step_q, bit for bit.
+ * Enqueues only: capturable. */
+int p2t_llama_decode_step_rows(const p2t_llama_config* cfg, const p2t_llama_weights* w, const p2t_llama_layer_stream* w_stream,
+                               const p2t_llama_layer_mxfp4* mx_layers, const void* lm_head, int64_t ld_head, int lm_head_preshuffled,
+                               const p2t_lm_head_q* head_q, const p2t_kv_cache* cache, const float* x, void* logits, int64_t ld_logits,
+                               int flags, void* workspace, size_t workspace_bytes, int32_t* row_step, const int32_t* frozen,
+                               p2t_stream stream);
+/* p2t_greedy_select over per-row counters: logits row i (of n) belongs to engine row r = row_map[i] (device i32 [n]; NULL: r = i and
+ * n == BB; an r outside [0, BB) touches nothing).  finished[r] != 0: next_tokens[r] = pad_id and NOTHING is written to out_tokens (the
+ * row's counter no longer moves: the token at it is its last one).  Otherwise next_tokens[r] = out_tokens[r, clamp(row_step[r], 0,
+ * G - 1)] = argmax(logits[i, :V]) (lowest index among equal maxima), then finished[r] |= 1 if that token is in eos_ids and
+ * finished[r] |= 2 if row_step[r] + 1 >= row_limit[r] (device i32 [BB], 1 .. G: the row's own max_new_tokens).  row_step is not
+ * written.  Enqueues only: capturable. */
+int p2t_greedy_select_rows(const void* logits, int dtype, int64_t ld, int V, int n, const int64_t* eos_ids, int n_eos, int64_t pad_id,
+                           int32_t* finished, int64_t* next_tokens, int64_t* out_tokens, int64_t ld_tokens, const int32_t* row_step,
+                           const int32_t* row_limit, const int32_t* row_map, int BB, int G, p2t_stream stream);
+/* Loads k freshly prefilled prompts into slots of a running engine.  p2t_llama_prefill wants cache->B0 == B, so the k prompts are
+ * prefilled into `staging` (a p2t_kv_cache with B0 = k, the same Tp and the same prompt-segment format; its generated segment is not
+ * touched); this call copies staging row i's prompt segment -- K, transposed V and, when set, both scale arrays, ALL Tp entries of every
+ * layer, so nothing of the previous occupant stays -- into slot slots[i] of `cache` in ONE launch of 16-byte loads and stores, and sets
+ * cache->prompt_len[slot] = staging->prompt_len[i], row_step[slot] = 0, finished[slot] = 0, row_limit[slot] = limits[i].  slots, limits:
+ * HOST i32 [k] (they travel in the launch's arguments).  Refused before the launch: a slot outside [0, cache->B0) or named twice, a
+ * limit outside 1 .. cache->G, k != staging->B0, different Tp, scale arrays on one cache only, buffers that are not 16-byte aligned
+ * (P2T_ERR_ARG); more than 256 slots per call (P2T_ERR_UNSUPPORTED).  No allocation, copy or synchronisation; meant to run between
+ * graph replays, not inside a capture. */
+int p2t_kv_slot_load(const p2t_llama_config* cfg, const p2t_kv_cache* staging, const p2t_kv_cache* cache, const int32_t* slots,
+                     const int32_t* limits, int k, int32_t* row_step, int32_t* finished, int32_t* row_limit, p2t_stream stream);
+/* p2t_attention_decode (k_prompt_scale == v_prompt_scale == NULL) / p2t_attention_decode_prompt_fp8 (both set) with one counter per row:
+ * row r attends to prompt_len[r] keys of the prompt segment and row_step[r] + 1 of the generated one (group == 1, BB = B0). */
+int p2t_attention_decode_rows(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
+                              const int32_t* prompt_len, const int32_t* row_step, int B0, int nh, int nkv, int head_dim, int Tp, int G,
+                              float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out,
+                              const uint8_t* k_prompt_scale, const uint8_t* v_prompt_scale, p2t_stream stream);
 /* Beam re-ordering of the generated segment: row r of (k_dst, vt_dst) = row src_row[r] of the cache's generated segment, the
  * first step[0] tokens of every layer / head (k_dst, vt_dst: second buffers of the same shape; the caller swaps). */
 int p2t_kv_reorder(const p2t_llama_config* cfg, const p2t_kv_cache* cache, const int64_t* src_row, void* k_dst, void* vt_dst,

@@ -63,7 +63,7 @@ __device__ __forceinline__ void skinny_finish(float (&red)[kSkWaves][NT][MT][64]
                 const int hd = ra.d, half = hd >> 1, blk = n >> 6;
                 const int head = hd == 64 ? blk : blk >> 1;
                 const int ch = (hd == 64 ? 0 : 32 * (blk & 1)) + (n & 31);
-                const int step = min(max(ra.step[0], 0), ra.G - 1);
+                const int step = min(max(ra.step[(int64_t)m * ra.step_stride], 0), ra.G - 1);
                 if (head < ra.nh + ra.nkv) {
                     const bool is_q = head < ra.nh;
                     const float qs = is_q ? ra.q_scale : 1.0f, pos = (float)(ra.prompt_len[m / ra.group] + step);

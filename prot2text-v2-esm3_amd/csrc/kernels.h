@@ -142,10 +142,11 @@ static inline GemmArgs gemm_args_fp8(const void* A, int64_t lda, const uint8_t* 
 static inline void with_fix(GemmArgs& g, void* ws, unsigned& epoch) { g.fix_ws = ws; g.fix_bytes = gemm_fix_workspace_bytes(); g.fix_epoch = ++epoch; }
 // weight-streaming GEMM for M <= 64 rows (gemm_skinny.hip): bf16, epilogues STORE / STORE_F32 / RESID / SWIGLU, no bias;
 // P2T_ERR_UNSUPPORTED for anything else
-// epilogue arguments of launch_gemm_skinny_qkv_rope: rotation at position prompt_len[row / group] + step[0] and the cache append
+// epilogue arguments of launch_gemm_skinny_qkv_rope: rotation at position prompt_len[row / group] + step[row * step_stride] and the cache
+// append (step_stride 0: the shared lock-step counter, 1: every row's own)
 struct SkinnyRope {
     const float* inv_freq = nullptr; const int32_t* prompt_len = nullptr; const int32_t* step = nullptr;
-    int group = 1, nh = 0, nkv = 0, d = 0, G = 0; float q_scale = 1.f;
+    int group = 1, nh = 0, nkv = 0, d = 0, G = 0; float q_scale = 1.f; int step_stride = 0;
     void* q = nullptr;       // bf16 [M, nh, d]
     void* k = nullptr;       // bf16 [M, nkv, G, d]   (one layer of p2t_kv_cache.k_gen)
     void* vt = nullptr;      // bf16 [M, nkv, d, G]   (one layer of p2t_kv_cache.vt_gen)

@@ -13,6 +13,10 @@
 //   * every row generates in lock-step: ONE device counter `step` = generated tokens already in the cache.  A decode step reads it on
 //     the device (so the whole step replays as a HIP graph without a host round trip), appends at index `step`, attends to
 //     prompt_len[b0] + step + 1 keys and increments it last;
+//   * opt-in (continuous batching, p2t_llama_decode_step_rows; group == 1): every row carries its OWN counter, row_step[row], beside the
+//     cache -- the same kernels read step[row * stride] with stride 1 where the lock-step entry points pass stride 0.  A finished row
+//     is frozen (it re-appends at its own index and does not advance); p2t_kv_slot_load copies a freshly prefilled prompt segment from a
+//     staging cache into its slot and resets its counters, between two replays of the step graph;
 //   * opt-in for bf16 models (p2t_kv_cache's scale arrays set): the PROMPT segment as e4m3 codes in the same index order + one E8M0 scale
 //     byte per key for K and for V -- quantised by the prefill's store (kv_quant_store_kernel), read by the F8 tiles of the attention.
 #include "common.h"
@@ -154,14 +158,14 @@ template <typename T>
 __global__ void __launch_bounds__(256) rope_append_kernel(const float* __restrict__ qkv, int64_t ldq, const float* __restrict__ inv_freq,
                                                           const float* __restrict__ qw, const float* __restrict__ kw, float eps,
                                                           const int32_t* __restrict__ prompt_len, const int32_t* __restrict__ step_ptr,
-                                                          int group, T* __restrict__ qbuf, T* __restrict__ kg, T* __restrict__ vtg, int BB,
+                                                          int step_stride, int group, T* __restrict__ qbuf, T* __restrict__ kg, T* __restrict__ vtg, int BB,
                                                           int nh, int nkv, int d, int dp, int G, float q_scale, int packed128,
                                                           int round_first) {
     const int lane = threadIdx.x & 63, heads = nh + 2 * nkv, half = d / 2;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= BB * heads) return;
     const int bb = row / heads, hh = row - bb * heads;
-    const int step = min(max(step_ptr[0], 0), G - 1);
+    const int step = min(max(step_ptr[(int64_t)bb * step_stride], 0), G - 1);      // stride 0: the shared counter, 1: row bb's own
     const int pos = prompt_len[bb / group] + step;
     const float* src = qkv + (int64_t)bb * ldq + (int64_t)hh * d;
     auto at = [&](int j) {
@@ -249,7 +253,7 @@ template <typename T, int DP, int GH>
 __global__ void __launch_bounds__(512) attn_decode_kernel(const T* __restrict__ q, const T* __restrict__ kp, const T* __restrict__ vtp,
                                                           const T* __restrict__ kg, const T* __restrict__ vtg,
                                                           const int32_t* __restrict__ prompt_len, const int32_t* __restrict__ step_ptr,
-                                                          int group, int nh, int nkv, int G, int Tp, int Gcap, float c_exp, int round_p,
+                                                          int step_stride, int group, int nh, int nkv, int G, int Tp, int Gcap, float c_exp, int round_p,
                                                           T* __restrict__ out, int64_t ld_out, int d) {
     constexpr int PN = Piece<T>::N, R = DP > 64 ? DP / 64 : 1, PW = DP + 2, NW = 8;
     __shared__ float sq[GH][DP];
@@ -264,7 +268,7 @@ __global__ void __launch_bounds__(512) attn_decode_kernel(const T* __restrict__ 
         sq[g][c] = g < nhead ? to_f32(q[((int64_t)bb * nh + h0 + g) * DP + c]) : 0.f;
     }
     __syncthreads();
-    const int n0 = min(max(prompt_len[b0], 0), Tp), n1 = min(max(step_ptr[0], 0) + 1, Gcap);
+    const int n0 = min(max(prompt_len[b0], 0), Tp), n1 = min(max(step_ptr[(int64_t)bb * step_stride], 0) + 1, Gcap);
     const int tiles0 = (n0 + 63) >> 6, tiles = tiles0 + ((n1 + 63) >> 6);
     const T* k_seg0 = kp + ((int64_t)b0 * nkv + kvh) * Tp * DP;
     const T* k_seg1 = kg + ((int64_t)bb * nkv + kvh) * Gcap * DP;
@@ -513,8 +517,8 @@ __global__ void __launch_bounds__(NW * 64) attn_decode_mfma_kernel(const bf16_t*
                                                                const void* __restrict__ vtp, const bf16_t* __restrict__ kg,
                                                                const bf16_t* __restrict__ vtg, const uint8_t* __restrict__ kps,
                                                                const uint8_t* __restrict__ vps, const int32_t* __restrict__ prompt_len,
-                                                               const int32_t* __restrict__ step_ptr, int group, int nh, int nkv, int G, int Tp,
-                                                               int Gcap, float c_exp, bf16_t* __restrict__ out, int64_t ld_out, int d) {
+                                                               const int32_t* __restrict__ step_ptr, int step_stride, int group, int nh, int nkv, int G,
+                                                               int Tp, int Gcap, float c_exp, bf16_t* __restrict__ out, int64_t ld_out, int d) {
     constexpr int PW = DP + 2, KK = DP / 32, DT = DP / 16, EP = P8 ? 1 : 2;       // EP: bytes per element of the prompt segment
     __shared__ float red[NW][GH][PW];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
@@ -532,7 +536,7 @@ __global__ void __launch_bounds__(NW * 64) attn_decode_mfma_kernel(const bf16_t*
     };
     bf16x8 qf[KK];
     load_q(qf, P8);
-    const int n0 = min(max(prompt_len[b0], 0), Tp), n1 = min(max(step_ptr[0], 0) + 1, Gcap);
+    const int n0 = min(max(prompt_len[b0], 0), Tp), n1 = min(max(step_ptr[(int64_t)bb * step_stride], 0) + 1, Gcap);
     const int tiles0 = (n0 + 63) >> 6, tiles = tiles0 + ((n1 + 63) >> 6);
     const char* k_seg0 = (const char*)kp + ((int64_t)b0 * nkv + kvh) * Tp * DP * EP;
     const bf16_t* k_seg1 = kg + ((int64_t)bb * nkv + kvh) * Gcap * DP;
@@ -575,16 +579,13 @@ __global__ void __launch_bounds__(NW * 64) attn_decode_mfma_kernel(const bf16_t*
 // ---------------------------------------------------------------------------------------------
 // torch.argmax semantics over the first V columns (lowest index among equal maxima), then HF's finished-row rule
 // (generation/utils.py, _sample: next = next * unfinished + pad * (1 - unfinished); a row finishes once it emits an eos id).
+// argmax of one logits row by a block of 1024 threads; thread 0 returns it (the other threads' value is their wave's or their own)
 template <typename T>
-__global__ void __launch_bounds__(1024) greedy_select_kernel(const T* __restrict__ logits, int64_t ld, int V, const int64_t* __restrict__ eos,
-                                                             int n_eos, int64_t pad, int32_t* __restrict__ finished,
-                                                             int64_t* __restrict__ next, int64_t* __restrict__ out_tokens, int64_t ld_tok,
-                                                             const int32_t* __restrict__ step_ptr, int Gcap) {
+__device__ __forceinline__ int greedy_argmax(const T* __restrict__ row, int64_t ld, int V) {
     constexpr int PN = Piece<T>::N, kNone = 0x7fffffff;
     __shared__ float bv[16];
     __shared__ int bi[16];
-    const int bb = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const T* row = logits + (int64_t)bb * ld;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     float best = -INFINITY;
     int idx = kNone;
     auto take = [&](float v, int c) {                   // ascending c per thread: a later equal value never replaces an earlier one
@@ -610,6 +611,18 @@ __global__ void __launch_bounds__(1024) greedy_select_kernel(const T* __restrict
     if (tid == 0) {
         for (int ww = 1; ww < 16; ++ww)
             if (better(bv[ww], bi[ww], best, idx)) { best = bv[ww]; idx = bi[ww]; }
+    }
+    return idx;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(1024) greedy_select_kernel(const T* __restrict__ logits, int64_t ld, int V, const int64_t* __restrict__ eos,
+                                                             int n_eos, int64_t pad, int32_t* __restrict__ finished,
+                                                             int64_t* __restrict__ next, int64_t* __restrict__ out_tokens, int64_t ld_tok,
+                                                             const int32_t* __restrict__ step_ptr, int Gcap) {
+    const int bb = blockIdx.x;
+    const int idx = greedy_argmax<T>(logits + (int64_t)bb * ld, ld, V);
+    if (threadIdx.x == 0) {
         int64_t tok = idx;
         const int fin = finished[bb];
         if (fin) tok = pad;
@@ -619,6 +632,63 @@ __global__ void __launch_bounds__(1024) greedy_select_kernel(const T* __restrict
         if (!fin) {
             for (int e = 0; e < n_eos; ++e)
                 if (tok == eos[e]) finished[bb] = 1;
+        }
+    }
+}
+
+// The greedy choice of rows that carry their OWN counters (continuous batching): logits row blockIdx.x belongs to engine row
+// row_map[blockIdx.x] (nullptr: itself).  A finished row emits pad and writes no token -- its counter no longer moves, and the token
+// at it is its last one; a live row writes its token at its own index and picks up the eos bit (1) and the limit bit (2).
+template <typename T>
+__global__ void __launch_bounds__(1024) greedy_select_rows_kernel(const T* __restrict__ logits, int64_t ld, int V, const int64_t* __restrict__ eos,
+                                                                  int n_eos, int64_t pad, int32_t* __restrict__ finished,
+                                                                  int64_t* __restrict__ next, int64_t* __restrict__ out_tokens, int64_t ld_tok,
+                                                                  const int32_t* __restrict__ row_step, const int32_t* __restrict__ row_limit,
+                                                                  const int32_t* __restrict__ row_map, int BB, int Gcap) {
+    const int r = row_map ? row_map[blockIdx.x] : (int)blockIdx.x;
+    if (r < 0 || r >= BB) return;                        // the whole block: a row the engine does not have touches nothing
+    const int idx = greedy_argmax<T>(logits + (int64_t)blockIdx.x * ld, ld, V);
+    if (threadIdx.x == 0) {
+        if (finished[r]) { next[r] = pad; return; }
+        const int64_t tok = idx;
+        const int st = min(max(row_step[r], 0), Gcap - 1);
+        next[r] = tok;
+        out_tokens[(int64_t)r * ld_tok + st] = tok;
+        int fin = 0;
+        for (int e = 0; e < n_eos; ++e)
+            if (tok == eos[e]) fin |= 1;
+        if (st + 1 >= min(max(row_limit[r], 1), Gcap)) fin |= 2;
+        if (fin) finished[r] |= fin;
+    }
+}
+
+// Staging row i's prompt segment -> slot tab.slot[i] of the engine's cache, every layer: per (layer, i) the kv heads of a tensor are ONE
+// contiguous run in both caches (K [kv][Tp][dp], V^T [kv][dp][Tp], the scale bytes [kv][Tp]), a multiple of 16 bytes since Tp % 64 == 0.
+// grid (pieces, layers * k, tensors): 16-byte loads and stores, whole capacity Tp -- nothing of the slot's previous occupant stays.
+// The slots and limits travel in the launch's arguments (host arrays, checked there): no copy, no allocation.
+constexpr int kSlotLoadMax = 256;
+struct SlotTable { int32_t slot[kSlotLoadMax]; int32_t limit[kSlotLoadMax]; };
+
+__global__ void __launch_bounds__(256) kv_slot_load_kernel(const char* __restrict__ ks, const char* __restrict__ vs, const char* __restrict__ kss,
+                                                           const char* __restrict__ vss, char* __restrict__ kd, char* __restrict__ vd, char* __restrict__ ksd,
+                                                           char* __restrict__ vsd, int64_t seg_bytes, int64_t scale_bytes, int k, int B0,
+                                                           const int32_t* __restrict__ len_src, int32_t* __restrict__ len_dst, int32_t* __restrict__ row_step,
+                                                           int32_t* __restrict__ finished, int32_t* __restrict__ row_limit, SlotTable tab) {
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    const int l = blockIdx.y / k, i = blockIdx.y - l * k, which = blockIdx.z;
+    const int slot = tab.slot[i];                        // 0 .. B0 - 1, distinct: checked on the host before the launch
+    const int64_t n = which < 2 ? seg_bytes : scale_bytes;
+    const char* src = (which == 0 ? ks : which == 1 ? vs : which == 2 ? kss : vss) + ((int64_t)l * k + i) * n;
+    char* dst = (which == 0 ? kd : which == 1 ? vd : which == 2 ? ksd : vsd) + ((int64_t)l * B0 + slot) * n;
+    for (int64_t o = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16; o < n; o += (int64_t)gridDim.x * 256 * 16)
+        *reinterpret_cast<u32x4*>(dst + o) = *reinterpret_cast<const u32x4*>(src + o);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && which == 0) {
+        for (int j = threadIdx.x; j < k; j += 256) {
+            const int s = tab.slot[j];
+            len_dst[s] = len_src[j];
+            row_step[s] = 0;
+            finished[s] = 0;
+            row_limit[s] = tab.limit[j];
         }
     }
 }
@@ -640,7 +710,11 @@ __global__ void __launch_bounds__(256) kv_reorder_kernel(const T* __restrict__ k
     }
 }
 
-__global__ void advance_kernel(int32_t* step) { step[0] += 1; }
+// n counters `stride` apart (lock-step: ONE, <<<1, 1>>>; per-row counters: BB at stride 1); a frozen row keeps its own
+__global__ void advance_kernel(int32_t* step, int stride, const int32_t* __restrict__ frozen, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && !(frozen && frozen[i])) step[(int64_t)i * stride] += 1;
+}
 
 struct DecodeBuffers {
     float* x; void* h; float* qkv; void* qb; void* ao; void* act; float* inv_freq;
@@ -686,7 +760,7 @@ size_t decode_plan(const p2t_llama_config* c, int BB, int Tp, int Gcap, Arena* a
 
 template <typename T>
 int launch_attn_decode_t(const DecodeBuffers& b, const p2t_kv_cache* kc, int layer, int BB, int nh, int nkv, int d, int dp, float c_exp, int round_p,
-                         int64_t QO, hipStream_t s, int use_mfma = 1) {
+                         int64_t QO, hipStream_t s, int use_mfma = 1, int step_stride = 0) {
     const int G = nh / nkv;
     const size_t per_p = (size_t)kc->B0 * nkv * kc->Tp * dp, per_g = (size_t)BB * nkv * kc->G * dp;
     const T* kp = (const T*)kc->k_prompt + per_p * layer;
@@ -705,7 +779,7 @@ int launch_attn_decode_t(const DecodeBuffers& b, const p2t_kv_cache* kc, int lay
 #define P2T_ADM(DPV, GHV, P8V)                                                                                                        \
     attn_decode_mfma_kernel<DPV, GHV, (GHV <= 4 && DPV <= 64 ? 16 : 8), P8V><<<grid, (GHV <= 4 && DPV <= 64 ? 16 : 8) * 64, 0, s>>>(    \
         (const bf16_t*)b.qb, P8V ? (const void*)kp8 : (const void*)kp, P8V ? (const void*)vtp8 : (const void*)vtp, (const bf16_t*)kg,  \
-        (const bf16_t*)vtg, kps, vps, kc->prompt_len, kc->step, kc->group, nh, nkv, G, kc->Tp, kc->G, c_exp, (bf16_t*)b.ao, QO, d)
+        (const bf16_t*)vtg, kps, vps, kc->prompt_len, kc->step, step_stride, kc->group, nh, nkv, G, kc->Tp, kc->G, c_exp, (bf16_t*)b.ao, QO, d)
 #define P2T_ADM_G(DPV, P8V)                                                                                                           \
     do {                                                                                                                              \
         if (b.GH == 1) P2T_ADM(DPV, 1, P8V); else if (b.GH == 2) P2T_ADM(DPV, 2, P8V); else if (b.GH == 4) P2T_ADM(DPV, 4, P8V);       \
@@ -724,7 +798,7 @@ int launch_attn_decode_t(const DecodeBuffers& b, const p2t_kv_cache* kc, int lay
     }
     P2T_REQUIRE(!kc->k_prompt_scale, "attention over an fp8 prompt segment: the matrix-pipe kernel only");
 #define P2T_AD(DPV, GHV)                                                                                                              \
-    attn_decode_kernel<T, DPV, GHV><<<grid, 512, 0, s>>>((const T*)b.qb, kp, vtp, kg, vtg, kc->prompt_len, kc->step, kc->group, nh, nkv, G, \
+    attn_decode_kernel<T, DPV, GHV><<<grid, 512, 0, s>>>((const T*)b.qb, kp, vtp, kg, vtg, kc->prompt_len, kc->step, step_stride, kc->group, nh, nkv, G, \
                                                          kc->Tp, kc->G, c_exp, round_p, (T*)b.ao, QO, d)
 #define P2T_AD_G(DPV)                                                                                                                 \
     do {                                                                                                                              \
@@ -896,14 +970,36 @@ static int lm_head_q_run(const float* x, int64_t ld_x, const float* norm_w, floa
                                       P2T_EPI_STORE), s);
 }
 
+// the step's last launch: the shared counter (stride 0: one thread, as ever), or every row's own where it is not frozen
+static int launch_advance(int32_t* step, int stride, const int32_t* frozen, int BB, hipStream_t s) {
+    if (stride == 0) advance_kernel<<<1, 1, 0, s>>>(step, 0, nullptr, 1);
+    else advance_kernel<<<(unsigned)ceil_div(BB, 256), 256, 0, s>>>(step, stride, frozen, BB);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
 // mx: the MXFP4 form of the projections (p2t_llama_decode_step_mxfp4; a gemm_fp8 model, at most 64 rows) or nullptr
 static int decode_step_impl(const p2t_llama_config* c, const p2t_llama_weights* w, const p2t_llama_layer_stream* ws_layers, const p2t_llama_layer_mxfp4* mx,
                             const void* lm_head, int64_t ld_head, int lm_head_preshuffled, const p2t_kv_cache* cache, const float* x_in, void* logits,
                             int64_t ld_logits, int flags, void* workspace, size_t workspace_bytes, p2t_stream stream, const p2t_lm_head_q* head_q = nullptr,
-                            const char* who = "p2t_llama_decode_step") {
+                            const char* who = "p2t_llama_decode_step", int32_t* row_step = nullptr, const int32_t* frozen = nullptr) {
     P2T_REQUIRE(c && w && w->layers && w->final_norm_w && (lm_head || head_q) && x_in && logits && workspace, "%s: null argument", who);
     const bool fuse_rope = !(flags & P2T_DECODE_NO_ROPE_FUSION);
+    // per-row counters (p2t_llama_decode_step_rows): the same launches read row_step[row] where the lock-step ones read step[0]; the
+    // cache's own counter is neither read nor written
+    p2t_kv_cache rows_cache;
+    const int sstride = row_step ? 1 : 0;
+    if (row_step) {
+        P2T_REQUIRE(cache, "%s: null cache", who);
+        rows_cache = *cache;
+        rows_cache.step = row_step;
+        cache = &rows_cache;
+    }
     P2T_TRY(check_cache(c, cache, who));
+    if (row_step && cache->group != 1) {
+        set_error("%s: per-row counters serve group == 1 only (got %d)", who, cache->group);
+        return P2T_ERR_UNSUPPORTED;
+    }
     P2T_REQUIRE(!c->gemm_fp8 || c->dtype == P2T_BF16, "%s: gemm_fp8 needs bf16 activations (dtype = P2T_BF16)", who);
     const int BB = cache->B0 * cache->group;
     const int dt = c->dtype;
@@ -974,7 +1070,7 @@ static int decode_step_impl(const p2t_llama_config* c, const p2t_llama_weights* 
         bool roped = false;
         if (fused_prefill && fuse_rope) {
             SkinnyRope ra;
-            ra.inv_freq = inv_freq; ra.prompt_len = cache->prompt_len; ra.step = cache->step; ra.group = cache->group;
+            ra.inv_freq = inv_freq; ra.prompt_len = cache->prompt_len; ra.step = cache->step; ra.step_stride = sstride; ra.group = cache->group;
             ra.nh = nh; ra.nkv = nkv; ra.d = d; ra.G = cache->G; ra.q_scale = q_fold;
             ra.q = b.qb; ra.k = (bf16_t*)cache->k_gen + per_g * l; ra.vt = (bf16_t*)cache->vt_gen + per_g * l;
             const int r = gemm8(b.hq, Hq, b.hs, L.qkv_w, L.qkv_ws, S ? S->qkv_w : nullptr, nullptr, 0, NQKV, Hq, dt, 0, &ra, s, xq);
@@ -984,11 +1080,11 @@ static int decode_step_impl(const p2t_llama_config* c, const p2t_llama_weights* 
             P2T_TRY(gemm8(b.hq, Hq, b.hs, L.qkv_w, L.qkv_ws, S ? S->qkv_w : nullptr, b.qkv, NQKV, NQKV, Hq, P2T_F32, P2T_EPI_STORE_F32, nullptr, s, xq));
             const unsigned grid = (unsigned)ceil_div((int64_t)BB * (nh + 2 * nkv), 4);
             rope_append_kernel<bf16_t><<<grid, 256, 0, s>>>(b.qkv, NQKV, inv_freq, L.q_norm_w, L.k_norm_w, c->rms_norm_eps, cache->prompt_len, cache->step,
-                                                            cache->group, (bf16_t*)b.qb, (bf16_t*)cache->k_gen + per_g * l, (bf16_t*)cache->vt_gen + per_g * l,
+                                                            sstride, cache->group, (bf16_t*)b.qb, (bf16_t*)cache->k_gen + per_g * l, (bf16_t*)cache->vt_gen + per_g * l,
                                                             BB, nh, nkv, d, dp, cache->G, q_fold, d == 128 && !L.q_norm_w, !fused_prefill);
             P2T_LAUNCH_CHECK();
         }
-        P2T_TRY(launch_attn_decode_t<bf16_t>(b, cache, l, BB, nh, nkv, d, dp, c_exp, 1, QO, s));
+        P2T_TRY(launch_attn_decode_t<bf16_t>(b, cache, l, BB, nh, nkv, d, dp, c_exp, 1, QO, s, 1, sstride));
         P2T_TRY(launch_quant_rows_few(b.ao, dt, QO, M, (int64_t)nh * d, b.aoq, QOq, b.aos, s));
         P2T_TRY(gemm8(b.aoq, QOq, b.aos, L.o_w, L.o_ws, S ? S->o_w : nullptr, b.x, H, H, QOq, P2T_F32, P2T_EPI_RESID, nullptr, s, xo));
         P2T_TRY(launch_rmsnorm_fp8_few(b.x, H, L.ln2_w, c->rms_norm_eps, b.hq, Hq, b.hs, M, H, s));
@@ -1005,7 +1101,7 @@ static int decode_step_impl(const p2t_llama_config* c, const p2t_llama_weights* 
         if (fused_prefill && dt == P2T_BF16 && fuse_rope) {   // projection + rotation + cache append in one launch (SK_QKV_ROPE)
             const size_t per_g = (size_t)BB * nkv * cache->G * dp;
             SkinnyRope ra;
-            ra.inv_freq = inv_freq; ra.prompt_len = cache->prompt_len; ra.step = cache->step; ra.group = cache->group;
+            ra.inv_freq = inv_freq; ra.prompt_len = cache->prompt_len; ra.step = cache->step; ra.step_stride = sstride; ra.group = cache->group;
             ra.nh = nh; ra.nkv = nkv; ra.d = d; ra.G = cache->G; ra.q_scale = q_fold;
             ra.q = b.qb; ra.k = (bf16_t*)cache->k_gen + per_g * l; ra.vt = (bf16_t*)cache->vt_gen + per_g * l;
             const int r = launch_gemm_skinny_qkv_rope(b.h, Hp, stream_w ? ws_layers[l].qkv_w : L.qkv_w, Hp, M, NQKV, Hp, ra, s, stream_w);
@@ -1020,19 +1116,19 @@ static int decode_step_impl(const p2t_llama_config* c, const p2t_llama_weights* 
                 const size_t per_g = (size_t)BB * nkv * cache->G * dp;
                 if (dt == P2T_BF16)
                     rope_append_kernel<bf16_t><<<grid, 256, 0, s>>>(b.qkv, NQKV, inv_freq, L.q_norm_w, L.k_norm_w, c->rms_norm_eps, cache->prompt_len,
-                                                                    cache->step, cache->group, (bf16_t*)b.qb, (bf16_t*)cache->k_gen + per_g * l,
+                                                                    cache->step, sstride, cache->group, (bf16_t*)b.qb, (bf16_t*)cache->k_gen + per_g * l,
                                                                     (bf16_t*)cache->vt_gen + per_g * l, BB, nh, nkv, d, dp, cache->G, q_fold,
                                                                     d == 128 && !L.q_norm_w, !fused_prefill);
                 else
                     rope_append_kernel<float><<<grid, 256, 0, s>>>(b.qkv, NQKV, inv_freq, L.q_norm_w, L.k_norm_w, c->rms_norm_eps, cache->prompt_len,
-                                                                   cache->step, cache->group, (float*)b.qb, (float*)cache->k_gen + per_g * l,
+                                                                   cache->step, sstride, cache->group, (float*)b.qb, (float*)cache->k_gen + per_g * l,
                                                                    (float*)cache->vt_gen + per_g * l, BB, nh, nkv, d, dp, cache->G, q_fold,
                                                                    d == 128 && !L.q_norm_w, 0);
                 P2T_LAUNCH_CHECK();
             }
         }
-        if (dt == P2T_BF16) P2T_TRY(launch_attn_decode_t<bf16_t>(b, cache, l, BB, nh, nkv, d, dp, c_exp, 1, QO, s));
-        else P2T_TRY(launch_attn_decode_t<float>(b, cache, l, BB, nh, nkv, d, dp, c_exp, 0, QO, s));
+        if (dt == P2T_BF16) P2T_TRY(launch_attn_decode_t<bf16_t>(b, cache, l, BB, nh, nkv, d, dp, c_exp, 1, QO, s, 1, sstride));
+        else P2T_TRY(launch_attn_decode_t<float>(b, cache, l, BB, nh, nkv, d, dp, c_exp, 0, QO, s, 1, sstride));
         GemmArgs g2(b.ao, QO, L.o_w, QO, M, H, QO, dt, b.x, H, P2T_F32, P2T_EPI_RESID);
         P2T_TRY(gemm_nt(g2, s, stream_w ? ws_layers[l].o_w : nullptr));
         P2T_TRY(launch_rmsnorm_few_rows(b.x, H, L.ln2_w, c->rms_norm_eps, b.h, Hp, M, H, dt, s));
@@ -1043,9 +1139,7 @@ static int decode_step_impl(const p2t_llama_config* c, const p2t_llama_weights* 
     }
     if (head_q) {                                        // one more branch after the layer loops: the e4m3 / MXFP4 head on the residual stream
         P2T_TRY(lm_head_q_run(b.x, H, w->final_norm_w, c->rms_norm_eps, head_q, M, H, c->vocab, logits, ld_logits, head_aq, head_as, s));
-        advance_kernel<<<1, 1, 0, s>>>(cache->step);
-        P2T_LAUNCH_CHECK();
-        return P2T_OK;
+        return launch_advance(cache->step, sstride, frozen, BB, s);
     }
     P2T_REQUIRE(!lm_head_preshuffled || dt == P2T_BF16, "%s: pre-shuffled weights are a bf16 layout", who);
     // the stream-order copy is only readable by the skinny kernels (<= 64 rows): beyond that the general GEMM would read the
@@ -1055,9 +1149,7 @@ static int decode_step_impl(const p2t_llama_config* c, const p2t_llama_weights* 
     P2T_TRY(launch_rmsnorm_few_rows(b.x, H, w->final_norm_w, c->rms_norm_eps, b.h, Hp, M, H, dt, s));
     GemmArgs gh(b.h, Hp, lm_head, ld_head, M, c->vocab, Hp, dt, logits, ld_logits, dt, P2T_EPI_STORE);
     P2T_TRY(gemm_nt(gh, s, lm_head_preshuffled ? lm_head : nullptr));
-    advance_kernel<<<1, 1, 0, s>>>(cache->step);
-    P2T_LAUNCH_CHECK();
-    return P2T_OK;
+    return launch_advance(cache->step, sstride, frozen, BB, s);
 }
 
 extern "C" int p2t_llama_decode_step(const p2t_llama_config* c, const p2t_llama_weights* w, const p2t_llama_layer_stream* ws_layers,
@@ -1101,6 +1193,27 @@ extern "C" int p2t_llama_decode_step_q(const p2t_llama_config* c, const p2t_llam
                             stream, head_q, "p2t_llama_decode_step_q");
 }
 
+// p2t_llama_decode_step_q for rows that carry their own counters (continuous batching, include/p2t_hip.h): the same launches, every
+// `step[0]` read as row_step[row]; the last launch advances the rows that are not frozen.
+extern "C" int p2t_llama_decode_step_rows(const p2t_llama_config* c, const p2t_llama_weights* w, const p2t_llama_layer_stream* ws_layers,
+                                          const p2t_llama_layer_mxfp4* mx_layers, const void* lm_head, int64_t ld_head, int lm_head_preshuffled,
+                                          const p2t_lm_head_q* head_q, const p2t_kv_cache* cache, const float* x_in, void* logits, int64_t ld_logits,
+                                          int flags, void* workspace, size_t workspace_bytes, int32_t* row_step, const int32_t* frozen,
+                                          p2t_stream stream) {
+    P2T_REQUIRE(row_step, "p2t_llama_decode_step_rows: null row_step");
+    P2T_REQUIRE(!(ws_layers && mx_layers), "p2t_llama_decode_step_rows: w_stream and mx_layers are two forms of the same projections: pass one");
+    if (mx_layers) {
+        P2T_REQUIRE(c && cache, "p2t_llama_decode_step_rows: null argument");
+        P2T_REQUIRE(c->gemm_fp8 && c->dtype == P2T_BF16, "p2t_llama_decode_step_rows: mx_layers need a gemm_fp8 configuration with bf16 activations");
+        P2T_REQUIRE((int64_t)cache->B0 * cache->group <= 64, "p2t_llama_decode_step_rows: mx_layers serve at most 64 rows (got %lld): beyond that the e4m3 weights serve",
+                    (long long)cache->B0 * cache->group);
+        for (int l = 1; l < c->n_layers; ++l)
+            P2T_REQUIRE(!mx_layers[l].stream_order == !mx_layers[0].stream_order, "p2t_llama_decode_step_rows: layers differ in stream_order");
+    }
+    return decode_step_impl(c, w, ws_layers, mx_layers, lm_head, ld_head, lm_head_preshuffled, cache, x_in, logits, ld_logits, flags, workspace, workspace_bytes,
+                            stream, head_q, "p2t_llama_decode_step_rows", row_step, frozen);
+}
+
 extern "C" size_t p2t_lm_head_q_workspace_bytes(int64_t M, int64_t hidden) { return lm_head_q_ws_bytes(M, hidden); }
 
 extern "C" int p2t_lm_head_logits_q(const float* x, int64_t ld_x, const float* norm_w, float eps, const p2t_lm_head_q* head, int64_t M, int64_t hidden,
@@ -1141,6 +1254,66 @@ extern "C" int p2t_greedy_select(const void* logits, int dtype, int64_t ld, int 
     return P2T_OK;
 }
 
+extern "C" int p2t_greedy_select_rows(const void* logits, int dtype, int64_t ld, int V, int n, const int64_t* eos_ids, int n_eos, int64_t pad_id,
+                                      int32_t* finished, int64_t* next_tokens, int64_t* out_tokens, int64_t ld_tokens, const int32_t* row_step,
+                                      const int32_t* row_limit, const int32_t* row_map, int BB, int G, p2t_stream stream) {
+    P2T_REQUIRE(logits && finished && next_tokens && out_tokens && row_step && row_limit, "p2t_greedy_select_rows: null argument");
+    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_greedy_select_rows: logits are f32 or bf16 (got dtype %d)", dtype);
+    P2T_REQUIRE(n > 0 && BB > 0 && n <= BB && (row_map || n == BB), "p2t_greedy_select_rows: %d logits rows for %d engine rows (all of them, or a row_map subset)", n,
+                BB);
+    P2T_REQUIRE(V > 0 && ld >= V && G > 0 && ld_tokens >= G && n_eos >= 0 && (n_eos == 0 || eos_ids), "p2t_greedy_select_rows: bad shape arguments");
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == P2T_BF16)
+        greedy_select_rows_kernel<bf16_t><<<n, 1024, 0, s>>>((const bf16_t*)logits, ld, V, eos_ids, n_eos, pad_id, finished, next_tokens, out_tokens,
+                                                            ld_tokens, row_step, row_limit, row_map, BB, G);
+    else
+        greedy_select_rows_kernel<float><<<n, 1024, 0, s>>>((const float*)logits, ld, V, eos_ids, n_eos, pad_id, finished, next_tokens, out_tokens,
+                                                           ld_tokens, row_step, row_limit, row_map, BB, G);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
+extern "C" int p2t_kv_slot_load(const p2t_llama_config* c, const p2t_kv_cache* staging, const p2t_kv_cache* cache, const int32_t* slots,
+                                const int32_t* limits, int k, int32_t* row_step, int32_t* finished, int32_t* row_limit, p2t_stream stream) {
+    P2T_REQUIRE(c && staging && cache && slots && limits && row_step && finished && row_limit, "p2t_kv_slot_load: null argument");
+    P2T_REQUIRE(c->n_layers > 0 && c->kv_heads > 0, "p2t_kv_slot_load: empty model");
+    p2t_kv_cache from = *staging, to = *cache;           // neither cache's own counter is read or written: the rows' counters stand in for the check
+    from.step = to.step = row_step;
+    P2T_TRY(check_cache(c, &from, "p2t_kv_slot_load (staging)"));
+    P2T_TRY(check_cache(c, &to, "p2t_kv_slot_load"));
+    P2T_REQUIRE(cache->group == 1, "p2t_kv_slot_load: group == 1 only (got %d)", cache->group);
+    P2T_REQUIRE(staging->Tp == cache->Tp, "p2t_kv_slot_load: the staging cache holds %d prompt tokens per row, the engine's %d", staging->Tp, cache->Tp);
+    P2T_REQUIRE(!staging->k_prompt_scale == !cache->k_prompt_scale,
+                "p2t_kv_slot_load: the two caches differ in the prompt segment's format (scale arrays on one of them only)");
+    P2T_REQUIRE(k > 0 && k == staging->B0 && k <= cache->B0, "p2t_kv_slot_load: %d slots from a staging cache of %d rows into %d slots", k, staging->B0, cache->B0);
+    if (k > kSlotLoadMax || (int64_t)c->n_layers * k > 65535) {
+        set_error("p2t_kv_slot_load: at most %d slots per call and 65535 (layer, slot) pairs (got %d slots)", kSlotLoadMax, k);
+        return P2T_ERR_UNSUPPORTED;
+    }
+    SlotTable tab;
+    for (int i = 0; i < k; ++i) {
+        P2T_REQUIRE(slots[i] >= 0 && slots[i] < cache->B0, "p2t_kv_slot_load: slot %d (entry %d) outside [0, %d)", slots[i], i, cache->B0);
+        for (int j = 0; j < i; ++j) P2T_REQUIRE(slots[j] != slots[i], "p2t_kv_slot_load: slot %d is named twice (entries %d and %d)", slots[i], j, i);
+        P2T_REQUIRE(limits[i] >= 1 && limits[i] <= cache->G, "p2t_kv_slot_load: row limit %d (entry %d) outside 1 .. %d", limits[i], i, cache->G);
+        tab.slot[i] = slots[i];
+        tab.limit[i] = limits[i];
+    }
+    for (int i = k; i < kSlotLoadMax; ++i) tab.slot[i] = tab.limit[i] = 0;
+    const void* bufs[] = {staging->k_prompt, staging->vt_prompt, staging->k_prompt_scale, staging->v_prompt_scale, cache->k_prompt, cache->vt_prompt,
+                          cache->k_prompt_scale, cache->v_prompt_scale};
+    for (const void* p : bufs) P2T_REQUIRE(((uintptr_t)p & 15) == 0, "p2t_kv_slot_load: the prompt segments' buffers must be 16-byte aligned");
+    const bool f8 = cache->k_prompt_scale != nullptr;
+    const int dp = head_dim_padded(c->head_dim);
+    const int64_t scale_bytes = (int64_t)c->kv_heads * cache->Tp, seg_bytes = scale_bytes * dp * (f8 ? 1 : (int64_t)dtype_size(c->dtype));
+    const dim3 grid((unsigned)std::min<int64_t>(ceil_div(seg_bytes, 256 * 16), 64), (unsigned)(c->n_layers * k), f8 ? 4u : 2u);
+    kv_slot_load_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const char*)staging->k_prompt, (const char*)staging->vt_prompt, (const char*)staging->k_prompt_scale,
+                                                              (const char*)staging->v_prompt_scale, (char*)cache->k_prompt, (char*)cache->vt_prompt,
+                                                              (char*)cache->k_prompt_scale, (char*)cache->v_prompt_scale, seg_bytes, scale_bytes, k, cache->B0,
+                                                              staging->prompt_len, const_cast<int32_t*>(cache->prompt_len), row_step, finished, row_limit, tab);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
 extern "C" int p2t_kv_reorder(const p2t_llama_config* c, const p2t_kv_cache* cache, const int64_t* src_row, void* k_dst, void* vt_dst,
                               p2t_stream stream) {
     P2T_REQUIRE(c && src_row && k_dst && vt_dst, "p2t_kv_reorder: null argument");
@@ -1162,7 +1335,7 @@ extern "C" int p2t_kv_reorder(const p2t_llama_config* c, const p2t_kv_cache* cac
 static int attention_decode_impl(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
                                  const int32_t* prompt_len, const int32_t* step, int B0, int group, int nh, int nkv, int head_dim, int Tp, int G,
                                  float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out, const uint8_t* k_prompt_scale,
-                                 const uint8_t* v_prompt_scale, p2t_stream stream) {
+                                 const uint8_t* v_prompt_scale, p2t_stream stream, int step_stride = 0) {
     P2T_REQUIRE(q && out && (dtype == P2T_F32 || dtype == P2T_BF16) && nkv > 0 && nh % nkv == 0 && ld_out >= (int64_t)nh * head_dim,
                 "p2t_attention_decode: bad arguments");
     p2t_llama_config c{};
@@ -1181,9 +1354,9 @@ static int attention_decode_impl(const void* q, const void* k_prompt, const void
     b.ao = out;
     hipStream_t s = (hipStream_t)stream;
     const float c_exp = log2_scores ? 1.0f : scale * kLog2e;
-    if (dtype == P2T_BF16) return launch_attn_decode_t<bf16_t>(b, &kc, 0, BB, nh, nkv, head_dim, dp, c_exp, 1, ld_out, s, use_mfma != 0);
+    if (dtype == P2T_BF16) return launch_attn_decode_t<bf16_t>(b, &kc, 0, BB, nh, nkv, head_dim, dp, c_exp, 1, ld_out, s, use_mfma != 0, step_stride);
     P2T_REQUIRE(use_mfma <= 0, "p2t_attention_decode: the matrix-pipe kernel is bf16 only");
-    return launch_attn_decode_t<float>(b, &kc, 0, BB, nh, nkv, head_dim, dp, c_exp, 0, ld_out, s);
+    return launch_attn_decode_t<float>(b, &kc, 0, BB, nh, nkv, head_dim, dp, c_exp, 0, ld_out, s, 1, step_stride);
 }
 
 extern "C" int p2t_attention_decode(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
@@ -1201,6 +1374,17 @@ extern "C" int p2t_attention_decode_prompt_fp8(const void* q, const void* k_prom
     P2T_REQUIRE(k_prompt_scale, "p2t_attention_decode_prompt_fp8: null scale arrays (p2t_attention_decode serves the bf16 prompt segment)");
     return attention_decode_impl(q, k_prompt, vt_prompt, k_gen, vt_gen, prompt_len, step, B0, group, nh, nkv, head_dim, Tp, G, scale, log2_scores, dtype,
                                  use_mfma, out, ld_out, k_prompt_scale, v_prompt_scale, stream);
+}
+
+// p2t_attention_decode / p2t_attention_decode_prompt_fp8 (the scale arrays both set) with one counter per row: group == 1
+extern "C" int p2t_attention_decode_rows(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
+                                         const int32_t* prompt_len, const int32_t* row_step, int B0, int nh, int nkv, int head_dim, int Tp, int G,
+                                         float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out,
+                                         const uint8_t* k_prompt_scale, const uint8_t* v_prompt_scale, p2t_stream stream) {
+    P2T_REQUIRE(row_step, "p2t_attention_decode_rows: null row_step");
+    P2T_REQUIRE(!k_prompt_scale == !v_prompt_scale, "p2t_attention_decode_rows: k_prompt_scale and v_prompt_scale go together");
+    return attention_decode_impl(q, k_prompt, vt_prompt, k_gen, vt_gen, prompt_len, row_step, B0, 1, nh, nkv, head_dim, Tp, G, scale, log2_scores, dtype,
+                                 use_mfma, out, ld_out, k_prompt_scale, v_prompt_scale, stream, 1);
 }
 
 extern "C" int p2t_kv_quant_store(const void* k, const void* v, int B, int kv_heads, int T, int head_dim, int Tp, void* k_codes, void* vt_codes,

@@ -25,7 +25,8 @@ __all__ = ["specs", "synth", "Esm2LlamaInstructConfig", "ModalityAdapterConfig",
            "EsmSequenceTokenizer", "ContrastiveCollater", "DevicePrefetcher", "sort_batch_by_length", "pack_instruct_batch", "CosineWarmupSchedule", "save_checkpoint",
            "load_model_checkpoint", "load_optimizer_scheduler_checkpoint", "train_epoch", "eval_epoch", "run_epochs",
            "iterative_generation_loop", "inference_epoch", "load_and_merge_adapter",
-           "InstructTrainer", "FlatAdamW", "save_instruct_checkpoint", "load_instruct_checkpoint", "run_instruct_epochs", "instruct_schedule"]
+           "InstructTrainer", "FlatAdamW", "save_instruct_checkpoint", "load_instruct_checkpoint", "run_instruct_epochs", "instruct_schedule",
+           "ContinuousDecoder", "ContinuousScheduler"]
 
 _LAZY = {
     "Esm2LlamaInstructConfig": "configuration", "ModalityAdapterConfig": "configuration",
@@ -40,6 +41,7 @@ _LAZY = {
     "train_epoch": "loop", "eval_epoch": "loop", "run_epochs": "loop", "iterative_generation_loop": "loop", "inference_epoch": "loop", "load_and_merge_adapter": "lora",
     "InstructTrainer": "instruct", "FlatAdamW": "instruct", "save_instruct_checkpoint": "instruct", "load_instruct_checkpoint": "instruct",
     "run_instruct_epochs": "instruct", "instruct_schedule": "instruct",
+    "ContinuousDecoder": "continuous", "ContinuousScheduler": "continuous",
 }
 
 

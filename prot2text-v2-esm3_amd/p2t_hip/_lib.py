@@ -175,6 +175,12 @@ SIGNATURES = {
                                     C.POINTER(KvCacheC), vp, vp, i64, i32, vp, sz, vp]),
     "p2t_llama_decode_step_q": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), C.POINTER(LlamaLayerStreamC), C.POINTER(LlamaLayerMxfp4C), vp, i64,
                                 i32, C.POINTER(LmHeadQC), C.POINTER(KvCacheC), vp, vp, i64, i32, vp, sz, vp]),
+    "p2t_llama_decode_step_rows": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), C.POINTER(LlamaLayerStreamC), C.POINTER(LlamaLayerMxfp4C), vp,
+                                   i64, i32, C.POINTER(LmHeadQC), C.POINTER(KvCacheC), vp, vp, i64, i32, vp, sz, vp, vp, vp]),
+    "p2t_greedy_select_rows": (i32, [vp, i32, i64, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, vp, vp, i32, i32, vp]),
+    "p2t_kv_slot_load": (i32, [C.POINTER(LlamaConfigC), C.POINTER(KvCacheC), C.POINTER(KvCacheC), C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, vp, vp,
+                         vp, vp]),
+    "p2t_attention_decode_rows": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp, i64, vp, vp, vp]),
     "p2t_lm_head_q_workspace_bytes": (sz, [i64, i64]),
     "p2t_lm_head_logits_q": (i32, [vp, i64, vp, f32, C.POINTER(LmHeadQC), i64, i64, i64, vp, i64, i32, vp, vp, vp, sz, vp]),
     "p2t_greedy_select": (i32, [vp, i32, i64, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, i32, vp]),

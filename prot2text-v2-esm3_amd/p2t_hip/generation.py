@@ -370,28 +370,31 @@ class DecodeEngine:
                                    v_prompt_scale=self.v_prompt_scale.data_ptr() if self.v_prompt_scale is not None else None)
 
     # -- prompt -------------------------------------------------------------------------------------------------------------
-    def compact(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor):
-        """Valid tokens first (positions = HF's cumsum(mask) - 1 on them); -> (embeds, prefix mask) trimmed to the longest row."""
+    def compact(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, lens: Optional[torch.Tensor] = None):
+        """Valid tokens first (positions = HF's cumsum(mask) - 1 on them); -> (embeds, prefix mask) trimmed to the longest row.
+        `lens` (i32 [B], device): receives the rows' lengths in the cache's own prompt_len's place (a staging cache's)."""
+        lens = self.lens if lens is None else lens
         B, T, H = inputs_embeds.shape
         x = inputs_embeds.to(device=self.dev, dtype=torch.float32).contiguous()
         mask = attention_mask.to(device=self.dev, dtype=torch.int64).contiguous()
         out, out_mask = torch.empty_like(x), torch.empty_like(mask)
         scratch = torch.empty((B * T,), dtype=torch.int32, device=self.dev)
-        call("p2t_compact_rows", ptr(x), ptr(mask), B, T, H, ptr(out), ptr(out_mask), ptr(self.lens), ptr(scratch), stream())
-        longest = int(self.lens.max().item())                            # the one host read of the prompt phase
+        call("p2t_compact_rows", ptr(x), ptr(mask), B, T, H, ptr(out), ptr(out_mask), ptr(lens), ptr(scratch), stream())
+        longest = int(lens.max().item())                            # the one host read of the prompt phase
         if longest < 1:
             raise ValueError("every prompt row needs at least one token under its attention mask")
         if longest < T:
             out, out_mask = out[:, :longest].contiguous(), out_mask[:, :longest].contiguous()
         return out, out_mask
 
-    def prefill(self, embeds: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
-        """-> logits of the first new token, model dtype [B0, ld] (row b from prompt b's last valid token)."""
+    def prefill(self, embeds: torch.Tensor, mask: torch.Tensor, cache=None) -> torch.Tensor:
+        """-> logits of the first new token, model dtype [B0, ld] (row b from prompt b's last valid token).  `cache`: another
+        p2t_kv_cache of exactly the batch's rows than the engine's own (continuous batching's staging cache)."""
         B, T, H = embeds.shape
         cfg = self.e["cfg"]
         ws = torch.empty((call("p2t_llama_prefill_workspace_bytes", C.byref(cfg), B, T),), dtype=torch.uint8, device=self.dev)
         last = torch.empty((B, H), dtype=torch.float32, device=self.dev)
-        call("p2t_llama_prefill", C.byref(cfg), C.byref(self.e["w"]), ptr(embeds), ptr(mask), B, T, C.byref(self.cache), ptr(last), ptr(ws),
+        call("p2t_llama_prefill", C.byref(cfg), C.byref(self.e["w"]), ptr(embeds), ptr(mask), B, T, C.byref(self.cache if cache is None else cache), ptr(last), ptr(ws),
              ws.numel(), stream())
         if self.head_q_first is not None:        # token 0 is scored by the matrix that scores token 1: the normalised rows, quantised, on the same head
             return lm_head_logits_q(last, None, 0.0, self.head_q_first[0], self.spec.vocab_size, self.ld_logits)

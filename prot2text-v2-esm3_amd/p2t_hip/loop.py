@@ -206,17 +206,55 @@ def generation_seed(seed: int, rank: int, batch_index: int) -> int:
     return mix64(mix64(mix64((int(seed) + 0x9E3779B97F4A7C15) & (2 ** 64 - 1)) ^ (int(rank) & (2 ** 64 - 1))) ^ (int(batch_index) & (2 ** 64 - 1)))
 
 
+def _inference_continuous(rank, model, dataloader, llama_tokenizer, args: Dict[str, Any], progress, eos_token_id=128009, pad_token_id: int = 128002):
+    """inference_epoch's generation with args["continuous_slots"] rows that refill as requests finish (p2t_hip/continuous.py; greedy
+    only): every batch is submitted as it comes, the results return to dataset order by request id, and each prediction is decoded as
+    the row `generate` would have returned (the tokens up to its eos, pad behind)."""
+    model = getattr(model, "module", model)
+    dev = torch.device("cuda", rank) if isinstance(rank, int) else torch.device(rank)
+    batches = list(dataloader)
+    if not batches:
+        return [], [], []
+    longest = max(int(b["attention_mask"].shape[1]) for b in batches)     # the placeholders are replaced in place: the id prompt's length
+    kw = {k: args[k] for k in ("prompt_kv_dtype", "lm_head_dtype", "sync_every") if args.get(k) is not None}
+    gen = model.continuous_generator(slots=int(args["continuous_slots"]), max_prompt_tokens=longest, max_new_tokens=args["max_generation_length"],
+                                     eos_token_id=eos_token_id, pad_token_id=pad_token_id, num_beams=args.get("num_beams", 1),
+                                     do_sample=args.get("do_sample", False), **kw)
+    names, labels, ids = [], [], []
+    for data_batch in batches:
+        to = lambda k: data_batch[k].to(dev)
+        with torch.no_grad():
+            ids.extend(gen.submit(to("input_ids"), to("attention_mask"), to("protein_input_ids"), to("protein_attention_mask")))
+        names.extend(data_batch["name"])
+        labels.extend(llama_tokenizer.batch_decode(data_batch["description_input_ids"], skip_special_tokens=True))
+    done = {}
+    for n, (rid, toks) in enumerate(gen.run()):
+        done[rid] = toks.cpu()
+        if progress is not None:
+            progress(n, {"mode": "inference", "batch_maxlen_gen": int(toks.numel()), "device": f"rank:{rank}"})
+    width = max(int(t.numel()) for t in done.values())
+    out = torch.full((len(ids), width), pad_token_id, dtype=torch.int64)
+    for row, rid in enumerate(ids):
+        out[row, : done[rid].numel()] = done[rid]
+    return names, llama_tokenizer.batch_decode(out, skip_special_tokens=True), labels
+
+
 def inference_epoch(rank, model, dataloader: Iterable[Dict[str, Any]], llama_tokenizer, args: Dict[str, Any],
                     progress: Optional[Callable] = None) -> Optional[str]:
     """scripts/generate_instruct.py:90-147: generate for every batch of this rank's shard, decode predictions and labels with the
     description tokenizer (`batch_decode(..., skip_special_tokens=True)`) and write
     `generation_{save_generation_postfix_identifier}_rank{rank}.json` = {name: {"true": label, "pred": prediction}} into
-    `save_generation_dir` (returned).  Every rank generates on its own (a DistributedSampler shard per rank upstream): no collective."""
+    `save_generation_dir` (returned).  Every rank generates on its own (a DistributedSampler shard per rank upstream): no collective.
+    args["continuous_slots"] (optional, greedy only): that many decode rows with continuous batching instead of one lock-step `generate`
+    per batch (p2t_hip/continuous.py) -- the same JSON, names in dataset order."""
     import json
     import os
     model.eval()
     names, preds, labels = [], [], []
     r = rank if isinstance(rank, int) else (torch.device(rank).index or 0)
+    if args.get("continuous_slots"):
+        names, preds, labels = _inference_continuous(rank, model, dataloader, llama_tokenizer, args, progress)
+        dataloader = ()
     for i, data_batch in enumerate(dataloader):
         # args["seed"] (optional): the device sampler's seed of this call, mixed from (seed, rank, batch index) so that neither two ranks
         # nor two successive batches draw from one stream (generate(seed=): row and step are the stream's other two coordinates)

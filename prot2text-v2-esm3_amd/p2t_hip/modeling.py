@@ -1099,6 +1099,17 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
                                               return_decoder_inputs=True)
         return self.llama_decoder.generate(inputs_embeds=prompt_embeds, attention_mask=prompt_mask, **kwargs)
 
+    def continuous_generator(self, slots: int, max_prompt_tokens: int, max_new_tokens: int, **kwargs):
+        """Greedy `generate` over a queue of requests with continuous batching (p2t_hip/continuous.py): `slots` rows decode together, each
+        on its own step counter, and a finished row's slot takes the next waiting prompt.  Returns a ContinuousGenerator: `submit(inputs,
+        attention_mask, protein_input_ids, protein_attention_mask, max_new_tokens=None)` runs the encoder + adapter + placeholder
+        scatter of that batch exactly as `generate` does and returns request ids; `run()` yields (request id, tokens) as requests
+        finish.  kwargs: eos_token_id, pad_token_id, sync_every, use_graph, stream_copy, prompt_kv_dtype, lm_head_dtype, output_logits."""
+        if getattr(self.esm_encoder, "lora", None) is not None:
+            raise NotImplementedError(_ENCODER_LORA_MSG)
+        from .continuous import ContinuousGenerator
+        return ContinuousGenerator(self, slots, max_prompt_tokens, max_new_tokens, **kwargs)
+
     def add_lora(self, r: int, lora_alpha: Optional[float] = None, lora_dropout: float = 0.1, target_modules=None, seed: int = 0):
         """`get_peft_model(model, LoraConfig(r, lora_alpha = 2 r, lora_dropout = 0.1, target_modules = [...],
         modules_to_save = adapter.fc1 / fc2))` of scripts/train_instruct.py:155-183: trainable A / B pairs on every module a target

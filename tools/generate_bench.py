@@ -28,7 +28,14 @@ python tools/generate_bench.py [B] [N] [beams] kv8 [fp8 | mxfp4]: the step with 
 prompt share its prompt segment): median and min .. max, and the cache bytes a step reads either way.
 python tools/generate_bench.py [B] [N] [beams] head [fp8 | mxfp4] [kv8] [fp8 | mxfp4]: the step with the bf16 LM head (off) and with the
 quantised one (`lm_head_dtype=`; both formats when none is named), interleaved in one process, three runs each under graph replay, each
-next to a run of its prompt phase; `kv8`: the same again over the fp8 prompt segment; last: the tower GEMM dtype."""
+next to a run of its prompt phase; `kv8`: the same again over the fp8 prompt segment; last: the tower GEMM dtype.
+python tools/generate_bench.py [slots] [Tnew] continuous [fp8 | mxfp4] [kv8] [head fp8 | head mxfp4]: continuous batching (p2t_hip/continuous.py)
+against lock-step decoding on one queue of 8 x slots requests at the bench's prompt shape, whose limits are drawn once from a seeded
+log-normal clipped to 1 .. Tnew (random weights have no natural eos: the limit is what ends a row).  (a) batches of `slots` through the
+decoder's plain `generate` with max_new_tokens = the batch's longest limit -- what lock-step decoding with an eos costs; (b) the same
+requests through ContinuousDecoder.  Interleaved, three runs each, on the decoder alone (the prompt embeddings are computed once and
+shared): useful tokens/s (sum of limits / wall time) and the fraction of row-steps spent on finished rows, for both; then ms per step of
+p2t_llama_decode_step_rows against the lock-step step at equal counters, under graph replay."""
 import os
 import sys
 import time
@@ -348,6 +355,81 @@ def head_mode(model, kw, B: int, N: int, beams: int, T: int, llama, gemm_dtype: 
                   f"{np.median(r) - off:+.3f} ms vs off; head bytes per step {head_bytes[f] / 1e9:.3f} GB", flush=True)
 
 
+def continuous_mode(model, kw, slots: int, Tnew: int, T: int, gemm_dtype: str, extra: dict):
+    from p2t_hip.continuous import ContinuousDecoder, ContinuousEngine
+    dec = model.llama_decoder
+    n_req = 8 * slots
+    rs = np.random.RandomState(1)
+    limits = np.clip(np.rint(np.exp(rs.normal(np.log(Tnew / 4.0), 0.8, size=n_req))), 1, Tnew).astype(int).tolist()
+    with torch.no_grad():
+        emb, mask = model(input_ids=kw["inputs"], attention_mask=kw["attention_mask"], protein_input_ids=kw["protein_input_ids"],
+                          protein_attention_mask=kw["protein_attention_mask"], return_decoder_inputs=True)
+    pad = kw["pad_token_id"]
+    batches = [limits[i:i + slots] for i in range(0, n_req, slots)]
+    useful_steps = sum(l - 1 for l in limits)                    # the first token of a request comes out of its prefill
+
+    def lock_step():
+        for lim in batches:
+            out = dec.generate(inputs_embeds=emb, attention_mask=mask, max_new_tokens=max(lim), eos_token_id=None, pad_token_id=pad, do_sample=False, **extra)
+            assert out.shape[1] == max(lim)
+        return sum(slots * (max(lim) - 1) for lim in batches)
+
+    def continuous():
+        cd = ContinuousDecoder(dec, slots, T, Tnew, eos_token_id=None, pad_token_id=pad, sync_every=8, **extra)
+        for i in range(0, n_req, slots):
+            cd.submit(emb, mask, max_new_tokens=limits[i:i + slots])
+        got = {rid: int(toks.numel()) for rid, toks in cd.run()}
+        assert [got[i] for i in range(n_req)] == limits
+        return cd.engine().steps_run * slots
+
+    cases = [("(a) lock-step batches of `slots` through generate, max_new_tokens = the batch's longest limit", lock_step),
+             ("(b) ContinuousDecoder, sync_every 8", continuous)]
+    for _, f in cases:                                           # warm-up of each path: engines, stream copies, lazy initialisation
+        f()
+    torch.cuda.synchronize()
+    wall, row_steps = {n: [] for n, _ in cases}, {}
+    for _ in range(3):                                           # interleaved: a drift of the box hits both alike
+        for name, f in cases:
+            t0 = time.perf_counter()
+            row_steps[name] = f()
+            torch.cuda.synchronize()
+            wall[name].append(time.perf_counter() - t0)
+    tag = f"generate cfg3{' ' + gemm_dtype + ' GEMMs' if gemm_dtype != 'model' else ''}{''.join(' ' + k + '=' + str(v) for k, v in extra.items())}"
+    print(f"{tag}: {n_req} requests through {slots} slots, prompt {T} tokens, limits log-normal (median {int(np.median(limits))}, mean {np.mean(limits):.1f}, "
+          f"max {max(limits)}, clipped to 1 .. {Tnew}; synthetic lengths: no claim about real descriptions), decoder only", flush=True)
+    tps = {}
+    for name, _ in cases:
+        w = wall[name]
+        tps[name] = sum(limits) / np.median(w)
+        print(f"{tag}: {name}: median {np.median(w) * 1e3:.0f} ms (min {min(w) * 1e3:.0f}, max {max(w) * 1e3:.0f}; 3 runs) = {tps[name]:.0f} useful tokens/s; "
+              f"{row_steps[name]} row-steps, {1 - useful_steps / row_steps[name]:.3f} of them on finished rows", flush=True)
+    (na, _), (nb, _) = cases
+    print(f"{tag}: (b) / (a) useful tokens/s = {tps[nb] / tps[na]:.2f}; the ratio of live row-step fractions bounds it at "
+          f"{(useful_steps / row_steps[nb]) / (useful_steps / row_steps[na]):.2f} (the rest: refill prefills between replays and sync_every slack)", flush=True)
+    # the step alone at equal counters: the lock-step entry point against p2t_llama_decode_step_rows, a graph of {embed, step} each
+    e1 = generation.DecodeEngine(dec, slots, 1, T, 256, **extra)
+    e1.prefill(*e1.compact(emb, mask))
+    e2 = ContinuousEngine(dec, slots, T, 256, [], pad, use_graph=False, **extra)
+    e2.load(list(range(slots)), [(emb[b], mask[b]) for b in range(slots)], [256] * slots)
+    tok = torch.full((slots,), 11, dtype=torch.int64, device=emb.device)
+    steps = {"lock-step step (p2t_llama_decode_step[_q])": (e1, lambda: (e1.feed(tok), e1.decode_step()), lambda: e1.step.zero_()),
+             "p2t_llama_decode_step_rows": (e2, lambda: (e2.feed(tok), e2._step_rows(frozen=False)), lambda: e2.row_step.zero_())}
+    graphs = {}
+    for name, (_, go, reset) in steps.items():
+        go(); go()
+        graphs[name] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[name], capture_error_mode="thread_local"):
+            go()
+        reset()
+    ms = {name: [] for name in steps}
+    for _ in range(3):
+        for name, (_, _, reset) in steps.items():
+            reset()
+            ms[name].append(_events(graphs[name].replay, 100) / 1e3)
+    for name, r in ms.items():
+        print(f"{tag}: {slots} rows, counters 0 .. 110, graph replay, {name}: median {np.median(r):.3f} ms/step (min {min(r):.3f}, max {max(r):.3f}; 3 runs)", flush=True)
+
+
 def main():
     dev = torch.device("cuda:0")
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
@@ -356,8 +438,18 @@ def main():
     process = len(sys.argv) > 3 and sys.argv[3] == "process"
     head = "head" in sys.argv[3:5]                               # [B] [N] [beams] head [fp8 | mxfp4] [kv8] [fp8 | mxfp4 weights]
     kv8 = "kv8" in sys.argv[3:5] and not head
-    beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample and not process and sys.argv[3] not in ("kv8", "head") else 1
+    continuous = len(sys.argv) > 3 and sys.argv[3] == "continuous"   # [slots] [Tnew] continuous [fp8 | mxfp4] [kv8] [head fp8 | head mxfp4]
+    beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample and not process and sys.argv[3] not in ("kv8", "head", "continuous") else 1
     gemm_dtype = sys.argv[4] if len(sys.argv) > 4 and sys.argv[4] in ("fp8", "mxfp4") else "model"
+    cont_extra = {}
+    if continuous:
+        after = sys.argv[4:]
+        gemm_dtype = after[0] if after and after[0] in ("fp8", "mxfp4") else "model"
+        if "kv8" in after:
+            cont_extra["prompt_kv_dtype"] = "fp8"
+        if "head" in after:
+            cont_extra["lm_head_dtype"] = after[after.index("head") + 1]
+        head = kv8 = False
     if kv8:                                                      # [B] [N] [beams] kv8 [fp8 | mxfp4]
         after = sys.argv[sys.argv.index("kv8") + 1:]
         gemm_dtype = after[0] if after and after[0] in ("fp8", "mxfp4") else "model"
@@ -388,6 +480,8 @@ def main():
     t = lambda a: torch.from_numpy(a).to(dev)
     kw = dict(inputs=t(ids), attention_mask=torch.ones((B, T), dtype=torch.int64, device=dev), protein_input_ids=t(pid),
               protein_attention_mask=t(pmask), max_new_tokens=N, eos_token_id=None, pad_token_id=128002, do_sample=False, num_beams=beams)
+    if continuous:
+        return continuous_mode(model, kw, B, N, T, gemm_dtype, cont_extra)
     if head:
         return head_mode(model, kw, B, N, beams, T, llama, gemm_dtype, head_fmts, head_kv8)
     if kv8:
