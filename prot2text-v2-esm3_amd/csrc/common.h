@@ -85,6 +85,13 @@ __device__ __forceinline__ void load8(const bf16_t* p, float (&v)[8]) {
     v[4] = __uint_as_float(t.z << 16); v[5] = __uint_as_float(t.z & 0xFFFF0000u);
     v[6] = __uint_as_float(t.w << 16); v[7] = __uint_as_float(t.w & 0xFFFF0000u);
 }
+// the 16-byte piece of a row of T: 8 bf16 / 4 f32 (the decode attention's key and value rows, the greedy selectors' logits rows)
+template <typename T> struct Piece;
+template <> struct Piece<bf16_t> { static constexpr int N = 8; };
+template <> struct Piece<float> { static constexpr int N = 4; };
+template <typename T, int N> __device__ __forceinline__ void load_piece(const T* p, float (&v)[N]) {
+    if constexpr (N == 8) load8(p, v); else load4(p, v);
+}
 
 // ---- wave / block reductions ------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {

@@ -138,6 +138,16 @@ static inline GemmArgs gemm_args_fp8(const void* A, int64_t lda, const uint8_t* 
     g.use_mfma = GEMM_KERNEL_MFMA; g.a_scale = a_scale; g.w_scale = w_scale;
     return g;
 }
+// The A operand of a projection: rows of the model dtype at stride ld (scale == nullptr), or (gemm_fp8) e4m3 bytes at stride ld
+// with one E8M0 scale byte per row.  Either way its rows are zero padded to ld, which is also the weight's row stride and the
+// GEMM's K (the width rounded up to 64 elements, or to 128 bytes).
+struct Operand { void* p; int64_t ld; uint8_t* scale; };
+
+// out[M, N] = epilogue(a . W[N, a.ld]^T); ws: the weight's row scales, read by the fp8 form only
+static inline GemmArgs projection(const Operand& a, const void* W, const uint8_t* ws, int64_t M, int64_t N, int dt, void* out, int64_t ldc, int out_dtype, int epi) {
+    return a.scale ? gemm_args_fp8(a.p, a.ld, a.scale, W, ws, M, N, a.ld, out, ldc, out_dtype, epi)
+                   : GemmArgs(a.p, a.ld, W, a.ld, M, N, a.ld, dt, out, ldc, out_dtype, epi);
+}
 // hand the call the split-K fix-up workspace `ws` (gemm_fix_workspace_bytes()); `epoch` counts the calls since its header was zeroed
 static inline void with_fix(GemmArgs& g, void* ws, unsigned& epoch) { g.fix_ws = ws; g.fix_bytes = gemm_fix_workspace_bytes(); g.fix_epoch = ++epoch; }
 // weight-streaming GEMM for M <= 64 rows (gemm_skinny.hip): bf16, epilogues STORE / STORE_F32 / RESID / SWIGLU, no bias;
@@ -209,8 +219,15 @@ size_t llama_tape_plan(const p2t_llama_config* c, int B, int T, void* base, size
 int llama_forward_impl(const p2t_llama_config* c, const p2t_llama_weights* w, const int64_t* ids, const float* inputs_embeds, const int64_t* mask,
                        int B, int T, int k, float* out, void* workspace, size_t workspace_bytes, p2t_stream stream, const LlamaTape* tape,
                        const p2t_kv_cache* kv = nullptr, const int32_t* docs = nullptr);
-// generation prefill (llama_decode.hip): layer l's rotated keys / values ([B, kv_heads, T, dp]) -> the prompt segment of the cache
+// generation prefill (kv_cache.hip): layer l's rotated keys / values ([B, kv_heads, T, dp]) -> the prompt segment of the cache
 int llama_kv_store(const p2t_llama_config* c, const p2t_kv_cache* kc, int layer, const void* k, const void* v, int B, int T, hipStream_t s);
+// every refusal of a cache descriptor against the model's head shape and dtype (kv_cache.hip).  `who`: the entry point's name
+int check_cache(const p2t_llama_config* c, const p2t_kv_cache* kc, const char* who);
+// attention of one query token per row over layer `layer` of the cache (attn_decode.hip): q [BB, heads, dp] -> out [BB, ld_out], both the
+// model dtype; c gives heads / kv_heads / head_dim / dtype.  use_mfma (bf16): 0 = the lane-per-key kernel, the one f32 runs;
+// step_stride: 0 = the cache's shared counter, 1 = kc->step[row]
+int launch_attn_decode(const p2t_llama_config* c, const void* q, void* out, int64_t ld_out, const p2t_kv_cache* kc, int layer, float c_exp, int round_p,
+                       int use_mfma, int step_stride, hipStream_t s);
 // SwiGLU on the interleaved gate / up pre-activations gu [M, 2F], forward and backward (activations.hip)
 int launch_swiglu_from_gu(const void* gu, int64_t ld_gu, void* act, int64_t ld_act, int64_t M, int64_t F, int dtype, hipStream_t s);
 int launch_swiglu_gu_bwd(const void* gu, int64_t ld_gu, const void* d_act, int64_t ld_da, void* d_gu, int64_t ld_dgu, int64_t M, int64_t F, int dtype,

@@ -89,17 +89,6 @@ size_t llama_plan(const p2t_llama_config* c, int B, int T, Arena* ar, LlamaBuffe
     return a.off + 256;
 }
 
-// The A operand of a projection: rows of the model dtype at stride ld (scale == nullptr), or (gemm_fp8) e4m3 bytes at stride ld
-// with one E8M0 scale byte per row.  Either way its rows are zero padded to ld, which is also the weight's row stride and the
-// GEMM's K (the width rounded up to 64 elements, or to 128 bytes).
-struct Operand { void* p; int64_t ld; uint8_t* scale; };
-
-// out[M, N] = epilogue(a . W[N, a.ld]^T); ws: the weight's row scales, read by the fp8 form only
-GemmArgs projection(const Operand& a, const void* W, const uint8_t* ws, int64_t M, int64_t N, int dt, void* out, int64_t ldc, int out_dtype, int epi) {
-    return a.scale ? gemm_args_fp8(a.p, a.ld, a.scale, W, ws, M, N, a.ld, out, ldc, out_dtype, epi)
-                   : GemmArgs(a.p, a.ld, W, a.ld, M, N, a.ld, dt, out, ldc, out_dtype, epi);
-}
-
 // "turn a model-dtype buffer into an operand": x is the operand itself, or (fp8) one quantise pass writes its e4m3 copy o
 int quantise_into(const Operand& o, const void* x, int dt, int64_t ld, int64_t M, int64_t cols, hipStream_t s) {
     return o.scale ? launch_quant_rows(x, dt, ld, M, cols, o.p, o.ld, o.scale, s) : (int)P2T_OK;

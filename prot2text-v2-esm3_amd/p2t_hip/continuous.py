@@ -2,7 +2,7 @@
 counter, and a slot whose request finished (eos, or the request's own limit) is loaded with the next waiting prompt while the other
 rows go on.  `generation.generate` decodes a batch in lock-step until its longest row is done; here no slot waits for another.
 
-What runs where (csrc/llama_decode.hip, include/p2t_hip.h "continuous batching"):
+What runs where (csrc/llama_decode.hip, csrc/kv_cache.hip, csrc/attn_decode.hip; include/p2t_hip.h "continuous batching"):
   * p2t_llama_decode_step_rows: the decode step with row r at position prompt_len[r] + row_step[r]; `frozen = finished`, so a finished
     (or never loaded) slot re-appends at its own index and stays where it is;
   * p2t_greedy_select_rows: the greedy choice per row, its eos bit (1) and limit bit (2) into `finished`;
@@ -150,14 +150,8 @@ class ContinuousEngine(DecodeEngine):
 
     def _step_rows(self, frozen: bool = True):
         """One token per row at its own counter; `frozen`: the finished rows stay where they are (False: every row advances)."""
-        st = self.stream
-        layers = C.cast(st["layers"], C.POINTER(_lib.LlamaLayerStreamC)) if (st and self.mx is None) else None
-        mx = C.cast(self.mx[0], C.POINTER(_lib.LlamaLayerMxfp4C)) if self.mx is not None else None
-        hq = C.byref(self.head_q[0]) if self.head_q is not None else None
-        head = None if self.head_q is not None else (st["lm_head"] if st else self.lm_head)
-        call("p2t_llama_decode_step_rows", C.byref(self.e["cfg"]), C.byref(self.e["w"]), layers, mx, ptr(head) if head is not None else None,
-             self.lm_head.stride(0), int(st is not None and head is not None), hq, C.byref(self.cache), ptr(self.x), ptr(self.logits), self.ld_logits,
-             self.flags, ptr(self.ws), self.ws.numel(), ptr(self.row_step), ptr(self.finished) if frozen else None, stream())
+        call("p2t_llama_decode_step_rows", C.byref(self.e["cfg"]), C.byref(self.e["w"]), *self.step_weights(), C.byref(self.cache), ptr(self.x),
+             ptr(self.logits), self.ld_logits, self.flags, ptr(self.ws), self.ws.numel(), ptr(self.row_step), ptr(self.finished) if frozen else None, stream())
 
     def _advance(self):
         self.feed(self.next_tokens)

@@ -5,7 +5,7 @@ temperature, do_sample, top_p, top_k, return_dict_in_generate=False).
 
 What runs where: the prompt compaction, the prefill (all decoder layers + KV-cache write), every decode step (RMSNorm, the
 projections, rotation + cache append, single-query attention over the cache, LM head) and the greedy choice are kernels of
-libp2t_hip (csrc/llama_decode.hip).  After the first step the greedy loop replays ONE captured HIP graph per token (every length
+libp2t_hip (csrc/llama_decode.hip: the step; csrc/kv_cache.hip, csrc/attn_decode.hip: its cache and attention).  After the first step the greedy loop replays ONE captured HIP graph per token (every length
 lives in device memory), and the host looks at the finished flags only every `sync_every` tokens.  Sampling with `seed=` is the same
 loop with p2t_sample_select (csrc/sample_select.hip: temperature / top-k / top-p and a counter-hashed draw per row and step) in the
 place of the greedy choice, captured and replayed alike.  Beam search selects with p2t_beam_select (csrc/beam_select.hip: log-softmax,
@@ -406,24 +406,26 @@ class DecodeEngine:
         """x <- embedding rows of the chosen tokens (i64 [BB], device)."""
         call("p2t_llama_embed_tokens", C.byref(self.e["cfg"]), C.byref(self.e["w"]), ptr(tokens), self.BB, ptr(self.x), stream())
 
+    def step_weights(self):
+        """-> (w_stream, mx_layers, lm_head, ld_head, lm_head_preshuffled, head_q) for every door of the step: stream-order copies or MXFP4 layers
+        (never both) or neither; the model-dtype head (its stream copy where there is one) or the quantised head's descriptor in its place."""
+        st = self.stream
+        layers = C.cast(st["layers"], C.POINTER(_lib.LlamaLayerStreamC)) if (st and self.mx is None) else None
+        mx = C.cast(self.mx[0], C.POINTER(_lib.LlamaLayerMxfp4C)) if self.mx is not None else None
+        if self.head_q is not None:
+            return layers, mx, None, self.lm_head.stride(0), 0, C.byref(self.head_q[0])
+        return layers, mx, ptr(st["lm_head"] if st else self.lm_head), self.lm_head.stride(0), int(st is not None), None
+
     def decode_step(self):
         """One token per row from self.x -> self.logits; the device step counter advances."""
-        st = self.stream
-        if self.head_q is not None:
-            layers = C.cast(st["layers"], C.POINTER(_lib.LlamaLayerStreamC)) if (st and self.mx is None) else None
-            mx = C.cast(self.mx[0], C.POINTER(_lib.LlamaLayerMxfp4C)) if self.mx is not None else None
-            call("p2t_llama_decode_step_q", C.byref(self.e["cfg"]), C.byref(self.e["w"]), layers, mx, None, 0, 0, C.byref(self.head_q[0]), C.byref(self.cache),
-                 ptr(self.x), ptr(self.logits), self.ld_logits, self.flags, ptr(self.ws), self.ws.numel(), stream())
-            return
-        head = st["lm_head"] if st else self.lm_head
-        if self.mx is not None:
-            call("p2t_llama_decode_step_mxfp4", C.byref(self.e["cfg"]), C.byref(self.e["w"]), C.cast(self.mx[0], C.POINTER(_lib.LlamaLayerMxfp4C)), ptr(head),
-                 self.lm_head.stride(0), int(st is not None), C.byref(self.cache), ptr(self.x), ptr(self.logits), self.ld_logits, self.flags, ptr(self.ws),
-                 self.ws.numel(), stream())
-            return
-        layers = C.cast(st["layers"], C.POINTER(_lib.LlamaLayerStreamC)) if st else None
-        call("p2t_llama_decode_step", C.byref(self.e["cfg"]), C.byref(self.e["w"]), layers, ptr(head), self.lm_head.stride(0), int(st is not None),
-             C.byref(self.cache), ptr(self.x), ptr(self.logits), self.ld_logits, self.flags, ptr(self.ws), self.ws.numel(), stream())
+        layers, mx, head, ld_head, pre, hq = self.step_weights()
+        rest = (C.byref(self.cache), ptr(self.x), ptr(self.logits), self.ld_logits, self.flags, ptr(self.ws), self.ws.numel(), stream())
+        if hq is not None:
+            call("p2t_llama_decode_step_q", C.byref(self.e["cfg"]), C.byref(self.e["w"]), layers, mx, head, ld_head, pre, hq, *rest)
+        elif mx is not None:
+            call("p2t_llama_decode_step_mxfp4", C.byref(self.e["cfg"]), C.byref(self.e["w"]), mx, head, ld_head, pre, *rest)
+        else:
+            call("p2t_llama_decode_step", C.byref(self.e["cfg"]), C.byref(self.e["w"]), layers, head, ld_head, pre, *rest)
 
     def greedy_select(self, logits: torch.Tensor, eos: torch.Tensor, pad_id: int):
         call("p2t_greedy_select", ptr(logits), ops.dt_of(logits), logits.stride(0), self.spec.vocab_size, self.BB, ptr(eos) if eos.numel() else None,

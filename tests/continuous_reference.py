@@ -1,4 +1,4 @@
-"""numpy restatement of what continuous batching's kernels compute (include/p2t_hip.h, "continuous batching"; csrc/llama_decode.hip):
+"""numpy restatement of what continuous batching's kernels compute (include/p2t_hip.h, "continuous batching"; csrc/llama_decode.hip, csrc/kv_cache.hip, csrc/attn_decode.hip):
 every row carries its own step counter.  numpy only.
 
 * `decode_attention_rows`: one query token per row over prompt_len[r] keys of its prompt segment and row_step[r] + 1 keys of its

@@ -1,4 +1,4 @@
-"""Continuous batching, kernel by kernel (csrc/llama_decode.hip, csrc/gemm_skinny.hip; include/p2t_hip.h "continuous batching";
+"""Continuous batching, kernel by kernel (csrc/llama_decode.hip, csrc/attn_decode.hip, csrc/kv_cache.hip, csrc/gemm_skinny.hip; include/p2t_hip.h "continuous batching";
 reference restated in tests/continuous_reference.py):
 
 * the decode step's attention with one counter PER ROW against numpy -- one row past the 64-key tile of its generated segment while

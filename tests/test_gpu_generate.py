@@ -1,5 +1,5 @@
 """`generate` of Esm2LlamaInstructForCausalLM (reference models/modeling_esm2llama_instruct.py:217-251; call site
-scripts/generate_instruct.py:72-87) on the KV-cache decode path (csrc/llama_decode.hip, p2t_hip/generation.py).
+scripts/generate_instruct.py:72-87) on the KV-cache decode path (csrc/llama_decode.hip, csrc/kv_cache.hip, csrc/attn_decode.hip, p2t_hip/generation.py).
 
 * the kernels one by one against numpy: prompt compaction, single-query attention over the two cache segments (both dtypes, head_dim
   16 / 48 / 64 / 128, GQA groups 1 / 2 / 4 / 5, split-KV on and off, beams sharing a prompt segment), beam re-ordering of the

@@ -1,4 +1,4 @@
-"""The fp8 prompt segment of the KV cache, kernel by kernel (csrc/llama_decode.hip; format in include/p2t_hip.h, p2t_kv_cache):
+"""The fp8 prompt segment of the KV cache, kernel by kernel (csrc/kv_cache.hip, csrc/attn_decode.hip; format in include/p2t_hip.h, p2t_kv_cache):
 
 * p2t_kv_quant_store (the prefill's store: codes + one E8M0 byte per key for K and for V, V transposed) bit for bit against
   tests/kv8_reference.py, with sentinels behind the written positions;

@@ -114,6 +114,33 @@ def test_decode_step_q_refuses_what_it_cannot_run():
         step(head=_head(so=1), kc=cache(13, 5))
 
 
+def test_decode_step_q_refuses_before_its_first_enqueue():
+    """The refusals that used to sit behind launches -- the pre-shuffled head beyond 64 rows (after all layers), a layer's row scales, its
+    q_norm / k_norm pairing and its MXFP4 codes (inside the layer loop, after the layers before it) -- come from the checking pass in front
+    of the first copy: fake pointers, no device, a ValueError by name."""
+    from p2t_hip import _lib
+    C = ctypes
+    mk = lambda **kw: _lib.LlamaConfigC(**{**dict(n_layers=2, hidden=128, ffn=256, heads=2, kv_heads=2, head_dim=64, vocab=512, dtype=1, gemm_fp8=0), **kw})
+    scales = dict(qkv_ws=FAKE, o_ws=FAKE, gu_ws=FAKE, down_ws=FAKE)
+    mxw = dict(qkv_w=FAKE, o_w=FAKE, gu_w=FAKE, down_w=FAKE, qkv_bs=FAKE, o_bs=FAKE, gu_bs=FAKE, down_bs=FAKE)
+
+    def step(cfg, layers, mx=None, pre=0, B0=4):
+        arr = (_lib.LlamaLayerC * 2)(*[_lib.LlamaLayerC(**kw) for kw in layers])
+        w = _lib.LlamaWeightsC(embed=FAKE, layers=C.cast(arr, C.POINTER(_lib.LlamaLayerC)), final_norm_w=FAKE)
+        mxa = (_lib.LlamaLayerMxfp4C * 2)(*[_lib.LlamaLayerMxfp4C(**kw) for kw in mx]) if mx is not None else None
+        kc = _lib.KvCacheC(k_prompt=FAKE, vt_prompt=FAKE, k_gen=FAKE, vt_gen=FAKE, prompt_len=FAKE, step=FAKE, B0=B0, group=1, Tp=64, G=64)
+        return _lib.call("p2t_llama_decode_step_q", C.byref(cfg), C.byref(w), None, C.cast(mxa, C.POINTER(_lib.LlamaLayerMxfp4C)) if mx is not None else None,
+                         FAKE, 128, pre, None, C.byref(kc), FAKE, FAKE, 512, 0, FAKE, 1 << 30, None)
+    with pytest.raises(ValueError, match="p2t_llama_decode_step_q: .*at most 64 rows"):
+        step(mk(), [{}, {}], pre=1, B0=65)
+    with pytest.raises(ValueError, match="p2t_llama_decode_step_q: .*row scales of layer 1"):
+        step(mk(gemm_fp8=1), [scales, {**scales, "down_ws": None}])
+    with pytest.raises(ValueError, match="p2t_llama_decode_step_q: .*go together"):
+        step(mk(), [{}, dict(q_norm_w=FAKE)])
+    with pytest.raises(ValueError, match="p2t_llama_decode_step_q: .*null codes"):
+        step(mk(gemm_fp8=1), [scales, scales], mx=[mxw, {**mxw, "o_w": None}])
+
+
 def test_generate_refuses_an_unknown_dtype_and_an_fp32_model():
     import torch
     from p2t_hip import generation
