@@ -974,6 +974,37 @@ int p2t_llama_decode_step_rows(const p2t_llama_config* cfg, const p2t_llama_weig
 int p2t_greedy_select_rows(const void* logits, int dtype, int64_t ld, int V, int n, const int64_t* eos_ids, int n_eos, int64_t pad_id,
                            int32_t* finished, int64_t* next_tokens, int64_t* out_tokens, int64_t ld_tokens, const int32_t* row_step,
                            const int32_t* row_limit, const int32_t* row_map, int BB, int G, p2t_stream stream);
+/* p2t_sample_select with p2t_greedy_select_rows' row model: its arguments without `step` and `row0`, n logits rows, and per engine row
+ * the counter row_step (i32 [BB]), the limit row_limit (i32 [BB], 1 .. G) and the draw key row_key (i64 [BB], any value), all on the
+ * device; row_map: device i32 [n], or NULL = r = i and n == BB (n <= BB either way).  Logits row i belongs to engine row r = row_map[i];
+ * an r outside [0, BB) touches nothing.
+ *   finished[r] != 0: next_tokens[r] = pad_id, and NOTHING is written to out_tokens, to finished or to scores row i; the block returns
+ *   before it reads logits row i (which may hold anything).  This differs from the lock-step kernels, which do the whole row's work
+ *   for a finished row and write its scores.
+ *   Otherwise temperature, top-k, survivor table, ranks, top-p cut and inverse CDF are p2t_sample_select's, the same arithmetic in the
+ *   same fixed reduction orders, on logits row i, with the draw u = uniform(seed, (uint64)row_key[r], row_step[r]): p2t_sample_select's
+ *   chain with row_key[r] in the place of row0 + r and row_step[r] (unclamped) in the place of step[0];
+ *   p2t_hip.synth.sample_uniform(seed, key, step).  The token goes to out_tokens[r, clamp(row_step[r], 0, G - 1)] and next_tokens[r];
+ *   then finished[r] |= 1 if it is in eos_ids and finished[r] |= 2 if row_step[r] + 1 >= row_limit[r].  row_step is not written.
+ * A row's token so depends on (seed, its key, its counter, its logits) and on nothing else: not on i, r, n or BB.  Equal counters s,
+ * row_map NULL, no finished row, row_key[r] = row0 + r: p2t_sample_select's tokens, eos bits and scores at step[0] = s, bit for bit.
+ * scores (or NULL): f32 [n, ld_scores >= V], row i as p2t_sample_select writes it.  flags: as there (bit 0: table full).  top_p on
+ * without top_k: P2T_ERR_UNSUPPORTED.  Every written column and every LDS index is clamped in the kernel.  Enqueues only: capturable. */
+int p2t_sample_select_rows(const void* logits, int dtype, int64_t ld, int V, int n, const int64_t* eos_ids, int n_eos, int64_t pad_id,
+                           int32_t* finished, int64_t* next_tokens, int64_t* out_tokens, int64_t ld_tokens, const int32_t* row_step,
+                           const int32_t* row_limit, const int32_t* row_map, const int64_t* row_key, int BB, int G, float temperature,
+                           int top_k, float top_p, uint64_t seed, float* scores, int64_t ld_scores, int32_t* flags, p2t_stream stream);
+/* p2t_logits_process with the same row model, in front of p2t_greedy_select_rows / p2t_sample_select_rows: logits row i (of n) belongs
+ * to engine row r = row_map[i] (NULL: r = i, n == BB; an r outside [0, BB) touches nothing).  Its history is out_tokens[r, 0 .. cur) with
+ * cur = clamp(row_step[r], 0, G) -- the row's OWN tokens, whatever the other rows' counters are -- and stage 5 compares that same cur
+ * with min_new_tokens.  The output row is row i of out (f32 [n, ld_out >= V]).  finished: device i32 [BB] or NULL; a row with
+ * finished[r] != 0 is skipped: nothing is read, and output row i keeps its bytes (the per-row selectors do not read it).  Stages 1 - 5,
+ * their order and their bits are p2t_logits_process's: equal counters s, row_map NULL and no finished row give its rows at step[0] = s,
+ * bit for bit.  Enqueues only: capturable. */
+int p2t_logits_process_rows(const void* logits, int dtype, int64_t ld, int V, int n, const int64_t* out_tokens, int64_t ld_tokens,
+                            const int32_t* row_step, const int32_t* row_map, const int32_t* finished, int BB, int G, float* out,
+                            int64_t ld_out, float repetition_penalty, int no_repeat_ngram_size, int min_new_tokens, const int64_t* eos_ids,
+                            int n_eos, const int64_t* word_ids, const int32_t* word_offsets, int n_words, int n_word_ids, p2t_stream stream);
 /* Loads k freshly prefilled prompts into slots of a running engine.  p2t_llama_prefill wants cache->B0 == B, so the k prompts are
  * prefilled into `staging` (a p2t_kv_cache with B0 = k, the same Tp and the same prompt-segment format; its generated segment is not
  * touched); this call copies staging row i's prompt segment -- K, transposed V and, when set, both scale arrays, ALL Tp entries of every

@@ -1,12 +1,14 @@
-// Token selection by sampling (p2t_sample_select): HF's TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper
+// Token selection by sampling (p2t_sample_select, p2t_sample_select_rows): HF's TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper
 // (transformers/generation/logits_process.py) and the multinomial draw of GenerationMixin._sample, one 1024-thread block per
 // row, with greedy_select_kernel's step bookkeeping (llama_decode.hip).  The contract, every tie-break included, is the comment
-// on p2t_sample_select in include/p2t_hip.h; tests/sampling_reference.py restates it in fp64.
+// on p2t_sample_select in include/p2t_hip.h; tests/sampling_reference.py restates it in fp64.  Both kernels are one body over a row
+// model (row_model.h): LockStepRows for p2t_sample_select, OwnRows -- greedy_select_rows_kernel's bookkeeping, every row on its own
+// counter, a finished row left before its logits are read -- for p2t_sample_select_rows (tests/continuous_choice_reference.py).
 //
-// The draw of row r (global row row0 + r) at step[0]:
-//     h = mix64(mix64(mix64(seed + 0x9E3779B97F4A7C15) ^ (uint64)(row0 + r)) ^ (uint64)(int64)step[0])      (mix64: common.h)
+// The draw of a row with key `key` at counter `step` (lock-step: key = row0 + r, step = step[0]; own rows: row_key[r], row_step[r]):
+//     h = mix64(mix64(mix64(seed + 0x9E3779B97F4A7C15) ^ (uint64)key) ^ (uint64)(int64)step)                 (mix64: common.h)
 //     hash24 = h >> 40,   u = (hash24 + 0.5) * 2^-24,   used as the nearest f32 (= float(2 hash24 + 1) * 2^-25)
-// p2t_hip/synth.py sample_uniform(seed, row, step) is the same chain on the host.
+// p2t_hip/synth.py sample_uniform(seed, key, step) is the same chain on the host.
 //
 // Filtered form (top_k on), sample_topk_kernel: the table pipeline of select_common.h, with x = stored logit / temperature as the
 // value a column stores and its score written as it is seen; the draw is this file's own.
@@ -24,7 +26,8 @@
 // columns in ascending order (64 columns per step, shuffle scan), the 16 segment sums are added in wave order, and the wave whose
 // segment holds u * S walks it again with the same arithmetic to find the column.
 // No float atomics; every float reduction has a fixed order: the same inputs give the same bits.  Every LDS index is bounded by
-// kCap / 256 / 16 whatever the counts say, step[0] is clamped, and the token is clamped to [0, V).
+// kCap / 256 / 16 whatever the counts say, the written column is clamped, and the token is clamped to [0, V).
+#include "row_model.h"
 #include "select_common.h"
 
 namespace p2t {
@@ -37,28 +40,11 @@ __device__ __forceinline__ float draw_uniform(uint64_t seed, int64_t row, int st
     return (float)(int)(2u * (uint32_t)(h >> 40) + 1u) * 0x1p-25f;
 }
 
-// greedy_select_kernel's rule (llama_decode.hip): a finished row emits pad, the token goes to column clamp(step[0]) of out_tokens,
-// a row finishes once it emits an eos id
-__device__ __forceinline__ void emit_token(int bb, int tok_in, int V, const int64_t* __restrict__ eos, int n_eos, int64_t pad,
-                                           int32_t* __restrict__ finished, int64_t* __restrict__ next, int64_t* __restrict__ out_tokens,
-                                           int64_t ld_tok, int step, int Gcap) {
-    int64_t tok = min(max(tok_in, 0), V - 1);
-    const int fin = finished[bb];
-    if (fin) tok = pad;
-    next[bb] = tok;
-    const int st = min(max(step, 0), Gcap - 1);
-    out_tokens[(int64_t)bb * ld_tok + st] = tok;
-    if (!fin) {
-        for (int e = 0; e < n_eos; ++e)
-            if (tok == eos[e]) finished[bb] = 1;
-    }
-}
-
-template <typename T>
+template <typename T, typename Rows>
 __global__ void __launch_bounds__(1024) sample_topk_kernel(const T* __restrict__ logits, int64_t ld, int V, const int64_t* __restrict__ eos,
                                                            int n_eos, int64_t pad, int32_t* __restrict__ finished, int64_t* __restrict__ next,
-                                                           int64_t* __restrict__ out_tokens, int64_t ld_tok, const int32_t* __restrict__ step_ptr,
-                                                           int Gcap, float temperature, int top_k, float top_p, uint64_t seed, int64_t row0,
+                                                           int64_t* __restrict__ out_tokens, int64_t ld_tok, Rows rows,
+                                                           int Gcap, float temperature, int top_k, float top_p, uint64_t seed,
                                                            float* __restrict__ scores, int64_t ld_scores, int32_t* __restrict__ flags) {
     __shared__ int hist[16][256];
     __shared__ float sv[kCap];            // survivors: x
@@ -66,6 +52,8 @@ __global__ void __launch_bounds__(1024) sample_topk_kernel(const T* __restrict__
     __shared__ float se[kCap];            //            exp(x - max)
     __shared__ int s_sel[2], s_cnt, s_wc[16], s_kept, s_tok;
     const int bb = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int r = rows.engine_row(bb);
+    if (!rows.enter(r, finished, next, pad, tid)) return;     // block-uniform; LockStepRows: never
     const T* row = logits + (int64_t)bb * ld;
     float* srow = scores ? scores + (int64_t)bb * ld_scores : nullptr;
     const int k = min(top_k, V);
@@ -93,7 +81,7 @@ __global__ void __launch_bounds__(1024) sample_topk_kernel(const T* __restrict__
     // ---- 3. total order: value descending, column ascending ----------------------------------------------------------------
     const int P = pad_and_sort_table(sv, si, n, tid);
     // ---- 4. top-p and the draw, one wave ---------------------------------------------------------------------------------
-    const int step = step_ptr[0];
+    const int step = rows.counter(r);
     if (w == 0) {
         const int per = P >> 6, j0 = lane * per;              // lane l: ranks l * per .. l * per + per - 1
         const float mx = sv[0];
@@ -107,7 +95,7 @@ __global__ void __launch_bounds__(1024) sample_topk_kernel(const T* __restrict__
                 if (j == m - 1) at_last = run;
             }
         }
-        const float target = draw_uniform(seed, row0 + bb, step) * __shfl(at_last, (m - 1) / per, 64);
+        const float target = draw_uniform(seed, rows.key(r), step) * __shfl(at_last, (m - 1) / per, 64);
         int cand = kNoIndex;
         run = excl;
         for (int i = 0; i < per; ++i) {
@@ -129,18 +117,20 @@ __global__ void __launch_bounds__(1024) sample_topk_kernel(const T* __restrict__
             if (c >= 0 && c < V) srow[c] = -INFINITY;
         }
     }
-    if (tid == 0) emit_token(bb, s_tok, V, eos, n_eos, pad, finished, next, out_tokens, ld_tok, step, Gcap);
+    if (tid == 0) rows.emit(r, s_tok, V, eos, n_eos, pad, finished, next, out_tokens, ld_tok, step, Gcap);
 }
 
-template <typename T>
+template <typename T, typename Rows>
 __global__ void __launch_bounds__(1024) sample_full_kernel(const T* __restrict__ logits, int64_t ld, int V, const int64_t* __restrict__ eos,
                                                            int n_eos, int64_t pad, int32_t* __restrict__ finished, int64_t* __restrict__ next,
-                                                           int64_t* __restrict__ out_tokens, int64_t ld_tok, const int32_t* __restrict__ step_ptr,
-                                                           int Gcap, float temperature, uint64_t seed, int64_t row0, float* __restrict__ scores,
+                                                           int64_t* __restrict__ out_tokens, int64_t ld_tok, Rows rows,
+                                                           int Gcap, float temperature, uint64_t seed, float* __restrict__ scores,
                                                            int64_t ld_scores) {
     __shared__ float s_max[16], s_sum[16];
     __shared__ int s_tok;
     const int bb = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int r = rows.engine_row(bb);
+    if (!rows.enter(r, finished, next, pad, tid)) return;     // block-uniform; LockStepRows: never
     const T* row = logits + (int64_t)bb * ld;
     float* srow = scores ? scores + (int64_t)bb * ld_scores : nullptr;
     float mx = -INFINITY;
@@ -173,8 +163,8 @@ __global__ void __launch_bounds__(1024) sample_full_kernel(const T* __restrict__
         if (ww == w) base = S;
         S += s_sum[ww];
     }
-    const int step = step_ptr[0];
-    const float target = draw_uniform(seed, row0 + bb, step) * S;
+    const int step = rows.counter(r);
+    const float target = draw_uniform(seed, rows.key(r), step) * S;
     // the wave whose segment holds the target: the cumulative mass before it does not pass the target, that of its last column does
     // (the running sums never decrease, so at most one wave; each wave judges for itself, on its own two numbers.  A block-uniform
     // "first ww with b + s_sum[ww] > target" loop over the 16 sums was miscompiled by hipcc: the v_cmp of its first round was followed
@@ -194,13 +184,49 @@ __global__ void __launch_bounds__(1024) sample_full_kernel(const T* __restrict__
         }
     }
     __syncthreads();
-    if (tid == 0) emit_token(bb, s_tok, V, eos, n_eos, pad, finished, next, out_tokens, ld_tok, step, Gcap);
+    if (tid == 0) rows.emit(r, s_tok, V, eos, n_eos, pad, finished, next, out_tokens, ld_tok, step, Gcap);
 }
 
 }  // namespace
 }  // namespace p2t
 
 using namespace p2t;
+
+// the checks both entry points share (P2T_ERR_ARG, then P2T_ERR_UNSUPPORTED, before any GPU call)
+static int sampler_args_check(const char* name, int V, const int64_t* eos_ids, int n_eos, int64_t ld_tokens, int G, float temperature, int top_k, float top_p,
+                              const float* scores, int64_t ld_scores) {
+    P2T_REQUIRE(G > 0 && ld_tokens >= G && n_eos >= 0 && (n_eos == 0 || eos_ids),
+                "%s: G = %d, ld_tokens = %lld, n_eos = %d: needs G > 0, ld_tokens >= G, eos_ids for n_eos > 0", name, G, (long long)ld_tokens, n_eos);
+    P2T_REQUIRE(temperature > 0.f && temperature < INFINITY, "%s: temperature %g is not a positive finite number", name, (double)temperature);
+    P2T_REQUIRE(top_k >= 0 && top_k <= 1024, "%s: top_k = %d: 0 (off) or 1 .. 1024", name, top_k);
+    P2T_REQUIRE(top_p > 0.f, "%s: top_p = %g: in (0, 1), or >= 1 for off", name, (double)top_p);
+    P2T_REQUIRE(!scores || ld_scores >= V, "%s: ld_scores = %lld < V = %d", name, (long long)ld_scores, V);
+    if (top_k == 0 && top_p < 1.f) {
+        set_error("%s: top_p = %g without top_k needs a sort of the whole vocabulary: supported are top_k 1 .. 1024 (top_p on or off) "
+                  "and both filters off", name, (double)top_p);
+        return P2T_ERR_UNSUPPORTED;
+    }
+    return P2T_OK;
+}
+
+// one block per logits row: the filtered or the unfiltered kernel over the row model
+template <typename Rows>
+static void launch_sample(const void* logits, int dtype, int64_t ld, int V, int n, const int64_t* eos_ids, int n_eos, int64_t pad_id, int32_t* finished,
+                          int64_t* next_tokens, int64_t* out_tokens, int64_t ld_tokens, Rows rows, int G, float temperature, int top_k, float top_p,
+                          uint64_t seed, float* scores, int64_t ld_scores, int32_t* flags, hipStream_t s) {
+#define P2T_SAMPLE_LAUNCH(T)                                                                                                                  \
+    do {                                                                                                                                      \
+        if (top_k > 0)                                                                                                                        \
+            sample_topk_kernel<T, Rows><<<n, 1024, 0, s>>>((const T*)logits, ld, V, eos_ids, n_eos, pad_id, finished, next_tokens, out_tokens, \
+                                                           ld_tokens, rows, G, temperature, top_k, top_p, seed, scores, ld_scores, flags);    \
+        else                                                                                                                                  \
+            sample_full_kernel<T, Rows><<<n, 1024, 0, s>>>((const T*)logits, ld, V, eos_ids, n_eos, pad_id, finished, next_tokens, out_tokens, \
+                                                           ld_tokens, rows, G, temperature, seed, scores, ld_scores);                         \
+    } while (0)
+    if (dtype == P2T_BF16) P2T_SAMPLE_LAUNCH(bf16_t);
+    else P2T_SAMPLE_LAUNCH(float);
+#undef P2T_SAMPLE_LAUNCH
+}
 
 extern "C" int p2t_sample_select(const void* logits, int dtype, int64_t ld, int V, int BB, const int64_t* eos_ids, int n_eos, int64_t pad_id,
                                  int32_t* finished, int64_t* next_tokens, int64_t* out_tokens, int64_t ld_tokens, const int32_t* step, int G,
@@ -209,31 +235,25 @@ extern "C" int p2t_sample_select(const void* logits, int dtype, int64_t ld, int 
     P2T_REQUIRE(logits && finished && next_tokens && out_tokens && step && flags, "p2t_sample_select: null argument");
     P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_sample_select: dtype %d is neither P2T_F32 nor P2T_BF16", dtype);
     P2T_REQUIRE(BB > 0 && V > 0 && ld >= V, "p2t_sample_select: BB = %d, V = %d, ld = %lld: needs BB > 0, V > 0, ld >= V", BB, V, (long long)ld);
-    P2T_REQUIRE(G > 0 && ld_tokens >= G && n_eos >= 0 && (n_eos == 0 || eos_ids),
-                "p2t_sample_select: G = %d, ld_tokens = %lld, n_eos = %d: needs G > 0, ld_tokens >= G, eos_ids for n_eos > 0", G, (long long)ld_tokens,
-                n_eos);
-    P2T_REQUIRE(temperature > 0.f && temperature < INFINITY, "p2t_sample_select: temperature %g is not a positive finite number", (double)temperature);
-    P2T_REQUIRE(top_k >= 0 && top_k <= 1024, "p2t_sample_select: top_k = %d: 0 (off) or 1 .. 1024", top_k);
-    P2T_REQUIRE(top_p > 0.f, "p2t_sample_select: top_p = %g: in (0, 1), or >= 1 for off", (double)top_p);
-    P2T_REQUIRE(!scores || ld_scores >= V, "p2t_sample_select: ld_scores = %lld < V = %d", (long long)ld_scores, V);
-    if (top_k == 0 && top_p < 1.f) {
-        set_error("p2t_sample_select: top_p = %g without top_k needs a sort of the whole vocabulary: supported are top_k 1 .. 1024 (top_p on or off) "
-                  "and both filters off", (double)top_p);
-        return P2T_ERR_UNSUPPORTED;
-    }
-    hipStream_t s = (hipStream_t)stream;
-#define P2T_SAMPLE_LAUNCH(T)                                                                                                                  \
-    do {                                                                                                                                      \
-        if (top_k > 0)                                                                                                                        \
-            sample_topk_kernel<T><<<BB, 1024, 0, s>>>((const T*)logits, ld, V, eos_ids, n_eos, pad_id, finished, next_tokens, out_tokens,     \
-                                                      ld_tokens, step, G, temperature, top_k, top_p, seed, row0, scores, ld_scores, flags);   \
-        else                                                                                                                                  \
-            sample_full_kernel<T><<<BB, 1024, 0, s>>>((const T*)logits, ld, V, eos_ids, n_eos, pad_id, finished, next_tokens, out_tokens,     \
-                                                      ld_tokens, step, G, temperature, seed, row0, scores, ld_scores);                        \
-    } while (0)
-    if (dtype == P2T_BF16) P2T_SAMPLE_LAUNCH(bf16_t);
-    else P2T_SAMPLE_LAUNCH(float);
-#undef P2T_SAMPLE_LAUNCH
+    P2T_TRY(sampler_args_check("p2t_sample_select", V, eos_ids, n_eos, ld_tokens, G, temperature, top_k, top_p, scores, ld_scores));
+    launch_sample(logits, dtype, ld, V, BB, eos_ids, n_eos, pad_id, finished, next_tokens, out_tokens, ld_tokens, LockStepRows{step, row0}, G, temperature,
+                  top_k, top_p, seed, scores, ld_scores, flags, (hipStream_t)stream);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
+extern "C" int p2t_sample_select_rows(const void* logits, int dtype, int64_t ld, int V, int n, const int64_t* eos_ids, int n_eos, int64_t pad_id,
+                                      int32_t* finished, int64_t* next_tokens, int64_t* out_tokens, int64_t ld_tokens, const int32_t* row_step,
+                                      const int32_t* row_limit, const int32_t* row_map, const int64_t* row_key, int BB, int G, float temperature,
+                                      int top_k, float top_p, uint64_t seed, float* scores, int64_t ld_scores, int32_t* flags, p2t_stream stream) {
+    P2T_REQUIRE(logits && finished && next_tokens && out_tokens && row_step && row_limit && row_key && flags, "p2t_sample_select_rows: null argument");
+    P2T_REQUIRE(dtype == P2T_F32 || dtype == P2T_BF16, "p2t_sample_select_rows: dtype %d is neither P2T_F32 nor P2T_BF16", dtype);
+    P2T_REQUIRE(n > 0 && BB > 0 && n <= BB && (row_map || n == BB),
+                "p2t_sample_select_rows: %d logits rows for %d engine rows (all of them, or a row_map subset)", n, BB);
+    P2T_REQUIRE(V > 0 && ld >= V, "p2t_sample_select_rows: V = %d, ld = %lld: needs V > 0, ld >= V", V, (long long)ld);
+    P2T_TRY(sampler_args_check("p2t_sample_select_rows", V, eos_ids, n_eos, ld_tokens, G, temperature, top_k, top_p, scores, ld_scores));
+    launch_sample(logits, dtype, ld, V, n, eos_ids, n_eos, pad_id, finished, next_tokens, out_tokens, ld_tokens,
+                  OwnRows{row_step, row_limit, row_map, row_key, BB}, G, temperature, top_k, top_p, seed, scores, ld_scores, flags, (hipStream_t)stream);
     P2T_LAUNCH_CHECK();
     return P2T_OK;
 }

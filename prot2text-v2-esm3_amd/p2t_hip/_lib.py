@@ -186,6 +186,8 @@ SIGNATURES = {
     "p2t_greedy_select": (i32, [vp, i32, i64, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, i32, vp]),
     "p2t_sample_select": (i32, [vp, i32, i64, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, i32, f32, i32, f32, u64, i64, vp, i64, vp, vp]),
     "p2t_logits_process": (i32, [vp, i32, i64, i32, i32, vp, i64, vp, i32, vp, i64, f32, i32, i32, vp, i32, vp, vp, i32, i32, vp]),
+    "p2t_sample_select_rows": (i32, [vp, i32, i64, i32, i32, vp, i32, i64, vp, vp, vp, i64, vp, vp, vp, vp, i32, i32, f32, i32, f32, u64, vp, i64, vp, vp]),
+    "p2t_logits_process_rows": (i32, [vp, i32, i64, i32, i32, vp, i64, vp, vp, vp, i32, i32, vp, i64, f32, i32, i32, vp, i32, vp, vp, i32, i32, vp]),
     "p2t_beam_workspace_bytes": (sz, [i32, i32]),
     "p2t_beam_select": (i32, [vp, i32, i64, i32, i32, i32, vp, i32, i64, f32, i32, i32, i32, vp, C.POINTER(BeamStateC), vp, vp, vp, i64, vp]),
     "p2t_beam_logprobs_process": (i32, [vp, i32, i64, i32, i32, i32, vp, i32, i32, C.POINTER(BeamStateC), f32, i32, i32, vp, i32, vp, vp, i32, i32, vp,

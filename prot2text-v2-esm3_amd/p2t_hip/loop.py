@@ -207,8 +207,8 @@ def generation_seed(seed: int, rank: int, batch_index: int) -> int:
 
 
 def _inference_continuous(rank, model, dataloader, llama_tokenizer, args: Dict[str, Any], progress, eos_token_id=128009, pad_token_id: int = 128002):
-    """inference_epoch's generation with args["continuous_slots"] rows that refill as requests finish (p2t_hip/continuous.py; greedy
-    only): every batch is submitted as it comes, the results return to dataset order by request id, and each prediction is decoded as
+    """inference_epoch's generation with args["continuous_slots"] rows that refill as requests finish (p2t_hip/continuous.py; greedy,
+    or with args["choice"] = "device" seeded sampling and the logits processors): every batch is submitted as it comes, the results return to dataset order by request id, and each prediction is decoded as
     the row `generate` would have returned (the tokens up to its eos, pad behind)."""
     model = getattr(model, "module", model)
     dev = torch.device("cuda", rank) if isinstance(rank, int) else torch.device(rank)
@@ -216,7 +216,12 @@ def _inference_continuous(rank, model, dataloader, llama_tokenizer, args: Dict[s
     if not batches:
         return [], [], []
     longest = max(int(b["attention_mask"].shape[1]) for b in batches)     # the placeholders are replaced in place: the id prompt's length
-    kw = {k: args[k] for k in ("prompt_kv_dtype", "lm_head_dtype", "sync_every") if args.get(k) is not None}
+    # what generate() takes as its choice rule goes through as it is: choice=None refuses all but greedy by name, choice="device" serves it
+    kw = {k: args[k] for k in ("prompt_kv_dtype", "lm_head_dtype", "sync_every", "choice", "temperature", "top_k", "top_p", "repetition_penalty",
+                               "no_repeat_ngram_size", "min_new_tokens", "bad_words_ids", "suppress_tokens") if args.get(k) is not None}
+    if args.get("seed") is not None:                         # ONE generator for the rank's whole shard: batch index 0; the draw keys are the
+        r = rank if isinstance(rank, int) else (dev.index or 0)          # request ids (dataset order on the rank), so `continuous_slots` does not matter
+        kw["seed"] = generation_seed(args["seed"], r, 0)
     gen = model.continuous_generator(slots=int(args["continuous_slots"]), max_prompt_tokens=longest, max_new_tokens=args["max_generation_length"],
                                      eos_token_id=eos_token_id, pad_token_id=pad_token_id, num_beams=args.get("num_beams", 1),
                                      do_sample=args.get("do_sample", False), **kw)
@@ -245,8 +250,10 @@ def inference_epoch(rank, model, dataloader: Iterable[Dict[str, Any]], llama_tok
     description tokenizer (`batch_decode(..., skip_special_tokens=True)`) and write
     `generation_{save_generation_postfix_identifier}_rank{rank}.json` = {name: {"true": label, "pred": prediction}} into
     `save_generation_dir` (returned).  Every rank generates on its own (a DistributedSampler shard per rank upstream): no collective.
-    args["continuous_slots"] (optional, greedy only): that many decode rows with continuous batching instead of one lock-step `generate`
-    per batch (p2t_hip/continuous.py) -- the same JSON, names in dataset order."""
+    args["continuous_slots"] (optional): that many decode rows with continuous batching instead of one lock-step `generate` per batch
+    (p2t_hip/continuous.py) -- the same JSON, names in dataset order.  Greedy only, unless args["choice"] = "device": then do_sample /
+    temperature / top_k / top_p and the logits-processor arguments go through, with seed = generation_seed(args["seed"], rank, 0) and the
+    request ids (dataset order on the rank) as draw keys, so the JSON does not depend on `continuous_slots`."""
     import json
     import os
     model.eval()

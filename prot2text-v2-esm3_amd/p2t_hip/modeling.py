@@ -1104,7 +1104,12 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
         on its own step counter, and a finished row's slot takes the next waiting prompt.  Returns a ContinuousGenerator: `submit(inputs,
         attention_mask, protein_input_ids, protein_attention_mask, max_new_tokens=None)` runs the encoder + adapter + placeholder
         scatter of that batch exactly as `generate` does and returns request ids; `run()` yields (request id, tokens) as requests
-        finish.  kwargs: eos_token_id, pad_token_id, sync_every, use_graph, stream_copy, prompt_kv_dtype, lm_head_dtype, output_logits."""
+        finish.  kwargs: eos_token_id, pad_token_id, sync_every, use_graph, stream_copy, prompt_kv_dtype, lm_head_dtype, output_logits.
+        `choice="device"` (default None: greedy only, everything else refused by name) serves generate()'s other single-sequence choice
+        rules on the device, per row: repetition_penalty / no_repeat_ngram_size / min_new_tokens / bad_words_ids / suppress_tokens,
+        `do_sample=True` with `seed=int` (temperature, top_k, top_p) and `output_scores=True` (yielded after the logits);
+        `submit(..., sample_keys=)` gives each request its draw key (default: its request id), and a request's tokens depend on (seed,
+        key, its own logits) alone -- not on its slot, the number of slots, `sync_every` or what else is queued."""
         if getattr(self.esm_encoder, "lora", None) is not None:
             raise NotImplementedError(_ENCODER_LORA_MSG)
         from .continuous import ContinuousGenerator

@@ -35,7 +35,14 @@ log-normal clipped to 1 .. Tnew (random weights have no natural eos: the limit i
 decoder's plain `generate` with max_new_tokens = the batch's longest limit -- what lock-step decoding with an eos costs; (b) the same
 requests through ContinuousDecoder.  Interleaved, three runs each, on the decoder alone (the prompt embeddings are computed once and
 shared): useful tokens/s (sum of limits / wall time) and the fraction of row-steps spent on finished rows, for both; then ms per step of
-p2t_llama_decode_step_rows against the lock-step step at equal counters, under graph replay."""
+p2t_llama_decode_step_rows against the lock-step step at equal counters, under graph replay.
+python tools/generate_bench.py [slots] [Tnew] continuous sample | process: the continuous leg with `choice="device"` -- `sample`: the
+device sampler (top_k=50, top_p=0.9, temperature=0.7, seed=1; p2t_sample_select_rows), `process`: all five logits processors in front of
+the greedy choice (p2t_logits_process_rows) -- against the greedy continuous leg on the same queue, interleaved, three runs each: ms per
+step and useful tokens/s; then the whole step {embed, step, [processors], choice} under graph replay at equal rows, the per-row engine
+against the lock-step engine with the SAME choice rule (the yardstick: what `generate(seed=)` / `generate(processors)` replays), three
+interleaved runs each, and whether the per-row step exceeds it by more than the runs' own min .. max spread.  Random weights have no eos:
+the limit ends a row, and nothing is claimed about the quality of what is decoded."""
 import os
 import sys
 import time
@@ -430,11 +437,106 @@ def continuous_mode(model, kw, slots: int, Tnew: int, T: int, gemm_dtype: str, e
         print(f"{tag}: {slots} rows, counters 0 .. 110, graph replay, {name}: median {np.median(r):.3f} ms/step (min {min(r):.3f}, max {max(r):.3f}; 3 runs)", flush=True)
 
 
+CHOICE_LEGS = {"sample": dict(do_sample=True, top_k=50, top_p=0.9, temperature=0.7, seed=1),
+               # every processor on; the eos ids end no row: they are banned for the first tokens by min_new_tokens and suppressed throughout
+               "process": dict(repetition_penalty=1.3, no_repeat_ngram_size=3, min_new_tokens=8, eos_token_id=[128001, 128009],
+                               bad_words_ids=[[11, 12], [13, 14, 15], [16]] * 8, suppress_tokens=list(range(100, 132)) + [128001, 128009])}
+
+
+def continuous_choice_mode(model, kw, slots: int, Tnew: int, T: int, leg: str):
+    from p2t_hip.continuous import ContinuousDecoder, ContinuousEngine, device_choice
+    dec, rule = model.llama_decoder, CHOICE_LEGS[leg]
+    V = dec.spec.vocab_size
+    n_req = 8 * slots
+    rs = np.random.RandomState(1)
+    limits = np.clip(np.rint(np.exp(rs.normal(np.log(Tnew / 4.0), 0.8, size=n_req))), 1, Tnew).astype(int).tolist()
+    with torch.no_grad():
+        emb, mask = model(input_ids=kw["inputs"], attention_mask=kw["attention_mask"], protein_input_ids=kw["protein_input_ids"],
+                          protein_attention_mask=kw["protein_attention_mask"], return_decoder_inputs=True)
+    pad = kw["pad_token_id"]
+
+    def continuous(**choice):
+        cd = ContinuousDecoder(dec, slots, T, Tnew, pad_token_id=pad, sync_every=8, **{"eos_token_id": None, **choice})
+        for i in range(0, n_req, slots):
+            cd.submit(emb, mask, max_new_tokens=limits[i:i + slots])
+        got = {item[0]: int(item[1].numel()) for item in cd.run()}
+        assert [got[i] for i in range(n_req)] == limits
+        return cd.engine().steps_run
+
+    cases = [("(b) ContinuousDecoder, greedy", lambda: continuous()),
+             (f"(c) ContinuousDecoder, choice='device', {leg}", lambda: continuous(choice="device", **rule))]
+    for _, f in cases:
+        f()
+    torch.cuda.synchronize()
+    wall, steps_run = {n: [] for n, _ in cases}, {}
+    for _ in range(3):                                           # interleaved: a drift of the box hits both alike
+        for name, f in cases:
+            t0 = time.perf_counter()
+            steps_run[name] = f()
+            torch.cuda.synchronize()
+            wall[name].append(time.perf_counter() - t0)
+    tag = f"generate cfg3 continuous {leg}"
+    print(f"{tag}: {n_req} requests through {slots} slots, prompt {T} tokens, limits log-normal (median {int(np.median(limits))}, mean {np.mean(limits):.1f}, "
+          f"max {max(limits)}, clipped to 1 .. {Tnew}; synthetic lengths, random weights without an eos: no claim about real descriptions or their quality), "
+          f"decoder only; rule: {', '.join(k + '=' + (str(v) if not isinstance(v, list) else '[' + str(len(v)) + ' entries]') for k, v in rule.items())}", flush=True)
+    for name, _ in cases:
+        w = wall[name]
+        print(f"{tag}: {name}: median {np.median(w) * 1e3:.0f} ms (min {min(w) * 1e3:.0f}, max {max(w) * 1e3:.0f}; 3 runs) = {sum(limits) / np.median(w):.0f} useful "
+              f"tokens/s; {steps_run[name]} steps, {np.median(w) * 1e3 / steps_run[name]:.3f} ms per step (prefills of the refills included)", flush=True)
+    # the whole step at equal rows under graph replay: the lock-step engine with the same choice rule against the per-row engine
+    eos_ids = rule.get("eos_token_id") or []
+    choice = device_choice(V, eos_ids, **{k: v for k, v in rule.items() if k != "eos_token_id"})
+    proc, sm = choice["processors"], choice["sampling"]
+    eos = torch.tensor(eos_ids, dtype=torch.int64, device=emb.device)
+    e1 = generation.DecodeEngine(dec, slots, 1, T, 256, processors=proc, eos_ids=eos_ids)
+    e1.prefill(*e1.compact(emb, mask))
+    e1.next_tokens.fill_(11)
+    e2 = ContinuousEngine(dec, slots, T, 256, eos_ids, pad, use_graph=False, choice=choice)
+    e2.load(list(range(slots)), [(emb[b], mask[b]) for b in range(slots)], [256] * slots, list(range(slots)))
+
+    def lock_step():
+        e1.feed(e1.next_tokens)
+        e1.decode_step()
+        lg = e1.process(e1.logits) if proc is not None else e1.logits
+        if sm is not None:
+            e1.sample_select(lg, eos, pad, sm["temperature"], sm["top_k"], sm["top_p"], sm["seed"])
+        else:
+            e1.greedy_select(lg, eos, pad)
+
+    def reset2():
+        e2.row_step.zero_()
+        e2.finished.zero_()
+
+    steps = {f"lock-step engine ({'p2t_logits_process + ' if proc else ''}{'p2t_sample_select' if sm else 'p2t_greedy_select'})": (lock_step, lambda: e1.step.zero_()),
+             f"per-row engine ({'p2t_logits_process_rows + ' if proc else ''}{'p2t_sample_select_rows' if sm else 'p2t_greedy_select_rows'})": (e2._advance, reset2)}
+    graphs = {}
+    for name, (go, reset) in steps.items():
+        go(); go()
+        graphs[name] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[name], capture_error_mode="thread_local"):
+            go()
+        reset()
+    ms = {name: [] for name in steps}
+    for _ in range(3):
+        for name, (_, reset) in steps.items():
+            reset()
+            ms[name].append(_events(graphs[name].replay, 100) / 1e3)
+    for name, r in ms.items():
+        print(f"{tag}: {slots} rows, counters 0 .. 110, graph replay of {{embed, step, choice}}, {name}: median {np.median(r):.3f} ms/step "
+              f"(min {min(r):.3f}, max {max(r):.3f}; 3 runs)", flush=True)
+    (la, ra), (lb, rb) = ms.items()
+    spread = max(max(ra) - min(ra), max(rb) - min(rb))
+    over = np.median(rb) - np.median(ra)
+    print(f"{tag}: per-row - lock-step = {over * 1e3:+.1f} us per step; the runs' min .. max spread is {spread * 1e3:.1f} us: "
+          f"{'within' if over <= spread else 'BEYOND'} the spread", flush=True)
+    assert not bool(e2.finished.any().item()) and int(e2.sample_flags.item()) == 0
+
+
 def main():
     dev = torch.device("cuda:0")
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
     N = int(sys.argv[2]) if len(sys.argv) > 2 else 128
-    sample = len(sys.argv) > 3 and sys.argv[3] == "sample"
+    sample = len(sys.argv) > 3 and sys.argv[3] == "sample"        # (after `continuous`, sample / process name that leg's choice rule)
     process = len(sys.argv) > 3 and sys.argv[3] == "process"
     head = "head" in sys.argv[3:5]                               # [B] [N] [beams] head [fp8 | mxfp4] [kv8] [fp8 | mxfp4 weights]
     kv8 = "kv8" in sys.argv[3:5] and not head
@@ -442,8 +544,10 @@ def main():
     beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample and not process and sys.argv[3] not in ("kv8", "head", "continuous") else 1
     gemm_dtype = sys.argv[4] if len(sys.argv) > 4 and sys.argv[4] in ("fp8", "mxfp4") else "model"
     cont_extra = {}
+    choice_leg = None
     if continuous:
         after = sys.argv[4:]
+        choice_leg = after[0] if after and after[0] in CHOICE_LEGS else None
         gemm_dtype = after[0] if after and after[0] in ("fp8", "mxfp4") else "model"
         if "kv8" in after:
             cont_extra["prompt_kv_dtype"] = "fp8"
@@ -480,6 +584,8 @@ def main():
     t = lambda a: torch.from_numpy(a).to(dev)
     kw = dict(inputs=t(ids), attention_mask=torch.ones((B, T), dtype=torch.int64, device=dev), protein_input_ids=t(pid),
               protein_attention_mask=t(pmask), max_new_tokens=N, eos_token_id=None, pad_token_id=128002, do_sample=False, num_beams=beams)
+    if continuous and choice_leg:
+        return continuous_choice_mode(model, kw, B, N, T, choice_leg)
     if continuous:
         return continuous_mode(model, kw, B, N, T, gemm_dtype, cont_extra)
     if head:

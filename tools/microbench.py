@@ -2,6 +2,9 @@
 """Kernel micro-benchmarks on the GPU box (HIP-event timed, random data): GEMM shapes of the
 cfg-3 towers, attention, norms.  Usage: python tools/microbench.py [gemm] [attn] [norm]
 `attn_decode` [m8] [m32]: the decode step's attention alone over the bf16 and the fp8 prompt segment of the KV cache.
+`choice_rows` [m8] [m32]: the per-row choice kernels of continuous batching alone (p2t_sample_select_rows, p2t_logits_process_rows) on
+[rows, 128256] bf16 logits next to their lock-step twins, with no row and with half of the rows finished (the per-row kernels leave a
+finished row before they read it; the lock-step ones do its whole work).
 
 The `gemm` / `cold` / `ksweep` modes force launch forms through p2t_set_gemm_policy, and `fp8abl` runs the fp8 K-loop ablations
 (tile 1001-1003): run them against the LAB build (P2T_HIP_LIB=tools/build/libp2t_lab.so, `make -C prot2text-v2-esm3_amd/csrc lab`);
@@ -312,6 +315,50 @@ def bench_attn_decode():
                   f"{nbytes / np.median(r) / 1e3:5.0f} GB/s of cache bytes ({nbytes / 1e6:.1f} MB)", flush=True)
 
 
+def bench_choice_rows():
+    """p2t_sample_select / p2t_sample_select_rows (top_k 50, top_p 0.9, temperature 0.7) and p2t_logits_process / p2t_logits_process_rows
+    (every stage on, 64 history tokens) on randn * 3 bf16 logits [rows, 128256] at pitch 128320, alternating, five rounds of 200 launches,
+    median and range; `finished`: 0 or every second row (the lock-step processors take no finished array: they process every row)."""
+    import numpy as np
+    from p2t_hip.ops import ptr, stream
+    V, G, hist, rounds, n = 128256, 256, 64, 5, 200
+    ld = ops.round_up(V, 64)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    for B in [int(a[1:]) for a in sys.argv if a.startswith("m") and a[1:].isdigit()] or [8, 32]:
+        lg = (torch.randn((B, ld), device=dev, generator=gen) * 3).to(torch.bfloat16)
+        out_tokens = torch.randint(0, 1000, (B, G), device=dev, generator=gen)
+        nxt, flags = torch.zeros((B,), dtype=torch.int64, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev)
+        step, row_step = torch.full((1,), hist, dtype=torch.int32, device=dev), torch.full((B,), hist, dtype=torch.int32, device=dev)
+        row_limit, row_key = torch.full((B,), G, dtype=torch.int32, device=dev), torch.arange(B, device=dev)
+        processed = torch.zeros((B, ld), dtype=torch.float32, device=dev)
+        eos = torch.tensor([128001, 128009], dtype=torch.int64, device=dev)
+        words = [[11, 12], [13, 14, 15], [16]] * 8 + [[t] for t in range(100, 132)]
+        word_ids = torch.tensor([t for w in words for t in w], dtype=torch.int64, device=dev)
+        offsets = torch.tensor(np.concatenate([[0], np.cumsum([len(w) for w in words])]), dtype=torch.int32, device=dev)
+        proc = (1.3, 3, G, ptr(eos), 2, ptr(word_ids), ptr(offsets), len(words), word_ids.numel())
+        for half in (False, True):
+            fin = torch.zeros((B,), dtype=torch.int32, device=dev)
+            if half:
+                fin[1::2] = 2
+            kernels = {
+                "p2t_sample_select      ": lambda: _lib.call("p2t_sample_select", ptr(lg), _lib.BF16, ld, V, B, None, 0, 0, ptr(fin), ptr(nxt), ptr(out_tokens), G,
+                                                             ptr(step), G, 0.7, 50, 0.9, 1, 0, None, 0, ptr(flags), stream()),
+                "p2t_sample_select_rows ": lambda: _lib.call("p2t_sample_select_rows", ptr(lg), _lib.BF16, ld, V, B, None, 0, 0, ptr(fin), ptr(nxt),
+                                                             ptr(out_tokens), G, ptr(row_step), ptr(row_limit), None, ptr(row_key), B, G, 0.7, 50, 0.9, 1, None, 0,
+                                                             ptr(flags), stream()),
+                "p2t_logits_process     ": lambda: _lib.call("p2t_logits_process", ptr(lg), _lib.BF16, ld, V, B, ptr(out_tokens), G, ptr(step), G, ptr(processed), ld,
+                                                             *proc, stream()),
+                "p2t_logits_process_rows": lambda: _lib.call("p2t_logits_process_rows", ptr(lg), _lib.BF16, ld, V, B, ptr(out_tokens), G, ptr(row_step), None,
+                                                             ptr(fin), B, G, ptr(processed), ld, *proc, stream())}
+            res = {k: [] for k in kernels}
+            for _ in range(rounds):
+                for k, go in kernels.items():
+                    res[k].append(timeit(go, iters=n, warm=10) * 1e3)
+            for k, r in res.items():
+                print(f"choice_rows rows={B:2d} [{B}, {V}] bf16, {hist} history tokens, {B // 2 if half else 0:2d} rows finished, {k}: median {np.median(r):6.1f} us "
+                      f"(min {min(r):.1f}, max {max(r):.1f}; {rounds} rounds of {n})", flush=True)
+
+
 def bench_fp8abl():
     """Lab ablations of the fp8 K loop (per-tile kernel, garbage results; lab build only): full / no DMA / no fragment reloads / neither."""
     for name, M, N, K in (("esm qkv b64", 65536, 7680, 2560), ("esm fc2 b64", 65536, 2560, 10240), ("square 8k", 8192, 8192, 8192)):
@@ -344,5 +391,7 @@ if __name__ == "__main__":
         bench_skinny()
     if "attn_decode" in which:
         bench_attn_decode()
+    if "choice_rows" in which:
+        bench_choice_rows()
     if "fp8abl" in which:
         bench_fp8abl()
