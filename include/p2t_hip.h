@@ -1026,6 +1026,34 @@ int p2t_attention_decode_rows(const void* q, const void* k_prompt, const void* v
  * first step[0] tokens of every layer / head (k_dst, vt_dst: second buffers of the same shape; the caller swaps). */
 int p2t_kv_reorder(const p2t_llama_config* cfg, const p2t_kv_cache* cache, const int64_t* src_row, void* k_dst, void* vt_dst,
                    p2t_stream stream);
+/* ---- beam search without the cache copy (opt-in): the generated keys / values stay in the physical row that wrote them, and an
+ * ANCESTRY TABLE beside the cache (as row_step is; p2t_kv_cache keeps its layout) says where a beam's history lies: ancestry, device
+ * u8 [B0 * group][cache->G], ancestry[r][i] = the index inside r's prompt (0 .. group - 1) of the physical row whose generated segment
+ * holds key i of beam row r's history.  Zero-initialised; columns > step[0] are never read. */
+/* The table's update, in p2t_kv_reorder's place in the step (before the step that appends at index step[0]): with s = clamp(step[0],
+ * 0, G - 1) read on the device, new[r][i] = old[src_rows[r]][i] for i < s, new[r][s] = r % group, columns > s untouched; in place, as
+ * if all reads preceded all writes (one thread per (prompt, column) reads the prompt's group bytes, then writes them).  src_rows: what
+ * p2t_beam_select* writes (global row indices inside the row's own prompt); a source outside the row's prompt is clamped into it.
+ * Null arguments, group < 2: P2T_ERR_ARG; group > 16: P2T_ERR_UNSUPPORTED; before any launch.  One launch, capturable. */
+int p2t_kv_ancestry_update(const p2t_kv_cache* cache, const int64_t* src_rows, uint8_t* ancestry, p2t_stream stream);
+/* p2t_attention_decode / p2t_attention_decode_prompt_fp8 (the scale arrays both set, or both NULL) for a beam group under an ancestry
+ * table: row r attends to prompt_len[r / group] prompt keys and to the step[0] + 1 generated keys (p, i) -- key i of physical row p of
+ * r's prompt -- with ancestry[r][i] == p % group.  The matrix-pipe kernel runs one block per (prompt, kv head) and chunk of 16 / (nh /
+ * nkv) beams: its 16 head slots are (beam, head) pairs, the prompt segment is streamed once for all of them, the generated tiles of
+ * the group's physical rows are streamed with the table as one more condition of the score select (a slot with no visible key in a
+ * tile keeps its running statistics as they were).  use_mfma = 0 / f32: the lane-per-key kernel, one block per (row, kv head), the
+ * same rule.  ancestry == NULL, group < 2: P2T_ERR_ARG; group > 16 or nh / nkv > 16: P2T_ERR_UNSUPPORTED. */
+int p2t_attention_decode_beams(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
+                               const int32_t* prompt_len, const int32_t* step, int B0, int group, int nh, int nkv, int head_dim, int Tp,
+                               int G, float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out,
+                               const uint8_t* k_prompt_scale, const uint8_t* v_prompt_scale, const uint8_t* ancestry, p2t_stream stream);
+/* p2t_llama_decode_step_q whose attention is p2t_attention_decode_beams': every other launch is that step's, for every weight form and
+ * head.  Row r appends at index step[0] of ITS OWN physical row, as ever; the caller has run p2t_kv_ancestry_update for this step.
+ * ancestry == NULL, cache->group < 2: P2T_ERR_ARG; group > 16 or heads / kv_heads > 16: P2T_ERR_UNSUPPORTED; all before any launch. */
+int p2t_llama_decode_step_beams(const p2t_llama_config* cfg, const p2t_llama_weights* w, const p2t_llama_layer_stream* w_stream,
+                                const p2t_llama_layer_mxfp4* mx_layers, const void* lm_head, int64_t ld_head, int lm_head_preshuffled,
+                                const p2t_lm_head_q* head_q, const p2t_kv_cache* cache, const float* x, void* logits, int64_t ld_logits,
+                                int flags, void* workspace, size_t workspace_bytes, const uint8_t* ancestry, p2t_stream stream);
 
 /* ---------------------------------------------------------------- optimizer tail */
 /* One clip_grad_norm_(max_norm) + AdamW step over n_tensors (<= 64) f32 parameter tensors (HOST arrays of

@@ -4,6 +4,9 @@
 //     HIP graph without a host round trip): a row attends to prompt_len[b0] + step + 1 keys;
 //   * per-row counters (continuous batching): the same kernels read step[row * stride] with stride 1 where the lock-step entry points
 //     pass stride 0;
+//   * a beam group under an ancestry table (p2t_attention_decode_beams, the lock-step counter): the generated keys of ALL rows of the
+//     prompt are streamed and key i of physical row p counts for beam row r where ancestry[r][i] == p; the matrix-pipe kernel then runs one
+//     block per (prompt, kv head) with (beam, head) pairs as its 16 head slots (attn_decode_beams_mfma_kernel);
 //   * the fp8 prompt segment (bf16 models, the cache's scale arrays set) is read by the F8 tiles of the matrix-pipe kernel.
 #include "common.h"
 #include "kernels.h"
@@ -24,34 +27,52 @@ namespace {
 // in wave order, and the store of the normalised rows.  One block owns ALL keys of its (row, kv head): a split over several blocks
 // with a last-arriver merge through global memory was measured at 42 us per launch against 24 for this form at 8 x 1121 keys -- three
 // more dependent round trips to memory and a release fence per block cost more than the idle CUs.
+template <int DP, int GH, int NW>
+__device__ __forceinline__ float merged_output(const float (&red)[NW][GH][DP + 2], int g, int c) {      // feature c of head slot g, normalised
+    float M = -INFINITY;
+#pragma unroll
+    for (int ww = 0; ww < NW; ++ww) M = fmaxf(M, red[ww][g][DP]);
+    float o = 0.f, L = 0.f;
+#pragma unroll
+    for (int ww = 0; ww < NW; ++ww) {
+        const float mw = red[ww][g][DP];
+        if (mw > -INFINITY) {
+            const float f = exp2f(mw - M);
+            o += f * red[ww][g][c];
+            L += f * red[ww][g][DP + 1];
+        }
+    }
+    return o / L;
+}
+
 template <typename T, int DP, int GH, int NW>
 __device__ __forceinline__ void decode_merge(float (&red)[NW][GH][DP + 2], int bb, int h0, int nhead, int d, T* __restrict__ out, int64_t ld_out) {
     for (int i = threadIdx.x; i < GH * DP; i += NW * 64) {
         const int g = i / DP, c = i - g * DP;
         if (g >= nhead || c >= d) continue;
-        float M = -INFINITY;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) M = fmaxf(M, red[ww][g][DP]);
-        float o = 0.f, L = 0.f;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) {
-            const float mw = red[ww][g][DP];
-            if (mw > -INFINITY) {
-                const float f = exp2f(mw - M);
-                o += f * red[ww][g][c];
-                L += f * red[ww][g][DP + 1];
-            }
-        }
-        out[(int64_t)bb * ld_out + (int64_t)(h0 + g) * d + c] = from_f32<T>(o / L);
+        out[(int64_t)bb * ld_out + (int64_t)(h0 + g) * d + c] = from_f32<T>(merged_output<DP, GH, NW>(red, g, c));
     }
 }
 
-template <typename T, int DP, int GH>
+// The same for the beam kernel's 16 head slots: slot j = (beam beam0 + j / G, head j % G) of prompt b0 writes its own row
+template <int DP, int NW>
+__device__ __forceinline__ void decode_merge_beams(float (&red)[NW][16][DP + 2], int b0, int group, int beam0, int BC, int kvh, int G, int d,
+                                                   bf16_t* __restrict__ out, int64_t ld_out) {
+    for (int i = threadIdx.x; i < 16 * DP; i += NW * 64) {
+        const int j = i / DP, c = i - j * DP, sb = j / G, sh = j - sb * G;
+        if (sb >= BC || beam0 + sb >= group || c >= d) continue;
+        out[(int64_t)(b0 * group + beam0 + sb) * ld_out + (int64_t)(kvh * G + sh) * d + c] = from_f32<bf16_t>(merged_output<DP, 16, NW>(red, j, c));
+    }
+}
+
+// ANC (a beam group under an ancestry table, `anc` u8 [BB][Gcap]): the generated tiles are those of ALL `group` physical rows of the
+// row's prompt, and key i of physical row p counts where anc[bb][i] == p -- a tile may then hold no visible key at all.
+template <typename T, int DP, int GH, bool ANC = false>
 __global__ void __launch_bounds__(512) attn_decode_kernel(const T* __restrict__ q, const T* __restrict__ kp, const T* __restrict__ vtp,
                                                           const T* __restrict__ kg, const T* __restrict__ vtg,
                                                           const int32_t* __restrict__ prompt_len, const int32_t* __restrict__ step_ptr,
                                                           int step_stride, int group, int nh, int nkv, int G, int Tp, int Gcap, float c_exp, int round_p,
-                                                          T* __restrict__ out, int64_t ld_out, int d) {
+                                                          T* __restrict__ out, int64_t ld_out, int d, const uint8_t* __restrict__ anc) {
     constexpr int PN = Piece<T>::N, R = DP > 64 ? DP / 64 : 1, PW = DP + 2, NW = 8;
     __shared__ float sq[GH][DP];
     __shared__ float sp[NW][GH][64];
@@ -66,11 +87,12 @@ __global__ void __launch_bounds__(512) attn_decode_kernel(const T* __restrict__ 
     }
     __syncthreads();
     const int n0 = min(max(prompt_len[b0], 0), Tp), n1 = min(max(step_ptr[(int64_t)bb * step_stride], 0) + 1, Gcap);
-    const int tiles0 = (n0 + 63) >> 6, tiles = tiles0 + ((n1 + 63) >> 6);
+    const int tiles0 = (n0 + 63) >> 6, tiles1 = (n1 + 63) >> 6, tiles = tiles0 + (ANC ? group : 1) * tiles1;
+    const int64_t seg1 = (int64_t)nkv * Gcap * DP;                            // one row of the generated segment
     const T* k_seg0 = kp + ((int64_t)b0 * nkv + kvh) * Tp * DP;
-    const T* k_seg1 = kg + ((int64_t)bb * nkv + kvh) * Gcap * DP;
+    const T* k_seg1 = kg + ((int64_t)(ANC ? b0 * group : bb) * nkv + kvh) * Gcap * DP;      // ANC: the prompt's physical row 0
     const T* v_seg0 = vtp + ((int64_t)b0 * nkv + kvh) * DP * Tp;
-    const T* v_seg1 = vtg + ((int64_t)bb * nkv + kvh) * DP * Gcap;
+    const T* v_seg1 = vtg + ((int64_t)(ANC ? b0 * group : bb) * nkv + kvh) * DP * Gcap;
 
     float m_run[GH], l_run[GH], acc[GH][R];
 #pragma unroll
@@ -81,10 +103,14 @@ __global__ void __launch_bounds__(512) attn_decode_kernel(const T* __restrict__ 
         for (int r = 0; r < R; ++r) acc[g][r] = 0.f;
     }
     for (int t = w; t < tiles; t += NW) {
-        const int sg = t >= tiles0, tt = sg ? t - tiles0 : t, n = sg ? n1 : n0, cap = sg ? Gcap : Tp;
+        const int sg = t >= tiles0, n = sg ? n1 : n0, cap = sg ? Gcap : Tp;
+        const int phys = ANC && sg ? (t - tiles0) / tiles1 : 0;               // ANC: which physical row of the prompt the tile lies in
+        const int tt = sg ? (ANC ? t - tiles0 - phys * tiles1 : t - tiles0) : t;
         const int key = tt * 64 + lane;
-        const bool valid = key < n, full = tt * 64 + 64 <= n;
-        const T* krow = (sg ? k_seg1 : k_seg0) + (int64_t)key * DP;
+        bool valid = key < n;
+        const bool full = tt * 64 + 64 <= n;
+        if (ANC && sg) valid = valid && anc[(int64_t)bb * Gcap + key] == phys;
+        const T* krow = (sg ? (ANC ? k_seg1 + phys * seg1 : k_seg1) : k_seg0) + (int64_t)key * DP;
         float sc[GH];
 #pragma unroll
         for (int g = 0; g < GH; ++g) sc[g] = 0.f;
@@ -104,9 +130,10 @@ __global__ void __launch_bounds__(512) attn_decode_kernel(const T* __restrict__ 
 #pragma unroll
         for (int g = 0; g < GH; ++g) {
             const float e2 = valid ? sc[g] * c_exp : -INFINITY;
-            const float m_new = fmaxf(m_run[g], wave_max(e2));            // every tile holds at least one valid key
-            const float alpha = exp2f(m_run[g] - m_new);
-            float p = valid ? exp2f(e2 - m_new) : 0.f;
+            const float m_new = fmaxf(m_run[g], wave_max(e2));            // every tile holds at least one valid key -- unless ANC:
+            const float m_ref = ANC && m_new == -INFINITY ? 0.f : m_new;  // nothing visible so far: alpha = 0 on (l, acc) = 0, no -inf - -inf
+            const float alpha = exp2f(m_run[g] - m_ref);
+            float p = valid ? exp2f(e2 - m_ref) : 0.f;
             l_run[g] = l_run[g] * alpha + p;
             if (round_p) p = to_f32(from_f32<T>(p));                      // the MFMA forward feeds P to the matrix pipe in bf16
             sp[w][g][lane] = p;
@@ -119,7 +146,7 @@ __global__ void __launch_bounds__(512) attn_decode_kernel(const T* __restrict__ 
         for (int r = 0; r < R; ++r) {
             const int dim = lane + 64 * r;
             if (dim < DP) {
-                const T* vrow = (sg ? v_seg1 : v_seg0) + (int64_t)dim * cap + tt * 64;
+                const T* vrow = (sg ? (ANC ? v_seg1 + phys * seg1 : v_seg1) : v_seg0) + (int64_t)dim * cap + tt * 64;
 #pragma unroll 2
                 for (int j = 0; j < 64; j += PN) {
                     float vv[PN];
@@ -182,13 +209,24 @@ __device__ __forceinline__ float e8m0_byte_to_f32(unsigned word, int byte) {    
 }
 
 // One 64-key tile `tt` of a segment of `cap` keys, `n` of them valid, into a wave's running (max, sum, output).
-template <int DP, bool F8>
+// ANC (bf16 tiles of a beam group's generated segment, attn_decode_beams_mfma_kernel): the segment is physical row `phys` of the prompt
+// and key i counts for the lane's head slot where anc_row[i] == phys (anc_row: the ancestry row of the slot's beam).  Two things differ
+// from the other tiles: a slot may see NO key of the tile, and then keeps (m_run, l_run, acc) exactly; and masked keys inside n hold
+// other beams' finite values, which p = 0 silences without zeroing V.
+template <int DP, bool F8, bool ANC = false>
 __device__ __forceinline__ void decode_tile(const void* __restrict__ k_seg, const void* __restrict__ v_seg, const uint8_t* __restrict__ ks_seg,
                                             const uint8_t* __restrict__ vs_seg, int tt, int n, int cap, const bf16x8 (&qf)[DP / 32], float c_exp, int j,
-                                            int g, float& m_run, float& l_run, f32x4 (&acc)[DP / 16]) {
+                                            int g, float& m_run, float& l_run, f32x4 (&acc)[DP / 16], const uint8_t* __restrict__ anc_row = nullptr,
+                                            int phys = 0) {
+    static_assert(!(F8 && ANC), "the generated segment is bf16");
     constexpr int KK = DP / 32, DT = DP / 16;
     const bool full = tt * 64 + 64 <= n;
     f32x4 sc[4];
+    uint2 aw[ANC ? 2 : 1] = {};              // the table bytes of the lane's two runs of 8 keys (32 hv + 8 g ..)
+    if constexpr (ANC) {
+#pragma unroll
+        for (int hv = 0; hv < 2; ++hv) aw[hv] = *reinterpret_cast<const uint2*>(anc_row + tt * 64 + 32 * hv + 8 * g);
+    }
     // all fragments of the tile first (32 loads of 16 bytes in flight per lane for bf16), then the arithmetic
     bf16x8 kf[F8 ? 1 : 4][F8 ? 1 : KK], vf[F8 ? 1 : 2][F8 ? 1 : DT];
     unsigned kw[F8 ? 4 : 1][2 * KK];
@@ -249,7 +287,8 @@ __device__ __forceinline__ void decode_tile(const void* __restrict__ k_seg, cons
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int key = F8 ? 16 * g + 4 * st + r : 32 * (st >> 1) + 8 * g + 4 * (st & 1) + r;
-            const bool ok = full || tt * 64 + key < n;
+            bool ok = full || tt * 64 + key < n;
+            if constexpr (ANC) ok = ok && (int)((((st & 1) ? aw[st >> 1].y : aw[st >> 1].x) >> (8 * r)) & 0xFFu) == phys;
             float s = sc[st][r];
             if constexpr (F8) s *= e8m0_byte_to_f32(ksw[st], r);
             sc[st][r] = ok ? s * c_exp : -INFINITY;                   // a select: what a key behind the prefix holds goes no further
@@ -257,9 +296,10 @@ __device__ __forceinline__ void decode_tile(const void* __restrict__ k_seg, cons
         }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = fmaxf(m_run, mx);                          // every tile holds at least one valid key
-    const float alpha = exp2f(m_run - m_new);
+    float m_new = fmaxf(m_run, mx);                                // every tile holds at least one valid key -- unless ANC:
+    const float alpha = exp2f(m_run - (ANC && m_new == -INFINITY ? 0.f : m_new));      // nothing visible so far: 0 on (l, acc) = 0, no -inf - -inf
     m_run = m_new;
+    if (ANC && m_new == -INFINITY) m_new = 0.f;                    // ... and p = exp2(-inf - 0) = 0
     if (F8 && !full) {                                             // code and scale bytes behind the valid prefix -> 0 (0 x garbage must stay 0)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -371,6 +411,72 @@ __global__ void __launch_bounds__(NW * 64) attn_decode_mfma_kernel(const bf16_t*
     decode_merge<bf16_t, DP, GH, NW>(red, bb, h0, nhead, d, out, ld_out);
 }
 
+// A beam group under an ancestry table (include/p2t_hip.h): grid (B0 * nkv, beam chunks), ONE block per (prompt, kv head) and chunk of
+// BC = 16 / G beams.  The 16 head slots of the products above are (beam, head) pairs -- slot j = (beam beam0 + j / G, head j % G), its
+// own q row -- so the prompt segment is streamed once for all beams of the chunk; then the generated tiles of the prompt's `group`
+// physical rows, each with the table as one more condition of the score select (decode_tile's ANC form).  Tile t of that one list goes
+// to wave t mod NW; the merge is decode_merge's, per slot.  LDS: red[NW][16][DP + 2] f32 = 66.5 KB at (NW 8, DP 128) and 67.6 KB at
+// (16, 64), of the CU's 160 KB.
+template <int DP, int NW, bool P8>
+__global__ void __launch_bounds__(NW * 64) attn_decode_beams_mfma_kernel(const bf16_t* __restrict__ q, const void* __restrict__ kp,
+                                                                     const void* __restrict__ vtp, const bf16_t* __restrict__ kg,
+                                                                     const bf16_t* __restrict__ vtg, const uint8_t* __restrict__ kps,
+                                                                     const uint8_t* __restrict__ vps, const int32_t* __restrict__ prompt_len,
+                                                                     const int32_t* __restrict__ step_ptr, const uint8_t* __restrict__ anc, int group,
+                                                                     int nh, int nkv, int G, int Tp, int Gcap, float c_exp, bf16_t* __restrict__ out,
+                                                                     int64_t ld_out, int d) {
+    constexpr int PW = DP + 2, KK = DP / 32, DT = DP / 16, EP = P8 ? 1 : 2;
+    __shared__ float red[NW][16][PW];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
+    const int pair = blockIdx.x, b0 = pair / nkv, kvh = pair - b0 * nkv;
+    const int BC = 16 / G, beam0 = blockIdx.y * BC, sb = j / G, sh = j - sb * G;
+    const bool live = sb < BC && beam0 + sb < group;
+    // a slot without a beam reads a real row's table and a zero q: its numbers stay finite and decode_merge_beams stores none of them
+    const int row = b0 * group + min(beam0 + sb, group - 1);
+    const bf16x8 zero8 = {};
+    const bf16_t* qrow = q + ((int64_t)row * nh + kvh * G + sh) * DP;
+    auto load_q = [&](bf16x8 (&qf)[KK], bool f8_order) {            // attn_decode_mfma_kernel's, per slot
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) {
+            const int f = f8_order && DP > 32 ? 64 * (kk >> 1) + 16 * g + 8 * (kk & 1) : 32 * kk + 8 * g;
+            qf[kk] = live ? *reinterpret_cast<const bf16x8*>(qrow + f) : zero8;
+        }
+    };
+    bf16x8 qf[KK];
+    load_q(qf, P8);
+    const int n0 = min(max(prompt_len[b0], 0), Tp), n1 = min(max(step_ptr[0], 0) + 1, Gcap);
+    const int tiles0 = (n0 + 63) >> 6, tiles1 = (n1 + 63) >> 6, tiles = tiles0 + group * tiles1;
+    const char* k_seg0 = (const char*)kp + ((int64_t)b0 * nkv + kvh) * Tp * DP * EP;
+    const char* v_seg0 = (const char*)vtp + ((int64_t)b0 * nkv + kvh) * DP * Tp * EP;
+    const uint8_t* ks_seg0 = P8 ? kps + ((int64_t)b0 * nkv + kvh) * Tp : nullptr;
+    const uint8_t* vs_seg0 = P8 ? vps + ((int64_t)b0 * nkv + kvh) * Tp : nullptr;
+    const int64_t seg1 = (int64_t)nkv * Gcap * DP;                    // one row of the generated segment (K and V^T alike)
+    const bf16_t* k_grp = kg + (int64_t)b0 * group * seg1 + (int64_t)kvh * Gcap * DP;       // physical row 0 of the prompt
+    const bf16_t* v_grp = vtg + (int64_t)b0 * group * seg1 + (int64_t)kvh * DP * Gcap;
+    const uint8_t* anc_row = anc + (int64_t)row * Gcap;
+    float m_run = -INFINITY, l_run = 0.f;
+    f32x4 acc[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    auto gen_tile = [&](int u) {                                     // tile u of the generated list: physical row u / tiles1
+        const int p = u / tiles1, tt = u - p * tiles1;
+        decode_tile<DP, false, true>(k_grp + p * seg1, v_grp + p * seg1, nullptr, nullptr, tt, n1, Gcap, qf, c_exp, j, g, m_run, l_run, acc, anc_row, p);
+    };
+    int t = w;
+    for (; t < tiles0; t += NW) decode_tile<DP, P8>(k_seg0, v_seg0, ks_seg0, vs_seg0, t, n0, Tp, qf, c_exp, j, g, m_run, l_run, acc);
+    if (P8 && t < tiles) load_q(qf, false);                          // the bf16 tiles' feature order
+    for (; t < tiles; t += NW) gen_tile(t - tiles0);
+    l_run += __shfl_xor(l_run, 16, 64);
+    l_run += __shfl_xor(l_run, 32, 64);
+    if (g == 0) { red[w][j][DP] = m_run; red[w][j][DP + 1] = l_run; }       // lane (slot j, g) holds the features 16 dt + 4 g + r of its slot
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[w][j][16 * dt + 4 * g + r] = acc[dt][r];
+    __syncthreads();
+    decode_merge_beams<DP, NW>(red, b0, group, beam0, BC, kvh, G, d, out, ld_out);
+}
+
 int pick_gh(int G) { return G <= 1 ? 1 : (G <= 2 ? 2 : (G <= 4 ? 4 : 8)); }
 
 template <typename T>
@@ -416,7 +522,7 @@ int launch_attn_decode_t(const p2t_llama_config* c, const void* q, void* out, in
     P2T_REQUIRE(!kc->k_prompt_scale, "attention over an fp8 prompt segment: the matrix-pipe kernel only");
 #define P2T_AD(DPV, GHV)                                                                                                              \
     attn_decode_kernel<T, DPV, GHV><<<grid, 512, 0, s>>>((const T*)q, kp, vtp, kg, vtg, kc->prompt_len, kc->step, step_stride, kc->group, nh, nkv, G, \
-                                                         kc->Tp, kc->G, c_exp, round_p, (T*)out, ld_out, d)
+                                                         kc->Tp, kc->G, c_exp, round_p, (T*)out, ld_out, d, nullptr)
 #define P2T_AD_G(DPV)                                                                                                                 \
     do {                                                                                                                              \
         if (GH == 1) P2T_AD(DPV, 1); else if (GH == 2) P2T_AD(DPV, 2); else if (GH == 4) P2T_AD(DPV, 4); else P2T_AD(DPV, 8);      \
@@ -428,7 +534,63 @@ int launch_attn_decode_t(const p2t_llama_config* c, const void* q, void* out, in
     return P2T_OK;
 }
 
+// launch_attn_decode_t for a beam group under an ancestry table (checked: group 2 .. 16, G <= 16, the shared counter)
+template <typename T>
+int launch_attn_decode_beams_t(const p2t_llama_config* c, const void* q, void* out, int64_t ld_out, const p2t_kv_cache* kc, int layer, float c_exp,
+                               int round_p, int use_mfma, const uint8_t* anc, hipStream_t s) {
+    const int nh = c->heads, nkv = c->kv_heads, d = c->head_dim, dp = head_dim_padded(d), G = nh / nkv, BB = kc->B0 * kc->group;
+    const size_t per_p = (size_t)kc->B0 * nkv * kc->Tp * dp, per_g = (size_t)BB * nkv * kc->G * dp;
+    const T* kg = (const T*)kc->k_gen + per_g * layer;
+    const T* vtg = (const T*)kc->vt_gen + per_g * layer;
+    if constexpr (sizeof(T) == 2) {
+        if (use_mfma) {
+            const int BC = 16 / G;                   // beams per block: its 16 head slots are (beam, head) pairs
+            const dim3 grid((unsigned)(kc->B0 * nkv), (unsigned)ceil_div(kc->group, BC));
+            const size_t per_s = (size_t)kc->B0 * nkv * kc->Tp, e = kc->k_prompt_scale ? 1 : 2;
+            const char* kp = (const char*)kc->k_prompt + per_p * layer * e;
+            const char* vtp = (const char*)kc->vt_prompt + per_p * layer * e;
+            const uint8_t* kps = kc->k_prompt_scale ? kc->k_prompt_scale + per_s * layer : nullptr;
+            const uint8_t* vps = kc->k_prompt_scale ? kc->v_prompt_scale + per_s * layer : nullptr;
+#define P2T_ADB(DPV, P8V)                                                                                                             \
+    attn_decode_beams_mfma_kernel<DPV, (DPV <= 64 ? 16 : 8), P8V><<<grid, (DPV <= 64 ? 16 : 8) * 64, 0, s>>>(                          \
+        (const bf16_t*)q, kp, vtp, (const bf16_t*)kg, (const bf16_t*)vtg, kps, vps, kc->prompt_len, kc->step, anc, kc->group, nh, nkv, G, kc->Tp,   \
+        kc->G, c_exp, (bf16_t*)out, ld_out, d)
+            if (kps) {
+                if (dp == 32) P2T_ADB(32, true); else if (dp == 64) P2T_ADB(64, true); else P2T_ADB(128, true);
+            } else {
+                if (dp == 32) P2T_ADB(32, false); else if (dp == 64) P2T_ADB(64, false); else P2T_ADB(128, false);
+            }
+#undef P2T_ADB
+            P2T_LAUNCH_CHECK();
+            return P2T_OK;
+        }
+    }
+    P2T_REQUIRE(!kc->k_prompt_scale, "attention over an fp8 prompt segment: the matrix-pipe kernel only");
+    const int GH = pick_gh(G), ZC = (G + GH - 1) / GH;
+    const dim3 grid((unsigned)(BB * nkv), (unsigned)ZC);
+    const T* kp = (const T*)kc->k_prompt + per_p * layer;
+    const T* vtp = (const T*)kc->vt_prompt + per_p * layer;
+#define P2T_ADL(DPV, GHV)                                                                                                             \
+    attn_decode_kernel<T, DPV, GHV, true><<<grid, 512, 0, s>>>((const T*)q, kp, vtp, kg, vtg, kc->prompt_len, kc->step, 0, kc->group, nh, nkv, G, kc->Tp, \
+                                                               kc->G, c_exp, round_p, (T*)out, ld_out, d, anc)
+#define P2T_ADL_G(DPV)                                                                                                                \
+    do {                                                                                                                              \
+        if (GH == 1) P2T_ADL(DPV, 1); else if (GH == 2) P2T_ADL(DPV, 2); else if (GH == 4) P2T_ADL(DPV, 4); else P2T_ADL(DPV, 8);  \
+    } while (0)
+    if (dp == 32) P2T_ADL_G(32); else if (dp == 64) P2T_ADL_G(64); else P2T_ADL_G(128);
+#undef P2T_ADL_G
+#undef P2T_ADL
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
 }  // namespace
+
+int launch_attn_decode_beams(const p2t_llama_config* c, const void* q, void* out, int64_t ld_out, const p2t_kv_cache* kc, int layer, float c_exp,
+                             int round_p, int use_mfma, const uint8_t* ancestry, hipStream_t s) {
+    return c->dtype == P2T_BF16 ? launch_attn_decode_beams_t<bf16_t>(c, q, out, ld_out, kc, layer, c_exp, round_p, use_mfma, ancestry, s)
+                                : launch_attn_decode_beams_t<float>(c, q, out, ld_out, kc, layer, c_exp, round_p, use_mfma, ancestry, s);
+}
 
 // one layer's attention of the step (llama_decode.hip) or of the doors below: c says the head shape and the dtype, kc the cache
 int launch_attn_decode(const p2t_llama_config* c, const void* q, void* out, int64_t ld_out, const p2t_kv_cache* kc, int layer, float c_exp, int round_p,
@@ -444,7 +606,7 @@ using namespace p2t;
 static int attention_decode_impl(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
                                  const int32_t* prompt_len, const int32_t* step, int B0, int group, int nh, int nkv, int head_dim, int Tp, int G,
                                  float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out, const uint8_t* k_prompt_scale,
-                                 const uint8_t* v_prompt_scale, int step_stride, p2t_stream stream) {
+                                 const uint8_t* v_prompt_scale, int step_stride, const uint8_t* ancestry, p2t_stream stream) {
     P2T_REQUIRE(q && out && (dtype == P2T_F32 || dtype == P2T_BF16) && nkv > 0 && nh % nkv == 0 && ld_out >= (int64_t)nh * head_dim,
                 "p2t_attention_decode: bad arguments");
     p2t_llama_config c{};
@@ -458,6 +620,7 @@ static int attention_decode_impl(const void* q, const void* k_prompt, const void
     }
     P2T_REQUIRE(dtype == P2T_BF16 || use_mfma <= 0, "p2t_attention_decode: the matrix-pipe kernel is bf16 only");
     const float c_exp = log2_scores ? 1.0f : scale * kLog2e;
+    if (ancestry) return launch_attn_decode_beams(&c, q, out, ld_out, &kc, 0, c_exp, dtype == P2T_BF16, use_mfma != 0, ancestry, (hipStream_t)stream);
     return launch_attn_decode(&c, q, out, ld_out, &kc, 0, c_exp, dtype == P2T_BF16, use_mfma != 0, step_stride, (hipStream_t)stream);
 }
 
@@ -465,7 +628,7 @@ extern "C" int p2t_attention_decode(const void* q, const void* k_prompt, const v
                                     const int32_t* prompt_len, const int32_t* step, int B0, int group, int nh, int nkv, int head_dim, int Tp, int G,
                                     float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out, p2t_stream stream) {
     return attention_decode_impl(q, k_prompt, vt_prompt, k_gen, vt_gen, prompt_len, step, B0, group, nh, nkv, head_dim, Tp, G, scale, log2_scores, dtype,
-                                 use_mfma, out, ld_out, nullptr, nullptr, 0, stream);
+                                 use_mfma, out, ld_out, nullptr, nullptr, 0, nullptr, stream);
 }
 
 extern "C" int p2t_attention_decode_prompt_fp8(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
@@ -475,7 +638,7 @@ extern "C" int p2t_attention_decode_prompt_fp8(const void* q, const void* k_prom
     P2T_REQUIRE(!k_prompt_scale == !v_prompt_scale, "p2t_attention_decode_prompt_fp8: k_prompt_scale and v_prompt_scale go together");
     P2T_REQUIRE(k_prompt_scale, "p2t_attention_decode_prompt_fp8: null scale arrays (p2t_attention_decode serves the bf16 prompt segment)");
     return attention_decode_impl(q, k_prompt, vt_prompt, k_gen, vt_gen, prompt_len, step, B0, group, nh, nkv, head_dim, Tp, G, scale, log2_scores, dtype,
-                                 use_mfma, out, ld_out, k_prompt_scale, v_prompt_scale, 0, stream);
+                                 use_mfma, out, ld_out, k_prompt_scale, v_prompt_scale, 0, nullptr, stream);
 }
 
 // p2t_attention_decode / p2t_attention_decode_prompt_fp8 (the scale arrays both set) with one counter per row: group == 1
@@ -486,5 +649,17 @@ extern "C" int p2t_attention_decode_rows(const void* q, const void* k_prompt, co
     P2T_REQUIRE(row_step, "p2t_attention_decode_rows: null row_step");
     P2T_REQUIRE(!k_prompt_scale == !v_prompt_scale, "p2t_attention_decode_rows: k_prompt_scale and v_prompt_scale go together");
     return attention_decode_impl(q, k_prompt, vt_prompt, k_gen, vt_gen, prompt_len, row_step, B0, 1, nh, nkv, head_dim, Tp, G, scale, log2_scores, dtype,
-                                 use_mfma, out, ld_out, k_prompt_scale, v_prompt_scale, 1, stream);
+                                 use_mfma, out, ld_out, k_prompt_scale, v_prompt_scale, 1, nullptr, stream);
+}
+
+// p2t_attention_decode / p2t_attention_decode_prompt_fp8 for a beam group whose generated keys stay in the rows that wrote them
+extern "C" int p2t_attention_decode_beams(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
+                                          const int32_t* prompt_len, const int32_t* step, int B0, int group, int nh, int nkv, int head_dim, int Tp, int G,
+                                          float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out,
+                                          const uint8_t* k_prompt_scale, const uint8_t* v_prompt_scale, const uint8_t* ancestry, p2t_stream stream) {
+    P2T_REQUIRE(nkv > 0 && nh > 0, "p2t_attention_decode_beams: bad arguments");
+    P2T_TRY(check_ancestry(ancestry, group, nh / nkv, "p2t_attention_decode_beams"));
+    P2T_REQUIRE(!k_prompt_scale == !v_prompt_scale, "p2t_attention_decode_beams: k_prompt_scale and v_prompt_scale go together");
+    return attention_decode_impl(q, k_prompt, vt_prompt, k_gen, vt_gen, prompt_len, step, B0, group, nh, nkv, head_dim, Tp, G, scale, log2_scores, dtype,
+                                 use_mfma, out, ld_out, k_prompt_scale, v_prompt_scale, 0, ancestry, stream);
 }

@@ -223,11 +223,18 @@ int llama_forward_impl(const p2t_llama_config* c, const p2t_llama_weights* w, co
 int llama_kv_store(const p2t_llama_config* c, const p2t_kv_cache* kc, int layer, const void* k, const void* v, int B, int T, hipStream_t s);
 // every refusal of a cache descriptor against the model's head shape and dtype (kv_cache.hip).  `who`: the entry point's name
 int check_cache(const p2t_llama_config* c, const p2t_kv_cache* kc, const char* who);
+// every refusal of a beam group under an ancestry table (kv_cache.hip): a null table, fewer than 2 or more than 16 rows per prompt, more
+// than 16 query heads per kv head (heads_per_kv 0: not the caller's concern)
+int check_ancestry(const void* ancestry, int group, int heads_per_kv, const char* who);
 // attention of one query token per row over layer `layer` of the cache (attn_decode.hip): q [BB, heads, dp] -> out [BB, ld_out], both the
 // model dtype; c gives heads / kv_heads / head_dim / dtype.  use_mfma (bf16): 0 = the lane-per-key kernel, the one f32 runs;
 // step_stride: 0 = the cache's shared counter, 1 = kc->step[row]
 int launch_attn_decode(const p2t_llama_config* c, const void* q, void* out, int64_t ld_out, const p2t_kv_cache* kc, int layer, float c_exp, int round_p,
                        int use_mfma, int step_stride, hipStream_t s);
+// the same over a beam group whose generated keys stay where they were written: key i of row r's history is in physical row
+// ancestry[r][i] of r's prompt (u8 [BB][kc->G], kv_cache.hip).  The shared counter; group 2 .. 16, at most 16 query heads per kv head
+int launch_attn_decode_beams(const p2t_llama_config* c, const void* q, void* out, int64_t ld_out, const p2t_kv_cache* kc, int layer, float c_exp,
+                             int round_p, int use_mfma, const uint8_t* ancestry, hipStream_t s);
 // SwiGLU on the interleaved gate / up pre-activations gu [M, 2F], forward and backward (activations.hip)
 int launch_swiglu_from_gu(const void* gu, int64_t ld_gu, void* act, int64_t ld_act, int64_t M, int64_t F, int dtype, hipStream_t s);
 int launch_swiglu_gu_bwd(const void* gu, int64_t ld_gu, const void* d_act, int64_t ld_da, void* d_gu, int64_t ld_dgu, int64_t M, int64_t F, int dtype,

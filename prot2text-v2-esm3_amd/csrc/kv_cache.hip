@@ -12,6 +12,9 @@
 //   * opt-in (continuous batching; group == 1): every row carries its OWN counter, row_step[row], beside the cache; p2t_kv_slot_load
 //     copies a freshly prefilled prompt segment from a staging cache into its slot and resets its counters, between two replays of the
 //     step graph;
+//   * opt-in (beam groups, group >= 2): the generated keys and values STAY in the row that wrote them and an ancestry table beside the
+//     cache, u8 [BB][G], names the row of the prompt that holds key i of a beam's history; p2t_kv_ancestry_update stands where the
+//     re-ordering copy stood, and the attention reads the table as a mask (attn_decode.hip);
 //   * opt-in for bf16 models (p2t_kv_cache's scale arrays set): the PROMPT segment as e4m3 codes in the same index order + one E8M0 scale
 //     byte per key for K and for V -- quantised by the prefill's store (kv_quant_store_kernel), read by the F8 tiles of the attention.
 #include "common.h"
@@ -182,6 +185,28 @@ __global__ void __launch_bounds__(256) kv_reorder_kernel(const T* __restrict__ k
     }
 }
 
+// The ancestry table of a beam group (include/p2t_hip.h), updated where kv_reorder_kernel would copy: grid (columns / 256, prompts), ONE
+// thread per (prompt, column <= s).  Column i of a prompt's rows depends on column i of the same rows only, so a thread that reads its
+// group bytes and then writes them is an in-place update without a barrier.
+constexpr int kAncestryGroupMax = 16;
+__global__ void __launch_bounds__(256) kv_ancestry_update_kernel(uint8_t* __restrict__ anc, const int64_t* __restrict__ src_rows,
+                                                                 const int32_t* __restrict__ step_ptr, int group, int G) {
+    const int s = min(max(step_ptr[0], 0), G - 1);
+    const int i = blockIdx.x * 256 + threadIdx.x, b0 = blockIdx.y;
+    if (i > s) return;
+    uint8_t* col = anc + (int64_t)b0 * group * G + i;
+    uint8_t v[kAncestryGroupMax];
+#pragma unroll
+    for (int g = 0; g < kAncestryGroupMax; ++g) {
+        if (g >= group) continue;
+        const int64_t sr = min(max(src_rows[b0 * group + g] - (int64_t)b0 * group, (int64_t)0), (int64_t)group - 1);      // clamped into the prompt
+        v[g] = i == s ? (uint8_t)g : col[sr * G];
+    }
+#pragma unroll
+    for (int g = 0; g < kAncestryGroupMax; ++g)
+        if (g < group) col[(int64_t)g * G] = v[g];
+}
+
 int launch_kv_quant_store(const void* k, const void* v, int BH, int T, int d, int Tp, uint8_t* kq, uint8_t* vtq, uint8_t* ks, uint8_t* vs, hipStream_t s) {
     const int dp = head_dim_padded(d);
     const dim3 grid((unsigned)ceil_div(T, 64), (unsigned)BH);
@@ -206,6 +231,17 @@ int check_cache(const p2t_llama_config* c, const p2t_kv_cache* kc, const char* w
     }
     P2T_REQUIRE(!kc->k_prompt_scale || (((uintptr_t)kc->k_prompt | (uintptr_t)kc->vt_prompt | (uintptr_t)kc->k_prompt_scale | (uintptr_t)kc->v_prompt_scale) & 15) == 0,
                 "%s: the fp8 prompt segment's buffers must be 16-byte aligned", who);
+    return P2T_OK;
+}
+
+int check_ancestry(const void* ancestry, int group, int heads_per_kv, const char* who) {
+    P2T_REQUIRE(ancestry && ((uintptr_t)ancestry & 15) == 0, "%s: null ancestry table (or not 16-byte aligned)", who);
+    P2T_REQUIRE(group >= 2, "%s: an ancestry table serves beam groups (group >= 2, got %d)", who, group);
+    if (group > kAncestryGroupMax || heads_per_kv > 16) {
+        set_error("%s: an ancestry table serves at most %d rows per prompt and 16 query heads per kv head (got group %d, %d heads)", who,
+                  kAncestryGroupMax, group, heads_per_kv);
+        return P2T_ERR_UNSUPPORTED;
+    }
     return P2T_OK;
 }
 
@@ -301,6 +337,17 @@ extern "C" int p2t_kv_reorder(const p2t_llama_config* c, const p2t_kv_cache* cac
     else
         kv_reorder_kernel<float><<<grid, 256, 0, s>>>((const float*)cache->k_gen, (const float*)cache->vt_gen, (float*)k_dst, (float*)vt_dst, src_row,
                                                      cache->step, BB, nkv, dp, cache->G);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
+extern "C" int p2t_kv_ancestry_update(const p2t_kv_cache* cache, const int64_t* src_rows, uint8_t* ancestry, p2t_stream stream) {
+    P2T_REQUIRE(cache && src_rows && cache->step, "p2t_kv_ancestry_update: null argument");
+    P2T_TRY(check_ancestry(ancestry, cache->group, 0, "p2t_kv_ancestry_update"));
+    P2T_REQUIRE(cache->B0 > 0 && cache->B0 <= 65535 && cache->G > 0 && cache->G % 64 == 0,
+                "p2t_kv_ancestry_update: 1 .. 65535 prompts and a capacity that is a positive multiple of 64 (B0 %d, G %d)", cache->B0, cache->G);
+    const dim3 grid((unsigned)ceil_div(cache->G, 256), (unsigned)cache->B0);
+    kv_ancestry_update_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(ancestry, src_rows, cache->step, cache->group, cache->G);
     P2T_LAUNCH_CHECK();
     return P2T_OK;
 }

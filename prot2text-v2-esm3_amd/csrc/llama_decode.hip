@@ -345,6 +345,7 @@ struct StepCall {
     const p2t_kv_cache* cache = nullptr; const float* x_in = nullptr; void* logits = nullptr; int64_t ld_logits = 0; int flags = 0;
     void* workspace = nullptr; size_t workspace_bytes = 0;
     int32_t* row_step = nullptr; const int32_t* frozen = nullptr;       // per-row counters (p2t_llama_decode_step_rows)
+    const uint8_t* ancestry = nullptr;                                  // the beam group's ancestry table (p2t_llama_decode_step_beams)
     p2t_stream stream = nullptr;
 };
 // the arguments that all four doors have, under the same names
@@ -385,6 +386,7 @@ static int check_step(const StepCall& a, p2t_kv_cache* kc, DecodeBuffers* b, uin
         set_error("%s: per-row counters serve group == 1 only (got %d)", who, kc->group);
         return P2T_ERR_UNSUPPORTED;
     }
+    if (a.ancestry) P2T_TRY(check_ancestry(a.ancestry, kc->group, c->heads / c->kv_heads, who));
     P2T_REQUIRE(!c->gemm_fp8 || c->dtype == P2T_BF16, "%s: gemm_fp8 needs bf16 activations (dtype = P2T_BF16)", who);
     const int BB = kc->B0 * kc->group;
     const int64_t H = c->hidden, Hp = round_up(H, 64);
@@ -499,7 +501,8 @@ static int decode_step(const StepCall& a) {
             r = launch_rope_append(b.qkv, NQKV, ra, L, c->rms_norm_eps, BB, dp, !fused_prefill, dt, s);
         }
         P2T_TRY(r);
-        P2T_TRY(launch_attn_decode(c, b.qb, b.ao, QO, &kc, l, c_exp, dt == P2T_BF16, 1, sstride, s));
+        if (a.ancestry) P2T_TRY(launch_attn_decode_beams(c, b.qb, b.ao, QO, &kc, l, c_exp, dt == P2T_BF16, 1, a.ancestry, s));
+        else P2T_TRY(launch_attn_decode(c, b.qb, b.ao, QO, &kc, l, c_exp, dt == P2T_BF16, 1, sstride, s));
         P2T_TRY(quantise_into(ao, b.ao, QO, (int64_t)nh * d));
         P2T_TRY(project(ao, Wo, H, b.x, H, P2T_F32, P2T_EPI_RESID, nullptr));
         P2T_TRY(norm_into_h(L.ln2_w));
@@ -557,6 +560,18 @@ extern "C" int p2t_llama_decode_step_rows(const p2t_llama_config* c, const p2t_l
     P2T_REQUIRE(row_step, "p2t_llama_decode_step_rows: null row_step");
     P2T_STEP_CALL(a, "p2t_llama_decode_step_rows");
     a.ws_layers = ws_layers; a.mx = mx_layers; a.head_q = head_q; a.row_step = row_step; a.frozen = frozen;
+    return decode_step(a);
+}
+
+// p2t_llama_decode_step_q for a beam group whose generated keys stay in the rows that wrote them (include/p2t_hip.h): the same launches
+// but the attention's, which reads the ancestry table.
+extern "C" int p2t_llama_decode_step_beams(const p2t_llama_config* c, const p2t_llama_weights* w, const p2t_llama_layer_stream* ws_layers,
+                                           const p2t_llama_layer_mxfp4* mx_layers, const void* lm_head, int64_t ld_head, int lm_head_preshuffled,
+                                           const p2t_lm_head_q* head_q, const p2t_kv_cache* cache, const float* x_in, void* logits, int64_t ld_logits,
+                                           int flags, void* workspace, size_t workspace_bytes, const uint8_t* ancestry, p2t_stream stream) {
+    P2T_REQUIRE(ancestry, "p2t_llama_decode_step_beams: null ancestry table");
+    P2T_STEP_CALL(a, "p2t_llama_decode_step_beams");
+    a.ws_layers = ws_layers; a.mx = mx_layers; a.head_q = head_q; a.ancestry = ancestry;
     return decode_step(a);
 }
 

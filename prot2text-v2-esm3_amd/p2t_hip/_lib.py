@@ -208,7 +208,11 @@ SIGNATURES = {
     "p2t_preshuffle_w_mxfp4": (i32, [vp, i64, vp, i64, i64, vp, vp]),
     "p2t_gemm_nt_skinny_mxfp4": (i32, [vp, i64, vp, vp, i64, vp, i32, vp, i64, i64, i64, i64, i32, i32, vp]),
     "p2t_kv_reorder": (i32, [C.POINTER(LlamaConfigC), C.POINTER(KvCacheC), vp, vp, vp, vp]),
-    "p2t_llama_tape_bytes": (sz, [C.POINTER(LlamaConfigC), i32, i32]),
+    "p2t_kv_ancestry_update": (i32, [C.POINTER(KvCacheC), vp, vp, vp]),
+    "p2t_attention_decode_beams": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp, i64, vp, vp, vp, vp]),
+    "p2t_llama_decode_step_beams": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), C.POINTER(LlamaLayerStreamC), C.POINTER(LlamaLayerMxfp4C), vp,
+                                    i64, i32, C.POINTER(LmHeadQC), C.POINTER(KvCacheC), vp, vp, i64, i32, vp, sz, vp, vp]),
+    "p2t_llama_tape_bytes":(sz, [C.POINTER(LlamaConfigC), i32, i32]),
     "p2t_llama_train_workspace_bytes": (sz, [C.POINTER(LlamaConfigC), i32, i32]),
     "p2t_llama_train_forward": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), vp, vp, i32, i32, vp, vp, sz, vp, sz, vp]),
     "p2t_llama_train_backward": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), C.POINTER(LlamaLayerTC), vp, i32, i32, vp, vp, sz,

@@ -10,7 +10,8 @@ lives in device memory), and the host looks at the finished flags only every `sy
 loop with p2t_sample_select (csrc/sample_select.hip: temperature / top-k / top-p and a counter-hashed draw per row and step) in the
 place of the greedy choice, captured and replayed alike.  Beam search selects with p2t_beam_select (csrc/beam_select.hip: log-softmax,
 the cut to max(2, 1 + n_eos) * beams candidates, the finished slots, the stop condition and the token tables, all in device memory)
-and replays a graph of two steps, since the beam re-ordering swaps two cache buffers.  Beam sampling (`num_beams > 1, do_sample=True`
+and replays a graph of two steps, since the beam re-ordering swaps two cache buffers (`beam_cache="ancestry"`: no re-ordering copy --
+p2t_kv_ancestry_update keeps a table of where each beam's keys lie and p2t_llama_decode_step_beams' attention reads it).  Beam sampling (`num_beams > 1, do_sample=True`
 with `seed=` and `beam_select="device"`) is that loop with p2t_beam_sample_select (csrc/beam_sample_select.hip: the warpers on the
 log-probabilities and keep draws without replacement as the descending order of score + counter-hashed Gumbel noise).  The logits
 processors of `num_beams == 1` (repetition penalty, n-gram, bad-word / suppressed-token and min-new-token bans) are p2t_logits_process
@@ -289,8 +290,13 @@ class DecodeEngine:
 
     def __init__(self, decoder, B0: int, group: int, T: int, max_new_tokens: int, stream_copy: bool = True, fuse_rope: bool = True,
                  processors: Optional[dict] = None, eos_ids: Sequence[int] = (), prompt_kv_dtype: Optional[str] = None,
-                 lm_head_dtype: Optional[str] = None):
+                 lm_head_dtype: Optional[str] = None, beam_cache: Optional[str] = None):
         m, s = decoder.model, decoder.spec
+        if beam_cache not in (None, "ancestry"):
+            raise ValueError(f"beam_cache must be None or 'ancestry' (got {beam_cache!r})")
+        if beam_cache is not None and not (2 <= group <= BEAMS_MAX and s.num_attention_heads // s.num_key_value_heads <= 16):
+            raise ValueError(f"beam_cache='ancestry' serves 2 .. {BEAMS_MAX} rows per prompt and at most 16 query heads per kv head (got {group} rows, "
+                             f"{s.num_attention_heads // s.num_key_value_heads} heads)")
         if prompt_kv_dtype not in (None, "fp8"):
             raise ValueError(f"prompt_kv_dtype must be None or 'fp8' (got {prompt_kv_dtype!r})")
         if prompt_kv_dtype == "fp8" and m.dtype != torch.bfloat16:
@@ -323,6 +329,9 @@ class DecodeEngine:
             self.k_prompt, self.vt_prompt = z(L, B0, nkv, self.Tp, dp), z(L, B0, nkv, dp, self.Tp)
         self.k_gen, self.vt_gen = z(L, self.BB, nkv, self.G, dp), z(L, self.BB, nkv, dp, self.G)
         self.k_alt = self.vt_alt = None                                  # second generated segment, beam search only
+        # beam_cache="ancestry": the generated keys stay in the rows that wrote them, and this table says where a beam's history lies
+        # (include/p2t_hip.h, p2t_kv_ancestry_update); reorder() is never called, k_alt / vt_alt are never allocated
+        self.ancestry = torch.zeros((B0 * group, self.G), dtype=torch.uint8, device=self.dev) if beam_cache is not None else None
         self.lens = torch.zeros((B0,), dtype=torch.int32, device=self.dev)
         self.step = torch.zeros((1,), dtype=torch.int32, device=self.dev)
         self.ld_logits = round_up(s.vocab_size, 64)
@@ -420,7 +429,10 @@ class DecodeEngine:
         """One token per row from self.x -> self.logits; the device step counter advances."""
         layers, mx, head, ld_head, pre, hq = self.step_weights()
         rest = (C.byref(self.cache), ptr(self.x), ptr(self.logits), self.ld_logits, self.flags, ptr(self.ws), self.ws.numel(), stream())
-        if hq is not None:
+        if self.ancestry is not None:
+            call("p2t_llama_decode_step_beams", C.byref(self.e["cfg"]), C.byref(self.e["w"]), layers, mx, head, ld_head, pre, hq, *rest[:-1], ptr(self.ancestry),
+                 stream())
+        elif hq is not None:
             call("p2t_llama_decode_step_q", C.byref(self.e["cfg"]), C.byref(self.e["w"]), layers, mx, head, ld_head, pre, hq, *rest)
         elif mx is not None:
             call("p2t_llama_decode_step_mxfp4", C.byref(self.e["cfg"]), C.byref(self.e["w"]), mx, head, ld_head, pre, *rest)
@@ -460,6 +472,10 @@ class DecodeEngine:
              state.G, int(max_length), C.byref(state.c), pr["penalty"], pr["ngram"], pr["min_new"], opt(self.proc_eos), self.proc_eos.numel(),
              opt(self.word_ids), opt(self.word_offsets), len(pr["words"]), self.word_ids.numel(), ptr(lp), lp.stride(0), stream())
 
+    def ancestry_update(self, src_rows: torch.Tensor):
+        """beam_cache="ancestry": row r's history is row src_rows[r]'s, and its next key its own (in reorder's place; one launch, no copy)."""
+        call("p2t_kv_ancestry_update", C.byref(self.cache), ptr(src_rows), ptr(self.ancestry), stream())
+
     def reorder(self, src_rows: torch.Tensor):
         """Generated segment row r <- row src_rows[r] (beam re-ordering; the prompt segment is shared by a prompt's beams)."""
         if self.k_alt is None:
@@ -492,7 +508,7 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
              stream_copy: bool = True, fuse_rope: bool = True, seed: Optional[int] = None, beam_select: Optional[str] = None,
              repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
              bad_words_ids: Optional[list] = None, suppress_tokens=None, prompt_kv_dtype: Optional[str] = None,
-             lm_head_dtype: Optional[str] = None, **unused):
+             lm_head_dtype: Optional[str] = None, beam_cache: Optional[str] = None, **unused):
     """`LlamaForCausalLM.generate` for prompts given as embeddings (or ids): greedy, sampling (temperature / top-k / top-p) and beam
     search with length penalty.  Returns the new token ids i64 [batch * num_return_sequences, n] (or a GenerateOutput).
 
@@ -537,7 +553,23 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     the two-step graph (p2t_beam_logprobs_process, then p2t_beam_select_logprobs on its rows; ValueError outside p2t_beam_select's
     range), `beam_select="torch"` with p2t_logits_process on the torch path's log-softmax; `output_scores` returns the processed rows,
     `output_logits` the raw ones.  `beam_select=None` raises NotImplementedError, and so does beam sampling with a processor (HF then
-    runs the warpers after the processors, and the device beam sampler cuts by stored logit)."""
+    runs the warpers after the processors, and the device beam sampler cuts by stored logit).
+
+    `beam_cache="ancestry"` (opt-in; `num_beams > 1` on the device selection, i.e. `beam_select` None inside p2t_beam_select's range or
+    "device"; ValueError otherwise, and with more than 16 query heads per kv head) runs the search without the per-step copy of the
+    generated keys and values: they stay in the row that wrote them, p2t_kv_ancestry_update keeps one byte per row and token that says
+    in which row of the prompt a beam's key lies, and the step's attention (p2t_llama_decode_step_beams) runs one block per (prompt, kv
+    head) whose 16 head slots are (beam, head) pairs -- the prompt segment is streamed once for all beams.  No second generated segment
+    is allocated.  It serves beam search, seeded beam sampling and the logits processors under beams alike."""
+    if beam_cache is not None:
+        if beam_cache != "ancestry":
+            raise ValueError(f"generate: beam_cache = {beam_cache!r}: 'ancestry' or None")
+        if num_beams < 2:
+            raise ValueError("generate(beam_cache='ancestry'): a beam cache needs num_beams > 1")
+        if beam_select == "torch":
+            raise ValueError("generate(beam_cache='ancestry') runs on the device selection: beam_select None or 'device', not 'torch'")
+        if decoder.spec.num_attention_heads // decoder.spec.num_key_value_heads > 16:
+            raise ValueError("generate(beam_cache='ancestry'): at most 16 query heads per kv head")
     if (inputs_embeds is None) == (input_ids is None):
         raise ValueError("pass exactly one of inputs_embeds / input_ids")
     if unused:
@@ -587,7 +619,8 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
             max_length=max_new_tokens, eos_ids=eos_ids, pad_id=int(pad_token_id), nb=num_beams, length_penalty=float(length_penalty),
             early_stopping=early_stopping, num_return_sequences=num_return_sequences, return_dict=return_dict_in_generate,
             output_scores=output_scores, output_logits=output_logits, stream_copy=stream_copy, beam_select=beam_select, use_graph=use_graph,
-            sync_every=sync_every, sampling=sampling, processors=proc, prompt_kv_dtype=prompt_kv_dtype, lm_head_dtype=lm_head_dtype))
+            sync_every=sync_every, sampling=sampling, processors=proc, prompt_kv_dtype=prompt_kv_dtype, lm_head_dtype=lm_head_dtype,
+            beam_cache=beam_cache))
     R = int(num_return_sequences)
     if R != 1 and not do_sample:
         raise ValueError("greedy decoding returns one sequence per prompt: num_return_sequences > 1 needs do_sample=True or num_beams > 1")
@@ -822,8 +855,8 @@ def _beam_search(decoder, inputs_embeds, attention_mask, o):
     if o.beam_select != "torch":
         if beam_select_supported(B, nb, len(o.eos_ids), V):
             return _beam_search_device(decoder, inputs_embeds, attention_mask, o)
-        if o.beam_select == "device":
-            raise ValueError(f"generate(beam_select='device'): p2t_beam_select serves 1 <= num_beams <= {BEAMS_MAX} with max(2, 1 + number of eos ids) * "
+        if o.beam_select == "device" or o.beam_cache is not None:
+            raise ValueError(f"generate(beam_select='device'{'' if o.beam_cache is None else ', beam_cache=' + repr(o.beam_cache)}): p2t_beam_select serves 1 <= num_beams <= {BEAMS_MAX} with max(2, 1 + number of eos ids) * "
                              f"num_beams <= {KEEP_MAX} <= vocabulary (got num_beams = {nb}, {len(o.eos_ids)} eos ids); the torch path serves the rest")
     eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy, processors=o.processors, eos_ids=o.eos_ids,
                        prompt_kv_dtype=o.prompt_kv_dtype, lm_head_dtype=o.lm_head_dtype)
@@ -925,7 +958,7 @@ def _beam_search_device(decoder, inputs_embeds, attention_mask, o):
     the end; steps run past the stop leave the state as it is."""
     B, V, nb, max_length, sampling = inputs_embeds.shape[0], decoder.spec.vocab_size, o.nb, o.max_length, o.sampling
     eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy, processors=o.processors, eos_ids=o.eos_ids,
-                       prompt_kv_dtype=o.prompt_kv_dtype, lm_head_dtype=o.lm_head_dtype)
+                       prompt_kv_dtype=o.prompt_kv_dtype, lm_head_dtype=o.lm_head_dtype, beam_cache=o.beam_cache)
     dev = eng.dev
     embeds, mask = eng.compact(inputs_embeds, attention_mask)
     first = eng.prefill(embeds, mask).repeat_interleave(nb, dim=0).contiguous()     # HF expands the prompt nb times before its prefill
@@ -965,7 +998,10 @@ def _beam_search_device(decoder, inputs_embeds, attention_mask, o):
 
     def advance(slot):
         eng.logits = lslots[slot]
-        eng.reorder(src_rows)                           # generated keys / values follow their beams (a no-op while nothing is cached)
+        if eng.ancestry is not None:
+            eng.ancestry_update(src_rows)               # the generated keys / values stay; the table follows the beams
+        else:
+            eng.reorder(src_rows)                       # generated keys / values follow their beams (a no-op while nothing is cached)
         eng.feed(eng.next_tokens)
         eng.decode_step()
         select(eng.logits, slot)

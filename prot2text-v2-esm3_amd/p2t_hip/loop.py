@@ -270,6 +270,8 @@ def inference_epoch(rank, model, dataloader: Iterable[Dict[str, Any]], llama_tok
             kw["beam_select"] = args["beam_select"]
         if args.get("prompt_kv_dtype") is not None:          # "fp8": generate(prompt_kv_dtype=), the e4m3 prompt segment of the KV cache (bf16 models)
             kw["prompt_kv_dtype"] = args["prompt_kv_dtype"]
+        if args.get("beam_cache") is not None:               # "ancestry": generate(beam_cache=), beam search without the cache copy
+            kw["beam_cache"] = args["beam_cache"]
         with torch.no_grad():
             out = iterative_generation_loop(rank, model, data_batch, args["max_generation_length"], args.get("num_beams", 1),
                                             args.get("length_penalty", 1.0), args.get("temperature", 1.0), args.get("do_sample", False),

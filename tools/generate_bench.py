@@ -26,6 +26,8 @@ repetition_penalty 1.3 + no_repeat_ngram_size 3, the same with all five processo
 python tools/generate_bench.py [B] [N] [beams] kv8 [fp8 | mxfp4]: the step with the bf16 and with the fp8 prompt segment of the KV cache
 (`prompt_kv_dtype="fp8"`), interleaved in one process, three runs each under graph replay, each next to a run of its prompt phase (beams > 1: beam_select="device", the beams of a
 prompt share its prompt segment): median and min .. max, and the cache bytes a step reads either way.
+python tools/generate_bench.py [B] [N] [beams > 1] ancestry [kv8] [fp8 | mxfp4]: the device beam search with the per-step cache copy and with
+`beam_cache="ancestry"` (the ancestry table read by the attention), interleaved in one process, three runs each under graph replay.
 python tools/generate_bench.py [B] [N] [beams] head [fp8 | mxfp4] [kv8] [fp8 | mxfp4]: the step with the bf16 LM head (off) and with the
 quantised one (`lm_head_dtype=`; both formats when none is named), interleaved in one process, three runs each under graph replay, each
 next to a run of its prompt phase; `kv8`: the same again over the fp8 prompt segment; last: the tower GEMM dtype.
@@ -329,6 +331,35 @@ def kv8_mode(model, kw, B: int, N: int, beams: int, T: int, llama, gemm_dtype: s
               f"prompt phase {np.median(t_prompt[name]):.1f} ms", flush=True)
 
 
+def ancestry_mode(model, kw, B: int, N: int, beams: int, T: int, gemm_dtype: str, with_kv8: bool):
+    """The device beam search with the per-step cache copy (beam_cache=None: p2t_kv_reorder + the (row, kv head) attention) and without it
+    (beam_cache="ancestry": p2t_kv_ancestry_update + the (prompt, kv head) attention), interleaved in one process, three runs each under
+    graph replay, each next to a run of its prompt phase -- kv8_mode's method."""
+    cases = [("copy (beam_cache=None)", dict()), ("ancestry table (beam_cache=\"ancestry\")", dict(beam_cache="ancestry"))]
+    kw = {**kw, "beam_select": "device", **({"prompt_kv_dtype": "fp8"} if with_kv8 else {})}
+    for _, extra in cases:                                       # warm-up of each path
+        model.generate(**{**kw, **extra, "max_new_tokens": 6})
+    torch.cuda.synchronize()
+
+    def timed(**over):
+        t0 = time.perf_counter()
+        model.generate(**{**kw, **over})
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    runs = {name: [] for name, _ in cases}
+    for _ in range(3):                                           # interleaved: a drift of the box hits both alike
+        for name, extra in cases:
+            t1 = timed(**extra, max_new_tokens=1)
+            runs[name].append((timed(**extra) - t1) / (N - 1) * 1e3)
+    for name, _ in cases:
+        r = runs[name]
+        print(f"generate cfg3{' ' + gemm_dtype + ' GEMMs' if gemm_dtype != 'model' else ''}{' kv8' if with_kv8 else ''}: B={B} beams={beams} prompt {T} tokens, "
+              f"{N} new tokens, graph replay, {name}: median {np.median(r):.3f} ms/step (min {min(r):.3f}, max {max(r):.3f}; 3 runs)", flush=True)
+    a, c = np.median(runs[cases[1][0]]), np.median(runs[cases[0][0]])
+    print(f"  ancestry / copy = {a / c:.4f} (copy - ancestry = {(c - a) * 1e3:+.0f} us per step; ranges {max(runs[cases[0][0]]) - min(runs[cases[0][0]]):.3f} and "
+          f"{max(runs[cases[1][0]]) - min(runs[cases[1][0]]):.3f} ms)", flush=True)
+
+
 def head_mode(model, kw, B: int, N: int, beams: int, T: int, llama, gemm_dtype: str, fmts, with_kv8: bool):
     """The step with the bf16 LM head (off: the parent's arithmetic) and with the quantised one (`lm_head_dtype=`), interleaved in one
     process, three runs each under graph replay, each next to a run of its prompt phase -- kv8_mode's method; with `kv8` the same again
@@ -566,6 +597,11 @@ def main():
             head_kv8, after = True, after[1:]
         gemm_dtype = after[0] if after and after[0] in ("fp8", "mxfp4") else "model"
     fp8 = gemm_dtype != "model"
+    ancestry = beams > 1 and len(sys.argv) > 4 and sys.argv[4] == "ancestry"      # [B] [N] [beams] ancestry [kv8] [fp8 | mxfp4]
+    if ancestry:
+        after = sys.argv[5:]
+        gemm_dtype = after[-1] if after and after[-1] in ("fp8", "mxfp4") else "model"
+        fp8 = gemm_dtype != "model"
     beam_sample = beams > 1 and len(sys.argv) > 4 and sys.argv[4] == "sample"
     beam_process = beams > 1 and len(sys.argv) > 4 and sys.argv[4] == "process"
     esm_name, llama_name, _, _, Tp, _ = specs.CONFIGS["cfg3"]
@@ -588,6 +624,8 @@ def main():
         return continuous_choice_mode(model, kw, B, N, T, choice_leg)
     if continuous:
         return continuous_mode(model, kw, B, N, T, gemm_dtype, cont_extra)
+    if ancestry:
+        return ancestry_mode(model, kw, B, N, beams, T, gemm_dtype, "kv8" in sys.argv[5:])
     if head:
         return head_mode(model, kw, B, N, beams, T, llama, gemm_dtype, head_fmts, head_kv8)
     if kv8:

@@ -2,6 +2,8 @@
 """Kernel micro-benchmarks on the GPU box (HIP-event timed, random data): GEMM shapes of the
 cfg-3 towers, attention, norms.  Usage: python tools/microbench.py [gemm] [attn] [norm]
 `attn_decode` [m8] [m32]: the decode step's attention alone over the bf16 and the fp8 prompt segment of the KV cache.
+`attn_decode beams`: the attention of a beam group alone, the (row, kv head) kernel against the (prompt, kv head) kernel that reads an ancestry
+table, 8 x 4 and 32 x 4 beams, bf16 and fp8 prompt segment, 33 and 250 generated keys; then p2t_kv_reorder against p2t_kv_ancestry_update.
 `choice_rows` [m8] [m32]: the per-row choice kernels of continuous batching alone (p2t_sample_select_rows, p2t_logits_process_rows) on
 [rows, 128256] bf16 logits next to their lock-step twins, with no row and with half of the rows finished (the per-row kernels leave a
 finished row before they read it; the lock-step ones do its whole work).
@@ -315,6 +317,70 @@ def bench_attn_decode():
                   f"{nbytes / np.median(r) / 1e3:5.0f} GB/s of cache bytes ({nbytes / 1e6:.1f} MB)", flush=True)
 
 
+def bench_attn_decode_beams():
+    """`attn_decode beams`: the attention of a beam group alone at Llama-3.1-8B sizes, 8 x 4 and 32 x 4 beams over 1088 prompt keys and 33 /
+    250 generated ones, bf16 and fp8 prompt segment: p2t_attention_decode[_prompt_fp8] (one block per (row, kv head), the copy path) and
+    p2t_attention_decode_beams (one block per (prompt, kv head), identity table) alternating on a ring of cache copies; then
+    p2t_kv_reorder against p2t_kv_ancestry_update over 32 layers at both lengths."""
+    import ctypes as C
+    import numpy as np
+    from p2t_hip.ops import ptr, stream
+    nh, nkv, d, T, group, L = 32, 8, 128, 1088, 4, 32
+    Tp, G, copies, rounds, n = ops.round_up(T, 64), 256, 12, 5, 48
+    u8 = lambda *s: torch.empty(s, dtype=torch.uint8, device=dev)
+    for B0 in (8, 32):
+        BB = B0 * group
+        kp, vtp = [rand((B0, nkv, Tp, d), scale=0.5) for _ in range(copies)], [rand((B0, nkv, d, Tp), scale=0.5) for _ in range(copies)]
+        kg, vtg, q = rand((BB, nkv, G, d), scale=0.5), rand((BB, nkv, d, G), scale=0.5), rand((BB, nh, d), scale=0.5)
+        k8, v8, ks, vs = [], [], [], []
+        for c in range(copies):
+            k8.append(u8(B0, nkv, Tp, d)); v8.append(u8(B0, nkv, d, Tp)); ks.append(u8(B0, nkv, Tp)); vs.append(u8(B0, nkv, Tp))
+            _lib.call("p2t_kv_quant_store", ptr(kp[c]), ptr(vtp[c].transpose(2, 3).contiguous()), B0, nkv, Tp, d, Tp, ptr(k8[c]), ptr(v8[c]), ptr(ks[c]),
+                      ptr(vs[c]), stream())
+        lens = torch.full((B0,), T, dtype=torch.int32, device=dev)
+        anc = (torch.arange(BB, device=dev) % group).to(torch.uint8)[:, None].repeat(1, G).contiguous()      # every beam its own row's keys
+        out = torch.zeros((BB, nh * d), dtype=torch.bfloat16, device=dev)
+        for S in (32, 249):
+            step = torch.tensor([S], dtype=torch.int32, device=dev)
+            i = [0]
+
+            def run(fp8, beams):
+                c = i[0] % copies
+                i[0] += 1
+                a = (ptr(q), ptr(k8[c] if fp8 else kp[c]), ptr(v8[c] if fp8 else vtp[c]), ptr(kg), ptr(vtg), ptr(lens), ptr(step), B0, group, nh, nkv, d, Tp, G,
+                     1.0, 1, _lib.BF16, 1, ptr(out), nh * d)
+                sc = (ptr(ks[c]), ptr(vs[c])) if fp8 else (None, None)
+                if beams:
+                    _lib.call("p2t_attention_decode_beams", *a, *sc, ptr(anc), stream())
+                elif fp8:
+                    _lib.call("p2t_attention_decode_prompt_fp8", *a, *sc, stream())
+                else:
+                    _lib.call("p2t_attention_decode", *a, stream())
+            res = {(f, b): [] for f in (0, 1) for b in (0, 1)}
+            for _ in range(rounds):
+                for key in res:
+                    res[key].append(timeit(lambda: run(*key), iters=n, warm=copies) * 1e3)
+            for (f, b), r in res.items():
+                print(f"attn_decode {B0:2d} x {group} beams {T}+{S + 1} keys, {'fp8 ' if f else 'bf16'} prompt segment, "
+                      f"{'(prompt, kv head) blocks + ancestry table' if b else '(row, kv head) blocks                    '}: median {np.median(r):5.1f} us "
+                      f"(min {min(r):.1f}, max {max(r):.1f}; {rounds} rounds of {n})", flush=True)
+        del kp, vtp, k8, v8
+    # the per-step maintenance: the copy of every layer's generated keys and values against one byte per row and token
+    B0, BB = 8, 32
+    cfg = _lib.LlamaConfigC(n_layers=L, hidden=4096, ffn=14336, heads=nh, kv_heads=nkv, head_dim=d, vocab=128256, dtype=_lib.BF16)
+    bufs = [torch.zeros((L, BB, nkv, G, d), dtype=torch.bfloat16, device=dev) for _ in range(4)]
+    lens, step = torch.full((B0,), T, dtype=torch.int32, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev)
+    src = (torch.arange(BB, device=dev) // group * group + torch.tensor([1, 1, 0, 2], device=dev).repeat(B0)).to(torch.int64)
+    anc = torch.zeros((BB, G), dtype=torch.uint8, device=dev)
+    cache = _lib.KvCacheC(k_prompt=bufs[0].data_ptr(), vt_prompt=bufs[0].data_ptr(), k_gen=bufs[0].data_ptr(), vt_gen=bufs[1].data_ptr(),
+                          prompt_len=lens.data_ptr(), step=step.data_ptr(), B0=B0, group=group, Tp=Tp, G=G)
+    for S in (30, 250):
+        step.fill_(S)
+        t_copy = timeit(lambda: _lib.call("p2t_kv_reorder", C.byref(cfg), C.byref(cache), ptr(src), ptr(bufs[2]), ptr(bufs[3]), stream()), iters=20) * 1e3
+        t_tab = timeit(lambda: _lib.call("p2t_kv_ancestry_update", C.byref(cache), ptr(src), ptr(anc), stream()), iters=20) * 1e3
+        print(f"beam maintenance at {S} generated tokens, {BB} rows x {L} layers: p2t_kv_reorder {t_copy:.1f} us, p2t_kv_ancestry_update {t_tab:.1f} us", flush=True)
+
+
 def bench_choice_rows():
     """p2t_sample_select / p2t_sample_select_rows (top_k 50, top_p 0.9, temperature 0.7) and p2t_logits_process / p2t_logits_process_rows
     (every stage on, 64 history tokens) on randn * 3 bf16 logits [rows, 128256] at pitch 128320, alternating, five rounds of 200 launches,
@@ -389,7 +455,9 @@ if __name__ == "__main__":
         bench_fp8()
     if "skinny" in which:
         bench_skinny()
-    if "attn_decode" in which:
+    if "attn_decode" in which and "beams" in which:
+        bench_attn_decode_beams()
+    elif "attn_decode" in which:
         bench_attn_decode()
     if "choice_rows" in which:
         bench_choice_rows()
