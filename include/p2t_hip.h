@@ -611,6 +611,49 @@ size_t p2t_llama_prefill_workspace_bytes(const p2t_llama_config* cfg, int B, int
 int p2t_llama_prefill(const p2t_llama_config* cfg, const p2t_llama_weights* w, const float* inputs_embeds, const int64_t* mask,
                       int B, int T, const p2t_kv_cache* cache, float* last_hidden, void* workspace, size_t workspace_bytes,
                       p2t_stream stream);
+/* ---- padding-free prefill of ragged prompts (opt-in).  p2t_llama_prefill runs every layer over B x longest tokens; a PACKED prompt
+ * batch holds the same prompts back to back in R rows of Tpk tokens, f32 [R, Tpk, hidden]: prompt i occupies tokens start_i ..
+ * start_i + len_i - 1 of row row_i in p2t_compact_rows' token order (the r-th token under its mask is position r), position_ids restart
+ * at 0 per prompt, the row's mask is a prefix and the tail is padding (one-token documents of p2t_doc_prepare).  Attention and rotation
+ * are confined per prompt by docs (the packed rows of stage 2 above); every layer's keys and values are scattered into each prompt's
+ * OWN row of the cache's prompt segment, so nothing behind the prefill changes.  The placement `place` is a HOST array i32 [n][3] =
+ * (row, start, len), planned from the lengths (generation.plan_prompt_rows) and carried by value in the launch arguments: at most 256
+ * prompts per call (beyond: P2T_ERR_UNSUPPORTED).  Every entry point checks it before its launch: rows in [0, R), start >= 0, len >= 1,
+ * start + len <= Tpk, no two prompts overlapping in a row. */
+/* The first half of p2t_compact_rows alone: index[b * T + t] = r for the r-th token of row b with mask != 0, -1 off the mask; lens[b] =
+ * their number.  mask i64 [B, T]; index i32 [B * T], lens i32 [B] (device). */
+int p2t_prompt_index(const int64_t* mask, int B, int T, int32_t* index, int32_t* lens, p2t_stream stream);
+/* x f32 [B, T, H] (H % 4 == 0, 16-byte aligned) + p2t_prompt_index's index and lens + the placement of its B prompts -> out f32 [R, Tpk,
+ * H] (zero off the prompts), out_mask i64 [R, Tpk] (1 under a prompt), position_ids i32 [R, Tpk] (r under a prompt, 0 elsewhere).  One
+ * launch, one pass from the original rows with 16-byte loads and stores, every output element written once; no compacted copy in
+ * between.  The prompts of a row must lie back to back from token 0 (P2T_ERR_ARG otherwise): the mask is then the prefix that
+ * p2t_doc_prepare wants, and docs comes from it.  place[i][2] is lens[i] as the host read it. */
+int p2t_pack_rows(const float* x, const int32_t* index, const int32_t* lens, int B, int T, int H, const int32_t* place, int R, int Tpk,
+                  float* out, int64_t* out_mask, int32_t* position_ids, p2t_stream stream);
+/* ONE layer's rotated keys and values from packed rows into the prompt segment, ONE launch for every prompt: k, v `dtype` [R][kv_heads][Tpk][dp] -> layer `layer` of the cache, K rows [i][kvh][0 .. len_i)[dp],
+ * V transposed [i][kvh][dp][0 .. len_i).  grid (64-key tiles of the longest prompt, prompts x kv heads); a tile's source starts at any
+ * token of the packed row (a token is dp elements: 16-byte pieces stay aligned), its destination is tile-aligned.  fp32, bf16, and --
+ * cache with the scale arrays set -- the fp8 prompt segment: p2t_kv_quant_store's arithmetic on each key, codes and both scale arrays
+ * bit-equal to what it writes for the same keys laid out one prompt per row.  Positions >= len_i of a cache row, other layers and
+ * other prompts' rows are not written.  cache->B0 == n, len_i <= cache->Tp, buffers 16-byte aligned. */
+int p2t_kv_store_packed(const p2t_llama_config* cfg, const p2t_kv_cache* cache, int layer, const void* k, const void* v, int R, int Tpk,
+                        const int32_t* place, int n, p2t_stream stream);
+size_t p2t_llama_prefill_packed_workspace_bytes(const p2t_llama_config* cfg, int R, int Tpk);
+/* p2t_llama_prefill on a packed prompt batch: inputs_embeds / mask as p2t_pack_rows writes them, docs i32 [2][R][Tpk] from
+ * p2t_doc_prepare on its position_ids (flags bit 0 clear), cache->B0 == n and cache->prompt_len = the lengths.  last_hidden f32 [n,
+ * hidden]: the post-final-RMSNorm state of token start_i + len_i - 1 of row row_i.  The QKV projection is stored and rotated by
+ * p2t_qkv_post's positional form (as the packed rows of stage 2), so a model whose padded prefill rotates in the GEMM epilogue
+ * differs from it by rounding.  gemm_fp8 models: P2T_ERR_UNSUPPORTED (the packed prefill runs the model-dtype GEMMs).  Every refusal
+ * comes before the first launch.
+ * FINITE PADDING: the tokens of a packed row that no prompt covers must hold finite embeddings (p2t_pack_rows writes zeros).  A prompt
+ * is isolated from what else lies in its row by masks: the attention sets the probability of a key outside the document to an exact
+ * zero, and the bf16 kernel then multiplies that zero with the V rows of the whole 64-key tile -- 0 x finite = 0, but 0 x NaN = NaN.
+ * Known limit, measured: NaN embeddings behind the last prompt turn every first-token logit of a bf16 model into NaN (the fp32
+ * kernels gave the clean run's bits with the same NaN tail); finite junk there changes no bit in either dtype.  The padded
+ * prefill's padding tokens are under the same contract. */
+int p2t_llama_prefill_packed(const p2t_llama_config* cfg, const p2t_llama_weights* w, const float* inputs_embeds, const int64_t* mask,
+                             const int32_t* docs, int R, int Tpk, int n, const int32_t* place, const p2t_kv_cache* cache,
+                             float* last_hidden, void* workspace, size_t workspace_bytes, p2t_stream stream);
 size_t p2t_llama_decode_workspace_bytes(const p2t_llama_config* cfg, int BB, int Tp, int G);
 /* Optional second copies of the four projection weights of a layer in the STREAM order of the decode GEMM (p2t_preshuffle_w;
  * bf16 models; built once per generate-capable model: 288 GB of HBM hold both layouts of an 8-B decoder many times over).

@@ -216,11 +216,26 @@ struct LlamaTape {
 };
 size_t llama_tape_plan(const p2t_llama_config* c, int B, int T, void* base, size_t bytes, LlamaTape* tape);
 // docs (optional, packed rows): i32 [2][B][T] from launch_doc_prepare -- positional rotary and document-confined attention
+// Where the prompts of a packed prompt batch lie (include/p2t_hip.h, p2t_pack_rows): prompt i = tokens start[i] .. start[i] + len[i] - 1
+// of packed row row[i].  It travels by value in the launch arguments (like kv_cache.hip's SlotTable): a host array in, no copy, no
+// allocation.  `longest`: the largest len, the grid's extent.  Filled and checked by place_table (kv_cache.hip).
+constexpr int kPackedPromptsMax = 256;
+struct PlaceTable { int32_t row[kPackedPromptsMax]; int32_t start[kPackedPromptsMax]; int32_t len[kPackedPromptsMax]; };
+struct PackedPrompts { int n; int longest; PlaceTable tab; };
+// place: HOST i32 [n][3] = (row, start, len) -> pp, after every refusal: 1 <= n <= kPackedPromptsMax (beyond: P2T_ERR_UNSUPPORTED), rows in
+// [0, R), starts >= 0, len >= 1, start + len <= Tpk, len <= Tp (Tp 0: no cache to hold them), no two prompts overlapping in a row
+int place_table(const int32_t* place, int n, int R, int Tpk, int Tp, const char* who, PackedPrompts* pp);
+// docs with kv (the packed prefill): `packed` says where each prompt lies, and every layer's keys / values go through llama_kv_store_packed
 int llama_forward_impl(const p2t_llama_config* c, const p2t_llama_weights* w, const int64_t* ids, const float* inputs_embeds, const int64_t* mask,
                        int B, int T, int k, float* out, void* workspace, size_t workspace_bytes, p2t_stream stream, const LlamaTape* tape,
-                       const p2t_kv_cache* kv = nullptr, const int32_t* docs = nullptr);
+                       const p2t_kv_cache* kv = nullptr, const int32_t* docs = nullptr, const PackedPrompts* packed = nullptr);
 // generation prefill (kv_cache.hip): layer l's rotated keys / values ([B, kv_heads, T, dp]) -> the prompt segment of the cache
 int llama_kv_store(const p2t_llama_config* c, const p2t_kv_cache* kc, int layer, const void* k, const void* v, int B, int T, hipStream_t s);
+// the same from packed rows ([R, kv_heads, Tpk, dp]): prompt i's keys -> row i of the prompt segment, positions 0 .. len[i] - 1; ONE launch
+int llama_kv_store_packed(const p2t_llama_config* c, const p2t_kv_cache* kc, int layer, const void* k, const void* v, int Tpk, const PackedPrompts& pp,
+                          hipStream_t s);
+// last_hidden[i] = x[row[i], start[i] + len[i] - 1] (f32 rows of H): the packed form of the prefill's gather (kv_cache.hip)
+int launch_gather_last_packed(const float* x, int Tpk, int H, const PackedPrompts& pp, float* out, hipStream_t s);
 // every refusal of a cache descriptor against the model's head shape and dtype (kv_cache.hip).  `who`: the entry point's name
 int check_cache(const p2t_llama_config* c, const p2t_kv_cache* kc, const char* who);
 // every refusal of a beam group under an ancestry table (kv_cache.hip): a null table, fewer than 2 or more than 16 rows per prompt, more

@@ -47,6 +47,7 @@ __global__ void __launch_bounds__(256) compact_index_kernel(const int64_t* __res
     __syncthreads();
     int a = cnt[tid];
     for (int t = t0; t < t1; ++t) dst[(int64_t)b * T + t] = m[t] != 0 ? a++ : -1;
+    if (!out_mask) return;                               // p2t_prompt_index: the destinations and the lengths alone
     const int n = total;
     for (int t = tid; t < T; t += 256) out_mask[(int64_t)b * T + t] = t < n ? 1 : 0;
 }
@@ -127,6 +128,151 @@ __global__ void __launch_bounds__(256) kv_quant_store_kernel(const bf16_t* __res
         const int c = i >> 4, t = t0 + 4 * (i & 15);
         const unsigned w = *reinterpret_cast<const unsigned*>(&tile[c][4 * (i & 15)]);
         uint8_t* dst = vtq + ((int64_t)bh * DP + c) * Tp + t;
+        if (t + 4 <= seq) {
+            *reinterpret_cast<unsigned*>(dst) = w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (t + e < seq) dst[e] = (uint8_t)(w >> (8 * e));
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// packed prompt rows (include/p2t_hip.h, p2t_pack_rows): prompts back to back in a few long rows, placed by a PlaceTable
+// ---------------------------------------------------------------------------------------------
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+
+// x [B][T][H] -> packed [R][Tpk][H], mask, position_ids, every output element written ONCE.  grid (max(T, Tpk), B + R):
+//   * y < B, the copy blocks: token x of prompt y, the r-th under its mask (dst from compact_index_kernel), goes to token start + r of
+//     its packed row with mask 1 and position r -- straight from the original row, 16-byte loads and stores;
+//   * y >= B, the fill blocks: token x of packed row y - B that no prompt covers becomes zeros with mask 0 and position 0.
+__global__ void __launch_bounds__(256) pack_rows_kernel(const float* __restrict__ x, const int32_t* __restrict__ dst, const int32_t* __restrict__ lens,
+                                                        int B, int T, int H, int Tpk, float* __restrict__ out, int64_t* __restrict__ out_mask,
+                                                        int32_t* __restrict__ pos, PlaceTable tab) {
+    const int t = blockIdx.x, y = blockIdx.y;
+    if (y < B) {
+        if (t >= T) return;
+        const int r = dst[(int64_t)y * T + t];
+        if (r < 0 || r >= min(lens[y], tab.len[y])) return;           // (the host planned from these lengths: a guard, not a case)
+        const int64_t to = (int64_t)tab.row[y] * Tpk + tab.start[y] + r;
+        const float4* s = reinterpret_cast<const float4*>(x + ((int64_t)y * T + t) * H);
+        float4* d = reinterpret_cast<float4*>(out + to * H);
+        for (int c = threadIdx.x; c < H / 4; c += 256) d[c] = s[c];
+        if (threadIdx.x == 0) { out_mask[to] = 1; pos[to] = r; }
+        return;
+    }
+    if (t >= Tpk) return;
+    const int row = y - B;
+    for (int i = 0; i < B; ++i)                                       // uniform over the block: scalar reads of the launch arguments
+        if (tab.row[i] == row && t >= tab.start[i] && t < tab.start[i] + tab.len[i]) return;
+    const int64_t to = (int64_t)row * Tpk + t;
+    float4* d = reinterpret_cast<float4*>(out + to * H);
+    for (int c = threadIdx.x; c < H / 4; c += 256) d[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (threadIdx.x == 0) { out_mask[to] = 0; pos[to] = 0; }
+}
+
+// last_hidden[i] = x[row_i][start_i + len_i - 1]: gather_last_kernel (llama_decode.hip) on packed rows
+__global__ void __launch_bounds__(256) gather_last_packed_kernel(const float* __restrict__ x, int Tpk, int H, float* __restrict__ out, PlaceTable tab) {
+    const int i = blockIdx.x;
+    const float* s = x + ((int64_t)tab.row[i] * Tpk + tab.start[i] + tab.len[i] - 1) * H;
+    for (int c = threadIdx.x; c < H; c += 256) out[(int64_t)i * H + c] = s[c];
+}
+
+// One layer's keys and values from packed rows into every prompt's own row of the prompt segment, ONE launch: k, v [R][nkv][Tpk][dp] ->
+// K [n][nkv][Tp][dp] rows 0 .. len - 1, V^T [n][nkv][dp][Tp] columns 0 .. len - 1.  grid (64-key tiles of the longest prompt, n * nkv).
+// A tile's source starts at token start + 64 * tile of the packed row -- any token, but a token is dp elements, so 16-byte pieces stay
+// aligned; its destination starts at key 64 * tile of a row whose capacity is a multiple of 64, so whole 16-byte groups of a V^T column
+// are aligned stores and only the last group of a prompt goes element by element.  Nothing at or behind len is written.
+template <typename T>
+__global__ void __launch_bounds__(256) kv_store_packed_kernel(const T* __restrict__ k, const T* __restrict__ v, T* __restrict__ kd, T* __restrict__ vtd,
+                                                              int nkv, int Tpk, int dp, int Tp, PlaceTable tab) {
+    constexpr int N = 16 / (int)sizeof(T);                            // elements per 16-byte piece
+    __shared__ __attribute__((aligned(16))) T tile[128][64 + N];      // V [feature][key of the tile]
+    const int i = blockIdx.y / nkv, kvh = blockIdx.y - i * nkv, t0 = blockIdx.x * 64;
+    const int cnt = min(64, tab.len[i] - t0);                         // keys of this tile
+    if (cnt <= 0) return;
+    const int64_t from = (((int64_t)tab.row[i] * nkv + kvh) * Tpk + tab.start[i] + t0) * dp, bh = (int64_t)i * nkv + kvh;
+    const u32x4_t* ks = reinterpret_cast<const u32x4_t*>(k + from);
+    u32x4_t* kt = reinterpret_cast<u32x4_t*>(kd + (bh * Tp + t0) * dp);
+    const int ppk = dp / N;                                           // pieces per key
+    for (int p = threadIdx.x; p < cnt * ppk; p += 256) kt[p] = ks[p];
+    const u32x4_t* vs = reinterpret_cast<const u32x4_t*>(v + from);
+    for (int p = threadIdx.x; p < cnt * ppk; p += 256) {
+        const int tl = p / ppk, c0 = (p - tl * ppk) * N;
+        const u32x4_t w = vs[p];
+        T e[N];
+        __builtin_memcpy(e, &w, 16);
+#pragma unroll
+        for (int j = 0; j < N; ++j) tile[c0 + j][tl] = e[j];
+    }
+    __syncthreads();
+    constexpr int GPC = 64 / N;                                       // 16-byte groups per column of the tile
+    for (int p = threadIdx.x; p < dp * GPC; p += 256) {
+        const int c = p / GPC, t = (p - c * GPC) * N;
+        if (t >= cnt) continue;
+        T* dst = vtd + (bh * dp + c) * Tp + t0 + t;
+        if (t + N <= cnt) {
+            *reinterpret_cast<u32x4_t*>(dst) = *reinterpret_cast<const u32x4_t*>(&tile[c][t]);
+        } else {
+            for (int j = 0; t + j < cnt; ++j) dst[j] = tile[c][t + j];
+        }
+    }
+}
+
+// The same into an fp8 prompt segment: kv_quant_store_kernel's arithmetic on every key (amax over the key's d features among the DP / 8
+// lanes that share it -> e8m0_of_amax -> x * 2^-e -> pack_fp8x4; columns d .. DP zero codes; one scale byte per key for K and for V), read
+// from where the prompt lies in its packed row and written to the prompt's own cache row.  Codes and scales are bit-equal to
+// kv_quant_store_kernel's on the same keys laid out one prompt per row.
+template <int DP>
+__global__ void __launch_bounds__(256) kv_quant_store_packed_kernel(const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, uint8_t* __restrict__ kq,
+                                                                    uint8_t* __restrict__ vtq, uint8_t* __restrict__ ks, uint8_t* __restrict__ vs, int nkv,
+                                                                    int Tpk, int d, int Tp, PlaceTable tab) {
+    constexpr int LG = DP / 8, KPP = 256 / LG;                        // lanes per key, keys per pass
+    __shared__ __attribute__((aligned(16))) uint8_t tile[DP][68];     // V codes [feature][key of the tile]
+    const int i = blockIdx.y / nkv, kvh = blockIdx.y - i * nkv, t0 = blockIdx.x * 64;
+    const int seq = tab.len[i];
+    if (t0 >= seq) return;
+    const int64_t from = ((int64_t)tab.row[i] * nkv + kvh) * Tpk + tab.start[i], bh = (int64_t)i * nkv + kvh;
+    const int sub = threadIdx.x % LG, kl = threadIdx.x / LG;
+    auto quant8 = [&](const bf16_t* src, bool ok, int& E) {           // 8 features of one key -> their codes; E of the whole key
+        float x[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] = 0.f;
+        if (ok) load8(src, x);
+        float amax = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            x[e] = 8 * sub + e < d ? x[e] : 0.f;
+            amax = fmaxf(amax, fabsf(x[e]));
+        }
+#pragma unroll
+        for (int o = LG / 2; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+        E = e8m0_of_amax(amax);
+        const float inv = pow2_neg(E);
+        return make_uint2(pack_fp8x4(x[0] * inv, x[1] * inv, x[2] * inv, x[3] * inv), pack_fp8x4(x[4] * inv, x[5] * inv, x[6] * inv, x[7] * inv));
+    };
+#pragma unroll
+    for (int pass = 0; pass < 64 / KPP; ++pass) {
+        const int tl = pass * KPP + kl, t = t0 + tl;
+        const bool ok = t < seq;                                      // the same for the lanes of a key
+        const int64_t in = (from + t) * DP + 8 * sub, row = bh * Tp + t;
+        int E;
+        const uint2 kc = quant8(k + in, ok, E);
+        if (ok) {
+            *reinterpret_cast<uint2*>(kq + row * DP + 8 * sub) = kc;
+            if (sub == 0) ks[row] = (uint8_t)E;
+        }
+        const uint2 vc = quant8(v + in, ok, E);
+        if (ok && sub == 0) vs[row] = (uint8_t)E;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) tile[8 * sub + e][tl] = (uint8_t)((e < 4 ? vc.x : vc.y) >> (8 * (e & 3)));
+    }
+    __syncthreads();
+    for (int p = threadIdx.x; p < DP * 16; p += 256) {
+        const int c = p >> 4, t = t0 + 4 * (p & 15);
+        const unsigned w = *reinterpret_cast<const unsigned*>(&tile[c][4 * (p & 15)]);
+        uint8_t* dst = vtq + (bh * DP + c) * Tp + t;
         if (t + 4 <= seq) {
             *reinterpret_cast<unsigned*>(dst) = w;
         } else {
@@ -265,9 +411,106 @@ int llama_kv_store(const p2t_llama_config* c, const p2t_kv_cache* kc, int layer,
     return P2T_OK;
 }
 
+int place_table(const int32_t* place, int n, int R, int Tpk, int Tp, const char* who, PackedPrompts* pp) {
+    P2T_REQUIRE(place && n > 0 && R > 0 && Tpk > 0, "%s: null/empty placement (%d prompts in %d rows of %d tokens)", who, n, R, Tpk);
+    if (n > kPackedPromptsMax) {
+        set_error("%s: at most %d prompts per call (got %d)", who, kPackedPromptsMax, n);
+        return P2T_ERR_UNSUPPORTED;
+    }
+    pp->n = n;
+    pp->longest = 0;
+    for (int i = 0; i < n; ++i) {
+        const int row = place[3 * i], start = place[3 * i + 1], len = place[3 * i + 2];
+        P2T_REQUIRE(row >= 0 && row < R, "%s: prompt %d lies in packed row %d, outside [0, %d)", who, i, row, R);
+        P2T_REQUIRE(len >= 1, "%s: prompt %d has %d tokens (every prompt needs at least one)", who, i, len);
+        P2T_REQUIRE(start >= 0 && (int64_t)start + len <= Tpk, "%s: prompt %d (start %d, %d tokens) does not fit a packed row of %d tokens", who, i, start, len,
+                    Tpk);
+        P2T_REQUIRE(Tp <= 0 || len <= Tp, "%s: prompt %d has %d tokens, the cache's prompt segment holds %d", who, i, len, Tp);
+        for (int j = 0; j < i; ++j)
+            P2T_REQUIRE(pp->tab.row[j] != row || start >= pp->tab.start[j] + pp->tab.len[j] || pp->tab.start[j] >= start + len,
+                        "%s: prompts %d and %d overlap in packed row %d", who, j, i, row);
+        pp->tab.row[i] = row;
+        pp->tab.start[i] = start;
+        pp->tab.len[i] = len;
+        pp->longest = std::max(pp->longest, len);
+    }
+    for (int i = n; i < kPackedPromptsMax; ++i) pp->tab.row[i] = pp->tab.start[i] = pp->tab.len[i] = 0;
+    return P2T_OK;
+}
+
+// packed prefill hook of llama_forward_impl (towers.hip): layer l's rotated keys / values -> every prompt's row of the prompt segment
+int llama_kv_store_packed(const p2t_llama_config* c, const p2t_kv_cache* kc, int layer, const void* k, const void* v, int Tpk, const PackedPrompts& pp,
+                          hipStream_t s) {
+    const int dp = head_dim_padded(c->head_dim), nkv = c->kv_heads;
+    const size_t per = (size_t)kc->B0 * nkv * kc->Tp * dp, per_s = (size_t)kc->B0 * nkv * kc->Tp;
+    const dim3 grid((unsigned)ceil_div(pp.longest, 64), (unsigned)(pp.n * nkv));
+    if (kc->k_prompt_scale) {                 // fp8 prompt segment (check_cache: a bf16 model)
+        uint8_t *kq = (uint8_t*)kc->k_prompt + per * layer, *vtq = (uint8_t*)kc->vt_prompt + per * layer;
+        uint8_t *ks = kc->k_prompt_scale + per_s * layer, *vs = kc->v_prompt_scale + per_s * layer;
+#define P2T_KVQP(DPV) kv_quant_store_packed_kernel<DPV><<<grid, 256, 0, s>>>((const bf16_t*)k, (const bf16_t*)v, kq, vtq, ks, vs, nkv, Tpk, c->head_dim, kc->Tp, pp.tab)
+        if (dp == 32) P2T_KVQP(32); else if (dp == 64) P2T_KVQP(64); else P2T_KVQP(128);
+#undef P2T_KVQP
+    } else if (c->dtype == P2T_BF16) {
+        kv_store_packed_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)k, (const bf16_t*)v, (bf16_t*)kc->k_prompt + per * layer,
+                                                            (bf16_t*)kc->vt_prompt + per * layer, nkv, Tpk, dp, kc->Tp, pp.tab);
+    } else {
+        kv_store_packed_kernel<float><<<grid, 256, 0, s>>>((const float*)k, (const float*)v, (float*)kc->k_prompt + per * layer,
+                                                           (float*)kc->vt_prompt + per * layer, nkv, Tpk, dp, kc->Tp, pp.tab);
+    }
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
+int launch_gather_last_packed(const float* x, int Tpk, int H, const PackedPrompts& pp, float* out, hipStream_t s) {
+    gather_last_packed_kernel<<<pp.n, 256, 0, s>>>(x, Tpk, H, out, pp.tab);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
 }  // namespace p2t
 
 using namespace p2t;
+
+extern "C" int p2t_prompt_index(const int64_t* mask, int B, int T, int32_t* index, int32_t* lens, p2t_stream stream) {
+    P2T_REQUIRE(mask && index && lens && B > 0 && T > 0, "p2t_prompt_index: null/empty argument");
+    compact_index_kernel<<<B, 256, 0, (hipStream_t)stream>>>(mask, T, index, nullptr, lens);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
+extern "C" int p2t_pack_rows(const float* x, const int32_t* index, const int32_t* lens, int B, int T, int H, const int32_t* place, int R, int Tpk,
+                             float* out, int64_t* out_mask, int32_t* position_ids, p2t_stream stream) {
+    P2T_REQUIRE(x && index && lens && out && out_mask && position_ids && B > 0 && T > 0 && H > 0 && H % 4 == 0 && x != out,
+                "p2t_pack_rows: bad arguments (H must be a multiple of 4, out of place)");
+    P2T_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 15) == 0, "p2t_pack_rows: x and out must be 16-byte aligned");
+    PackedPrompts pp;
+    P2T_TRY(place_table(place, B, R, Tpk, 0, "p2t_pack_rows", &pp));
+    for (int i = 0; i < B; ++i) {            // the packed mask must be a prefix (p2t_doc_prepare): every prompt starts at 0 or where another ends
+        bool ok = pp.tab.start[i] == 0;
+        for (int j = 0; j < B && !ok; ++j) ok = pp.tab.row[j] == pp.tab.row[i] && pp.tab.start[j] + pp.tab.len[j] == pp.tab.start[i];
+        P2T_REQUIRE(ok, "p2t_pack_rows: prompt %d starts at token %d of packed row %d behind a gap (prompts lie back to back from token 0)", i,
+                    pp.tab.start[i], pp.tab.row[i]);
+    }
+    P2T_REQUIRE(R <= 65535 - B, "p2t_pack_rows: %d prompts + %d packed rows exceed one launch (grid.y)", B, R);
+    const dim3 grid((unsigned)std::max(T, Tpk), (unsigned)(B + R));
+    pack_rows_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(x, index, lens, B, T, H, Tpk, out, out_mask, position_ids, pp.tab);
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
+extern "C" int p2t_kv_store_packed(const p2t_llama_config* c, const p2t_kv_cache* cache, int layer, const void* k, const void* v, int R, int Tpk,
+                                   const int32_t* place, int n, p2t_stream stream) {
+    P2T_REQUIRE(c && cache && k && v, "p2t_kv_store_packed: null argument");
+    P2T_TRY(check_cache(c, cache, "p2t_kv_store_packed"));
+    P2T_REQUIRE(c->kv_heads > 0 && layer >= 0 && layer < c->n_layers, "p2t_kv_store_packed: layer %d outside [0, %d)", layer, c->n_layers);
+    P2T_REQUIRE(cache->B0 == n, "p2t_kv_store_packed: cache holds %d rows, the packed batch %d prompts", cache->B0, n);
+    PackedPrompts pp;
+    P2T_TRY(place_table(place, n, R, Tpk, cache->Tp, "p2t_kv_store_packed", &pp));
+    P2T_REQUIRE((((uintptr_t)k | (uintptr_t)v | (uintptr_t)cache->k_prompt | (uintptr_t)cache->vt_prompt) & 15) == 0,
+                "p2t_kv_store_packed: buffers must be 16-byte aligned");
+    P2T_REQUIRE((int64_t)n * c->kv_heads <= 65535, "p2t_kv_store_packed: %d prompts x %d kv heads exceed one launch", n, c->kv_heads);
+    return llama_kv_store_packed(c, cache, layer, k, v, Tpk, pp, (hipStream_t)stream);
+}
 
 extern "C" int p2t_compact_rows(const float* x, const int64_t* mask, int B, int T, int H, float* out, int64_t* out_mask, int32_t* lens,
                                 int32_t* scratch, p2t_stream stream) {

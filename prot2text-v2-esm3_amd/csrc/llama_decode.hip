@@ -256,6 +256,36 @@ extern "C" int p2t_llama_prefill(const p2t_llama_config* c, const p2t_llama_weig
     return P2T_OK;
 }
 
+extern "C" size_t p2t_llama_prefill_packed_workspace_bytes(const p2t_llama_config* cfg, int R, int Tpk) {
+    return p2t_llama_prefill_workspace_bytes(cfg, R, Tpk);
+}
+
+// p2t_llama_prefill over packed rows: the same layers on R x Tpk tokens, attention and rotation confined per prompt by docs, the keys and
+// values scattered to each prompt's cache row.  Every refusal stands in front of the first launch.
+extern "C" int p2t_llama_prefill_packed(const p2t_llama_config* c, const p2t_llama_weights* w, const float* inputs_embeds, const int64_t* mask,
+                                        const int32_t* docs, int R, int Tpk, int n, const int32_t* place, const p2t_kv_cache* cache, float* last_hidden,
+                                        void* workspace, size_t workspace_bytes, p2t_stream stream) {
+    P2T_REQUIRE(c && w && inputs_embeds && mask && docs && place && last_hidden && workspace && R > 0 && Tpk > 0 && n > 0,
+                "p2t_llama_prefill_packed: null/empty argument");
+    P2T_TRY(check_cache(c, cache, "p2t_llama_prefill_packed"));
+    if (c->gemm_fp8) {
+        set_error("p2t_llama_prefill_packed: the packed prefill runs the model-dtype GEMMs; gemm_fp8 models (fp8 / MXFP4 weights) take p2t_llama_prefill");
+        return P2T_ERR_UNSUPPORTED;
+    }
+    P2T_REQUIRE(cache->B0 == n, "p2t_llama_prefill_packed: cache holds %d rows, the packed batch %d prompts", cache->B0, n);
+    PackedPrompts pp;
+    P2T_TRY(place_table(place, n, R, Tpk, cache->Tp, "p2t_llama_prefill_packed", &pp));
+    P2T_REQUIRE((int64_t)n * c->kv_heads <= 65535, "p2t_llama_prefill_packed: %d prompts x %d kv heads exceed one launch", n, c->kv_heads);
+    P2T_REQUIRE(workspace_bytes >= p2t_llama_prefill_packed_workspace_bytes(c, R, Tpk), "p2t_llama_prefill_packed: workspace too small");
+    Arena ar(workspace, workspace_bytes);
+    float* out = (float*)ar.take(sizeof(float) * (size_t)R * Tpk * c->hidden);
+    void* rest = ar.take(p2t_llama_workspace_bytes(c, R, Tpk));
+    P2T_REQUIRE(!ar.overflow, "p2t_llama_prefill_packed: workspace overflow");
+    P2T_TRY(llama_forward_impl(c, w, nullptr, inputs_embeds, mask, R, Tpk, c->n_layers, out, rest, p2t_llama_workspace_bytes(c, R, Tpk), stream, nullptr,
+                               cache, docs, &pp));
+    return launch_gather_last_packed(out, Tpk, c->hidden, pp, last_hidden, (hipStream_t)stream);
+}
+
 extern "C" size_t p2t_llama_decode_workspace_bytes(const p2t_llama_config* cfg, int BB, int Tp, int G) {
     if (!cfg || BB <= 0 || Tp <= 0 || G <= 0) return 0;
     return decode_plan(cfg, BB, Tp, G, nullptr, nullptr);

@@ -213,13 +213,16 @@ extern "C" size_t p2t_llama_workspace_bytes(const p2t_llama_config* cfg, int B, 
 // gate/up GEMM then stores them plainly and SwiGLU runs as its own pass).
 int p2t::llama_forward_impl(const p2t_llama_config* c, const p2t_llama_weights* w, const int64_t* ids, const float* inputs_embeds,
                             const int64_t* mask, int B, int T, int k, float* out, void* workspace,
-                            size_t workspace_bytes, p2t_stream stream, const LlamaTape* tape, const p2t_kv_cache* kv, const int32_t* docs) {
+                            size_t workspace_bytes, p2t_stream stream, const LlamaTape* tape, const p2t_kv_cache* kv, const int32_t* docs,
+                            const PackedPrompts* packed) {
     P2T_REQUIRE(c && w && (ids || inputs_embeds) && mask && out && workspace && B > 0 && T > 0, "p2t_llama_hidden_forward: null/empty argument");
     P2T_REQUIRE(k >= 0 && k <= c->n_layers, "p2t_llama_hidden_forward: hidden_states[%d] out of range for %d layers", k, c->n_layers);
     P2T_REQUIRE(c->heads % c->kv_heads == 0 && c->head_dim % 4 == 0 && c->head_dim <= 128 && c->hidden % 16 == 0 && c->ffn % 32 == 0 &&
                     ((int64_t)c->heads * c->head_dim) % 16 == 0,
                 "p2t_llama_hidden_forward: unsupported shape");
     P2T_REQUIRE((w->embed || !ids) && (k == 0 || w->layers) && (k < c->n_layers || w->final_norm_w), "p2t_llama_hidden_forward: missing weights");
+    P2T_REQUIRE(!docs || !c->gemm_fp8, "p2t_llama_hidden_forward: packed rows run the model-dtype GEMMs (gemm_fp8 = 0)");
+    P2T_REQUIRE(!packed == !(docs && kv), "p2t_llama_hidden_forward: packed rows fill a KV cache through their placement, and only they carry one");
     P2T_REQUIRE(workspace_bytes >= p2t_llama_workspace_bytes(c, B, T), "p2t_llama_hidden_forward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     Arena ar(workspace, workspace_bytes);
@@ -252,7 +255,6 @@ int p2t::llama_forward_impl(const p2t_llama_config* c, const p2t_llama_weights* 
     P2T_CHECK_HIP(hipMemsetAsync(b.fix, 0, gemm_fix_header_bytes(), s));      // split-K flags; epochs below are unique
     unsigned epoch = 0;
     P2T_REQUIRE(!c->gemm_fp8 || dt == P2T_BF16, "p2t_llama_hidden_forward: gemm_fp8 needs bf16 activations (dtype = P2T_BF16)");
-    P2T_REQUIRE(!docs || (!c->gemm_fp8 && !kv), "p2t_llama_hidden_forward: packed rows run the model-dtype GEMMs without a KV cache");
     P2T_REQUIRE(!tape || !c->gemm_fp8, "p2t_llama_hidden_forward: the tape keeps model-dtype activations (gemm_fp8 = 0)");
     // gemm_fp8: the same layer with e4m3 GEMM operands, as in p2t_esm2_forward (the RMSNorms write them, the attention output
     // and the SwiGLU output take a quantise pass)
@@ -294,7 +296,8 @@ int p2t::llama_forward_impl(const p2t_llama_config* c, const p2t_llama_weights* 
                 P2T_TRY(launch_qkv_post(b.qkv, NQKV, b.cs, b.q, b.k, b.v, B, T, nh, nkv, d, dp, q_fold, dt, s, docs, d == 128));
         }
         P2T_TRY(attention(b.q, b.k, b.v, b.key_mask, b.kv_info, b.ao, QO, B, T, nh, nkv, d, dp, scale, 1, dt, -1, l2s, s, lse, docs));
-        if (kv) P2T_TRY(llama_kv_store(c, kv, l, b.k, b.v, B, T, s));      // generation prefill: this layer's keys / values -> prompt segment
+        if (packed) P2T_TRY(llama_kv_store_packed(c, kv, l, b.k, b.v, T, *packed, s));      // packed prefill: every prompt to its own cache row
+        else if (kv) P2T_TRY(llama_kv_store(c, kv, l, b.k, b.v, B, T, s));      // generation prefill: this layer's keys / values -> prompt segment
         const Operand ao = fp8 ? Operand{b.aoq, QOq, b.aos} : Operand{b.ao, QO, nullptr};      // (b.ao: this layer's, see the tape above)
         P2T_TRY(quantise_into(ao, b.ao, dt, QO, M, (int64_t)nh * d, s));
         P2T_TRY(gemm_nt(projection(ao, L.o_w, L.o_ws, M, H, dt, b.x, H, P2T_F32, P2T_EPI_RESID), s));

@@ -168,6 +168,12 @@ SIGNATURES = {
     "p2t_compact_rows":(i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "p2t_llama_prefill_workspace_bytes": (sz, [C.POINTER(LlamaConfigC), i32, i32]),
     "p2t_llama_prefill": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), vp, vp, i32, i32, C.POINTER(KvCacheC), vp, vp, sz, vp]),
+    "p2t_prompt_index": (i32, [vp, i32, i32, vp, vp, vp]),
+    "p2t_pack_rows": (i32, [vp, vp, vp, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, vp, vp, vp, vp]),
+    "p2t_kv_store_packed": (i32, [C.POINTER(LlamaConfigC), C.POINTER(KvCacheC), i32, vp, vp, i32, i32, C.POINTER(C.c_int32), i32, vp]),
+    "p2t_llama_prefill_packed_workspace_bytes": (sz, [C.POINTER(LlamaConfigC), i32, i32]),
+    "p2t_llama_prefill_packed": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), vp, vp, vp, i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(KvCacheC),
+                                 vp, vp, sz, vp]),
     "p2t_llama_decode_workspace_bytes": (sz, [C.POINTER(LlamaConfigC), i32, i32, i32]),
     "p2t_llama_decode_step": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), C.POINTER(LlamaLayerStreamC), vp, i64, i32, C.POINTER(KvCacheC), vp, vp, i64,
                               i32, vp, sz, vp]),
@@ -275,7 +281,7 @@ for _i, _s in enumerate(_STRUCTS):
     if lib.p2t_struct_size(_i) != C.sizeof(_s):
         raise ImportError(f"ABI mismatch: {_s.__name__} is {C.sizeof(_s)} bytes here, {lib.p2t_struct_size(_i)} in the library")
 
-_NO_RC = {"p2t_gemm_fix_workspace_bytes", "p2t_version", "p2t_is_lab_build", "p2t_last_error", "p2t_struct_size", "p2t_esm2_workspace_bytes", "p2t_llama_workspace_bytes", "p2t_llama_tape_bytes", "p2t_llama_train_workspace_bytes", "p2t_llama_prefill_workspace_bytes", "p2t_llama_decode_workspace_bytes",
+_NO_RC = {"p2t_gemm_fix_workspace_bytes", "p2t_version", "p2t_is_lab_build", "p2t_last_error", "p2t_struct_size", "p2t_esm2_workspace_bytes", "p2t_llama_workspace_bytes", "p2t_llama_tape_bytes", "p2t_llama_train_workspace_bytes", "p2t_llama_prefill_workspace_bytes", "p2t_llama_prefill_packed_workspace_bytes", "p2t_llama_decode_workspace_bytes",
           "p2t_adapter_backward_workspace_bytes", "p2t_adapter_backward_dx_workspace_bytes", "p2t_lora_wgrad_workspace_bytes", "p2t_beam_workspace_bytes",
           "p2t_beam_sample_workspace_bytes", "p2t_lm_head_q_workspace_bytes"}
 

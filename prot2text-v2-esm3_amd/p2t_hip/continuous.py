@@ -281,7 +281,12 @@ class ContinuousDecoder:
 
     def __init__(self, decoder, slots: int, max_prompt_tokens: int, max_new_tokens: int, eos_token_id=None, pad_token_id: Optional[int] = None,
                  sync_every: int = 8, use_graph: bool = True, stream_copy: bool = True, prompt_kv_dtype: Optional[str] = None,
-                 lm_head_dtype: Optional[str] = None, output_logits: bool = False, choice: Optional[str] = None, **generate_kwargs):
+                 lm_head_dtype: Optional[str] = None, output_logits: bool = False, choice: Optional[str] = None, prefill: Optional[str] = None,
+                 pack_tokens: Optional[int] = None, **generate_kwargs):
+        if prefill not in (None, "padded") or pack_tokens is not None:
+            # generate(prefill="packed"): the refills prefill one to three prompts at a time, so there is little padding to remove
+            raise NotImplementedError(f"continuous batching prefills its refills padded: prefill={prefill!r} / pack_tokens={pack_tokens!r} are generate()'s "
+                                      "(prefill='packed' is not served here)")
         if choice not in (None, "device"):
             raise ValueError(f"choice must be None or 'device' (got {choice!r})")
         if choice is None:

@@ -285,6 +285,49 @@ def lm_head_logits_q(x: torch.Tensor, norm_w: Optional[torch.Tensor], eps: float
     return (out, aq, asc) if return_act else out
 
 
+# A guard on buffer sizes, not a tuned value: one packed row of every prompt is the default, and beyond this many tokens the prompts go
+# into rows of at most this many (the tower's workspace grows with rows x tokens either way; a row's attention tiles with its length).
+PACK_TOKENS_MAX = 32768
+# Tpk is a multiple of 64: the attention kernels walk a row's keys in 64-key tiles and p2t_kv_store_packed moves 64-key tiles, so a row
+# that ends on a tile edge never has a partial tile behind its last prompt; the 128-query tile of the bf16 attention clamps by itself.
+PACK_ROW_MULTIPLE = 64
+PACK_PROMPTS_MAX = 256                                       # p2t_llama_prefill_packed: the placement travels in the launch arguments
+
+
+def plan_prompt_rows(lens: Sequence[int], pack_tokens: Optional[int] = None):
+    """Where the prompts of a packed prompt batch lie (include/p2t_hip.h, p2t_pack_rows): lens[b] valid tokens per prompt ->
+    (R, Tpk, place) with place[b] = (row, start, len) in batch order.  First-fit decreasing, as data.pack_instruct_batch packs its
+    samples: longest first, ties in batch order, each prompt into the first row with room, the prompts of a row back to back from token
+    0.  `pack_tokens`: the rows' capacity; None = PACK_TOKENS_MAX, i.e. ONE row holding every prompt unless they exceed it.  Tpk = the
+    fullest row rounded up to PACK_ROW_MULTIPLE.  A prompt longer than the capacity, or an empty one, raises ValueError."""
+    lens = [int(n) for n in lens]
+    cap = PACK_TOKENS_MAX if pack_tokens is None else int(pack_tokens)
+    if not lens or cap < 1:
+        raise ValueError("plan_prompt_rows: at least one prompt and pack_tokens >= 1")
+    for b, n in enumerate(lens):
+        if n < 1:
+            raise ValueError("every prompt row needs at least one token under its attention mask")
+        if n > cap:
+            raise ValueError(f"prompt {b} has {n} tokens, more than pack_tokens = {cap}")
+    used: list = []
+    place: list = [None] * len(lens)
+    for b in sorted(range(len(lens)), key=lambda i: -lens[i]):          # stable: ties keep the batch order
+        r = next((r for r in range(len(used)) if cap - used[r] >= lens[b]), len(used))
+        if r == len(used):
+            used.append(0)
+        place[b] = (r, used[r], lens[b])
+        used[r] += lens[b]
+    return len(used), round_up(max(used), PACK_ROW_MULTIPLE), place
+
+
+class PackedPrompts:
+    """What DecodeEngine.pack returns: embeds f32 [R, Tpk, H], mask i64 [R, Tpk], docs i32 [2, R, Tpk] (p2t_doc_prepare) and the placement."""
+
+    def __init__(self, embeds, mask, position_ids, docs, place):
+        self.embeds, self.mask, self.position_ids, self.docs, self.place = embeds, mask, position_ids, docs, place
+        self.c_place = (C.c_int32 * (3 * len(place)))(*[v for p in place for v in p])
+
+
 class DecodeEngine:
     """Cache + buffers of ONE generate() call: B0 prompts, `group` rows per prompt (beams), capacities Tp / G (multiples of 64)."""
 
@@ -405,10 +448,54 @@ class DecodeEngine:
         last = torch.empty((B, H), dtype=torch.float32, device=self.dev)
         call("p2t_llama_prefill", C.byref(cfg), C.byref(self.e["w"]), ptr(embeds), ptr(mask), B, T, C.byref(self.cache if cache is None else cache), ptr(last), ptr(ws),
              ws.numel(), stream())
+        return self._first_logits(last)
+
+    def _first_logits(self, last: torch.Tensor) -> torch.Tensor:
+        """The first new token's logits from the prompts' last normalised hidden rows f32 [B0, H]."""
         if self.head_q_first is not None:        # token 0 is scored by the matrix that scores token 1: the normalised rows, quantised, on the same head
             return lm_head_logits_q(last, None, 0.0, self.head_q_first[0], self.spec.vocab_size, self.ld_logits)
         a = last if self.dtype == torch.float32 else ops.cast(last, self.dtype)
-        return ops.gemm_nt(a, self.lm_head, None, n=self.spec.vocab_size, k=H, out_dtype=self.dtype)
+        return ops.gemm_nt(a, self.lm_head, None, n=self.spec.vocab_size, k=last.shape[1], out_dtype=self.dtype)
+
+    def pack(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, pack_tokens: Optional[int] = None) -> PackedPrompts:
+        """compact()'s counterpart for the padding-free prefill: the prompts back to back in a few long rows (plan_prompt_rows), each in
+        compact()'s token order with positions restarting at 0, straight from the original rows (p2t_prompt_index + p2t_pack_rows), and
+        the rows' documents (p2t_doc_prepare).  The cache's prompt_len receives the lengths."""
+        B, T, H = inputs_embeds.shape
+        if self.decoder.model.gemm_fp8:
+            raise ValueError("prefill='packed' runs the model-dtype GEMMs: it does not serve set_gemm_dtype('fp8') / ('mxfp4') models")
+        if B > PACK_PROMPTS_MAX:
+            raise ValueError(f"prefill='packed' serves at most {PACK_PROMPTS_MAX} prompts per call (got {B})")
+        x = inputs_embeds.to(device=self.dev, dtype=torch.float32).contiguous()
+        mask = attention_mask.to(device=self.dev, dtype=torch.int64).contiguous()
+        index = torch.empty((B * T,), dtype=torch.int32, device=self.dev)
+        call("p2t_prompt_index", ptr(mask), B, T, ptr(index), ptr(self.lens), stream())
+        R, Tpk, place = plan_prompt_rows(self.lens.tolist(), pack_tokens)      # the one host read of the prompt phase: the B lengths
+        out = torch.empty((R, Tpk, H), dtype=torch.float32, device=self.dev)
+        out_mask = torch.empty((R, Tpk), dtype=torch.int64, device=self.dev)
+        pos = torch.empty((R, Tpk), dtype=torch.int32, device=self.dev)
+        packed = PackedPrompts(out, out_mask, pos, torch.empty((2, R, Tpk), dtype=torch.int32, device=self.dev), place)
+        call("p2t_pack_rows", ptr(x), ptr(index), ptr(self.lens), B, T, H, packed.c_place, R, Tpk, ptr(out), ptr(out_mask), ptr(pos), stream())
+        flags = torch.empty((1,), dtype=torch.int32, device=self.dev)          # (zeroed by the call; the rows are well-formed by construction)
+        call("p2t_doc_prepare", ptr(pos), 0, ptr(out_mask), R, Tpk, ptr(packed.docs), ptr(flags), stream())
+        return packed
+
+    def prefill_packed(self, packed: PackedPrompts) -> torch.Tensor:
+        """prefill() on a packed prompt batch: the same layers over R x Tpk tokens instead of B0 x longest, every layer's keys and values
+        scattered to each prompt's own row of the prompt segment (p2t_llama_prefill_packed) -> the first new token's logits, as prefill."""
+        R, Tpk, H = packed.embeds.shape
+        cfg = self.e["cfg"]
+        ws = torch.empty((call("p2t_llama_prefill_packed_workspace_bytes", C.byref(cfg), R, Tpk),), dtype=torch.uint8, device=self.dev)
+        last = torch.empty((self.B0, H), dtype=torch.float32, device=self.dev)
+        call("p2t_llama_prefill_packed", C.byref(cfg), C.byref(self.e["w"]), ptr(packed.embeds), ptr(packed.mask), ptr(packed.docs), R, Tpk, len(packed.place),
+             packed.c_place, C.byref(self.cache), ptr(last), ptr(ws), ws.numel(), stream())
+        return self._first_logits(last)
+
+    def prompt(self, inputs_embeds: torch.Tensor, attention_mask: torch.Tensor, prefill: Optional[str] = None, pack_tokens: Optional[int] = None):
+        """The prompt phase of generate(): compact + prefill, or (prefill="packed") pack + prefill_packed -> the first token's logits."""
+        if prefill == "packed":
+            return self.prefill_packed(self.pack(inputs_embeds, attention_mask, pack_tokens))
+        return self.prefill(*self.compact(inputs_embeds, attention_mask))
 
     # -- steps --------------------------------------------------------------------------------------------------------------
     def feed(self, tokens: torch.Tensor):
@@ -508,7 +595,8 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
              stream_copy: bool = True, fuse_rope: bool = True, seed: Optional[int] = None, beam_select: Optional[str] = None,
              repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
              bad_words_ids: Optional[list] = None, suppress_tokens=None, prompt_kv_dtype: Optional[str] = None,
-             lm_head_dtype: Optional[str] = None, beam_cache: Optional[str] = None, **unused):
+             lm_head_dtype: Optional[str] = None, beam_cache: Optional[str] = None, prefill: Optional[str] = None,
+             pack_tokens: Optional[int] = None, **unused):
     """`LlamaForCausalLM.generate` for prompts given as embeddings (or ids): greedy, sampling (temperature / top-k / top-p) and beam
     search with length penalty.  Returns the new token ids i64 [batch * num_return_sequences, n] (or a GenerateOutput).
 
@@ -560,7 +648,22 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     generated keys and values: they stay in the row that wrote them, p2t_kv_ancestry_update keeps one byte per row and token that says
     in which row of the prompt a beam's key lies, and the step's attention (p2t_llama_decode_step_beams) runs one block per (prompt, kv
     head) whose 16 head slots are (beam, head) pairs -- the prompt segment is streamed once for all beams.  No second generated segment
-    is allocated.  It serves beam search, seeded beam sampling and the logits processors under beams alike."""
+    is allocated.  It serves beam search, seeded beam sampling and the logits processors under beams alike.
+
+    `prefill="packed"` (opt-in; None / "padded" = compact + p2t_llama_prefill over batch x longest tokens, unchanged) runs the decoder's
+    prompt phase without padding: the prompts lie back to back in a few long rows (plan_prompt_rows; `pack_tokens` = the rows' capacity,
+    default one row up to PACK_TOKENS_MAX tokens), attention and rotation are confined per prompt, and each layer's keys and values are
+    scattered into each prompt's own row of the cache's prompt segment (p2t_llama_prefill_packed).  Only the writer of the prompt
+    segment changes, so every decoding mode, `prompt_kv_dtype` and `lm_head_dtype` run unchanged behind it; the first token's logits
+    differ from the padded path's by rounding (another summation order, and the rotation after the projection instead of inside it).
+    ValueError for another value, for `pack_tokens` without it, for more than PACK_PROMPTS_MAX prompts and on set_gemm_dtype("fp8") /
+    ("mxfp4") models: the packed prefill runs the model-dtype GEMMs."""
+    if prefill not in (None, "padded", "packed"):
+        raise ValueError(f"generate: prefill = {prefill!r}: None, 'padded' or 'packed'")
+    if pack_tokens is not None and prefill != "packed":
+        raise ValueError("generate: pack_tokens is the row capacity of prefill='packed'")
+    if prefill == "packed" and decoder.model.gemm_fp8:
+        raise ValueError("generate(prefill='packed') runs the model-dtype GEMMs: it does not serve set_gemm_dtype('fp8') / ('mxfp4') models")
     if beam_cache is not None:
         if beam_cache != "ancestry":
             raise ValueError(f"generate: beam_cache = {beam_cache!r}: 'ancestry' or None")
@@ -620,15 +723,14 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
             early_stopping=early_stopping, num_return_sequences=num_return_sequences, return_dict=return_dict_in_generate,
             output_scores=output_scores, output_logits=output_logits, stream_copy=stream_copy, beam_select=beam_select, use_graph=use_graph,
             sync_every=sync_every, sampling=sampling, processors=proc, prompt_kv_dtype=prompt_kv_dtype, lm_head_dtype=lm_head_dtype,
-            beam_cache=beam_cache))
+            beam_cache=beam_cache, prefill=prefill, pack_tokens=pack_tokens))
     R = int(num_return_sequences)
     if R != 1 and not do_sample:
         raise ValueError("greedy decoding returns one sequence per prompt: num_return_sequences > 1 needs do_sample=True or num_beams > 1")
     # R samples per prompt (HF repeats the prompt R times): R rows that SHARE the prompt segment of the cache, like the beams of a prompt
     eng = DecodeEngine(decoder, B, R, T, max_new_tokens, stream_copy, fuse_rope, processors=proc, eos_ids=eos_ids, prompt_kv_dtype=prompt_kv_dtype,
                        lm_head_dtype=lm_head_dtype)
-    embeds, mask = eng.compact(inputs_embeds, attention_mask)
-    logits = eng.prefill(embeds, mask)
+    logits = eng.prompt(inputs_embeds, attention_mask, prefill, pack_tokens)
     if R > 1:
         logits = logits.repeat_interleave(R, dim=0)
     eos = torch.tensor(eos_ids, dtype=torch.int64, device=eng.dev)
@@ -861,8 +963,7 @@ def _beam_search(decoder, inputs_embeds, attention_mask, o):
     eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy, processors=o.processors, eos_ids=o.eos_ids,
                        prompt_kv_dtype=o.prompt_kv_dtype, lm_head_dtype=o.lm_head_dtype)
     dev = eng.dev
-    embeds, mask = eng.compact(inputs_embeds, attention_mask)
-    first_logits = eng.prefill(embeds, mask)                                 # [B, ld]: the beams of a prompt start from the same state
+    first_logits = eng.prompt(inputs_embeds, attention_mask, o.prefill, o.pack_tokens)      # [B, ld]: the beams of a prompt start from the same state
     eos = torch.tensor(o.eos_ids, dtype=torch.int64, device=dev)
     st = beam_state_init(B, nb, max_length, o.pad_id, dev)
     all_scores, all_logits = [], []
@@ -960,8 +1061,7 @@ def _beam_search_device(decoder, inputs_embeds, attention_mask, o):
     eng = DecodeEngine(decoder, B, nb, inputs_embeds.shape[1], max_length, o.stream_copy, processors=o.processors, eos_ids=o.eos_ids,
                        prompt_kv_dtype=o.prompt_kv_dtype, lm_head_dtype=o.lm_head_dtype, beam_cache=o.beam_cache)
     dev = eng.dev
-    embeds, mask = eng.compact(inputs_embeds, attention_mask)
-    first = eng.prefill(embeds, mask).repeat_interleave(nb, dim=0).contiguous()     # HF expands the prompt nb times before its prefill
+    first = eng.prompt(inputs_embeds, attention_mask, o.prefill, o.pack_tokens).repeat_interleave(nb, dim=0).contiguous()     # HF expands the prompt nb times before its prefill
     eos = torch.tensor(o.eos_ids, dtype=torch.int64, device=dev)
     st = BeamState(B, nb, eng.G, o.pad_id, dev, sample=sampling is not None)
     src_rows = torch.zeros((eng.BB,), dtype=torch.int64, device=dev)

@@ -218,7 +218,8 @@ def _inference_continuous(rank, model, dataloader, llama_tokenizer, args: Dict[s
     longest = max(int(b["attention_mask"].shape[1]) for b in batches)     # the placeholders are replaced in place: the id prompt's length
     # what generate() takes as its choice rule goes through as it is: choice=None refuses all but greedy by name, choice="device" serves it
     kw = {k: args[k] for k in ("prompt_kv_dtype", "lm_head_dtype", "sync_every", "choice", "temperature", "top_k", "top_p", "repetition_penalty",
-                               "no_repeat_ngram_size", "min_new_tokens", "bad_words_ids", "suppress_tokens") if args.get(k) is not None}
+                               "no_repeat_ngram_size", "min_new_tokens", "bad_words_ids", "suppress_tokens", "prefill", "pack_tokens")
+          if args.get(k) is not None}                         # (prefill / pack_tokens: refused by name there)
     if args.get("seed") is not None:                         # ONE generator for the rank's whole shard: batch index 0; the draw keys are the
         r = rank if isinstance(rank, int) else (dev.index or 0)          # request ids (dataset order on the rank), so `continuous_slots` does not matter
         kw["seed"] = generation_seed(args["seed"], r, 0)
@@ -272,6 +273,10 @@ def inference_epoch(rank, model, dataloader: Iterable[Dict[str, Any]], llama_tok
             kw["prompt_kv_dtype"] = args["prompt_kv_dtype"]
         if args.get("beam_cache") is not None:               # "ancestry": generate(beam_cache=), beam search without the cache copy
             kw["beam_cache"] = args["beam_cache"]
+        if args.get("prefill") is not None:                  # "packed": generate(prefill=), the padding-free prefill of ragged prompts
+            kw["prefill"] = args["prefill"]
+        if args.get("pack_tokens") is not None:              # with it: the packed rows' capacity (generation.plan_prompt_rows)
+            kw["pack_tokens"] = args["pack_tokens"]
         with torch.no_grad():
             out = iterative_generation_loop(rank, model, data_batch, args["max_generation_length"], args.get("num_beams", 1),
                                             args.get("length_penalty", 1.0), args.get("temperature", 1.0), args.get("do_sample", False),

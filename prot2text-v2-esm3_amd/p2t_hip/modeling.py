@@ -1089,7 +1089,8 @@ class Esm2LlamaInstructForCausalLM(PreTrainedModel):
         """Reference :217-251: `inputs` is the [prompt] only; the prompt embeddings (placeholders replaced by the adapter rows) come
         from `forward(return_decoder_inputs=True)` and go to `llama_decoder.generate(inputs_embeds=, attention_mask=, **kwargs)`.
         The output does not repeat the prompt (it went in as embeddings).  `prompt_kv_dtype="fp8"` among the kwargs (bf16 models): the
-        e4m3 prompt segment of the KV cache; `lm_head_dtype="fp8" | "mxfp4"` (bf16 models): the quantised LM head (generation.generate)."""
+        e4m3 prompt segment of the KV cache; `lm_head_dtype="fp8" | "mxfp4"` (bf16 models): the quantised LM head; `prefill="packed"`
+        (with `pack_tokens=`): the decoder's padding-free prefill of ragged prompts -- the encoder stays padded (generation.generate)."""
         if getattr(self.esm_encoder, "lora", None) is not None:
             raise NotImplementedError(_ENCODER_LORA_MSG)
         with torch.no_grad():

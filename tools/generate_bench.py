@@ -44,7 +44,13 @@ the greedy choice (p2t_logits_process_rows) -- against the greedy continuous leg
 step and useful tokens/s; then the whole step {embed, step, [processors], choice} under graph replay at equal rows, the per-row engine
 against the lock-step engine with the SAME choice rule (the yardstick: what `generate(seed=)` / `generate(processors)` replays), three
 interleaved runs each, and whether the per-row step exceeds it by more than the runs' own min .. max spread.  Random weights have no eos:
-the limit ends a row, and nothing is claimed about the quality of what is decoded."""
+the limit ends a row, and nothing is claimed about the quality of what is decoded.
+python tools/generate_bench.py [B] [N] ragged [uniform]: the padded prompt phase against the padding-free one (`prefill="packed"`) on B prompts
+whose protein lengths are drawn once from bench.py's lognormal(5.75, 0.6) clipped to [16, 1024] (seed 0) + 64 chat tokens, left-padded to
+the longest as the collater does (`uniform`: 1024 residues each -- packing can win nothing there and pays for the unfused rotation).
+Interleaved in one process, three runs each, medians: (a) the decoder's share alone (compact + prefill | pack + prefill_packed, first-token
+head included), (b) the whole prompt phase with the still-padded ESM2 + adapter, (c) a whole generate of N tokens; and padded / valid
+tokens, the bound on (a)."""
 import os
 import sys
 import time
@@ -563,6 +569,65 @@ def continuous_choice_mode(model, kw, slots: int, Tnew: int, T: int, leg: str):
     assert not bool(e2.finished.any().item()) and int(e2.sample_flags.item()) == 0
 
 
+def ragged_mode(model, B: int, N: int, dev, uniform: bool):
+    """The padded prompt phase (compact + p2t_llama_prefill over B x longest tokens) against the packed one (generate(prefill="packed")),
+    interleaved in one process, three runs each: (a) the decoder's share alone on shared prompt embeddings, first-token head included,
+    (b) the whole prompt phase (ESM2 + adapter + scatter included: the encoder stays padded), (c) a whole generate of N tokens."""
+    Tp, n_chat = 1024, 64
+    rs = np.random.RandomState(0)
+    plens = [Tp] * B if uniform else np.clip(np.round(rs.lognormal(5.75, 0.6, B)), 16, Tp).astype(int).tolist()
+    Tl = int(max(plens))
+    T = Tl + n_chat
+    ids = rs.randint(0, 128000, size=(B, T)).astype(np.int64)
+    mask = np.zeros((B, T), dtype=np.int64)
+    for b, n in enumerate(plens):                                # left-padded as the collater does: [pad .. | 16 chat ids | n placeholders | 48 chat ids]
+        at = T - n - n_chat
+        ids[b, :at], mask[b, at:] = 128002, 1
+        ids[b, at + 16:at + 16 + n] = model.config.placeholder_id
+    pid, pmask = synth.protein_batch(5, B, Tl, plens)
+    t = lambda a: torch.from_numpy(a).to(dev)
+    kw = dict(inputs=t(ids), attention_mask=t(mask), protein_input_ids=t(pid), protein_attention_mask=t(pmask), eos_token_id=None, pad_token_id=128002,
+              do_sample=False, num_beams=1)
+    valid = int(mask.sum())
+    bound = B * T / valid
+    R, Tpk, _ = generation.plan_prompt_rows(mask.sum(1).tolist())
+    tag = f"generate cfg3 ragged{' (uniform 1024 residues)' if uniform else ''}: B={B}"
+    print(f"{tag}: protein lengths {'1024 each' if uniform else 'lognormal(5.75, 0.6) clipped to [16, 1024], seed 0'} + {n_chat} chat tokens: "
+          f"mean {valid / B:.1f}, longest {T}; padded {B} x {T} = {B * T} tokens, valid {valid}, packed {R} x {Tpk} = {R * Tpk}; "
+          f"padded / valid tokens = {bound:.3f} (the bound on the decoder's share)", flush=True)
+    with torch.no_grad():
+        emb, dmask = model(input_ids=kw["inputs"], attention_mask=kw["attention_mask"], protein_input_ids=kw["protein_input_ids"],
+                           protein_attention_mask=kw["protein_attention_mask"], return_decoder_inputs=True)
+    dec = model.llama_decoder
+    eng = generation.DecodeEngine(dec, B, 1, T, 64)
+
+    def clock(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+    legs = [("(a) decoder share: compact + prefill | pack + prefill_packed, first-token head included",
+             lambda: eng.prefill(*eng.compact(emb, dmask)), lambda: eng.prefill_packed(eng.pack(emb, dmask))),
+            ("(b) whole prompt phase (ESM2 + adapter + scatter + prefill + first token)",
+             lambda: model.generate(**kw, max_new_tokens=1), lambda: model.generate(**kw, max_new_tokens=1, prefill="packed")),
+            (f"(c) generate, {N} new tokens", lambda: model.generate(**kw, max_new_tokens=N), lambda: model.generate(**kw, max_new_tokens=N, prefill="packed"))]
+    for name, padded, packed in legs:
+        padded(); packed()                                       # warm-up of each path
+        runs = {"padded": [], "packed": []}
+        for _ in range(3):                                       # interleaved: a drift of the box hits both alike
+            runs["padded"].append(clock(padded))
+            runs["packed"].append(clock(packed))
+        a, b = np.median(runs["padded"]), np.median(runs["packed"])
+        spread = max(max(r) - min(r) for r in runs.values())
+        line = (f"{tag}: {name}: padded median {a:.1f} ms (min {min(runs['padded']):.1f}, max {max(runs['padded']):.1f}), packed median {b:.1f} ms "
+                f"(min {min(runs['packed']):.1f}, max {max(runs['packed']):.1f}); 3 runs each; padded / packed = {a / b:.3f}; padded - packed = {a - b:+.1f} ms, "
+                f"the runs' min .. max spread is {spread:.1f} ms: {'beyond' if abs(a - b) > spread else 'within'} the spread")
+        if name.startswith("(a)"):
+            line += f"; achieved / bound = {a / b:.3f} / {bound:.3f} = {a / b / bound:.3f}"
+        print(line, flush=True)
+
+
 def main():
     dev = torch.device("cuda:0")
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
@@ -572,7 +637,8 @@ def main():
     head = "head" in sys.argv[3:5]                               # [B] [N] [beams] head [fp8 | mxfp4] [kv8] [fp8 | mxfp4 weights]
     kv8 = "kv8" in sys.argv[3:5] and not head
     continuous = len(sys.argv) > 3 and sys.argv[3] == "continuous"   # [slots] [Tnew] continuous [fp8 | mxfp4] [kv8] [head fp8 | head mxfp4]
-    beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample and not process and sys.argv[3] not in ("kv8", "head", "continuous") else 1
+    ragged = len(sys.argv) > 3 and sys.argv[3] == "ragged"           # [B] [N] ragged [uniform]
+    beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample and not process and sys.argv[3] not in ("kv8", "head", "continuous", "ragged") else 1
     gemm_dtype = sys.argv[4] if len(sys.argv) > 4 and sys.argv[4] in ("fp8", "mxfp4") else "model"
     cont_extra = {}
     choice_leg = None
@@ -611,6 +677,8 @@ def main():
     model.eval()
     if fp8:
         model.set_gemm_dtype(gemm_dtype)
+    if ragged:
+        return ragged_mode(model, B, N, dev, "uniform" in sys.argv[4:])
     n_prompt = 64
     T = Tp + n_prompt
     rs = np.random.RandomState(0)

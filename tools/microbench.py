@@ -8,6 +8,9 @@ table, 8 x 4 and 32 x 4 beams, bf16 and fp8 prompt segment, 33 and 250 generated
 [rows, 128256] bf16 logits next to their lock-step twins, with no row and with half of the rows finished (the per-row kernels leave a
 finished row before they read it; the lock-step ones do its whole work).
 
+`kv_store` [m8] [m32]: the prefill's store of one layer's keys and values alone, p2t_kv_store_packed (bf16 and fp8 prompt segment) from a packed
+row of ragged prompts next to p2t_kv_quant_store on the padded batch.
+
 The `gemm` / `cold` / `ksweep` modes force launch forms through p2t_set_gemm_policy, and `fp8abl` runs the fp8 K-loop ablations
 (tile 1001-1003): run them against the LAB build (P2T_HIP_LIB=tools/build/libp2t_lab.so, `make -C prot2text-v2-esm3_amd/csrc lab`);
 the product library only knows policies 0 and 9 and fp8 tiles 0, 4, 128 and 256."""
@@ -425,6 +428,48 @@ def bench_choice_rows():
                       f"(min {min(r):.1f}, max {max(r):.1f}; {rounds} rounds of {n})", flush=True)
 
 
+def bench_kv_store():
+    """The prefill's store of ONE layer's keys and values at cfg3 shape (8 kv heads, head_dim 128), 8 and 32 prompts of bench.py's ragged
+    lengths (+ 64 chat tokens): p2t_kv_store_packed from one packed row, bf16 and into the fp8 prompt segment, next to p2t_kv_quant_store on
+    the padded batch (the padded path's fp8 store; its bf16 pair -- a 2-D copy + a transpose kernel -- has no entry point of its own and is
+    not timed alone).  Bytes: what a store must read and write for the VALID keys."""
+    import ctypes as C
+    import numpy as np
+    from p2t_hip import generation
+    from p2t_hip.ops import ptr, stream
+    nkv, d, L = 8, 128, 1
+    for B in [int(a[1:]) for a in sys.argv if a.startswith("m") and a[1:].isdigit()] or [8, 32]:
+        lens = (np.clip(np.round(np.random.RandomState(0).lognormal(5.75, 0.6, B)), 16, 1024).astype(int) + 64).tolist()
+        T, Tp = max(lens), ops.round_up(max(lens), 64)
+        R, Tpk, place = generation.plan_prompt_rows(lens)
+        c_place = (C.c_int32 * (3 * B))(*[v for p in place for v in p])
+        cfg = _lib.LlamaConfigC(n_layers=L, hidden=4096, ffn=14336, heads=32, kv_heads=nkv, head_dim=d, vocab=128256, dtype=_lib.BF16, rms_norm_eps=1e-5,
+                                rope_theta=5e5)
+        k, v = rand((R, nkv, Tpk, d)), rand((R, nkv, Tpk, d))
+        kpad, vpad = rand((B, nkv, T, d)), rand((B, nkv, T, d))
+        gen, cnt = torch.zeros((64,), device=dev), torch.zeros((B + 1,), dtype=torch.int32, device=dev)
+        z = lambda dt, *s: torch.zeros(s, dtype=dt, device=dev)
+        kp, vtp = z(torch.bfloat16, L, B, nkv, Tp, d), z(torch.bfloat16, L, B, nkv, d, Tp)
+        kq, vtq, ks, vs = z(torch.uint8, L, B, nkv, Tp, d), z(torch.uint8, L, B, nkv, d, Tp), z(torch.uint8, L, B, nkv, Tp), z(torch.uint8, L, B, nkv, Tp)
+        base = dict(k_gen=gen.data_ptr(), vt_gen=gen.data_ptr(), prompt_len=cnt.data_ptr(), step=cnt[B:].data_ptr(), B0=B, group=1, Tp=Tp, G=64)
+        c16 = _lib.KvCacheC(k_prompt=kp.data_ptr(), vt_prompt=vtp.data_ptr(), **base)
+        c8 = _lib.KvCacheC(k_prompt=kq.data_ptr(), vt_prompt=vtq.data_ptr(), k_prompt_scale=ks.data_ptr(), v_prompt_scale=vs.data_ptr(), **base)
+        packed = lambda cache: _lib.call("p2t_kv_store_packed", C.byref(cfg), C.byref(cache), 0, ptr(k), ptr(v), R, Tpk, c_place, B, stream())
+        runs = {"p2t_kv_store_packed, bf16": (lambda: packed(c16), 8.0),
+                "p2t_kv_store_packed, fp8 prompt segment": (lambda: packed(c8), 6.0),
+                f"p2t_kv_quant_store, padded {B} x {T} (fp8 prompt segment)": (
+                    lambda: _lib.call("p2t_kv_quant_store", ptr(kpad), ptr(vpad), B, nkv, T, d, Tp, ptr(kq), ptr(vtq), ptr(ks), ptr(vs), stream()), 6.0)}
+        res = {n: [] for n in runs}
+        for _ in range(5):
+            for n, (go, _) in runs.items():
+                res[n].append(timeit(go, iters=50, warm=5) * 1e3)
+        valid = sum(lens)
+        for n, r in res.items():
+            gb = runs[n][1] * valid * nkv * d / 1e9
+            print(f"kv_store prompts={B:2d} ({valid} valid keys x {nkv} kv heads x {d}, one layer; {R} packed row(s) of {Tpk}), {n}: median {np.median(r):6.1f} us "
+                  f"(min {min(r):.1f}, max {max(r):.1f}; 5 rounds of 50) = {gb / np.median(r) * 1e6 / 1e3:.2f} TB/s of valid-key traffic", flush=True)
+
+
 def bench_fp8abl():
     """Lab ablations of the fp8 K loop (per-tile kernel, garbage results; lab build only): full / no DMA / no fragment reloads / neither."""
     for name, M, N, K in (("esm qkv b64", 65536, 7680, 2560), ("esm fc2 b64", 65536, 2560, 10240), ("square 8k", 8192, 8192, 8192)):
@@ -455,6 +500,8 @@ if __name__ == "__main__":
         bench_fp8()
     if "skinny" in which:
         bench_skinny()
+    if "kv_store" in which:
+        bench_kv_store()
     if "attn_decode" in which and "beams" in which:
         bench_attn_decode_beams()
     elif "attn_decode" in which:
