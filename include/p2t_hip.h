@@ -1097,6 +1097,51 @@ int p2t_llama_decode_step_beams(const p2t_llama_config* cfg, const p2t_llama_wei
                                 const p2t_llama_layer_mxfp4* mx_layers, const void* lm_head, int64_t ld_head, int lm_head_preshuffled,
                                 const p2t_lm_head_q* head_q, const p2t_kv_cache* cache, const float* x, void* logits, int64_t ld_logits,
                                 int flags, void* workspace, size_t workspace_bytes, const uint8_t* ancestry, p2t_stream stream);
+/* ---- prompt-lookup decoding (opt-in; greedy; group == 1, per-row counters): a step carries Q = k + 1 tokens per row -- the token chosen
+ * last and a draft of up to k tokens found in the row's own generated text -- and keeps the longest prefix of the draft the model agrees
+ * with plus the model's own next token: greedy decoding's tokens in fewer steps.  History of row r: h[0 .. s] = out_tokens[r, 0 .. s],
+ * s = row_step[r]; h[s] is the token chosen last, not yet in the cache.  A rejected draft token's cache entry is simply stale: nothing
+ * reads past a row's counter plus the step's own tokens, and the next step overwrites it. */
+/* The draft (HF PromptLookupCandidateGenerator.get_candidates): for m = min(max_ngram, s) down to 1, the EARLIEST i <= s - m with
+ * h[i .. i + m) == h[s - m + 1 .. s]; the draft is h[i + m .. min(i + m + num_tokens, s + 1)), c tokens (no match at any m: c = 0).
+ * step_tokens (i64 [BB, num_tokens + 1]) row r = (h[s], the draft, pad_id behind it), draft_len[r] (i32 [BB]) = c.  finished[r] != 0:
+ * all pad_id, c = 0.  One block per row; 1 <= num_tokens <= 7, 1 <= max_ngram <= 4 (P2T_ERR_ARG).  One launch, capturable. */
+int p2t_lookup_draft_rows(const int64_t* out_tokens, int64_t ld_tokens, const int32_t* row_step, const int32_t* finished, int BB, int G,
+                          int num_tokens, int max_ngram, int64_t pad_id, int64_t* step_tokens, int32_t* draft_len, p2t_stream stream);
+/* p2t_attention_decode_rows for q_tokens query tokens per row: q and out have B0 * q_tokens rows, row r * q_tokens + j is token j of cache
+ * row r and attends to prompt_len[r] prompt keys and the generated keys 0 .. row_step[r] + j (this step's tokens 0 .. j among them: causal).
+ * bf16 on the matrix pipe (use_mfma != 0; the fp8 prompt segment with both scale arrays set): one block per (row, kv head) and chunk of
+ * 16 / (nh / nkv) queries, whose 16 head slots are (query, head) pairs -- the row's keys are streamed once per chunk; use_mfma = 0 / f32:
+ * the lane-per-key kernel over B0 * q_tokens virtual rows.  Either way row r * q_tokens + j holds the bits p2t_attention_decode_rows
+ * computes on the same cache with row r's counter at row_step[r] + j.  Cache entries behind row_step[r] + q_tokens - 1 are never read into a
+ * result.  q_tokens outside 1 .. 64: P2T_ERR_ARG; nh / nkv > 16: P2T_ERR_UNSUPPORTED. */
+int p2t_attention_decode_multi(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
+                               const int32_t* prompt_len, const int32_t* row_step, int B0, int nh, int nkv, int head_dim, int Tp, int G,
+                               float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out,
+                               const uint8_t* k_prompt_scale, const uint8_t* v_prompt_scale, int q_tokens, p2t_stream stream);
+/* p2t_llama_decode_step_rows for q_tokens tokens per row: x f32 [B0 * q_tokens, hidden] and logits [B0 * q_tokens, ld_logits], row
+ * r * q_tokens + j = token j of cache row r.  Token j runs at position prompt_len[r] + row_step[r] + j, its key and value are appended at
+ * index clamp(row_step[r] + j, 0, G - 1), its attention is p2t_attention_decode_multi's, and its logits row predicts token row_step[r] +
+ * j + 1.  The launches are those of a step of B0 * q_tokens rows but the attention's; row_step is READ ONLY (p2t_lookup_verify_rows
+ * advances it) and there is no `frozen`: a finished row re-appends behind its counter, where nothing is read.  The workspace is that of
+ * B0 * q_tokens rows: p2t_llama_decode_workspace_bytes(cfg, B0 * q_tokens, Tp, G) (+ p2t_lm_head_q_workspace_bytes(B0 * q_tokens, hidden)
+ * with head_q).  Every model and weight form of p2t_llama_decode_step_rows.  B0 * q_tokens > 64, group != 1, heads / kv_heads > 16:
+ * P2T_ERR_UNSUPPORTED; q_tokens outside 1 .. 64: P2T_ERR_ARG; all before the first enqueue.  Enqueues only: capturable. */
+int p2t_llama_decode_step_multi(const p2t_llama_config* cfg, const p2t_llama_weights* w, const p2t_llama_layer_stream* w_stream,
+                                const p2t_llama_layer_mxfp4* mx_layers, const void* lm_head, int64_t ld_head, int lm_head_preshuffled,
+                                const p2t_lm_head_q* head_q, const p2t_kv_cache* cache, const float* x, void* logits, int64_t ld_logits,
+                                int flags, void* workspace, size_t workspace_bytes, const int32_t* row_step, int q_tokens, p2t_stream stream);
+/* The verification behind such a step: g_j = argmax(logits[r * q_tokens + j, :V]) (lowest index among equal maxima, one block per logits
+ * row into choice, i32 [BB * q_tokens] scratch), then one thread per row: a = the largest value <= draft_len[r] with g_(j-1) ==
+ * step_tokens[r, j] for 1 <= j <= a (and s + j < row_limit[r]: a token behind the limit decides nothing); the new tokens g_0 .. g_a, cut behind the first one in eos_ids and at the row's limit, go to
+ * out_tokens[r, s + 1 ..]; row_step[r] = s + their number, next_tokens[r] = the last of them, finished[r] |= 1 (eos) | 2 (the token at
+ * index row_limit[r] - 1 was written), p2t_greedy_select_rows' bits.  finished[r] != 0 on entry: next_tokens[r] = pad_id and nothing else is
+ * written.  stats (i32 [BB, 3]) += (1, draft_len[r], a) for a live row (a: before the eos / limit cut).  No float atomics; every index is clamped; nothing
+ * is written outside out_tokens[r, 0 .. G).  2 <= q_tokens <= 8 (P2T_ERR_ARG).  Two launches, capturable. */
+int p2t_lookup_verify_rows(const void* logits, int dtype, int64_t ld, int V, int BB, int q_tokens, const int64_t* step_tokens,
+                           const int32_t* draft_len, const int64_t* eos_ids, int n_eos, int64_t pad_id, int32_t* finished,
+                           int64_t* next_tokens, int64_t* out_tokens, int64_t ld_tokens, int32_t* row_step, const int32_t* row_limit, int G,
+                           int32_t* stats, int32_t* choice, p2t_stream stream);
 
 /* ---------------------------------------------------------------- optimizer tail */
 /* One clip_grad_norm_(max_norm) + AdamW step over n_tensors (<= 64) f32 parameter tensors (HOST arrays of

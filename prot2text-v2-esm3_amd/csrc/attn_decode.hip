@@ -67,26 +67,32 @@ __device__ __forceinline__ void decode_merge_beams(float (&red)[NW][16][DP + 2],
 
 // ANC (a beam group under an ancestry table, `anc` u8 [BB][Gcap]): the generated tiles are those of ALL `group` physical rows of the
 // row's prompt, and key i of physical row p counts where anc[bb][i] == p -- a tile may then hold no visible key at all.
-template <typename T, int DP, int GH, bool ANC = false>
+// MQ (q_tokens query tokens per cache row, p2t_attention_decode_multi): the grid's rows are VIRTUAL rows m = row * q_tokens + j -- q and
+// out are indexed by m, the cache by row m / q_tokens, and token j sees step[row] + j + 1 generated keys: every other line is the
+// per-row kernel's, so virtual row m computes what that kernel computes for a row whose counter is step[row] + j, bit for bit.
+template <typename T, int DP, int GH, bool ANC = false, bool MQ = false>
 __global__ void __launch_bounds__(512) attn_decode_kernel(const T* __restrict__ q, const T* __restrict__ kp, const T* __restrict__ vtp,
                                                           const T* __restrict__ kg, const T* __restrict__ vtg,
                                                           const int32_t* __restrict__ prompt_len, const int32_t* __restrict__ step_ptr,
                                                           int step_stride, int group, int nh, int nkv, int G, int Tp, int Gcap, float c_exp, int round_p,
-                                                          T* __restrict__ out, int64_t ld_out, int d, const uint8_t* __restrict__ anc) {
+                                                          T* __restrict__ out, int64_t ld_out, int d, const uint8_t* __restrict__ anc, int q_tokens) {
+    static_assert(!(ANC && MQ), "a beam group decodes one token per row");
     constexpr int PN = Piece<T>::N, R = DP > 64 ? DP / 64 : 1, PW = DP + 2, NW = 8;
     __shared__ float sq[GH][DP];
     __shared__ float sp[NW][GH][64];
     __shared__ float red[NW][GH][PW];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int pair = blockIdx.x, bb = pair / nkv, kvh = pair - bb * nkv, b0 = bb / group;
+    const int pair = blockIdx.x, vrow = pair / nkv, kvh = pair - vrow * nkv;  // vrow: the row of q and out
+    const int bb = MQ ? vrow / q_tokens : vrow, b0 = bb / group;              // bb: the cache row
     const int hc = blockIdx.y;
     const int h0 = kvh * G + hc * GH, nhead = min(GH, G - hc * GH);          // query heads h0 .. h0 + nhead - 1
     for (int i = threadIdx.x; i < GH * DP; i += NW * 64) {
         const int g = i / DP, c = i - g * DP;
-        sq[g][c] = g < nhead ? to_f32(q[((int64_t)bb * nh + h0 + g) * DP + c]) : 0.f;
+        sq[g][c] = g < nhead ? to_f32(q[((int64_t)vrow * nh + h0 + g) * DP + c]) : 0.f;
     }
     __syncthreads();
-    const int n0 = min(max(prompt_len[b0], 0), Tp), n1 = min(max(step_ptr[(int64_t)bb * step_stride], 0) + 1, Gcap);
+    const int n0 = min(max(prompt_len[b0], 0), Tp);
+    const int n1 = min(max(step_ptr[(int64_t)bb * step_stride], 0) + (MQ ? vrow - bb * q_tokens : 0) + 1, Gcap);
     const int tiles0 = (n0 + 63) >> 6, tiles1 = (n1 + 63) >> 6, tiles = tiles0 + (ANC ? group : 1) * tiles1;
     const int64_t seg1 = (int64_t)nkv * Gcap * DP;                            // one row of the generated segment
     const T* k_seg0 = kp + ((int64_t)b0 * nkv + kvh) * Tp * DP;
@@ -174,7 +180,7 @@ __global__ void __launch_bounds__(512) attn_decode_kernel(const T* __restrict__ 
             if (lane + 64 * r < DP) red[w][g][lane + 64 * r] = acc[g][r];
     }
     __syncthreads();
-    decode_merge<T, DP, GH, NW>(red, bb, h0, nhead, d, out, ld_out);
+    decode_merge<T, DP, GH, NW>(red, vrow, h0, nhead, d, out, ld_out);
 }
 
 // bf16 form on the matrix pipe (`v_mfma_f32_16x16x32_bf16`, fragments straight from global memory -- no LDS staging, the step is a
@@ -213,12 +219,17 @@ __device__ __forceinline__ float e8m0_byte_to_f32(unsigned word, int byte) {    
 // and key i counts for the lane's head slot where anc_row[i] == phys (anc_row: the ancestry row of the slot's beam).  Two things differ
 // from the other tiles: a slot may see NO key of the tile, and then keeps (m_run, l_run, acc) exactly; and masked keys inside n hold
 // other beams' finite values, which p = 0 silences without zeroing V.
-template <int DP, bool F8, bool ANC = false>
+// MQ (bf16 tiles of the generated segment under several query tokens per row, attn_decode_multi_mfma_kernel): `n` is the LANE'S head
+// slot's own count -- the slot's query sees the keys in front of it and itself -- and n_v >= n the count of the chunk's last query.  As
+// under ANC a slot may see no key of the tile and then keeps (m_run, l_run, acc) exactly; the keys between n and n_v are this step's
+// own finite ones, which p = 0 silences, and V is zeroed behind n_v only.
+template <int DP, bool F8, bool ANC = false, bool MQ = false>
 __device__ __forceinline__ void decode_tile(const void* __restrict__ k_seg, const void* __restrict__ v_seg, const uint8_t* __restrict__ ks_seg,
                                             const uint8_t* __restrict__ vs_seg, int tt, int n, int cap, const bf16x8 (&qf)[DP / 32], float c_exp, int j,
                                             int g, float& m_run, float& l_run, f32x4 (&acc)[DP / 16], const uint8_t* __restrict__ anc_row = nullptr,
-                                            int phys = 0) {
-    static_assert(!(F8 && ANC), "the generated segment is bf16");
+                                            int phys = 0, int n_v = 0) {
+    static_assert(!(F8 && (ANC || MQ)) && !(ANC && MQ), "the generated segment is bf16; a beam group decodes one token per row");
+    constexpr bool EMPTY = ANC || MQ;        // a slot may see no key of the tile
     constexpr int KK = DP / 32, DT = DP / 16;
     const bool full = tt * 64 + 64 <= n;
     f32x4 sc[4];
@@ -296,10 +307,10 @@ __device__ __forceinline__ void decode_tile(const void* __restrict__ k_seg, cons
         }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float m_new = fmaxf(m_run, mx);                                // every tile holds at least one valid key -- unless ANC:
-    const float alpha = exp2f(m_run - (ANC && m_new == -INFINITY ? 0.f : m_new));      // nothing visible so far: 0 on (l, acc) = 0, no -inf - -inf
+    float m_new = fmaxf(m_run, mx);                                // every tile holds at least one valid key -- unless ANC / MQ:
+    const float alpha = exp2f(m_run - (EMPTY && m_new == -INFINITY ? 0.f : m_new));    // nothing visible so far: 0 on (l, acc) = 0, no -inf - -inf
     m_run = m_new;
-    if (ANC && m_new == -INFINITY) m_new = 0.f;                    // ... and p = exp2(-inf - 0) = 0
+    if (EMPTY && m_new == -INFINITY) m_new = 0.f;                  // ... and p = exp2(-inf - 0) = 0
     if (F8 && !full) {                                             // code and scale bytes behind the valid prefix -> 0 (0 x garbage must stay 0)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -324,7 +335,8 @@ __device__ __forceinline__ void decode_tile(const void* __restrict__ k_seg, cons
         pf[hv] = __builtin_bit_cast(bf16x8, u32x4{pack_bf16x2(p[0], p[1]), pack_bf16x2(p[2], p[3]), pack_bf16x2(p[4], p[5]), pack_bf16x2(p[6], p[7])});
     }
     l_run = l_run * alpha + psum;
-    if (!F8 && !full) {                                            // keys behind the valid prefix: 0 x garbage must stay 0
+    const int nz = MQ ? n_v : n;                                   // V is zeroed behind the last count any slot of the wave has
+    if (!F8 && (MQ ? tt * 64 + 64 > nz : !full)) {                 // keys behind the valid prefix: 0 x garbage must stay 0
 #pragma unroll
         for (int hv = 0; hv < 2; ++hv)
 #pragma unroll
@@ -332,7 +344,7 @@ __device__ __forceinline__ void decode_tile(const void* __restrict__ k_seg, cons
                 typedef short s16x8 __attribute__((ext_vector_type(8)));
                 s16x8 v = __builtin_bit_cast(s16x8, vf[hv][dt]);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = tt * 64 + 32 * hv + 8 * g + e < n ? v[e] : (short)0;
+                for (int e = 0; e < 8; ++e) v[e] = tt * 64 + 32 * hv + 8 * g + e < nz ? v[e] : (short)0;
                 vf[hv][dt] = __builtin_bit_cast(bf16x8, v);
             }
     }
@@ -477,6 +489,72 @@ __global__ void __launch_bounds__(NW * 64) attn_decode_beams_mfma_kernel(const b
     decode_merge_beams<DP, NW>(red, b0, group, beam0, BC, kvh, G, d, out, ld_out);
 }
 
+// Several query tokens per cache row (include/p2t_hip.h, p2t_attention_decode_multi): q / out row m = row * Q + i is token i of cache row
+// `row`, which sees the prompt and the generated keys 0 .. step[row] + i.  grid (BB * nkv, query chunks), ONE block per (row, kv head)
+// and chunk of QC = 16 / G queries: head slot j = (query q0 + j / G, head j % G), so the row's keys and values are streamed once for QC
+// queries.  Prompt tiles count for every slot; the generated tile list runs to the chunk's last query and every slot brings its own count
+// (decode_tile's MQ form).  Tile t goes to wave t mod NW and the merge is per slot, with the per-row kernel's NW for the same head shape:
+// a slot's tiles, their waves and their order are those of attn_decode_mfma_kernel for a row whose counter is step[row] + i, and a tile
+// behind the slot's count changes nothing -- the same bits.  Idle slots (16 % G, Q's last chunk) read a zero q and store nothing.
+template <int DP, int NW, bool P8>
+__global__ void __launch_bounds__(NW * 64) attn_decode_multi_mfma_kernel(const bf16_t* __restrict__ q, const void* __restrict__ kp,
+                                                                     const void* __restrict__ vtp, const bf16_t* __restrict__ kg,
+                                                                     const bf16_t* __restrict__ vtg, const uint8_t* __restrict__ kps,
+                                                                     const uint8_t* __restrict__ vps, const int32_t* __restrict__ prompt_len,
+                                                                     const int32_t* __restrict__ step_ptr, int Q, int nh, int nkv, int G, int Tp,
+                                                                     int Gcap, float c_exp, bf16_t* __restrict__ out, int64_t ld_out, int d) {
+    constexpr int PW = DP + 2, KK = DP / 32, DT = DP / 16, EP = P8 ? 1 : 2;
+    __shared__ float red[NW][16][PW];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
+    const int pair = blockIdx.x, bb = pair / nkv, kvh = pair - bb * nkv;
+    const int QC = 16 / G, q0 = blockIdx.y * QC, sq = j / G, sh = j - sq * G;
+    const int q_last = min(q0 + QC, Q) - 1;                           // the chunk's last query
+    const bool live = sq < QC && q0 + sq <= q_last;
+    const int qi = min(q0 + sq, q_last);                              // an idle slot: a real query's count, a zero q
+    const bf16x8 zero8 = {};
+    const bf16_t* qrow = q + (((int64_t)bb * Q + qi) * nh + kvh * G + sh) * DP;
+    auto load_q = [&](bf16x8 (&qf)[KK], bool f8_order) {            // attn_decode_mfma_kernel's, per slot
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) {
+            const int f = f8_order && DP > 32 ? 64 * (kk >> 1) + 16 * g + 8 * (kk & 1) : 32 * kk + 8 * g;
+            qf[kk] = live ? *reinterpret_cast<const bf16x8*>(qrow + f) : zero8;
+        }
+    };
+    bf16x8 qf[KK];
+    load_q(qf, P8);
+    const int st = max(step_ptr[bb], 0);
+    const int n0 = min(max(prompt_len[bb], 0), Tp), n1 = min(st + qi + 1, Gcap), n1_last = min(st + q_last + 1, Gcap);
+    const int tiles0 = (n0 + 63) >> 6, tiles = tiles0 + ((n1_last + 63) >> 6);
+    const char* k_seg0 = (const char*)kp + ((int64_t)bb * nkv + kvh) * Tp * DP * EP;
+    const bf16_t* k_seg1 = kg + ((int64_t)bb * nkv + kvh) * Gcap * DP;
+    const char* v_seg0 = (const char*)vtp + ((int64_t)bb * nkv + kvh) * DP * Tp * EP;
+    const bf16_t* v_seg1 = vtg + ((int64_t)bb * nkv + kvh) * DP * Gcap;
+    const uint8_t* ks_seg0 = P8 ? kps + ((int64_t)bb * nkv + kvh) * Tp : nullptr;
+    const uint8_t* vs_seg0 = P8 ? vps + ((int64_t)bb * nkv + kvh) * Tp : nullptr;
+    float m_run = -INFINITY, l_run = 0.f;
+    f32x4 acc[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    int t = w;
+    for (; t < tiles0; t += NW) decode_tile<DP, P8>(k_seg0, v_seg0, ks_seg0, vs_seg0, t, n0, Tp, qf, c_exp, j, g, m_run, l_run, acc);
+    if (P8 && t < tiles) load_q(qf, false);                          // the bf16 tiles' feature order
+    for (; t < tiles; t += NW)
+        decode_tile<DP, false, false, true>(k_seg1, v_seg1, nullptr, nullptr, t - tiles0, n1, Gcap, qf, c_exp, j, g, m_run, l_run, acc, nullptr, 0, n1_last);
+    l_run += __shfl_xor(l_run, 16, 64);
+    l_run += __shfl_xor(l_run, 32, 64);
+    if (g == 0) { red[w][j][DP] = m_run; red[w][j][DP + 1] = l_run; }       // lane (slot j, g) holds the features 16 dt + 4 g + r of its slot
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[w][j][16 * dt + 4 * g + r] = acc[dt][r];
+    __syncthreads();
+    for (int i = threadIdx.x; i < 16 * DP; i += NW * 64) {             // decode_merge_beams' store, slot = (query, head)
+        const int jj = i / DP, c = i - jj * DP, s2 = jj / G, h2 = jj - s2 * G;
+        if (s2 >= QC || q0 + s2 > q_last || c >= d) continue;
+        out[((int64_t)bb * Q + q0 + s2) * ld_out + (int64_t)(kvh * G + h2) * d + c] = from_f32<bf16_t>(merged_output<DP, 16, NW>(red, jj, c));
+    }
+}
+
 int pick_gh(int G) { return G <= 1 ? 1 : (G <= 2 ? 2 : (G <= 4 ? 4 : 8)); }
 
 template <typename T>
@@ -522,7 +600,7 @@ int launch_attn_decode_t(const p2t_llama_config* c, const void* q, void* out, in
     P2T_REQUIRE(!kc->k_prompt_scale, "attention over an fp8 prompt segment: the matrix-pipe kernel only");
 #define P2T_AD(DPV, GHV)                                                                                                              \
     attn_decode_kernel<T, DPV, GHV><<<grid, 512, 0, s>>>((const T*)q, kp, vtp, kg, vtg, kc->prompt_len, kc->step, step_stride, kc->group, nh, nkv, G, \
-                                                         kc->Tp, kc->G, c_exp, round_p, (T*)out, ld_out, d, nullptr)
+                                                         kc->Tp, kc->G, c_exp, round_p, (T*)out, ld_out, d, nullptr, 1)
 #define P2T_AD_G(DPV)                                                                                                                 \
     do {                                                                                                                              \
         if (GH == 1) P2T_AD(DPV, 1); else if (GH == 2) P2T_AD(DPV, 2); else if (GH == 4) P2T_AD(DPV, 4); else P2T_AD(DPV, 8);      \
@@ -572,7 +650,7 @@ int launch_attn_decode_beams_t(const p2t_llama_config* c, const void* q, void* o
     const T* vtp = (const T*)kc->vt_prompt + per_p * layer;
 #define P2T_ADL(DPV, GHV)                                                                                                             \
     attn_decode_kernel<T, DPV, GHV, true><<<grid, 512, 0, s>>>((const T*)q, kp, vtp, kg, vtg, kc->prompt_len, kc->step, 0, kc->group, nh, nkv, G, kc->Tp, \
-                                                               kc->G, c_exp, round_p, (T*)out, ld_out, d, anc)
+                                                               kc->G, c_exp, round_p, (T*)out, ld_out, d, anc, 1)
 #define P2T_ADL_G(DPV)                                                                                                                \
     do {                                                                                                                              \
         if (GH == 1) P2T_ADL(DPV, 1); else if (GH == 2) P2T_ADL(DPV, 2); else if (GH == 4) P2T_ADL(DPV, 4); else P2T_ADL(DPV, 8);  \
@@ -584,7 +662,77 @@ int launch_attn_decode_beams_t(const p2t_llama_config* c, const void* q, void* o
     return P2T_OK;
 }
 
+// launch_attn_decode_t for Q query tokens per row (checked: group 1, per-row counters, 1 <= G <= 16)
+template <typename T>
+int launch_attn_decode_multi_t(const p2t_llama_config* c, const void* q, void* out, int64_t ld_out, const p2t_kv_cache* kc, int layer, float c_exp,
+                               int round_p, int use_mfma, int Q, hipStream_t s) {
+    const int nh = c->heads, nkv = c->kv_heads, d = c->head_dim, dp = head_dim_padded(d), G = nh / nkv, BB = kc->B0;
+    const int GH = pick_gh(G), ZC = (G + GH - 1) / GH;
+    const size_t per_p = (size_t)kc->B0 * nkv * kc->Tp * dp, per_g = (size_t)BB * nkv * kc->G * dp;
+    const T* kg = (const T*)kc->k_gen + per_g * layer;
+    const T* vtg = (const T*)kc->vt_gen + per_g * layer;
+    if constexpr (sizeof(T) == 2) {
+        if (use_mfma) {
+            const int QC = 16 / G;                   // queries per block: its 16 head slots are (query, head) pairs
+            const dim3 grid((unsigned)(BB * nkv), (unsigned)ceil_div(Q, QC));
+            const size_t per_s = (size_t)kc->B0 * nkv * kc->Tp, e = kc->k_prompt_scale ? 1 : 2;
+            const char* kp = (const char*)kc->k_prompt + per_p * layer * e;
+            const char* vtp = (const char*)kc->vt_prompt + per_p * layer * e;
+            const uint8_t* kps = kc->k_prompt_scale ? kc->k_prompt_scale + per_s * layer : nullptr;
+            const uint8_t* vps = kc->k_prompt_scale ? kc->v_prompt_scale + per_s * layer : nullptr;
+            const bool nw16 = GH <= 4 && dp <= 64;   // the per-row kernel's waves for this head shape (the same tile -> wave map)
+#define P2T_ADQ(DPV, NWV, P8V)                                                                                                        \
+    attn_decode_multi_mfma_kernel<DPV, NWV, P8V><<<grid, NWV * 64, 0, s>>>((const bf16_t*)q, kp, vtp, (const bf16_t*)kg, (const bf16_t*)vtg, kps, vps, \
+                                                                           kc->prompt_len, kc->step, Q, nh, nkv, G, kc->Tp, kc->G, c_exp,     \
+                                                                           (bf16_t*)out, ld_out, d)
+#define P2T_ADQ_D(P8V)                                                                                                                \
+    do {                                                                                                                              \
+        if (dp == 32) { if (nw16) P2T_ADQ(32, 16, P8V); else P2T_ADQ(32, 8, P8V); }                                                   \
+        else if (dp == 64) { if (nw16) P2T_ADQ(64, 16, P8V); else P2T_ADQ(64, 8, P8V); }                                              \
+        else P2T_ADQ(128, 8, P8V);                                                                                                    \
+    } while (0)
+            if (kps) P2T_ADQ_D(true); else P2T_ADQ_D(false);
+#undef P2T_ADQ_D
+#undef P2T_ADQ
+            P2T_LAUNCH_CHECK();
+            return P2T_OK;
+        }
+    }
+    P2T_REQUIRE(!kc->k_prompt_scale, "attention over an fp8 prompt segment: the matrix-pipe kernel only");
+    const dim3 grid((unsigned)(BB * Q * nkv), (unsigned)ZC);
+    const T* kp = (const T*)kc->k_prompt + per_p * layer;
+    const T* vtp = (const T*)kc->vt_prompt + per_p * layer;
+#define P2T_ADV(DPV, GHV)                                                                                                             \
+    attn_decode_kernel<T, DPV, GHV, false, true><<<grid, 512, 0, s>>>((const T*)q, kp, vtp, kg, vtg, kc->prompt_len, kc->step, 1, 1, nh, nkv, G, kc->Tp, \
+                                                                      kc->G, c_exp, round_p, (T*)out, ld_out, d, nullptr, Q)
+#define P2T_ADV_G(DPV)                                                                                                                \
+    do {                                                                                                                              \
+        if (GH == 1) P2T_ADV(DPV, 1); else if (GH == 2) P2T_ADV(DPV, 2); else if (GH == 4) P2T_ADV(DPV, 4); else P2T_ADV(DPV, 8);  \
+    } while (0)
+    if (dp == 32) P2T_ADV_G(32); else if (dp == 64) P2T_ADV_G(64); else P2T_ADV_G(128);
+#undef P2T_ADV_G
+#undef P2T_ADV
+    P2T_LAUNCH_CHECK();
+    return P2T_OK;
+}
+
 }  // namespace
+
+int launch_attn_decode_multi(const p2t_llama_config* c, const void* q, void* out, int64_t ld_out, const p2t_kv_cache* kc, int layer, float c_exp,
+                             int round_p, int use_mfma, int q_tokens, hipStream_t s) {
+    return c->dtype == P2T_BF16 ? launch_attn_decode_multi_t<bf16_t>(c, q, out, ld_out, kc, layer, c_exp, round_p, use_mfma, q_tokens, s)
+                                : launch_attn_decode_multi_t<float>(c, q, out, ld_out, kc, layer, c_exp, round_p, use_mfma, q_tokens, s);
+}
+
+// what a call with several query tokens per row asks: 1 .. 64 of them, at most 16 query heads per kv head
+int check_multi(int q_tokens, int heads_per_kv, const char* who) {
+    P2T_REQUIRE(q_tokens >= 1 && q_tokens <= 64, "%s: q_tokens %d outside 1 .. 64", who, q_tokens);
+    if (heads_per_kv > 16) {
+        set_error("%s: several query tokens per row serve at most 16 query heads per kv head (got %d)", who, heads_per_kv);
+        return P2T_ERR_UNSUPPORTED;
+    }
+    return P2T_OK;
+}
 
 int launch_attn_decode_beams(const p2t_llama_config* c, const void* q, void* out, int64_t ld_out, const p2t_kv_cache* kc, int layer, float c_exp,
                              int round_p, int use_mfma, const uint8_t* ancestry, hipStream_t s) {
@@ -606,7 +754,7 @@ using namespace p2t;
 static int attention_decode_impl(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
                                  const int32_t* prompt_len, const int32_t* step, int B0, int group, int nh, int nkv, int head_dim, int Tp, int G,
                                  float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out, const uint8_t* k_prompt_scale,
-                                 const uint8_t* v_prompt_scale, int step_stride, const uint8_t* ancestry, p2t_stream stream) {
+                                 const uint8_t* v_prompt_scale, int step_stride, const uint8_t* ancestry, p2t_stream stream, int q_tokens = 0) {
     P2T_REQUIRE(q && out && (dtype == P2T_F32 || dtype == P2T_BF16) && nkv > 0 && nh % nkv == 0 && ld_out >= (int64_t)nh * head_dim,
                 "p2t_attention_decode: bad arguments");
     p2t_llama_config c{};
@@ -621,6 +769,7 @@ static int attention_decode_impl(const void* q, const void* k_prompt, const void
     P2T_REQUIRE(dtype == P2T_BF16 || use_mfma <= 0, "p2t_attention_decode: the matrix-pipe kernel is bf16 only");
     const float c_exp = log2_scores ? 1.0f : scale * kLog2e;
     if (ancestry) return launch_attn_decode_beams(&c, q, out, ld_out, &kc, 0, c_exp, dtype == P2T_BF16, use_mfma != 0, ancestry, (hipStream_t)stream);
+    if (q_tokens) return launch_attn_decode_multi(&c, q, out, ld_out, &kc, 0, c_exp, dtype == P2T_BF16, use_mfma != 0, q_tokens, (hipStream_t)stream);
     return launch_attn_decode(&c, q, out, ld_out, &kc, 0, c_exp, dtype == P2T_BF16, use_mfma != 0, step_stride, (hipStream_t)stream);
 }
 
@@ -650,6 +799,19 @@ extern "C" int p2t_attention_decode_rows(const void* q, const void* k_prompt, co
     P2T_REQUIRE(!k_prompt_scale == !v_prompt_scale, "p2t_attention_decode_rows: k_prompt_scale and v_prompt_scale go together");
     return attention_decode_impl(q, k_prompt, vt_prompt, k_gen, vt_gen, prompt_len, row_step, B0, 1, nh, nkv, head_dim, Tp, G, scale, log2_scores, dtype,
                                  use_mfma, out, ld_out, k_prompt_scale, v_prompt_scale, 1, nullptr, stream);
+}
+
+// p2t_attention_decode_rows for q_tokens query tokens per row: q / out row r * q_tokens + j is token j of cache row r
+extern "C" int p2t_attention_decode_multi(const void* q, const void* k_prompt, const void* vt_prompt, const void* k_gen, const void* vt_gen,
+                                          const int32_t* prompt_len, const int32_t* row_step, int B0, int nh, int nkv, int head_dim, int Tp, int G,
+                                          float scale, int log2_scores, int dtype, int use_mfma, void* out, int64_t ld_out,
+                                          const uint8_t* k_prompt_scale, const uint8_t* v_prompt_scale, int q_tokens, p2t_stream stream) {
+    P2T_REQUIRE(row_step, "p2t_attention_decode_multi: null row_step");
+    P2T_REQUIRE(nkv > 0 && nh > 0, "p2t_attention_decode_multi: bad arguments");
+    P2T_TRY(check_multi(q_tokens, nh / nkv, "p2t_attention_decode_multi"));
+    P2T_REQUIRE(!k_prompt_scale == !v_prompt_scale, "p2t_attention_decode_multi: k_prompt_scale and v_prompt_scale go together");
+    return attention_decode_impl(q, k_prompt, vt_prompt, k_gen, vt_gen, prompt_len, row_step, B0, 1, nh, nkv, head_dim, Tp, G, scale, log2_scores, dtype,
+                                 use_mfma, out, ld_out, k_prompt_scale, v_prompt_scale, 1, nullptr, stream, q_tokens);
 }
 
 // p2t_attention_decode / p2t_attention_decode_prompt_fp8 for a beam group whose generated keys stay in the rows that wrote them

@@ -63,10 +63,12 @@ __device__ __forceinline__ void skinny_finish(float (&red)[kSkWaves][NT][MT][64]
                 const int hd = ra.d, half = hd >> 1, blk = n >> 6;
                 const int head = hd == 64 ? blk : blk >> 1;
                 const int ch = (hd == 64 ? 0 : 32 * (blk & 1)) + (n & 31);
-                const int step = min(max(ra.step[(int64_t)m * ra.step_stride], 0), ra.G - 1);
+                // cr: the cache row; several tokens per row: token m % q_tokens of row m / q_tokens, that many keys further on
+                const int cr = ra.q_tokens > 1 ? m / ra.q_tokens : m;
+                const int step = min(max(ra.step[(int64_t)cr * ra.step_stride], 0) + (m - cr * ra.q_tokens), ra.G - 1);
                 if (head < ra.nh + ra.nkv) {
                     const bool is_q = head < ra.nh;
-                    const float qs = is_q ? ra.q_scale : 1.0f, pos = (float)(ra.prompt_len[m / ra.group] + step);
+                    const float qs = is_q ? ra.q_scale : 1.0f, pos = (float)(ra.prompt_len[cr / ra.group] + step);
                     float o1[4], o2[4];
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
@@ -76,11 +78,11 @@ __device__ __forceinline__ void skinny_finish(float (&red)[kSkWaves][NT][MT][64]
                         o2[t] = a2 * c + a1 * sn;
                     }
                     bf16_t* dst = is_q ? (bf16_t*)ra.q + ((int64_t)m * ra.nh + head) * hd
-                                       : (bf16_t*)ra.k + (((int64_t)m * ra.nkv + (head - ra.nh)) * ra.G + step) * hd;
+                                       : (bf16_t*)ra.k + (((int64_t)cr * ra.nkv + (head - ra.nh)) * ra.G + step) * hd;
                     store4(dst + ch, o1);
                     store4(dst + ch + half, o2);
                 } else {
-                    bf16_t* dst = (bf16_t*)ra.vt + ((int64_t)m * ra.nkv + (head - ra.nh - ra.nkv)) * hd * ra.G + step;
+                    bf16_t* dst = (bf16_t*)ra.vt + ((int64_t)cr * ra.nkv + (head - ra.nh - ra.nkv)) * hd * ra.G + step;
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
                         dst[(int64_t)(ch + t) * ra.G] = from_f32<bf16_t>(v[t]);

@@ -153,10 +153,12 @@ static inline void with_fix(GemmArgs& g, void* ws, unsigned& epoch) { g.fix_ws =
 // weight-streaming GEMM for M <= 64 rows (gemm_skinny.hip): bf16, epilogues STORE / STORE_F32 / RESID / SWIGLU, no bias;
 // P2T_ERR_UNSUPPORTED for anything else
 // epilogue arguments of launch_gemm_skinny_qkv_rope: rotation at position prompt_len[row / group] + step[row * step_stride] and the cache
-// append (step_stride 0: the shared lock-step counter, 1: every row's own)
+// append (step_stride 0: the shared lock-step counter, 1: every row's own).  q_tokens > 1 (several tokens per cache row, per-row counters):
+// GEMM row m is token m % q_tokens of cache row m / q_tokens -- its counter is step[m / q_tokens] + m % q_tokens, its q goes to row m of q
 struct SkinnyRope {
     const float* inv_freq = nullptr; const int32_t* prompt_len = nullptr; const int32_t* step = nullptr;
     int group = 1, nh = 0, nkv = 0, d = 0, G = 0; float q_scale = 1.f; int step_stride = 0;
+    int q_tokens = 1;
     void* q = nullptr;       // bf16 [M, nh, d]
     void* k = nullptr;       // bf16 [M, nkv, G, d]   (one layer of p2t_kv_cache.k_gen)
     void* vt = nullptr;      // bf16 [M, nkv, d, G]   (one layer of p2t_kv_cache.vt_gen)
@@ -250,6 +252,11 @@ int launch_attn_decode(const p2t_llama_config* c, const void* q, void* out, int6
 // ancestry[r][i] of r's prompt (u8 [BB][kc->G], kv_cache.hip).  The shared counter; group 2 .. 16, at most 16 query heads per kv head
 int launch_attn_decode_beams(const p2t_llama_config* c, const void* q, void* out, int64_t ld_out, const p2t_kv_cache* kc, int layer, float c_exp,
                              int round_p, int use_mfma, const uint8_t* ancestry, hipStream_t s);
+// the same for q_tokens query tokens per row (group 1, kc->step = the rows' own counters): q [BB * q_tokens, heads, dp], row r * q_tokens + j
+// is token j of cache row r and sees the generated keys 0 .. kc->step[r] + j.  At most 16 query heads per kv head (check_multi)
+int launch_attn_decode_multi(const p2t_llama_config* c, const void* q, void* out, int64_t ld_out, const p2t_kv_cache* kc, int layer, float c_exp,
+                             int round_p, int use_mfma, int q_tokens, hipStream_t s);
+int check_multi(int q_tokens, int heads_per_kv, const char* who);
 // SwiGLU on the interleaved gate / up pre-activations gu [M, 2F], forward and backward (activations.hip)
 int launch_swiglu_from_gu(const void* gu, int64_t ld_gu, void* act, int64_t ld_act, int64_t M, int64_t F, int dtype, hipStream_t s);
 int launch_swiglu_gu_bwd(const void* gu, int64_t ld_gu, const void* d_act, int64_t ld_da, void* d_gu, int64_t ld_dgu, int64_t M, int64_t F, int dtype,

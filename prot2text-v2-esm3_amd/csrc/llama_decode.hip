@@ -11,6 +11,7 @@
 //     cache -- the same kernels read step[row * stride] with stride 1 where the lock-step entry points pass stride 0.  A finished row
 //     is frozen (it re-appends at its own index and does not advance).
 #include "common.h"
+#include "greedy_argmax.h"
 #include "kernels.h"
 
 namespace p2t {
@@ -37,14 +38,16 @@ __global__ void __launch_bounds__(256) rope_append_kernel(const float* __restric
                                                           const int32_t* __restrict__ prompt_len, const int32_t* __restrict__ step_ptr,
                                                           int step_stride, int group, T* __restrict__ qbuf, T* __restrict__ kg, T* __restrict__ vtg, int BB,
                                                           int nh, int nkv, int d, int dp, int G, float q_scale, int packed128,
-                                                          int round_first) {
+                                                          int round_first, int q_tokens) {
     const int lane = threadIdx.x & 63, heads = nh + 2 * nkv, half = d / 2;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= BB * heads) return;
-    const int bb = row / heads, hh = row - bb * heads;
-    const int step = min(max(step_ptr[(int64_t)bb * step_stride], 0), G - 1);      // stride 0: the shared counter, 1: row bb's own
+    // m: the projection's row (BB of them); bb: its cache row -- several tokens per row: token m % q_tokens of row m / q_tokens
+    const int m = row / heads, hh = row - m * heads, bb = q_tokens > 1 ? m / q_tokens : m;
+    // stride 0: the shared counter, 1: row bb's own (+ the token's place among the row's new ones)
+    const int step = min(max(step_ptr[(int64_t)bb * step_stride], 0) + (m - bb * q_tokens), G - 1);
     const int pos = prompt_len[bb / group] + step;
-    const float* src = qkv + (int64_t)bb * ldq + (int64_t)hh * d;
+    const float* src = qkv + (int64_t)m * ldq + (int64_t)hh * d;
     auto at = [&](int j) {
         int p = j;
         if (packed128) { const int blk = j >> 5; p = blk == 1 ? j + 32 : (blk == 2 ? j - 32 : j); }
@@ -75,7 +78,7 @@ __global__ void __launch_bounds__(256) rope_append_kernel(const float* __restric
             o1 = a1 * c - a2 * s;
             o2 = a2 * c + a1 * s;
         }
-        T* dst = is_q ? qbuf + ((int64_t)bb * nh + hh) * dp : kg + (((int64_t)bb * nkv + (hh - nh)) * G + step) * dp;
+        T* dst = is_q ? qbuf + ((int64_t)m * nh + hh) * dp : kg + (((int64_t)bb * nkv + (hh - nh)) * G + step) * dp;
         if (lane < half) { dst[lane] = from_f32<T>(o1); dst[lane + half] = from_f32<T>(o2); }
         for (int cc = d + lane; cc < dp; cc += 64) dst[cc] = from_f32<T>(0.f);
     } else {
@@ -90,42 +93,6 @@ __global__ void __launch_bounds__(256) rope_append_kernel(const float* __restric
 // ---------------------------------------------------------------------------------------------
 // torch.argmax semantics over the first V columns (lowest index among equal maxima), then HF's finished-row rule
 // (generation/utils.py, _sample: next = next * unfinished + pad * (1 - unfinished); a row finishes once it emits an eos id).
-// argmax of one logits row by a block of 1024 threads; thread 0 returns it (the other threads' value is their wave's or their own)
-template <typename T>
-__device__ __forceinline__ int greedy_argmax(const T* __restrict__ row, int64_t ld, int V) {
-    constexpr int PN = Piece<T>::N, kNone = 0x7fffffff;
-    __shared__ float bv[16];
-    __shared__ int bi[16];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    float best = -INFINITY;
-    int idx = kNone;
-    auto take = [&](float v, int c) {                   // ascending c per thread: a later equal value never replaces an earlier one
-        if (idx == kNone || v > best) { best = v; idx = c; }
-    };
-    const int Vv = (ld % PN == 0) ? V / PN * PN : 0;     // 16-byte pieces while the row pitch keeps them aligned
-    for (int c = tid * PN; c < Vv; c += 1024 * PN) {
-        float v[PN];
-        load_piece<T, PN>(row + c, v);
-#pragma unroll
-        for (int e = 0; e < PN; ++e) take(v[e], c + e);
-    }
-    for (int c = Vv + tid; c < V; c += 1024) take(to_f32(row[c]), c);
-    auto better = [](float v, int i, float bvv, int bii) { return i != kNone && (bii == kNone || v > bvv || (v == bvv && i < bii)); };
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float v = __shfl_xor(best, o, 64);
-        const int i2 = __shfl_xor(idx, o, 64);
-        if (better(v, i2, best, idx)) { best = v; idx = i2; }
-    }
-    if (lane == 0) { bv[w] = best; bi[w] = idx; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int ww = 1; ww < 16; ++ww)
-            if (better(bv[ww], bi[ww], best, idx)) { best = bv[ww]; idx = bi[ww]; }
-    }
-    return idx;
-}
-
 template <typename T>
 __global__ void __launch_bounds__(1024) greedy_select_kernel(const T* __restrict__ logits, int64_t ld, int V, const int64_t* __restrict__ eos,
                                                              int n_eos, int64_t pad, int32_t* __restrict__ finished,
@@ -216,7 +183,8 @@ void rope_append_t(const float* qkv, int64_t ldq, const SkinnyRope& ra, const p2
                    hipStream_t s) {
     const unsigned grid = (unsigned)ceil_div((int64_t)BB * (ra.nh + 2 * ra.nkv), 4);
     rope_append_kernel<T><<<grid, 256, 0, s>>>(qkv, ldq, ra.inv_freq, L.q_norm_w, L.k_norm_w, eps, ra.prompt_len, ra.step, ra.step_stride, ra.group, (T*)ra.q,
-                                               (T*)ra.k, (T*)ra.vt, BB, ra.nh, ra.nkv, ra.d, dp, ra.G, ra.q_scale, ra.d == 128 && !L.q_norm_w, round_first);
+                                               (T*)ra.k, (T*)ra.vt, BB, ra.nh, ra.nkv, ra.d, dp, ra.G, ra.q_scale, ra.d == 128 && !L.q_norm_w, round_first,
+                                               ra.q_tokens);
 }
 int launch_rope_append(const float* qkv, int64_t ldq, const SkinnyRope& ra, const p2t_llama_layer& L, float eps, int BB, int dp, int round_first, int dt,
                        hipStream_t s) {
@@ -376,6 +344,7 @@ struct StepCall {
     void* workspace = nullptr; size_t workspace_bytes = 0;
     int32_t* row_step = nullptr; const int32_t* frozen = nullptr;       // per-row counters (p2t_llama_decode_step_rows)
     const uint8_t* ancestry = nullptr;                                  // the beam group's ancestry table (p2t_llama_decode_step_beams)
+    int q_tokens = 0;                                                   // tokens per row, row_step read only (p2t_llama_decode_step_multi); 0: one, as ever
     p2t_stream stream = nullptr;
 };
 // the arguments that all four doors have, under the same names
@@ -390,11 +359,11 @@ struct StepCall {
 struct StepWeight { const void* w; int64_t ld; const uint8_t* row_scale; const void* stream; const void* mx; const uint8_t* mx_bs; };
 
 // what the MXFP4 form of the projections asks of the call
-static int check_mx(const p2t_llama_config* c, const p2t_kv_cache* cache, const p2t_llama_layer_mxfp4* mx, const char* who) {
+static int check_mx(const p2t_llama_config* c, const p2t_kv_cache* cache, const p2t_llama_layer_mxfp4* mx, const char* who, int q_tokens) {
     P2T_REQUIRE(c && cache, "%s: null argument", who);
     P2T_REQUIRE(c->gemm_fp8 && c->dtype == P2T_BF16, "%s: mx_layers need a gemm_fp8 configuration with bf16 activations", who);
-    P2T_REQUIRE((int64_t)cache->B0 * cache->group <= 64, "%s: mx_layers serve at most 64 rows (got %lld): beyond that the e4m3 weights serve", who,
-                (long long)cache->B0 * cache->group);
+    P2T_REQUIRE((int64_t)cache->B0 * cache->group * q_tokens <= 64, "%s: mx_layers serve at most 64 rows (got %lld): beyond that the e4m3 weights serve", who,
+                (long long)cache->B0 * cache->group * q_tokens);
     for (int l = 1; l < c->n_layers; ++l) P2T_REQUIRE(!mx[l].stream_order == !mx[0].stream_order, "%s: layers differ in stream_order", who);
     return P2T_OK;
 }
@@ -407,7 +376,12 @@ static int check_step(const StepCall& a, p2t_kv_cache* kc, DecodeBuffers* b, uin
     const char* who = a.who;
     const p2t_llama_config* c = a.c;
     P2T_REQUIRE(!(a.ws_layers && a.mx), "%s: w_stream and mx_layers are two forms of the same projections: pass one", who);
-    if (a.mx) P2T_TRY(check_mx(c, a.cache, a.mx, who));
+    const int Q = a.q_tokens ? a.q_tokens : 1;
+    if (a.q_tokens) {                                    // before anything multiplies by it
+        P2T_REQUIRE(c && a.cache, "%s: null argument", who);
+        P2T_TRY(check_multi(a.q_tokens, c->kv_heads > 0 ? c->heads / c->kv_heads : 0, who));
+    }
+    if (a.mx) P2T_TRY(check_mx(c, a.cache, a.mx, who, Q));
     P2T_REQUIRE(c && a.w && a.w->layers && a.w->final_norm_w && (a.lm_head || a.head_q) && a.x_in && a.logits && a.workspace, "%s: null argument", who);
     if (a.cache) *kc = *a.cache;
     if (a.cache && a.row_step) kc->step = a.row_step;
@@ -418,7 +392,11 @@ static int check_step(const StepCall& a, p2t_kv_cache* kc, DecodeBuffers* b, uin
     }
     if (a.ancestry) P2T_TRY(check_ancestry(a.ancestry, kc->group, c->heads / c->kv_heads, who));
     P2T_REQUIRE(!c->gemm_fp8 || c->dtype == P2T_BF16, "%s: gemm_fp8 needs bf16 activations (dtype = P2T_BF16)", who);
-    const int BB = kc->B0 * kc->group;
+    const int BB = kc->B0 * kc->group * Q;               // the step's rows: Q tokens per cache row
+    if (a.q_tokens && BB > 64) {
+        set_error("%s: %d rows x %d tokens exceed the 64 rows of one weight-streaming step", who, kc->B0, Q);
+        return P2T_ERR_UNSUPPORTED;
+    }
     const int64_t H = c->hidden, Hp = round_up(H, 64);
     P2T_REQUIRE((a.head_q || a.lm_head_preshuffled || a.ld_head >= Hp) && a.ld_logits >= c->vocab, "%s: ld_head %lld < %lld or ld_logits %lld < vocab", who,
                 (long long)a.ld_head, (long long)Hp, (long long)a.ld_logits);
@@ -459,7 +437,8 @@ static int decode_step(const StepCall& a) {
     const p2t_llama_weights* w = a.w;
     hipStream_t s = (hipStream_t)a.stream;
     const bool fp8 = c->gemm_fp8, fuse_rope = !(a.flags & P2T_DECODE_NO_ROPE_FUSION);
-    const int sstride = a.row_step ? 1 : 0, BB = kc.B0 * kc.group, dt = c->dtype;
+    const int Q = a.q_tokens ? a.q_tokens : 1;           // tokens per cache row: BB rows of activations, BB / Q rows of cache
+    const int sstride = a.row_step ? 1 : 0, BB = kc.B0 * kc.group * Q, dt = c->dtype;
     const int64_t M = BB, H = c->hidden, F = c->ffn, Hp = round_up(H, 64), Fp = round_up(F, 64);
     const int d = c->head_dim, dp = head_dim_padded(d), nh = c->heads, nkv = c->kv_heads;
     const int64_t NQKV = (int64_t)(nh + 2 * nkv) * d, QO = round_up((int64_t)nh * d, 64);
@@ -510,7 +489,7 @@ static int decode_step(const StepCall& a) {
         if (epi == P2T_EPI_STORE_F32) g.n_zero = (int)N;
         return gemm_nt(g, s);
     };
-    const size_t per_g = (size_t)BB * nkv * kc.G * dp * dtype_size(dt);        // one layer of the generated segment, bytes
+    const size_t per_g = (size_t)(BB / Q) * nkv * kc.G * dp * dtype_size(dt);  // one layer of the generated segment, bytes
     for (int l = 0; l < c->n_layers; ++l) {
         const p2t_llama_layer& L = w->layers[l];
         const p2t_llama_layer_stream S = stream_w ? a.ws_layers[l] : p2t_llama_layer_stream{};
@@ -521,7 +500,7 @@ static int decode_step(const StepCall& a) {
         const int fused_prefill = !L.q_norm_w && (d == 64 || d == 128);
         SkinnyRope ra;                                   // where this layer's rotation reads its position and appends
         ra.inv_freq = inv_freq; ra.prompt_len = kc.prompt_len; ra.step = kc.step; ra.step_stride = sstride; ra.group = kc.group;
-        ra.nh = nh; ra.nkv = nkv; ra.d = d; ra.G = kc.G; ra.q_scale = q_fold;
+        ra.nh = nh; ra.nkv = nkv; ra.d = d; ra.G = kc.G; ra.q_scale = q_fold; ra.q_tokens = Q;
         ra.q = b.qb; ra.k = (char*)kc.k_gen + per_g * l; ra.vt = (char*)kc.vt_gen + per_g * l;
         P2T_TRY(norm_into_h(L.ln1_w));
         int r = P2T_ERR_UNSUPPORTED;
@@ -532,6 +511,7 @@ static int decode_step(const StepCall& a) {
         }
         P2T_TRY(r);
         if (a.ancestry) P2T_TRY(launch_attn_decode_beams(c, b.qb, b.ao, QO, &kc, l, c_exp, dt == P2T_BF16, 1, a.ancestry, s));
+        else if (a.q_tokens) P2T_TRY(launch_attn_decode_multi(c, b.qb, b.ao, QO, &kc, l, c_exp, dt == P2T_BF16, 1, Q, s));
         else P2T_TRY(launch_attn_decode(c, b.qb, b.ao, QO, &kc, l, c_exp, dt == P2T_BF16, 1, sstride, s));
         P2T_TRY(quantise_into(ao, b.ao, QO, (int64_t)nh * d));
         P2T_TRY(project(ao, Wo, H, b.x, H, P2T_F32, P2T_EPI_RESID, nullptr));
@@ -547,6 +527,7 @@ static int decode_step(const StepCall& a) {
         P2T_TRY(launch_rmsnorm_few_rows(b.x, H, w->final_norm_w, c->rms_norm_eps, b.h, Hp, M, H, dt, s));
         P2T_TRY(project(Operand{b.h, Hp, nullptr}, Whead, c->vocab, a.logits, a.ld_logits, dt, P2T_EPI_STORE, nullptr));
     }
+    if (a.q_tokens) return P2T_OK;                       // the counters are the verify kernel's to advance (p2t_lookup_verify_rows)
     return launch_advance(kc.step, sstride, a.frozen, BB, s);
 }
 
@@ -602,6 +583,20 @@ extern "C" int p2t_llama_decode_step_beams(const p2t_llama_config* c, const p2t_
     P2T_REQUIRE(ancestry, "p2t_llama_decode_step_beams: null ancestry table");
     P2T_STEP_CALL(a, "p2t_llama_decode_step_beams");
     a.ws_layers = ws_layers; a.mx = mx_layers; a.head_q = head_q; a.ancestry = ancestry;
+    return decode_step(a);
+}
+
+// p2t_llama_decode_step_rows for q_tokens tokens per row (include/p2t_hip.h): the launches of a step of B0 * q_tokens rows, the rotation
+// and the attention indexed by (row, token); row_step is read only.
+extern "C" int p2t_llama_decode_step_multi(const p2t_llama_config* c, const p2t_llama_weights* w, const p2t_llama_layer_stream* ws_layers,
+                                           const p2t_llama_layer_mxfp4* mx_layers, const void* lm_head, int64_t ld_head, int lm_head_preshuffled,
+                                           const p2t_lm_head_q* head_q, const p2t_kv_cache* cache, const float* x_in, void* logits, int64_t ld_logits,
+                                           int flags, void* workspace, size_t workspace_bytes, const int32_t* row_step, int q_tokens,
+                                           p2t_stream stream) {
+    P2T_REQUIRE(row_step, "p2t_llama_decode_step_multi: null row_step");
+    P2T_REQUIRE(q_tokens >= 1, "p2t_llama_decode_step_multi: q_tokens %d outside 1 .. 64", q_tokens);
+    P2T_STEP_CALL(a, "p2t_llama_decode_step_multi");
+    a.ws_layers = ws_layers; a.mx = mx_layers; a.head_q = head_q; a.row_step = const_cast<int32_t*>(row_step); a.q_tokens = q_tokens;
     return decode_step(a);
 }
 

@@ -218,6 +218,11 @@ SIGNATURES = {
     "p2t_attention_decode_beams": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp, i64, vp, vp, vp, vp]),
     "p2t_llama_decode_step_beams": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), C.POINTER(LlamaLayerStreamC), C.POINTER(LlamaLayerMxfp4C), vp,
                                     i64, i32, C.POINTER(LmHeadQC), C.POINTER(KvCacheC), vp, vp, i64, i32, vp, sz, vp, vp]),
+    "p2t_lookup_draft_rows": (i32, [vp, i64, vp, vp, i32, i32, i32, i32, i64, vp, vp, vp]),
+    "p2t_attention_decode_multi": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, vp, i64, vp, vp, i32, vp]),
+    "p2t_llama_decode_step_multi": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), C.POINTER(LlamaLayerStreamC), C.POINTER(LlamaLayerMxfp4C), vp,
+                                    i64, i32, C.POINTER(LmHeadQC), C.POINTER(KvCacheC), vp, vp, i64, i32, vp, sz, vp, i32, vp]),
+    "p2t_lookup_verify_rows": (i32, [vp, i32, i64, i32, i32, i32, vp, vp, vp, i32, i64, vp, vp, vp, i64, vp, vp, i32, vp, vp, vp]),
     "p2t_llama_tape_bytes":(sz, [C.POINTER(LlamaConfigC), i32, i32]),
     "p2t_llama_train_workspace_bytes": (sz, [C.POINTER(LlamaConfigC), i32, i32]),
     "p2t_llama_train_forward": (i32, [C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), vp, vp, i32, i32, vp, vp, sz, vp, sz, vp]),

@@ -43,9 +43,10 @@ from .ops import ptr, round_up, stream
 class GenerateOutput:
     """`return_dict_in_generate=True`: the fields of HF's GenerateDecoderOnlyOutput / GenerateBeamDecoderOnlyOutput this path fills."""
 
-    def __init__(self, sequences, scores=None, logits=None, sequences_scores=None, beam_indices=None):
+    def __init__(self, sequences, scores=None, logits=None, sequences_scores=None, beam_indices=None, lookup_stats=None):
         self.sequences, self.scores, self.logits = sequences, scores, logits
         self.sequences_scores, self.beam_indices = sequences_scores, beam_indices
+        self.lookup_stats = lookup_stats                   # prompt_lookup_num_tokens: i64 [batch, 3] = (verify steps, drafted, accepted) per row
         self.past_key_values = None
 
     def __getitem__(self, k):
@@ -329,12 +330,15 @@ class PackedPrompts:
 
 
 class DecodeEngine:
-    """Cache + buffers of ONE generate() call: B0 prompts, `group` rows per prompt (beams), capacities Tp / G (multiples of 64)."""
+    """Cache + buffers of ONE generate() call: B0 prompts, `group` rows per prompt (beams), capacities Tp / G (multiples of 64).
+    `step_rows` (None: B0 * group): the rows a decode step carries where that is more than the cache's -- several tokens per row
+    (lookup.LookupEngine): the step's x / logits / workspace and the row limits of the weight forms are sized by it."""
 
     def __init__(self, decoder, B0: int, group: int, T: int, max_new_tokens: int, stream_copy: bool = True, fuse_rope: bool = True,
                  processors: Optional[dict] = None, eos_ids: Sequence[int] = (), prompt_kv_dtype: Optional[str] = None,
-                 lm_head_dtype: Optional[str] = None, beam_cache: Optional[str] = None):
+                 lm_head_dtype: Optional[str] = None, beam_cache: Optional[str] = None, step_rows: Optional[int] = None):
         m, s = decoder.model, decoder.spec
+        rows = B0 * group if step_rows is None else int(step_rows)
         if beam_cache not in (None, "ancestry"):
             raise ValueError(f"beam_cache must be None or 'ancestry' (got {beam_cache!r})")
         if beam_cache is not None and not (2 <= group <= BEAMS_MAX and s.num_attention_heads // s.num_key_value_heads <= 16):
@@ -348,8 +352,8 @@ class DecodeEngine:
             raise ValueError(f"lm_head_dtype must be None, 'fp8' or 'mxfp4' (got {lm_head_dtype!r})")
         if lm_head_dtype is not None and m.dtype != torch.bfloat16:
             raise ValueError(f"lm_head_dtype={lm_head_dtype!r} (the quantised LM head of the decode step) serves bf16 models only")
-        if lm_head_dtype is not None and B0 * group > 64 and s.vocab_size % 16:
-            raise ValueError(f"lm_head_dtype={lm_head_dtype!r} with more than 64 rows (got {B0 * group}) runs the general fp8 GEMM, which serves a "
+        if lm_head_dtype is not None and rows > 64 and s.vocab_size % 16:
+            raise ValueError(f"lm_head_dtype={lm_head_dtype!r} with more than 64 rows (got {rows}) runs the general fp8 GEMM, which serves a "
                              f"vocabulary that is a multiple of 16 only (got {s.vocab_size})")
         self.flags = 0 if fuse_rope else 1          # P2T_DECODE_NO_ROPE_FUSION
         if s.hidden_size % 64:
@@ -378,22 +382,22 @@ class DecodeEngine:
         self.lens = torch.zeros((B0,), dtype=torch.int32, device=self.dev)
         self.step = torch.zeros((1,), dtype=torch.int32, device=self.dev)
         self.ld_logits = round_up(s.vocab_size, 64)
-        self.logits = torch.zeros((self.BB, self.ld_logits), dtype=self.dtype, device=self.dev)
-        self.x = torch.zeros((self.BB, s.hidden_size), dtype=torch.float32, device=self.dev)
+        self.logits = torch.zeros((rows, self.ld_logits), dtype=self.dtype, device=self.dev)
+        self.x = torch.zeros((rows, s.hidden_size), dtype=torch.float32, device=self.dev)
         self.next_tokens = torch.zeros((self.BB,), dtype=torch.int64, device=self.dev)
         self.finished = torch.zeros((self.BB,), dtype=torch.int32, device=self.dev)
         self.sample_flags = torch.zeros((1,), dtype=torch.int32, device=self.dev)      # p2t_sample_select ORs into it (bit 0: table full)
         self.out_tokens = torch.zeros((self.BB, self.G), dtype=torch.int64, device=self.dev)
-        self.ws = torch.empty((call("p2t_llama_decode_workspace_bytes", C.byref(self.e["cfg"]), self.BB, self.Tp, self.G),), dtype=torch.uint8,
+        self.ws = torch.empty((call("p2t_llama_decode_workspace_bytes", C.byref(self.e["cfg"]), rows, self.Tp, self.G),), dtype=torch.uint8,
                               device=self.dev)
         self.lm_head = decoder._lm_head_padded()
         # the stream-order copies are read by the skinny GEMMs only (<= 64 rows): beyond that every projection and the LM head
         # run on the row-major weights (the LM head had no row-major fallback and returned wrong logits)
-        self.stream = stream_weights(decoder, lm_head=lm_head_dtype is None) if (stream_copy and self.dtype == torch.bfloat16 and B0 * group <= 64) else None
+        self.stream = stream_weights(decoder, lm_head=lm_head_dtype is None) if (stream_copy and self.dtype == torch.bfloat16 and rows <= 64) else None
         # "mxfp4" decoders: up to 64 rows step on the 4-bit weights (their stream copies, or row-major under stream_copy=False);
         # beyond that the e4m3 copies of the same values serve, as in "fp8" mode
         self.mx = None                                                    # (host array of p2t_llama_layer_mxfp4, what it points to)
-        if m.gemm_mxfp4 and B0 * group <= 64:
+        if m.gemm_mxfp4 and rows <= 64:
             self.mx = (self.stream["layers"], self.stream["keep"]) if self.stream else mxfp4_layers(self.e, False)
         # lm_head_dtype: the final RMSNorm + LM head of the prefill's first token AND of every step on ONE quantised head (p2t_lm_head_q);
         # its stream-order copy under the bf16 copies' condition (stream_copy, at most 64 rows), row-major e4m3 codes beyond 64 rows.
@@ -401,9 +405,9 @@ class DecodeEngine:
         self.head_q = self.head_q_first = None
         if lm_head_dtype is not None:
             st = lm_head_q(decoder, lm_head_dtype)
-            self.head_q = head_q_struct(decoder, st, stream_copy and self.BB <= 64, self.BB)
+            self.head_q = head_q_struct(decoder, st, stream_copy and rows <= 64, rows)
             self.head_q_first = head_q_struct(decoder, st, stream_copy and B0 <= 64, B0)      # the prefill's B0 rows
-            self.ws = torch.empty((self.ws.numel() + call("p2t_lm_head_q_workspace_bytes", self.BB, s.hidden_size),), dtype=torch.uint8, device=self.dev)
+            self.ws = torch.empty((self.ws.numel() + call("p2t_lm_head_q_workspace_bytes", rows, s.hidden_size),), dtype=torch.uint8, device=self.dev)
         self._cache_struct()
         self.processors = processors                                      # _processor_args' settings, or None: nothing allocated, nothing launched
         if processors is not None:
@@ -596,7 +600,8 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
              repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
              bad_words_ids: Optional[list] = None, suppress_tokens=None, prompt_kv_dtype: Optional[str] = None,
              lm_head_dtype: Optional[str] = None, beam_cache: Optional[str] = None, prefill: Optional[str] = None,
-             pack_tokens: Optional[int] = None, **unused):
+             pack_tokens: Optional[int] = None, prompt_lookup_num_tokens: Optional[int] = None,
+             max_matching_ngram_size: Optional[int] = None, **unused):
     """`LlamaForCausalLM.generate` for prompts given as embeddings (or ids): greedy, sampling (temperature / top-k / top-p) and beam
     search with length penalty.  Returns the new token ids i64 [batch * num_return_sequences, n] (or a GenerateOutput).
 
@@ -657,7 +662,18 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     segment changes, so every decoding mode, `prompt_kv_dtype` and `lm_head_dtype` run unchanged behind it; the first token's logits
     differ from the padded path's by rounding (another summation order, and the rotation after the projection instead of inside it).
     ValueError for another value, for `pack_tokens` without it, for more than PACK_PROMPTS_MAX prompts and on set_gemm_dtype("fp8") /
-    ("mxfp4") models: the packed prefill runs the model-dtype GEMMs."""
+    ("mxfp4") models: the packed prefill runs the model-dtype GEMMs.
+
+    `prompt_lookup_num_tokens=k` (opt-in; HF's keyword, 1 .. 7; None: off, nothing changes) is HF's prompt-lookup decoding for greedy
+    decoding: every step carries k + 1 tokens per row -- the token chosen last and a draft of up to k tokens that follow the EARLIEST
+    earlier occurrence of the row's trailing n-gram in its own generated text (`max_matching_ngram_size=n`, 1 .. 4, None: HF's 2; longest
+    n first) -- through ONE decode step (p2t_llama_decode_step_multi), keeps the longest prefix of the draft the model agrees with plus
+    the model's own next token (p2t_lookup_verify_rows), and so returns greedy decoding's tokens in fewer steps (lookup.LookupEngine).
+    `return_dict_in_generate` adds `lookup_stats`, i64 [batch, 3] = (verify steps, drafted tokens, accepted tokens) per row.
+    NotImplementedError with sampling, beams, any logits processor or output_scores; ValueError for k or n outside its range, for
+    batch * (k + 1) > 64 and for more than 16 query heads per kv head."""
+    if max_matching_ngram_size is not None and prompt_lookup_num_tokens is None:
+        raise ValueError("generate: max_matching_ngram_size is the n-gram length of prompt_lookup_num_tokens")
     if prefill not in (None, "padded", "packed"):
         raise ValueError(f"generate: prefill = {prefill!r}: None, 'padded' or 'packed'")
     if pack_tokens is not None and prefill != "packed":
@@ -704,6 +720,13 @@ def generate(decoder, inputs_embeds: Optional[torch.Tensor] = None, attention_ma
     proc = _processor_args(V, eos_ids, repetition_penalty, no_repeat_ngram_size, min_new_tokens, bad_words_ids, suppress_tokens)
     if num_beams < 1 or num_return_sequences < 1 or num_return_sequences > num_beams and num_beams > 1:
         raise ValueError("num_beams >= 1 and 1 <= num_return_sequences <= num_beams")
+    if prompt_lookup_num_tokens is not None:
+        from . import lookup
+        lookup.refuse_unsupported(num_beams, do_sample, proc, output_scores, num_return_sequences)
+        return lookup.generate_lookup(decoder, inputs_embeds, attention_mask, SimpleNamespace(
+            k=prompt_lookup_num_tokens, n=max_matching_ngram_size, max_new_tokens=max_new_tokens, eos_ids=eos_ids, pad_id=int(pad_token_id),
+            return_dict=return_dict_in_generate, output_logits=output_logits, use_graph=use_graph, sync_every=sync_every, stream_copy=stream_copy,
+            fuse_rope=fuse_rope, prompt_kv_dtype=prompt_kv_dtype, lm_head_dtype=lm_head_dtype, prefill=prefill, pack_tokens=pack_tokens))
     if num_beams > 1 and proc is not None:
         if do_sample:
             raise NotImplementedError("generate(): repetition_penalty / no_repeat_ngram_size / min_new_tokens / bad_words_ids / suppress_tokens are not "

@@ -50,7 +50,12 @@ whose protein lengths are drawn once from bench.py's lognormal(5.75, 0.6) clippe
 the longest as the collater does (`uniform`: 1024 residues each -- packing can win nothing there and pays for the unfused rotation).
 Interleaved in one process, three runs each, medians: (a) the decoder's share alone (compact + prefill | pack + prefill_packed, first-token
 head included), (b) the whole prompt phase with the still-padded ESM2 + adapter, (c) a whole generate of N tokens; and padded / valid
-tokens, the bound on (a)."""
+tokens, the bound on (a).
+python tools/generate_bench.py 8 [N] lookup [fp8 | mxfp4] [kv8]: prompt-lookup decoding (`prompt_lookup_num_tokens`, p2t_hip/lookup.py): ms per
+multi-token step at 1 / 2 / 4 / 8 prompts x k = 1 / 3 / 7 next to the one-token step at the same prompts and at 32 rows, one process,
+interleaved, three runs each under graph replay, the break-even acceptance per step, and the random-weight run's observed tokens per
+step (labelled synthetic)."""
+import ctypes as C
 import os
 import sys
 import time
@@ -62,6 +67,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "prot2text-v2-esm3_amd"))
 import p2t_hip as P                                             # noqa: E402
 from p2t_hip import generation, specs, synth                    # noqa: E402
+from p2t_hip._lib import call                                   # noqa: E402
+from p2t_hip.ops import ptr, stream                             # noqa: E402
 
 
 def sampler_alone(B: int, V: int, dev, iters: int = 200) -> float:
@@ -474,6 +481,80 @@ def continuous_mode(model, kw, slots: int, Tnew: int, T: int, gemm_dtype: str, e
         print(f"{tag}: {slots} rows, counters 0 .. 110, graph replay, {name}: median {np.median(r):.3f} ms/step (min {min(r):.3f}, max {max(r):.3f}; 3 runs)", flush=True)
 
 
+def lookup_mode(model, kw, B: int, N: int, T: int, gemm_dtype: str, extra: dict):
+    """[B] [N] lookup [fp8 | mxfp4] [kv8]: prompt-lookup decoding (generate(prompt_lookup_num_tokens=k)) at 1 / 2 / 4 / 8 prompts x k = 1 / 3 / 7.
+    (1) the step alone, one process, interleaved, three runs each under graph replay: {embed, p2t_llama_decode_step_multi} of rows x (k + 1)
+    tokens next to {embed, p2t_llama_decode_step_rows} of the same rows (and of 32 rows), every counter held at 64 generated tokens (the rows
+    are marked finished: nothing advances, the work is that of live rows) -> the break-even acceptance t_multi / t_plain - 1 tokens per step;
+    (2) generate with the switch on this random-weight model: tokens per verify step as observed -- SYNTHETIC: random-weight greedy text
+    loops, so this says nothing about real descriptions."""
+    from p2t_hip.continuous import ContinuousEngine
+    from p2t_hip.lookup import LookupEngine
+    dec = model.llama_decoder
+    with torch.no_grad():
+        emb, mask = model(input_ids=kw["inputs"], attention_mask=kw["attention_mask"], protein_input_ids=kw["protein_input_ids"],
+                          protein_attention_mask=kw["protein_attention_mask"], return_decoder_inputs=True)
+    pad, S = kw["pad_token_id"], 64
+    tag = f"generate cfg3{' ' + gemm_dtype + ' GEMMs' if gemm_dtype != 'model' else ''}{''.join(' ' + k + '=' + str(v) for k, v in extra.items())} lookup"
+    rep = lambda t, rows: t.repeat((rows + t.shape[0] - 1) // t.shape[0], *([1] * (t.dim() - 1)))[:rows].contiguous()
+    graphs, keep = {}, []
+    for rows in (1, 2, 4, 8, 32):
+        e = ContinuousEngine(dec, rows, T, 256, [], pad, use_graph=False, **extra)
+        x, m = rep(emb, rows), rep(mask, rows)
+        e.load(list(range(rows)), [(x[b], m[b]) for b in range(rows)], [256] * rows)
+        e.row_step.fill_(S)
+        e.finished.fill_(2)
+        tok = torch.full((rows,), 11, dtype=torch.int64, device=emb.device)
+        graphs[(rows, 0)] = (e, tok, lambda e=e, tok=tok: (e.feed(tok), e._step_rows(frozen=True)))
+    for rows in (1, 2, 4, 8):
+        for k in (1, 3, 7):
+            e = LookupEngine(dec, rows, T, 256, k, 2, [], pad, use_graph=False, **extra)
+            e.first(e.prompt(rep(emb, rows), rep(mask, rows)))
+            e.row_step.fill_(S)
+            e.finished.fill_(2)
+            e.step_tokens.fill_(11)
+            graphs[(rows, k)] = (e, None, lambda e=e: (call("p2t_llama_embed_tokens", C.byref(e.e["cfg"]), C.byref(e.e["w"]), ptr(e.step_tokens),
+                                                            e.BB * e.Q, ptr(e.x), stream()), e.step_multi()))
+    for key, (e, tok, go) in graphs.items():
+        go(); go()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            go()
+        graphs[key] = (e, tok, g)
+    ms = {key: [] for key in graphs}
+    for _ in range(3):
+        for key, (_, _, g) in graphs.items():
+            ms[key].append(_events(g.replay, 100) / 1e3)
+    med = {key: float(np.median(r)) for key, r in ms.items()}
+    for (rows, k), r in ms.items():
+        if k == 0:
+            print(f"{tag}: {rows} rows, {T}+{S + 1} keys, graph replay, one-token step (p2t_llama_decode_step_rows): median {med[(rows, 0)]:.3f} ms/step "
+                  f"(min {min(r):.3f}, max {max(r):.3f}; 3 runs)", flush=True)
+    for (rows, k), r in ms.items():
+        if k:
+            print(f"{tag}: {rows} rows x {k + 1} tokens (k = {k}), graph replay, p2t_llama_decode_step_multi: median {med[(rows, k)]:.3f} ms/step (min {min(r):.3f}, "
+                  f"max {max(r):.3f}; 3 runs) = {med[(rows, k)] / med[(rows, 0)]:.3f} x the one-token step, {med[(rows, k)] / ((k + 1) * med[(rows, 0)]):.3f} x "
+                  f"{k + 1} of them; break-even at {med[(rows, k)] / med[(rows, 0)] - 1:.3f} accepted tokens per step", flush=True)
+    print(f"{tag}: 8 rows x 4 tokens {med[(8, 3)]:.3f} ms against the 32-row one-token step {med[(32, 0)]:.3f} ms", flush=True)
+    del graphs
+    torch.cuda.empty_cache()
+    # (2) the whole call, random weights: SYNTHETIC acceptance
+    for rows in (1, 8):
+        sub = {k2: (v[:rows] if isinstance(v, torch.Tensor) else v) for k2, v in kw.items()}
+        for k in (0, 3, 7):
+            over = dict(prompt_lookup_num_tokens=k) if k else {}
+            model.generate(**{**sub, **extra, **over, "max_new_tokens": 6})
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = model.generate(**{**sub, **extra, **over}, return_dict_in_generate=True)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            st = out.lookup_stats
+            note = (f"verify steps per row {st[:, 0].tolist()}, tokens per step {((N - 1) / st[:, 0].float()).mean().item():.2f} (SYNTHETIC: random weights)"
+                    if st is not None else "one token per step")
+            print(f"{tag}: generate, {rows} prompts, {N} new tokens, k = {k}: {dt * 1e3:.0f} ms wall with the prompt phase; {note}", flush=True)
+
+
 CHOICE_LEGS = {"sample": dict(do_sample=True, top_k=50, top_p=0.9, temperature=0.7, seed=1),
                # every processor on; the eos ids end no row: they are banned for the first tokens by min_new_tokens and suppressed throughout
                "process": dict(repetition_penalty=1.3, no_repeat_ngram_size=3, min_new_tokens=8, eos_token_id=[128001, 128009],
@@ -638,7 +719,8 @@ def main():
     kv8 = "kv8" in sys.argv[3:5] and not head
     continuous = len(sys.argv) > 3 and sys.argv[3] == "continuous"   # [slots] [Tnew] continuous [fp8 | mxfp4] [kv8] [head fp8 | head mxfp4]
     ragged = len(sys.argv) > 3 and sys.argv[3] == "ragged"           # [B] [N] ragged [uniform]
-    beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample and not process and sys.argv[3] not in ("kv8", "head", "continuous", "ragged") else 1
+    lookup = len(sys.argv) > 3 and sys.argv[3] == "lookup"           # [B >= 8] [N] lookup [fp8 | mxfp4] [kv8]
+    beams = int(sys.argv[3]) if len(sys.argv) > 3 and not sample and not process and sys.argv[3] not in ("kv8", "head", "continuous", "ragged", "lookup") else 1
     gemm_dtype = sys.argv[4] if len(sys.argv) > 4 and sys.argv[4] in ("fp8", "mxfp4") else "model"
     cont_extra = {}
     choice_leg = None
@@ -650,6 +732,12 @@ def main():
             cont_extra["prompt_kv_dtype"] = "fp8"
         if "head" in after:
             cont_extra["lm_head_dtype"] = after[after.index("head") + 1]
+        head = kv8 = False
+    if lookup:
+        after = sys.argv[4:]
+        gemm_dtype = after[0] if after and after[0] in ("fp8", "mxfp4") else "model"
+        if "kv8" in after:
+            cont_extra["prompt_kv_dtype"] = "fp8"
         head = kv8 = False
     if kv8:                                                      # [B] [N] [beams] kv8 [fp8 | mxfp4]
         after = sys.argv[sys.argv.index("kv8") + 1:]
@@ -688,6 +776,8 @@ def main():
     t = lambda a: torch.from_numpy(a).to(dev)
     kw = dict(inputs=t(ids), attention_mask=torch.ones((B, T), dtype=torch.int64, device=dev), protein_input_ids=t(pid),
               protein_attention_mask=t(pmask), max_new_tokens=N, eos_token_id=None, pad_token_id=128002, do_sample=False, num_beams=beams)
+    if lookup:
+        return lookup_mode(model, kw, B, N, T, gemm_dtype, cont_extra)
     if continuous and choice_leg:
         return continuous_choice_mode(model, kw, B, N, T, choice_leg)
     if continuous:

@@ -4,6 +4,8 @@ cfg-3 towers, attention, norms.  Usage: python tools/microbench.py [gemm] [attn]
 `attn_decode` [m8] [m32]: the decode step's attention alone over the bf16 and the fp8 prompt segment of the KV cache.
 `attn_decode beams`: the attention of a beam group alone, the (row, kv head) kernel against the (prompt, kv head) kernel that reads an ancestry
 table, 8 x 4 and 32 x 4 beams, bf16 and fp8 prompt segment, 33 and 250 generated keys; then p2t_kv_reorder against p2t_kv_ancestry_update.
+`attn_decode multi`: the attention of a step of Q tokens per row alone (p2t_attention_decode_multi, prompt-lookup decoding), 1 / 2 / 4 / 8 rows x
+Q = 2 / 4 / 8, bf16 and fp8 prompt segment, against Q launches of p2t_attention_decode_rows and against one.
 `choice_rows` [m8] [m32]: the per-row choice kernels of continuous batching alone (p2t_sample_select_rows, p2t_logits_process_rows) on
 [rows, 128256] bf16 logits next to their lock-step twins, with no row and with half of the rows finished (the per-row kernels leave a
 finished row before they read it; the lock-step ones do its whole work).
@@ -384,6 +386,52 @@ def bench_attn_decode_beams():
         print(f"beam maintenance at {S} generated tokens, {BB} rows x {L} layers: p2t_kv_reorder {t_copy:.1f} us, p2t_kv_ancestry_update {t_tab:.1f} us", flush=True)
 
 
+def bench_attn_decode_multi():
+    """`attn_decode multi`: p2t_attention_decode_multi alone at Llama-3.1-8B sizes (8 kv heads x 4 query heads x head_dim 128: 4 queries per
+    block) over 1088 prompt keys + 65 .. generated ones, next to Q launches of p2t_attention_decode_rows on the same cache with the counters
+    at s + j (what Q one-token steps run) and to ONE such launch (what a one-token step runs), alternating on a ring of cache copies."""
+    import numpy as np
+    from p2t_hip.ops import ptr, stream
+    nh, nkv, d, T, S = 32, 8, 128, 1088, 64
+    Tp, G, copies, rounds, n = ops.round_up(T, 64), 128, 24, 5, 48
+    u8 = lambda *s: torch.empty(s, dtype=torch.uint8, device=dev)
+    for B in (1, 2, 4, 8):
+        kp, vtp = [rand((B, nkv, Tp, d), scale=0.5) for _ in range(copies)], [rand((B, nkv, d, Tp), scale=0.5) for _ in range(copies)]
+        k8, v8, ks, vs = [], [], [], []
+        for c in range(copies):
+            k8.append(u8(B, nkv, Tp, d)); v8.append(u8(B, nkv, d, Tp)); ks.append(u8(B, nkv, Tp)); vs.append(u8(B, nkv, Tp))
+            _lib.call("p2t_kv_quant_store", ptr(kp[c]), ptr(vtp[c].transpose(2, 3).contiguous()), B, nkv, Tp, d, Tp, ptr(k8[c]), ptr(v8[c]), ptr(ks[c]),
+                      ptr(vs[c]), stream())
+        kg, vtg = rand((B, nkv, G, d), scale=0.5), rand((B, nkv, d, G), scale=0.5)
+        lens = torch.full((B,), T, dtype=torch.int32, device=dev)
+        for Q in (2, 4, 8):
+            q, out = rand((B * Q, nh, d), scale=0.5), torch.zeros((B * Q, nh * d), dtype=torch.bfloat16, device=dev)
+            steps = [torch.full((B,), S + j, dtype=torch.int32, device=dev) for j in range(Q)]
+            qj = [q.view(B, Q, nh, d)[:, j].contiguous() for j in range(Q)]
+            i = [0]
+
+            def run(fp8, what):
+                c = i[0] % copies
+                i[0] += 1
+                seg = (ptr(k8[c] if fp8 else kp[c]), ptr(v8[c] if fp8 else vtp[c]), ptr(kg), ptr(vtg), ptr(lens))
+                sc = (ptr(ks[c]), ptr(vs[c])) if fp8 else (None, None)
+                tail = (B, nh, nkv, d, Tp, G, 1.0, 1, _lib.BF16, 1)
+                if what == "multi":
+                    _lib.call("p2t_attention_decode_multi", ptr(q), *seg, ptr(steps[0]), *tail, ptr(out), nh * d, *sc, Q, stream())
+                else:
+                    for j in range(Q if what == "rows x Q" else 1):
+                        _lib.call("p2t_attention_decode_rows", ptr(qj[j]), *seg, ptr(steps[j]), *tail, ptr(out), nh * d, *sc, stream())
+            res = {(f, w): [] for f in (0, 1) for w in ("multi", "rows x Q", "rows x 1")}
+            for _ in range(rounds):
+                for key in res:
+                    res[key].append(timeit(lambda: run(*key), iters=n, warm=copies) * 1e3)
+            for (f, w), r in res.items():
+                print(f"attn_decode multi B={B} Q={Q} {T}+{S + 1}..{S + Q} keys, {'fp8 ' if f else 'bf16'} prompt segment, "
+                      f"{dict(multi='p2t_attention_decode_multi     ', **{'rows x Q': 'Q x p2t_attention_decode_rows  ', 'rows x 1': 'one p2t_attention_decode_rows  '})[w]}: "
+                      f"median {np.median(r):5.1f} us (min {min(r):.1f}, max {max(r):.1f}; {rounds} rounds of {n})", flush=True)
+        del kp, vtp, k8, v8
+
+
 def bench_choice_rows():
     """p2t_sample_select / p2t_sample_select_rows (top_k 50, top_p 0.9, temperature 0.7) and p2t_logits_process / p2t_logits_process_rows
     (every stage on, 64 history tokens) on randn * 3 bf16 logits [rows, 128256] at pitch 128320, alternating, five rounds of 200 launches,
@@ -502,7 +550,9 @@ if __name__ == "__main__":
         bench_skinny()
     if "kv_store" in which:
         bench_kv_store()
-    if "attn_decode" in which and "beams" in which:
+    if "attn_decode" in which and "multi" in which:
+        bench_attn_decode_multi()
+    elif "attn_decode" in which and "beams" in which:
         bench_attn_decode_beams()
     elif "attn_decode" in which:
         bench_attn_decode()
